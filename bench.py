@@ -2,7 +2,7 @@
 """bench.py -- the detect path's headline benchmark (BASELINE.json: frames/sec + p50 detect latency,
 YOLOv8n 416x416, batch 1 / 64, 1-8 MI355X).
 
-    python bench.py --gpus 1 --steps K --warmup W            (default: N=1)
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]            (default: N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path (preprocess -> YOLOv8n forward -> decode -> NMS -> result slab)
@@ -13,12 +13,18 @@ of consecutive steps overlap on the device; --engines 1 runs one engine with Det
 batch-64 throughput configuration (configs[2]); the batch-1 latency configuration (configs[1]: frames/s
 with resident frames, and the host-to-host p50 detect latency through zly_detect) is measured in the
 same run and reported in the same JSON line as `latency_path_b1`; `throughput_host_to_host` is the same path fed
-from host memory by >= 8 threads through zly_submit / zly_wait and through the plugin (native driver, child process).  With N > 1 each rank (one process per GPU) detects its own frames -- frames are sharded
+from host memory by >= 8 threads through zly_submit / zly_wait and through the plugin (native driver, child process).
+
+A plain run does what the headline needs and nothing else: it creates the engines, runs W warm-up steps, times exactly K steps of the
+headline configuration, writes the last timed step's result slabs with --dump-outputs, and prints the line.  --full adds everything else
+it measures or checks: the batch-1, latency and roofline legs (`latency_path_b1`, `roofline`, `roofline_b1`, `candidates_per_frame`), the
+CPU baseline, the host-to-host legs and, with N > 1, the check of the gathered slabs against a single-engine run and the gather's share
+of a step.  With N > 1 each rank (one process per GPU) detects its own frames -- frames are sharded
 one-per-GPU, no data-path collective -- and the per-frame result slabs are all-gathered over
 RCCL/xGMI, overlapped with the next step (weak scaling: per-GPU work is fixed).
 
 Everything measured goes through the C ABI of libzly.so; oracle/ is used only for the
-`cpu_baseline` leg (the CPU restatement timed on the host cores, rank 0, N=1).
+`cpu_baseline` leg of --full (the CPU restatement timed on the host cores, rank 0, N=1).
 """
 import argparse
 import json
@@ -135,8 +141,9 @@ def run_steps(engs, frame_sets, batch, steps, slabs, stream_ptr, world, gather_o
 
 
 def timed_blocks(engs, frame_sets, batch, steps, warmup, blocks, slabs, stream_ptr, world, gather_out, size=416, no_gather=False):
-    """`warmup` untimed steps, then `blocks` consecutive blocks of EXACTLY `steps` steps, each bracketed by barrier +
-    torch.cuda.synchronize() on both sides and timed with the maximum over ranks.  Returns the list of block times in seconds.
+    """`warmup` untimed steps, then EXACTLY `steps` timed steps as `blocks` consecutive blocks (their sizes differ by at most one step),
+    each bracketed by barrier + torch.cuda.synchronize() on both sides and timed with the maximum over ranks.  Returns one
+    (seconds, steps) pair per block.
     Why blocks: the chip ramps its clock for the first ~50 steps after an idle phase (measured: 0.94 -> 0.72 ms/step over the first
     60 batch-64 steps, again after 2 s of idling; tools/first_steps.py) -- a single 20-step window measured right after 5 warm-up steps
     lies inside that ramp.  The median block is the steady state the metric is about; all block times are reported."""
@@ -144,13 +151,14 @@ def timed_blocks(engs, frame_sets, batch, steps, warmup, blocks, slabs, stream_p
     run_steps(engs, frame_sets, batch, warmup, slabs, stream_ptr, world, gather_out, size, k0=0, no_gather=no_gather)
     k0 = warmup
     out = []
-    for _ in range(blocks):
+    for i in range(blocks):
+        n = steps // blocks + (1 if i < steps % blocks else 0)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_steps(engs, frame_sets, batch, steps, slabs, stream_ptr, world, gather_out, size, k0=k0, no_gather=no_gather)
+        run_steps(engs, frame_sets, batch, n, slabs, stream_ptr, world, gather_out, size, k0=k0, no_gather=no_gather)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -160,8 +168,8 @@ def timed_blocks(engs, frame_sets, batch, steps, warmup, blocks, slabs, stream_p
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        out.append(dt)
-        k0 += steps
+        out.append((dt, n))
+        k0 += n
     return out
 
 
@@ -227,6 +235,34 @@ def host_to_host(threads, seconds=4.0, max_batch=64, engines=1):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, raw, n, cap):
+    """--dump-outputs: the result slabs of the last timed step (u8 [n * slab_bytes], frames in global order) as a caller of the path
+    receives them, float64, one .npy per array:
+      slab_headers [frames][4]      n_kept, n_candidates, flags, frame_tag
+      detections   [frames][cap][8] x, y, w, h, confidence, class_id, track_id, timestamp; rows past min(n_kept, cap) are zero (the slab
+                                    holds whatever an earlier step left there)
+      frame_index  [frames]         which frames of the step these are: all of them, or a fixed seeded sample when all would exceed 64 MB"""
+    names = [f for f in zly.DET_DTYPE.names if f != "pad_"]
+    idx = np.arange(n)
+    per_frame = 8 * (len(zly.SLAB_HDR_DTYPE.names) + cap * len(names) + 1)
+    if n * per_frame > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // per_frame, replace=False))
+    slabs = zly.parse_slabs(raw, n, cap)
+    hdr = np.zeros((len(idx), len(zly.SLAB_HDR_DTYPE.names)))
+    det = np.zeros((len(idx), cap, len(names)))
+    for r, i in enumerate(idx):
+        h, d = slabs[i]
+        hdr[r] = [h[f] for f in zly.SLAB_HDR_DTYPE.names]
+        for c, f in enumerate(names):
+            det[r, :len(d), c] = d[f]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("slab_headers", hdr), ("detections", det), ("frame_index", idx.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def self_launch(n):
     """bench.py --gpus N (N > 1) without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>` as a child
     and hand its one JSON line (rank 0's) through.  Exits non-zero when the node has fewer than N GPUs or the child fails."""
@@ -273,11 +309,14 @@ def main():
 def run():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps of the headline configuration")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed steps before them")
     ap.add_argument("--batch", type=int, default=64, help="frames per step per GPU for the headline value (BASELINE configs[2] = 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the batch-64 / latency / roofline legs")
+    ap.add_argument("--full", action="store_true", help="also run the batch-1 / latency / roofline legs, the CPU baseline, the host-to-host legs and, "
+                                                         "with N > 1, the gather check (everything beyond the headline figure)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's result slabs to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the batch-1 / latency / roofline legs")
     ap.add_argument("--eager", action="store_true", help="no hipGraph replay")
     ap.add_argument("--keep-head", action="store_true", help="also materialise the fp32 [4+nc][N] head tensor (parity/debug output; the shipped plugin does not)")
     ap.add_argument("--size", type=int, default=416, help="square model/frame size; 640 = BASELINE configs[3] (then only the headline leg runs)")
@@ -287,8 +326,9 @@ def run():
                                                           "side streams + deferred NMS")
     ap.add_argument("--sync-nms", action="store_true", help="run NMS in stream order at the end of every step instead of beside the next step's first kernels")
     ap.add_argument("--dump-ops", default="", help="write the per-launch hipEvent profile as a text table to this file")
-    ap.add_argument("--blocks", type=int, default=0, help="timed blocks of --steps steps each (default: max(10, ceil(400 / steps))); the median block is reported")
-    ap.add_argument("--per-launch-out", default=os.path.join(ROOT, "gpurun_out", "bench_per_launch.json"), help="where the per-launch roofline tables go (kept out of the JSON line)")
+    ap.add_argument("--blocks", type=int, default=0, help="consecutive blocks the --steps timed steps are split into (default: 10, fewer when a block "
+                                                          "would hold less than 20 steps); the median block is reported")
+    ap.add_argument("--per-launch-out", default=os.path.join(ROOT, "bench_out", "bench_per_launch.json"), help="where the per-launch roofline tables go (kept out of the JSON line)")
     a = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -296,6 +336,8 @@ def run():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" in os.environ and world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: the line would claim a GPU count it did not run on")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -356,21 +398,28 @@ def run():
     def gather_bufs(n):
         return [torch.zeros(world * n * sb, dtype=torch.uint8, device="cuda") for _ in range(2)] if (world > 1 or force_gather) else None
 
-    n_blocks = a.blocks if a.blocks > 0 else max(10, -(-400 // max(1, a.steps)))
-    log(f"engine ready (rank {rank}/{world}), headline leg: batch {B}, {a.warmup} warm-up steps, {n_blocks} blocks x {a.steps} steps")
+    n_blocks = min(a.steps, a.blocks if a.blocks > 0 else max(1, min(10, a.steps // 20)))
+    log(f"engine ready (rank {rank}/{world}), headline leg: batch {B}, {a.warmup} warm-up steps, {a.steps} timed steps in {n_blocks} blocks")
     # ---- headline: BASELINE configs[2] (batch B per GPU per step) -----------------------------------
     gb_head = gather_bufs(B)
     slabs_head = slab_bufs(B)
     bt = timed_blocks(engs, sets_b, B, a.steps, a.warmup, n_blocks, slabs_head, sp, world, gb_head, a.size)
-    dt = float(np.median(bt))
-    value = world * B * a.steps / dt
-    ms_per_step = dt / a.steps * 1e3
+    last = a.warmup + a.steps - 1                  # global number of the last timed step
+    if a.dump_outputs:
+        g = shard.global_order(gb_head[last % 2], world * B, world, sb) if gb_head is not None else slabs_head[last % len(slabs_head)]
+        raw = g.cpu().numpy()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, raw, world * B, eng.max_dets)
+    block_s = [t for t, _ in bt]
+    step_s = float(np.median([t / n for t, n in bt]))
+    value = world * B / step_s
+    ms_per_step = step_s * 1e3
     result = {
         "metric": "frames_per_sec", "value": round(value, 1), "unit": "frames/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 5),
-        # what was timed: `blocks` consecutive blocks of `steps` steps, every block bracketed by barrier + synchronize; value = the MEDIAN block
-        "blocks": n_blocks, "steps_timed": n_blocks * a.steps, "timed_region_s": round(float(sum(bt)), 5), "median_block_s": round(dt, 6),
-        "mean_ms_per_step_all_blocks": round(float(sum(bt)) / (n_blocks * a.steps) * 1e3, 5),
+        # what was timed: the `steps` steps as `blocks` consecutive blocks, every block bracketed by barrier + synchronize; value = the MEDIAN block
+        "blocks": n_blocks, "steps_timed": a.steps, "timed_region_s": round(float(sum(block_s)), 5), "median_block_s": round(float(np.median(block_s)), 6),
+        "mean_ms_per_step_all_blocks": round(float(sum(block_s)) / a.steps * 1e3, 5),
         # ranks of the RCCL communicator the slab gather ran on (torch.distributed backend nccl = RCCL); 1 = no communicator, no collective
         "rccl_ranks": (dist.get_world_size() if dist.is_initialized() else 1),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -380,17 +429,18 @@ def run():
                    "engines_per_gpu": n_eng, "frames_per_step_per_gpu": B, "global_frames_per_step": world * B, "conf": 0.5, "iou": 0.45,
                    "weights": "seeded synthetic (no real weights offline)", "graph": not a.eager,
                    "parallelism": f"frame-sharded x{world}" if world > 1 else "single GPU",
-                   "timing": f"median of {n_blocks} consecutive blocks of {a.steps} steps, each bracketed by barrier+sync (max over ranks)"},
-        "blocks_ms_per_step": [round(t / a.steps * 1e3, 4) for t in bt],
-        "first_block_ms_per_step": round(bt[0] / a.steps * 1e3, 4), "best_block_ms_per_step": round(min(bt) / a.steps * 1e3, 4),
+                   "timing": f"{a.steps} steps in {n_blocks} consecutive blocks, each bracketed by barrier+sync (max over ranks); the median block per step"},
+        "blocks_ms_per_step": [round(t / n * 1e3, 4) for t, n in bt],
+        "first_block_ms_per_step": round(bt[0][0] / bt[0][1] * 1e3, 4), "best_block_ms_per_step": round(min(t / n for t, n in bt) * 1e3, 4),
     }
+    log(f"headline {value:.0f} frames/s (blocks ms/step: {result['blocks_ms_per_step']})")
     lat_b1 = None
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         # ---- BASELINE configs[1]: batch 1, the latency path, frames resident in HBM ---------------------
-        k1 = max(200, a.steps * 2)
-        log(f"headline {value:.0f} frames/s (blocks ms/step: {result['blocks_ms_per_step']}); batch-1 leg")
-        bt1 = timed_blocks(engs[:1], sets_1, 1, k1, max(20, a.warmup), 5, slab_bufs(1), sp, world, gather_bufs(1), a.size)      # the latency path: ONE in-order chain
-        dt1 = float(np.median(bt1))
+        k1 = max(200, 2 * (a.steps // n_blocks))       # twice the headline's block
+        log("batch-1 leg")
+        bt1 = timed_blocks(engs[:1], sets_1, 1, 5 * k1, max(20, a.warmup), 5, slab_bufs(1), sp, world, gather_bufs(1), a.size)      # the latency path: ONE in-order chain
+        dt1 = float(np.median([t for t, _ in bt1]))
         lat_b1 = {"value": round(world * k1 / dt1, 1), "unit": "frames/s", "steps": k1, "ms_per_step_device_resident": round(dt1 / k1 * 1e3, 5)}
         if rank == 0:
             # ---- p50 detect latency, request bytes in host memory -> detections in host memory -----------
@@ -497,15 +547,14 @@ def run():
             hdrs = [h for h, _ in eng.read_slabs(min(B, 64))]
             result["candidates_per_frame"] = {"median": float(np.median([int(h["n_candidates"]) for h in hdrs])),
                                               "max": int(max(int(h["n_candidates"]) for h in hdrs)), "kept_max": int(max(int(h["n_kept"]) for h in hdrs))}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(frames_np[:8])
         result["speedup_vs_cpu_baseline"] = round(value / result["cpu_baseline"]["value"], 1)
     st = eng.stats()
     result["engine_stats"] = {"inference_count": st["inference_count"], "inference_errors": st["inference_errors"]}
-    if world > 1 or force_gather:
+    if a.full and (world > 1 or force_gather):
         # the gathered slabs of the last headline step, back in global frame order, must be well-formed, and this rank's slice of them must
         # be, byte for byte, what ONE engine writes for the same frames in a plain synchronous call
-        last = a.warmup + n_blocks * a.steps - 1
         g = shard.global_order(gb_head[last % 2], world * B, world, sb)
         hd = g[:, :16].contiguous().view(torch.int32).cpu().numpy()
         assert (hd[:, 0] >= 0).all() and (hd[:, 1] >= hd[:, 0]).all(), "malformed gathered slabs"
@@ -523,13 +572,13 @@ def run():
             assert np.array_equal(mine[f, :16 + 40 * nk], want[f, :16 + 40 * nk]), f"gathered slab of frame {f} of the last step differs from a single-engine run on the same frames"
         result["gather"] = {"ranks": world, "rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(), "bytes_per_rank_per_step": B * sb,
                             "frames_checked": int(hd.shape[0]), "equals_single_engine_run": True}
-        # the gather's share of a step: the same steps once more WITHOUT the collective (3 blocks, same bracket, max over ranks)
-        bt_ng = timed_blocks(engs, sets_b, B, a.steps, 0, 3, slabs_head, sp, world, gb_head, a.size, no_gather=True)
-        ms_ng = float(np.median(bt_ng)) / a.steps * 1e3
+        # the gather's share of a step: the same steps once more WITHOUT the collective (same blocks, same bracket, max over ranks)
+        bt_ng = timed_blocks(engs, sets_b, B, a.steps, 0, n_blocks, slabs_head, sp, world, gb_head, a.size, no_gather=True)
+        ms_ng = float(np.median([t / n for t, n in bt_ng])) * 1e3
         result["gather"]["ms_per_step_without_gather"] = round(ms_ng, 5)
         result["gather"]["share_of_step"] = round(max(0.0, 1.0 - ms_ng / ms_per_step), 4)
         dist.barrier()
-    if rank == 0 and world == 1 and not a.no_extras and default_cfg and os.environ.get("ZLY_BENCH_NO_H2H") != "1":
+    if a.full and rank == 0 and world == 1 and not a.no_extras and default_cfg and os.environ.get("ZLY_BENCH_NO_H2H") != "1":
         for e_ in engs:                # the native driver creates its own engines: free this process's first
             e_.close()
         engs = []

@@ -34,19 +34,34 @@ def test_detection_layout_matches_reference_types_h():
     assert zly.SLAB_HDR_DTYPE.itemsize == 16
 
 
-REFERENCE = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE, "src", "common", "types.h")), reason="build container only: the reference tree is not on the GPU box")
-def test_detection_layout_against_the_reference_header_itself():
-    """tests/cpp/abi_vs_reference_types.cpp includes the reference's own src/common/types.h (read where it lies, never copied) and
-    static_asserts sizeof / alignof / offsetof of zero_latency::Detection against zly_det: the compiler, not a table of numbers."""
+def test_detection_layout_against_the_reference_header_itself(tmp_path):
+    """tests/golden/reference_abi.json is what the compiler reports for the reference's own src/common/types.h and result.h
+    (tests/cpp/abi_reference_probe.cpp, built against them by tests/golden/make_abi_golden.py): sizeof / alignof / offsetof of
+    zero_latency::Detection and the zero_latency::ErrorCode values.  A translation unit with include/zly.h static_asserts zly_det and
+    the ZLY_* return codes against that record: the compiler checks the header, not a second table of numbers."""
+    import json
     import subprocess
-    for tu in ("abi_vs_reference_types.cpp", "abi_vs_reference_result.cpp"):       # result.h: the return codes against zero_latency::ErrorCode
-        src = os.path.join(ROOT, "tests", "cpp", tu)
-        r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(REFERENCE, "src", "common"), "-I", os.path.join(ROOT, "include"), src],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, (tu, r.stderr)
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_abi.json")))
+    det, state = ref["Detection"], ref["GameState"]["sizeof_member"]
+    fields = {"box": "x", "box.x": "x", "box.y": "y", "box.width": "w", "box.height": "h", "confidence": "confidence",
+              "class_id": "class_id", "track_id": "track_id", "timestamp": "timestamp"}
+    codes = {"OK": "ZLY_OK", "INVALID_ARGUMENT": "ZLY_ERR_INVALID_ARGUMENT", "NOT_INITIALIZED": "ZLY_ERR_NOT_INITIALIZED",
+             "INFERENCE_ERROR": "ZLY_ERR_INFERENCE", "MODEL_NOT_FOUND": "ZLY_ERR_MODEL_NOT_FOUND", "MODEL_LOAD_FAILED": "ZLY_ERR_MODEL_LOAD",
+             "INVALID_INPUT": "ZLY_ERR_INVALID_INPUT", "SYSTEM_ERROR": "ZLY_ERR_SYSTEM"}
+    assert set(det["offsetof"]) == set(fields) and set(ref["ErrorCode"]) == set(codes)
+    lines = ["#include <cstddef>", '#include "zly.h"',
+             f'static_assert(sizeof(zly_det) == {det["sizeof"]}, "sizeof(Detection)");',
+             f'static_assert(alignof(zly_det) == {det["alignof"]}, "alignof(Detection)");',
+             f'static_assert(sizeof(((zly_det*)nullptr)->class_id) == {det["sizeof_member"]["class_id"]}, "class_id width");',
+             f'static_assert(sizeof(((zly_det*)nullptr)->timestamp) == {det["sizeof_member"]["timestamp"]}, "timestamp width");',
+             # GameState: the members the plugin fills (frame_id, timestamp, detections) have the reference's widths
+             f'static_assert({state["frame_id"]} == 4 && {state["timestamp"]} == 8 && {state["detections_element"]} == sizeof(zly_det), "GameState");']
+    lines += [f'static_assert(offsetof(zly_det, {f}) == {det["offsetof"][k]}, "{k}");' for k, f in fields.items()]
+    lines += [f'static_assert({c} == {ref["ErrorCode"][k]}, "ErrorCode::{k}");' for k, c in codes.items()]
+    tu = tmp_path / "abi_vs_reference.cpp"
+    tu.write_text("\n".join(lines) + "\nint main() { return 0; }\n")
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(tu)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
     # the plugin's compat header re-declares the same record (the reference's headers do not compile as a whole): same layout as zly_det
     compat = open(os.path.join(ROOT, "zero-latency-yolo_amd", "host", "hip_inference_engine.cpp")).read()
     assert "static_assert(sizeof(zly_det) == sizeof(Detection)" in compat

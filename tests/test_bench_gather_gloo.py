@@ -149,3 +149,44 @@ def test_bench_step_loop_without_gather_leg():
         assert p.exitcode == 0
     for rank, untouched, calls in res:
         assert untouched and calls == 9, rank
+
+
+def test_timed_blocks_time_exactly_the_steps_asked_for(monkeypatch):
+    """--steps K times exactly K steps: split over the blocks (sizes differ by at most one), after the warm-up steps, numbered on from them"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda: None)
+    registry = {}
+    engs = [FakeEngine(registry, 3, 0) for _ in range(3)]
+    slabs = [torch.zeros(4 * engs[0].slab_bytes, dtype=torch.uint8) for _ in range(6)]
+    for t in slabs:
+        registry[t.data_ptr()] = t
+    for steps, blocks in ((23, 10), (20, 1), (7, 7)):
+        for e in engs:
+            e.calls.clear()
+        bt = bench.timed_blocks(engs, [torch.zeros(48, dtype=torch.uint8)], 4, steps, 5, blocks, slabs, 1234, 1, None)
+        sizes = [n for _, n in bt]
+        assert len(bt) == blocks and sum(sizes) == steps and max(sizes) - min(sizes) <= 1 and all(t >= 0 for t, _ in bt)
+        assert sorted(tag0 for e in engs for tag0, _ in e.calls) == [4 * k for k in range(5 + steps)]
+
+
+def test_dump_outputs_writes_the_slabs_as_a_caller_reads_them(tmp_path):
+    """--dump-outputs: float64 arrays, header fields and the first min(n_kept, cap) detections of every frame, zero past them"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import zly
+    n, cap = 3, 4
+    raw = np.zeros((n, 16 + cap * 40), dtype=np.uint8)
+    raw[:, 16:] = 0xAB                                                 # stale bytes of an earlier step behind the written detections
+    for i, kept in enumerate((0, 2, 9)):                               # 9 > cap: overflowed slab, cap stored
+        hdr = raw[i, :16].view(zly.SLAB_HDR_DTYPE)
+        hdr["n_kept"], hdr["n_candidates"], hdr["flags"], hdr["frame_tag"] = kept, kept + 3, int(kept > cap), 100 + i
+        d = raw[i, 16:].view(zly.DET_DTYPE)[:min(kept, cap)]
+        for j in range(len(d)):
+            d[j] = (0.1 * j, 0.2, 0.3, 0.4, 0.5 + 0.01 * j, 7 + j, 0, 0, 0)
+    bench.dump_outputs(str(tmp_path / "out"), raw.reshape(-1), n, cap)
+    hdr, det, idx = (np.load(tmp_path / "out" / f"{k}.npy") for k in ("slab_headers", "detections", "frame_index"))
+    assert hdr.dtype == det.dtype == idx.dtype == np.float64
+    assert hdr.tolist() == [[0, 3, 0, 100], [2, 5, 0, 101], [9, 12, 1, 102]] and idx.tolist() == [0, 1, 2]
+    assert det.shape == (n, cap, 8) and not det[0].any() and not det[1, 2:].any()
+    assert np.allclose(det[2, :, 0], np.float32([0.0, 0.1, 0.2, 0.3])) and det[2, :, 5].tolist() == [7, 8, 9, 10]

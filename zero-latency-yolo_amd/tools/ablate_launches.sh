@@ -7,7 +7,7 @@ out=gpurun_out/ablate; mkdir -p $out
 export ZLY_LIB=$(pwd)/zero-latency-yolo_amd/_build/libzly_diag.so
 [ -f "$ZLY_LIB" ] || { echo "build it first: make diaglib"; exit 1; }
 export ZLY_BENCH_NO_H2H=1
-run() { python3 bench.py --batch 64 --steps 20 --warmup 5 --blocks 12 --no-extras --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'])"; }
+run() { python3 bench.py --batch 64 --steps 240 --warmup 5 --blocks 12 --no-extras --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'])"; }
 base=$(run)
 base2=$(run)
 echo "baseline ms/step: $base $base2" > gpurun_out/ablate.txt

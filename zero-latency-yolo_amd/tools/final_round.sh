@@ -7,13 +7,13 @@ timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $out/gpu_tests.log 2>&1
 bash zero-latency-yolo_amd/tools/profile_round.sh $tag > $out/profile_round.log 2>&1 && cp gpurun_out/prof_$tag/* $out/ && cp gpurun_out/prof_$tag/traffic_b64.json profiles/${tag}_traffic_b64.json
 bash zero-latency-yolo_amd/tools/pmc_kernels.sh > $out/pmc_kernels.txt 2> $out/pmc_kernels.err
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-ZLY_BENCH_NO_H2H=1 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_b1 -- python3 bench.py --batch 1 --engines 1 --steps 200 --warmup 20 --blocks 3 --no-extras --no-cpu-baseline > $out/kt_b1_bench.json 2> $out/kt_b1.err
+ZLY_BENCH_NO_H2H=1 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_b1 -- python3 bench.py --batch 1 --engines 1 --steps 600 --warmup 20 --blocks 3 --no-extras --no-cpu-baseline > $out/kt_b1_bench.json 2> $out/kt_b1.err
 cp "$(find $out/kt_b1 -name '*kernel_stats.csv' | head -1)" $out/kernel_stats_b1.csv; rm -rf $out/kt_b1
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --per-launch-out $out/per_launch.json > $out/bench_driver_cmd.json 2> $out/bench_driver_cmd.err
+timeout -k 10 600 python3 bench.py --gpus 1 --full --steps 400 --blocks 20 --warmup 5 --per-launch-out $out/per_launch.json > $out/bench_driver_cmd.json 2> $out/bench_driver_cmd.err
 export ZLY_BENCH_NO_H2H=1
-timeout -k 10 300 python3 bench.py --size 640 --batch 32 --steps 20 --warmup 5 --no-cpu-baseline --per-launch-out $out/per_launch_yolov8n_640_b32.json > $out/bench_yolov8n_640_b32.json 2> $out/b640n.err
-timeout -k 10 300 python3 bench.py --size 640 --batch 32 --scale s --steps 20 --warmup 5 --no-cpu-baseline --per-launch-out $out/per_launch_yolov8s_640_b32.json > $out/bench_yolov8s_640_b32.json 2> $out/b640s.err
-timeout -k 10 300 python3 bench.py --size 640 --batch 32 --scale s --fp8 --steps 20 --warmup 5 --no-cpu-baseline --per-launch-out $out/per_launch_yolov8s_640_b32_fp8.json > $out/bench_yolov8s_640_b32_fp8weights.json 2> $out/b640f.err
+timeout -k 10 300 python3 bench.py --full --size 640 --batch 32 --steps 400 --blocks 20 --warmup 5 --no-cpu-baseline --per-launch-out $out/per_launch_yolov8n_640_b32.json > $out/bench_yolov8n_640_b32.json 2> $out/b640n.err
+timeout -k 10 300 python3 bench.py --full --size 640 --batch 32 --scale s --steps 400 --blocks 20 --warmup 5 --no-cpu-baseline --per-launch-out $out/per_launch_yolov8s_640_b32.json > $out/bench_yolov8s_640_b32.json 2> $out/b640s.err
+timeout -k 10 300 python3 bench.py --full --size 640 --batch 32 --scale s --fp8 --steps 400 --blocks 20 --warmup 5 --no-cpu-baseline --per-launch-out $out/per_launch_yolov8s_640_b32_fp8.json > $out/bench_yolov8s_640_b32_fp8weights.json 2> $out/b640f.err
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; tail -2 $out/smoke.log
 python3 - <<'PY'
 import json

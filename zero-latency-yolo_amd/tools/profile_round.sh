@@ -8,10 +8,10 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 export ZLY_BENCH_NO_H2H=1
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt3 -- python3 bench.py --batch 64 --steps 40 --warmup 5 --blocks 2 --no-extras --no-cpu-baseline > $out/kt3_bench.json 2> $out/kt3.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt3 -- python3 bench.py --batch 64 --steps 80 --warmup 5 --blocks 2 --no-extras --no-cpu-baseline > $out/kt3_bench.json 2> $out/kt3.err
 cp "$(find $out/kt3 -name '*kernel_stats.csv' | head -1)" $out/kernel_stats_3engines.csv
 rm -rf $out/kt3
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 bench.py --batch 64 --steps 40 --warmup 5 --blocks 2 --no-extras --no-cpu-baseline --engines 1 > $out/kt_bench.json 2> $out/kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 bench.py --batch 64 --steps 80 --warmup 5 --blocks 2 --no-extras --no-cpu-baseline --engines 1 > $out/kt_bench.json 2> $out/kt.err
 kt=$(find $out/kt -name "*kernel_trace.csv" | head -1)
 st=$(find $out/kt -name "*kernel_stats.csv" | head -1)
 cp "$st" $out/kernel_stats.csv
@@ -26,7 +26,7 @@ PY
 python3 zero-latency-yolo_amd/tools/trace_summary.py "$kt" $n $out/per_position.txt
 python3 zero-latency-yolo_amd/tools/trace_timeline.py "$kt" 3 > $out/timeline.txt
 # the latency path (batch 1, one engine): per-dispatch begin / end / gap of one step, and the kernel stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt1 -- python3 bench.py --batch 1 --steps 200 --warmup 20 --blocks 2 --no-extras --no-cpu-baseline --engines 1 > $out/kt1_bench.json 2> $out/kt1.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt1 -- python3 bench.py --batch 1 --steps 400 --warmup 20 --blocks 2 --no-extras --no-cpu-baseline --engines 1 > $out/kt1_bench.json 2> $out/kt1.err
 kt1=$(find $out/kt1 -name "*kernel_trace.csv" | head -1)
 cp "$(find $out/kt1 -name '*kernel_stats.csv' | head -1)" $out/kernel_stats_b1.csv
 python3 zero-latency-yolo_amd/tools/trace_timeline.py "$kt1" 5 > $out/timeline_b1.txt

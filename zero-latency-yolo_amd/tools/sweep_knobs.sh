@@ -1,7 +1,7 @@
 #!/bin/bash
 # One box, one sitting: the headline configuration under a list of tuning-switch settings with baseline runs in between (noise: +-0.8 %).
 # Round 3 result: nothing beyond noise -- stream grids of 768 / 1536 workgroups -2 %, ZLY_LDS_MIN_TILES=768 -6 %, ZLY_C2F_LDS_KB=120 -4 %.
-run() { name=$1; shift; v=$(env ZLY_BENCH_NO_H2H=1 "$@" timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --blocks 10 --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'])"); echo "$name $v"; }
+run() { name=$1; shift; v=$(env ZLY_BENCH_NO_H2H=1 "$@" timeout -k 10 200 python3 bench.py --steps 200 --warmup 5 --blocks 10 --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'])"); echo "$name $v"; }
 run base A=1
 run stream_wgs768 ZLY_STREAM_WGS=768
 run stream_wgs1536 ZLY_STREAM_WGS=1536
