@@ -34,7 +34,7 @@ def _unfused_state_dict(spec, seed):
     return sd
 
 
-@pytest.mark.parametrize("scale,nc", [("n", 80), ("n", 4), ("s", 80)])
+@pytest.mark.parametrize("scale,nc", [("n", 80), ("n", 4), ("s", 80), ("m", 80)])
 def test_state_dict_bn_folding_matches_torch(scale, nc):
     spec = zm.build_spec(scale, nc)
     sd = _unfused_state_dict(spec, seed=3)
@@ -52,6 +52,21 @@ def test_state_dict_bn_folding_matches_torch(scale, nc):
         else:
             want = F.conv2d(x, torch.from_numpy(sd[c.name + ".weight"]), torch.from_numpy(sd[c.name + ".bias"]))
         assert torch.allclose(got, want, rtol=1e-5, atol=2e-6), c.name
+
+
+@pytest.mark.parametrize("scale,nc", [("m", 80), ("l", 80), ("x", 80), ("l", 1), ("x", 17)])
+def test_infer_spec_picks_every_variant(scale, nc):
+    """the variant is read off the stem width (48 / 64 / 80 -> m / l / x) and every conv shape is checked; shapes only, so that
+    no multi-hundred-MB state dict is built for l and x"""
+    spec = zm.build_spec(scale, nc)
+    shapes = {c.name: (c.cout, c.cin, c.k, c.k) for c in spec.convs}
+    got = cw.infer_spec(shapes.__getitem__)
+    assert (got.scale, got.nc, got.reg_max) == (scale, nc, 16) and got.convs == spec.convs
+    other = dict(shapes)
+    other["model.8.m.2.cv1"] = (1, 1, 3, 3)                     # one bottleneck of the wrong shape: the variant's check must name it
+    if scale in ("l", "x"):
+        with pytest.raises(ValueError, match="model.8.m.2.cv1"):
+            cw.infer_spec(other.__getitem__)
 
 
 def test_rejects_wrong_models():

@@ -227,10 +227,11 @@ def _all_conv_names():
     return [c.name for c in zm.build_spec("n").convs]
 
 
-def _check_taps(eng, ref, frame_ids, skip_ok=()):
-    """every conv output the engine can expose, for the given frames, against the oracle's taps; returns the names checked"""
+def _check_taps(eng, ref, frame_ids, skip_ok=(), names=None):
+    """every conv output the engine can expose, for the given frames, against the oracle's taps; returns the names checked
+    (names: the model's conv names, default YOLOv8n's)"""
     checked = []
-    for name in _all_conv_names():
+    for name in names if names is not None else _all_conv_names():
         for i in frame_ids:
             try:
                 g = eng.tap(name, i)
@@ -740,11 +741,19 @@ def test_yolov8s_widths(tmp_path, oracle):
     assert np.abs(got[:, :4] - want[:, :4]).max() <= 4 * FP32_BOX_TOL * scale
     assert np.abs(got[:, 4:] - want[:, 4:]).max() <= 2 * FP32_SCORE_TOL
     e.close()
-    e = zly.Engine(p, model_w=320, model_h=320, dtype=zly.DTYPE_BF16, max_batch=2, max_dets=512, conf_thr=0.05, warmup_runs=0)
+    e = zly.Engine(p, model_w=320, model_h=320, dtype=zly.DTYPE_BF16, max_batch=2, max_dets=512, conf_thr=0.05, warmup_runs=0,
+                   flags=zly.FLAG_DUMP_LOGITS)
     for f in frames:
         dets, n = e.detect(f, cap=512)
         own = oracle.postprocess(e.head_tensor(0), 320, 320, 0.05, 0.45)
         assert n == len(own) and det_fields_equal(dets, own[:512])
+    # the bf16 head against both oracles, and every conv output against the bf16-rounding oracle's
+    ref16 = yolov8_ref.load(p, "bf16")
+    want16 = ref16.forward(torch.from_numpy(x)).numpy()
+    got = e.forward(x)
+    _assert_bf16_close(got, want16)
+    _assert_bf16_close(got, want)
+    assert len(_check_taps(e, ref16, (0, 1), skip_ok=(".m.0.cv1", ".m.1.cv1"), names=[c.name for c in spec.convs])) >= 55
     e.close()
 
 
@@ -1094,6 +1103,9 @@ def test_four_class_cs16_head(tmp_path, oracle):
     assert np.abs(got[:, 4:] - want[:, 4:]).max() <= 2 * FP32_SCORE_TOL
     e.close()
     e = zly.Engine(p, dtype=zly.DTYPE_BF16, max_batch=3, max_dets=512, conf_thr=0.3, warmup_runs=0)
+    got = e.forward(x)
+    _assert_bf16_close(got, yolov8_ref.load(p, "bf16").forward(torch.from_numpy(x)).numpy())
+    _assert_bf16_close(got, want)
     total = 0
     for f in frames:
         dets, n = e.detect(f, cap=512)

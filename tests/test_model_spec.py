@@ -1,5 +1,6 @@
 """CPU tests of the model description, the ZLYW weight file and the torch oracle's plumbing."""
 import numpy as np
+import pytest
 import torch
 
 import zly_model as zm
@@ -15,6 +16,27 @@ def test_layer_table_reproduces_published_sizes():
     assert abs(s.params() / 1e6 - 11.157) < 1e-2 and abs(2 * s.macs(640, 640) / 1e9 - 28.6) < 0.05
     assert n.num_anchors(416, 416) == 3549 and n.num_anchors(640, 640) == 8400
     assert n.head_c2 == 64 and n.head_c3 == 80
+    # m / l / x: build_spec's counts agree with ultralytics' fused model summaries as recalled (25.9 M / 78.9, 43.7 M / 165.2, 68.2 M / 257.8
+    # GFLOPs at 640); those cannot be checked offline, hence a 0.1 GFLOP tolerance on the rounded published figures
+    for scale, params, gflops, convs, ch, n_c2f, c3 in (("m", 25886080, 78.9, 83, (48, 96, 192, 384, 576), (2, 4, 4, 2, 2, 2, 2, 2), 192),
+                                                         ("l", 43668288, 165.2, 103, (64, 128, 256, 512, 512), (3, 6, 6, 3, 3, 3, 3, 3), 256),
+                                                         ("x", 68200608, 257.8, 103, (80, 160, 320, 640, 640), (3, 6, 6, 3, 3, 3, 3, 3), 320)):
+        sp = zm.build_spec(scale)
+        assert sp.ch == ch and sp.n_c2f == n_c2f and len(sp.convs) == convs, scale
+        assert sp.params() + 16 == params, (scale, sp.params() + 16)
+        assert abs(2 * sp.macs(640, 640) / 1e9 - gflops) < 0.1, (scale, 2 * sp.macs(640, 640) / 1e9)
+        assert sp.head_c2 == max(64, ch[2] // 4) and sp.head_c3 == c3
+
+
+def test_synthetic_weights_need_a_calibrated_table():
+    """every variant the synthetic generator serves has its own calibrated gain table; x has none and must not silently get n's"""
+    for scale in ("n", "s", "m", "l"):
+        spec = zm.build_spec(scale)
+        assert set(zm.SYNTH_GAINS[scale]) == {c.name for c in spec.convs}, scale
+    with pytest.raises(ValueError, match="yolov8x"):
+        zm.synth_weights(zm.build_spec("x"))
+    spec = zm.build_spec("n", 17)
+    assert set(zm.synth_weights(spec)) == {c.name for c in spec.convs}      # the class count does not change the table's keys
 
 
 def test_zlyw_roundtrip(tmp_path):

@@ -495,6 +495,9 @@ static int build_plan_host(zly_engine* e, PlanState* ps, std::string* err)
     int anchor_off = 0;
     e->N = fh[0] * fw[0] + fh[1] * fw[1] + fh[2] * fw[2];
     if (m.nc > 80) { *err = "nc > 80 is not supported by the fused Detect kernel"; return ZLY_ERR_MODEL_LOAD; }
+    // the class branch's stored width is c3 itself: for 65 <= nc <= 79 (YOLOv8n) its pixel rows would not be whole 16-channel
+    // tiles, and no conv epilogue nor the Detect tail's 16-byte fragment loads is written for that
+    if (c3 % 16 != 0) { *err = "Detect class-branch width max(ch[2], nc) = " + std::to_string(c3) + " is not a multiple of 16 (nc = " + std::to_string(m.nc) + ")"; return ZLY_ERR_MODEL_LOAD; }
     Op hd;
     hd.kind = OP_HEAD; hd.name = "detect.tail(1x1 convs+DFL+sigmoid+decode)";
     if (hd.name.size() > 47) hd.name.resize(47);
@@ -524,6 +527,12 @@ static int build_plan_host(zly_engine* e, PlanState* ps, std::string* err)
         HeadLevel& hl = hd.head.lv[l];
         ok = ok && pb.pack_only("model.22.cv2." + L + ".2", c2, &pend[l].wb, &pend[l].bb, &hl.nkb);
         ok = ok && pb.pack_only("model.22.cv3." + L + ".2", c3, &pend[l].wc, &pend[l].bc, &hl.nkc);
+        // the fused tail holds a branch's fragments in HEAD_KMAX k-steps of registers (launch_head_fused refuses more): refuse the model here, at load
+        if (ok && (hl.nkb > HEAD_KMAX || hl.nkc > HEAD_KMAX)) {
+            *err = "Detect branch too wide for the fused tail: " + std::to_string(c2) + " / " + std::to_string(c3) + " channels = " + std::to_string(hl.nkb) + " / " +
+                   std::to_string(hl.nkc) + " k-steps, at most " + std::to_string(HEAD_KMAX) + (e->dtype == ZLY_DTYPE_BF16 ? " in bf16" : " in fp32");
+            return ZLY_ERR_MODEL_LOAD;
+        }
         pend[l].hb2 = hb2; pend[l].hc2 = hc2; pend[l].hout = hout;
         hl.box_cs = c2; hl.cls_cs = c3; hl.box_cin = c2; hl.cls_cin = c3;
         hl.H = fh[l]; hl.W = fw[l]; hl.hw = fh[l] * fw[l]; hl.stride_px = 8 << l; hl.anchor_off = anchor_off; hl.block0 = block0;

@@ -35,6 +35,8 @@ SCALES = {
     "n": (0.25, 1024, 1.0 / 3.0),
     "s": (0.50, 1024, 1.0 / 3.0),
     "m": (0.75, 768, 2.0 / 3.0),
+    "l": (1.00, 512, 1.0),
+    "x": (1.25, 512, 1.0),
 }
 
 
@@ -415,8 +417,208 @@ SYNTH_GAIN_S: Dict[str, float] = {   # yolov8s (python oracle/calibrate_synth.py
 }
 
 
+SYNTH_GAIN_M: Dict[str, float] = {   # yolov8m (python oracle/calibrate_synth.py m)
+    "model.0": 0.9155,
+    "model.1": 1.9653,
+    "model.2.cv1": 1.9595,
+    "model.2.m.0.cv1": 1.9161,
+    "model.2.m.0.cv2": 1.9278,
+    "model.2.m.1.cv1": 1.4350,
+    "model.2.m.1.cv2": 1.9673,
+    "model.2.cv2": 1.4430,
+    "model.3": 1.9155,
+    "model.4.cv1": 1.9261,
+    "model.4.m.0.cv1": 1.9662,
+    "model.4.m.0.cv2": 1.9883,
+    "model.4.m.1.cv1": 1.3711,
+    "model.4.m.1.cv2": 1.9102,
+    "model.4.m.2.cv1": 1.1005,
+    "model.4.m.2.cv2": 1.9869,
+    "model.4.m.3.cv1": 0.9542,
+    "model.4.m.3.cv2": 1.9984,
+    "model.4.cv2": 1.1892,
+    "model.5": 1.9759,
+    "model.6.cv1": 1.9534,
+    "model.6.m.0.cv1": 1.9702,
+    "model.6.m.0.cv2": 1.9386,
+    "model.6.m.1.cv1": 1.3807,
+    "model.6.m.1.cv2": 1.9489,
+    "model.6.m.2.cv1": 1.1338,
+    "model.6.m.2.cv2": 2.0286,
+    "model.6.m.3.cv1": 1.0019,
+    "model.6.m.3.cv2": 1.9705,
+    "model.6.cv2": 1.2139,
+    "model.7": 1.9393,
+    "model.8.cv1": 1.9586,
+    "model.8.m.0.cv1": 1.9673,
+    "model.8.m.0.cv2": 1.9304,
+    "model.8.m.1.cv1": 1.3810,
+    "model.8.m.1.cv2": 1.9801,
+    "model.8.cv2": 1.4463,
+    "model.9.cv1": 1.9315,
+    "model.9.cv2": 1.3343,
+    "model.12.cv1": 1.8671,
+    "model.12.m.0.cv1": 2.0132,
+    "model.12.m.0.cv2": 1.9668,
+    "model.12.m.1.cv1": 1.9097,
+    "model.12.m.1.cv2": 2.0943,
+    "model.12.cv2": 1.9781,
+    "model.15.cv1": 1.9902,
+    "model.15.m.0.cv1": 2.0137,
+    "model.15.m.0.cv2": 1.8628,
+    "model.15.m.1.cv1": 2.0326,
+    "model.15.m.1.cv2": 1.9101,
+    "model.15.cv2": 1.9640,
+    "model.16": 1.8818,
+    "model.18.cv1": 1.9193,
+    "model.18.m.0.cv1": 2.0024,
+    "model.18.m.0.cv2": 1.8754,
+    "model.18.m.1.cv1": 1.9626,
+    "model.18.m.1.cv2": 1.8352,
+    "model.18.cv2": 1.9532,
+    "model.19": 1.9504,
+    "model.21.cv1": 1.9143,
+    "model.21.m.0.cv1": 2.0955,
+    "model.21.m.0.cv2": 1.9499,
+    "model.21.m.1.cv1": 2.0225,
+    "model.21.m.1.cv2": 1.9724,
+    "model.21.cv2": 1.9325,
+    "model.22.cv2.0.0": 1.9010,
+    "model.22.cv2.0.1": 1.9068,
+    "model.22.cv2.0.2": 1.8678,
+    "model.22.cv2.1.0": 1.9606,
+    "model.22.cv2.1.1": 2.0661,
+    "model.22.cv2.1.2": 3.2614,
+    "model.22.cv2.2.0": 2.1273,
+    "model.22.cv2.2.1": 1.9974,
+    "model.22.cv2.2.2": 3.1396,
+    "model.22.cv3.0.0": 1.8858,
+    "model.22.cv3.0.1": 1.8935,
+    "model.22.cv3.0.2": 5.2032,
+    "model.22.cv3.1.0": 2.0734,
+    "model.22.cv3.1.1": 1.9310,
+    "model.22.cv3.1.2": 4.9048,
+    "model.22.cv3.2.0": 2.0041,
+    "model.22.cv3.2.1": 1.8609,
+    "model.22.cv3.2.2": 5.6297,
+}
+
+SYNTH_GAIN_L: Dict[str, float] = {   # yolov8l (python oracle/calibrate_synth.py l)
+    "model.0": 0.8830,
+    "model.1": 1.9456,
+    "model.2.cv1": 1.9942,
+    "model.2.m.0.cv1": 1.9347,
+    "model.2.m.0.cv2": 1.9231,
+    "model.2.m.1.cv1": 1.3767,
+    "model.2.m.1.cv2": 1.9922,
+    "model.2.m.2.cv1": 1.1207,
+    "model.2.m.2.cv2": 1.8948,
+    "model.2.cv2": 1.2685,
+    "model.3": 1.9323,
+    "model.4.cv1": 1.9350,
+    "model.4.m.0.cv1": 1.9779,
+    "model.4.m.0.cv2": 1.9561,
+    "model.4.m.1.cv1": 1.3917,
+    "model.4.m.1.cv2": 1.9417,
+    "model.4.m.2.cv1": 1.1037,
+    "model.4.m.2.cv2": 1.9583,
+    "model.4.m.3.cv1": 0.9491,
+    "model.4.m.3.cv2": 1.9581,
+    "model.4.m.4.cv1": 0.8401,
+    "model.4.m.4.cv2": 2.0046,
+    "model.4.m.5.cv1": 0.7473,
+    "model.4.m.5.cv2": 1.9532,
+    "model.4.cv2": 0.9901,
+    "model.5": 1.9932,
+    "model.6.cv1": 1.9132,
+    "model.6.m.0.cv1": 1.9607,
+    "model.6.m.0.cv2": 1.9976,
+    "model.6.m.1.cv1": 1.3684,
+    "model.6.m.1.cv2": 1.9061,
+    "model.6.m.2.cv1": 1.1502,
+    "model.6.m.2.cv2": 1.8885,
+    "model.6.m.3.cv1": 0.9890,
+    "model.6.m.3.cv2": 1.9321,
+    "model.6.m.4.cv1": 0.8789,
+    "model.6.m.4.cv2": 1.9636,
+    "model.6.m.5.cv1": 0.7956,
+    "model.6.m.5.cv2": 1.9300,
+    "model.6.cv2": 1.0115,
+    "model.7": 1.9850,
+    "model.8.cv1": 1.8952,
+    "model.8.m.0.cv1": 1.9859,
+    "model.8.m.0.cv2": 2.0730,
+    "model.8.m.1.cv1": 1.3824,
+    "model.8.m.1.cv2": 2.1044,
+    "model.8.m.2.cv1": 1.1905,
+    "model.8.m.2.cv2": 1.9805,
+    "model.8.cv2": 1.3267,
+    "model.9.cv1": 1.8726,
+    "model.9.cv2": 1.3650,
+    "model.12.cv1": 1.9916,
+    "model.12.m.0.cv1": 1.8954,
+    "model.12.m.0.cv2": 1.9489,
+    "model.12.m.1.cv1": 1.9904,
+    "model.12.m.1.cv2": 1.9458,
+    "model.12.m.2.cv1": 2.0403,
+    "model.12.m.2.cv2": 2.0358,
+    "model.12.cv2": 1.9778,
+    "model.15.cv1": 1.9238,
+    "model.15.m.0.cv1": 1.8472,
+    "model.15.m.0.cv2": 2.0240,
+    "model.15.m.1.cv1": 2.0209,
+    "model.15.m.1.cv2": 1.8574,
+    "model.15.m.2.cv1": 1.9620,
+    "model.15.m.2.cv2": 2.0490,
+    "model.15.cv2": 1.8992,
+    "model.16": 1.8843,
+    "model.18.cv1": 1.8876,
+    "model.18.m.0.cv1": 1.8787,
+    "model.18.m.0.cv2": 1.9497,
+    "model.18.m.1.cv1": 1.9716,
+    "model.18.m.1.cv2": 2.0546,
+    "model.18.m.2.cv1": 1.9120,
+    "model.18.m.2.cv2": 1.9989,
+    "model.18.cv2": 1.9480,
+    "model.19": 1.8899,
+    "model.21.cv1": 1.9612,
+    "model.21.m.0.cv1": 1.9117,
+    "model.21.m.0.cv2": 1.8733,
+    "model.21.m.1.cv1": 1.9238,
+    "model.21.m.1.cv2": 2.0384,
+    "model.21.m.2.cv1": 1.8926,
+    "model.21.m.2.cv2": 1.9428,
+    "model.21.cv2": 1.9002,
+    "model.22.cv2.0.0": 1.8610,
+    "model.22.cv2.0.1": 1.8621,
+    "model.22.cv2.0.2": 3.2213,
+    "model.22.cv2.1.0": 2.1766,
+    "model.22.cv2.1.1": 1.8858,
+    "model.22.cv2.1.2": 2.2546,
+    "model.22.cv2.2.0": 2.0075,
+    "model.22.cv2.2.1": 1.7411,
+    "model.22.cv2.2.2": 3.2410,
+    "model.22.cv3.0.0": 1.9585,
+    "model.22.cv3.0.1": 1.9143,
+    "model.22.cv3.0.2": 5.7719,
+    "model.22.cv3.1.0": 1.8939,
+    "model.22.cv3.1.1": 1.9223,
+    "model.22.cv3.1.2": 5.2317,
+    "model.22.cv3.2.0": 2.0014,
+    "model.22.cv3.2.1": 1.9690,
+    "model.22.cv3.2.2": 4.9117,
+}
+
+# one calibrated table per variant: an uncalibrated deep net is chaotic (see above) and the bf16 bounds would mean nothing on it
+SYNTH_GAINS: Dict[str, Dict[str, float]] = {"n": SYNTH_GAIN, "s": SYNTH_GAIN_S, "m": SYNTH_GAIN_M, "l": SYNTH_GAIN_L}
+
+
 def synth_weights(spec: ModelSpec, seed: int = SYNTH_SEED, gains: Dict[str, float] = None) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
-    gains = (SYNTH_GAIN_S if spec.scale == "s" else SYNTH_GAIN) if gains is None else gains
+    """gains=None: the calibrated table of spec.scale (ValueError for a variant that has none); {}: every gain 1.0 (calibration input)."""
+    if gains is None:
+        if spec.scale not in SYNTH_GAINS:
+            raise ValueError(f"no calibrated synthetic-weight gains for yolov8{spec.scale}: run oracle/calibrate_synth.py {spec.scale} first")
+        gains = SYNTH_GAINS[spec.scale]
     rng = np.random.default_rng(seed)
     out = {}
     for c in spec.convs:
