@@ -74,6 +74,29 @@ extern "C" {
                                    (leave GPU_MAX_HW_QUEUES alone: 8 measured 2x SLOWER on the host-to-host path) */
 #define ZLY_FLAG_NO_FUSION   2   /* run every conv as its own kernel (no fused bottleneck pairs): every zly_debug_tap is then available */
 
+/* Pixel formats of a request frame (the *_fmt entry points; the others take ZLY_PIX_BGR).  Planes are tight: no row pitch, no padding.
+ *   ZLY_PIX_BGR          packed B,G,R, 3 bytes per pixel: nbytes = w*h*3
+ *   ZLY_PIX_NV12_*       Y plane [h][w], then ONE plane of interleaved U,V pairs [h/2][w/2][2]: nbytes = w*h*3/2
+ *   ZLY_PIX_I420_*       Y plane [h][w], U plane [h/2][w/2], V plane [h/2][w/2]:            nbytes = w*h*3/2
+ * YUV frames (8-bit 4:2:0, limited range) need even w and h (>= 2).  Colour conversion happens in the front kernel: for the source pixel
+ * (sx, sy) that the stretch-nearest resize picks (the BGR map, unchanged),
+ *   Y = Yplane[sy*w + sx];  ci = (sy>>1)*(w/2) + (sx>>1);  NV12: U = UV[2ci], V = UV[2ci+1];  I420: U = Uplane[ci], V = Vplane[ci]
+ * and in int32 with >> an arithmetic shift (floor):
+ *   yy = max(Y-16, 0)*CY;  u = U-128;  v = V-128
+ *   R = clamp((yy + CVR*v          + (1<<19)) >> 20, 0, 255)
+ *   G = clamp((yy + CVG*v + CUG*u  + (1<<19)) >> 20, 0, 255)
+ *   B = clamp((yy + CUB*u          + (1<<19)) >> 20, 0, 255)
+ *            CY       CVR      CVG      CUG      CUB
+ *   BT.601   1220542  1673527  -852492  -409993  2116026   (1.164, 1.596, 0.813, 0.391, 2.018 x 2^20)
+ *   BT.709   1220945  1879825  -558796  -223607  2215014   (round(c x 2^20) from Kr = 0.2126, Kb = 0.0722, luma x 255/219, chroma x 255/224)
+ * Those B,G,R bytes then take the BGR path exactly (resize map, /255, BGR->RGB): a YUV frame gives, bit for bit, what its converted BGR frame
+ * gives.  Boxes stay normalised by the request's w, h. */
+#define ZLY_PIX_BGR          0
+#define ZLY_PIX_NV12_BT601   1
+#define ZLY_PIX_I420_BT601   2
+#define ZLY_PIX_NV12_BT709   3
+#define ZLY_PIX_I420_BT709   4
+
 typedef struct zly_engine zly_engine;
 
 /* Layout-identical to zero_latency::Detection: box{x,y,width,height}@0 (centre-x, centre-y, w, h,
@@ -145,6 +168,10 @@ int32_t zly_destroy(zly_engine* e);
 const char* zly_last_error(void);          /* thread-local message of the last failing call */
 const char* zly_version(void);
 
+/* Bytes of one frame of format fmt (ZLY_PIX_*) and size w x h: w*h*3 for BGR, w*h*3/2 for YUV 4:2:0; 0 for an unknown format or invalid
+ * dimensions (w or h < 1; for YUV: odd, or < 2).  Host only: needs no engine and no GPU. */
+size_t  zly_frame_bytes(int32_t fmt, int32_t w, int32_t h);
+
 /* --- whole path ------------------------------------------------------------------------------ */
 /* One frame, synchronous.  bgr: u8 [h][w][3] interleaved BGR in host memory, nbytes must equal
  * w*h*3 (else ZLY_ERR_INVALID_INPUT, as onnx_engine.cpp:659-665).  Writes min(n, cap) detections
@@ -155,6 +182,14 @@ int32_t zly_detect(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, 
 /* n frames (n <= max_batch), each with its own size.  out is [n][cap]; n_out is [n]. */
 int32_t zly_detect_batch(zly_engine* e, int32_t n, const uint8_t* const* bgr, const size_t* nbytes,
                          const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out);
+
+/* The same with a frame format (ZLY_PIX_*): one for zly_detect_fmt, one per frame for zly_detect_batch_fmt (a batch may mix formats).
+ * An unknown format fails with ZLY_ERR_INVALID_ARGUMENT; nbytes != zly_frame_bytes(fmt, w, h) (odd or too small YUV sizes included)
+ * with ZLY_ERR_INVALID_INPUT.  Format ZLY_PIX_BGR is exactly zly_detect / zly_detect_batch. */
+int32_t zly_detect_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h,
+                       zly_det* out, int32_t cap, int32_t* n_out);
+int32_t zly_detect_batch_fmt(zly_engine* e, int32_t n, const int32_t* fmt, const uint8_t* const* frames, const size_t* nbytes,
+                             const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out);
 
 /* --- asynchronous, pipelined host-to-host path ------------------------------------------------------
  * The throughput path of a server: many host threads hand over frames, the engine batches them and overlaps the PCIe
@@ -177,6 +212,10 @@ int32_t zly_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, 
  * several engines (the plugin: one per GPU / engine instance) offers a frame to the next engine in turn and, only if that one is
  * back-pressured, to the others -- with the blocking call alone, submitting threads that all wait on one engine's ring starve the rest. */
 int32_t zly_submit_try(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket);
+/* With a frame format (ZLY_PIX_*; errors as zly_detect_fmt, no ticket then).  Each frame keeps its format through the ring: a batch may mix
+ * formats.  A slot's capacity is in bytes (ZLY_STAGE_MB), so more YUV frames than BGR ones fit one. */
+int32_t zly_submit_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket);
+int32_t zly_submit_try_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket);
 int32_t zly_poll(zly_engine* e, uint64_t ticket);
 int32_t zly_wait(zly_engine* e, uint64_t ticket, zly_det* out, int32_t cap, int32_t* n_out);
 
@@ -187,6 +226,9 @@ int32_t zly_wait(zly_engine* e, uint64_t ticket, zly_det* out, int32_t cap, int3
  * slab i. */
 int32_t zly_detect_device(zly_engine* e, int32_t n, const void* d_frames, int32_t w, int32_t h,
                           void* d_slabs, uint32_t frame_tag0, void* stream);
+/* The same for n frames of one format fmt (ZLY_PIX_*), contiguous in device memory zly_frame_bytes(fmt, w, h) apart (decoder output in HBM). */
+int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void* d_frames, int32_t w, int32_t h,
+                              void* d_slabs, uint32_t frame_tag0, void* stream);
 size_t  zly_slab_bytes(const zly_engine* e);
 int32_t zly_read_slabs(zly_engine* e, int32_t n, void* host_slabs);   /* syncs the engine stream */
 int32_t zly_sync(zly_engine* e);
@@ -198,6 +240,7 @@ int32_t zly_join(zly_engine* e, void* stream, int32_t lag);
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw);
+int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, float* out_nchw);
 /* Session::Run: images is host fp32 [n][3][model_h][model_w] (rounded to the engine dtype on
  * upload); head_out is host fp32 [n][4+nc][N]. */
 int32_t zly_forward(zly_engine* e, int32_t n, const float* images_nchw, float* head_out);

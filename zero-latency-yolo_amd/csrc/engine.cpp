@@ -150,6 +150,7 @@ struct zly_engine {
     Stem1Args stem1a{};
     bool ingest_active = false;       // set while the pipelined host path (zly_submit) enqueues: see run_path
     bool last_stem1 = false;          // the most recent call ran it (model.0 then only exists in HBM with ZLY_FLAG_DUMP_LOGITS)
+    bool front_yuv = false;           // the current call's batch holds a YUV 4:2:0 frame: its front kernel is the YUV-capable instantiation (set by run_path)
     hipStream_t stream = nullptr;
     hipStream_t side[2] = {nullptr, nullptr};     // P3 / P4 Detect branches (forked from and joined to the main stream)
     hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
@@ -893,7 +894,7 @@ static hipError_t run_op(zly_engine* e, const Op& op, int n, const uint8_t* d_sr
 {
     switch (op.kind) {
     case OP_PREPROCESS:
-        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s);
+        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front_yuv);
     case OP_CONV: {
         const Buffer& ib = e->bufs[(size_t)op.in.buf];
         if (c2f_covered(e, op, n)) return hipSuccess;               // computed by the fused C2f kernel launched at its leader
@@ -1102,9 +1103,11 @@ static void harvest_timing(zly_engine* e)
 }
 
 // nms_stream_out: the stream the call's NMS (its last kernel) was launched on -- `s`, or the engine's NMS stream when deferred
+// yuv: the batch holds at least one YUV 4:2:0 frame (d_desc says which): the front kernel runs its YUV-capable instantiation
 static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s, bool with_pre, bool defer_nms = false,
-                    hipStream_t* nms_stream_out = nullptr)
+                    hipStream_t* nms_stream_out = nullptr, bool yuv = false)
 {
+    e->front_yuv = with_pre && yuv;
     const size_t nops = e->ops.size();
     harvest_timing(e);
     const bool sample = with_pre && !e->t_pending && (e->sample_ctr++ % zly_engine::SAMPLE_EVERY) == 0;
@@ -1136,12 +1139,12 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
 #ifdef ZLY_DIAG
         if (e->sw.ablate.find(",stem,") != std::string::npos) { /* ZLY_ABLATE_SKIP=stem (libzly_diag.so only) */ } else
 #endif
-        HIP_TRY(launch_stem_model1(st, n, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_stem_model1(st, n, s, e->front_yuv), ZLY_ERR_INFERENCE);
         first = 3;
     } else if (fused) {
         StemArgs st = e->stem;
         st.src = d_src; st.desc = e->d_desc;
-        HIP_TRY(launch_stem_fused(st, n, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_stem_fused(st, n, s, e->front_yuv), ZLY_ERR_INFERENCE);
         first = 2;
     } else if (with_pre) {
         HIP_TRY(run_op(e, e->ops[0], n, d_src, nullptr, 0, s), ZLY_ERR_INFERENCE);
@@ -1151,6 +1154,8 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
     // first call of any other batch size.  The pipelined host path (dispatcher threads, several per process) never captures: it replays
     // what exists -- a lone frame and a full batch, its two steady states -- and launches other partial batches eagerly with cached
     // kernel shapes: no capture storm over the 62 partial sizes, no capture while other engines run.
+    // No "YUV in batch" bit: the front kernel (preprocess / fused stem, the only kernel that reads pixels and hence the only one with a YUV
+    // instantiation) is launched above, outside the captured range [first, nops - 1), so one graph serves BGR, YUV and mixed batches alike.
     const int key = (n * 2 + (fused ? 1 : 0)) * 2 + par;     // the captured Detect tail holds the candidate buffer's address
     auto git = e->graphs.find(key);
     if (e->cfg.use_graph && git == e->graphs.end() && !e->ingest_active) {
@@ -1204,11 +1209,12 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
     return ZLY_OK;
 }
 
-static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, const size_t* offs, hipStream_t s)
+// fmt: per-frame ZLY_PIX_* (null = all BGR), packed into the top byte of src_off (zly_internal.h)
+static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, const size_t* offs, hipStream_t s, const int32_t* fmt = nullptr)
 {
     bool same = (int)e->desc_cache.size() >= n;
     for (int i = 0; i < n && same; ++i)
-        same = e->desc_cache[(size_t)i].w == w[i] && e->desc_cache[(size_t)i].h == h[i] && e->desc_cache[(size_t)i].src_off == offs[i];
+        same = e->desc_cache[(size_t)i].w == w[i] && e->desc_cache[(size_t)i].h == h[i] && e->desc_cache[(size_t)i].src_off == desc_pack(offs[i], fmt ? fmt[i] : ZLY_PIX_BGR);
     if (same) return ZLY_OK;
     // frame sizes / offsets changed: next entry of the pinned ring, uploaded in stream order.  Calls on one engine are
     // stream-ordered by contract (they share every activation buffer), so the upload cannot overtake a kernel of the
@@ -1219,7 +1225,7 @@ static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, co
     FrameDesc* hd = e->h_desc + (size_t)r * (size_t)e->cfg.max_batch;
     if ((int)e->desc_cache.size() < n) e->desc_cache.resize((size_t)n);
     for (int i = 0; i < n; ++i) {
-        FrameDesc d; d.src_off = offs[i]; d.w = w[i]; d.h = h[i];
+        FrameDesc d; d.src_off = desc_pack(offs[i], fmt ? fmt[i] : ZLY_PIX_BGR); d.w = w[i]; d.h = h[i];
         hd[i] = d;
         e->desc_cache[(size_t)i] = d;
     }
@@ -1261,6 +1267,22 @@ static uint64_t now_ms()
 }
 
 static void ingest_destroy(zly_engine* e);
+
+static bool fmt_known(int32_t fmt) { return fmt >= ZLY_PIX_BGR && fmt <= ZLY_PIX_I420_BT709; }
+
+// the request checks of every entry point that takes host frames (onnx_engine.cpp:659-665): an unknown format is an argument error; a byte count
+// that is not zly_frame_bytes(fmt, w, h) -- odd or too small YUV sizes included -- is ZLY_ERR_INVALID_INPUT
+static int check_frame(int32_t fmt, const uint8_t* p, size_t nbytes, int32_t w, int32_t h)
+{
+    if (!fmt_known(fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(fmt));
+    const size_t want = zly_frame_bytes(fmt, w, h);
+    if (!p || want == 0 || nbytes != want) {
+        const size_t shown = want ? want : (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * (fmt == ZLY_PIX_BGR ? 6u : 3u) / 2u;
+        return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: expected " + std::to_string(shown) + ", got " + std::to_string(nbytes) +
+                                           (fmt != ZLY_PIX_BGR && (w < 2 || h < 2 || (w | h) & 1) ? " (YUV 4:2:0 needs even width and height >= 2)" : ""));
+    }
+    return ZLY_OK;
+}
 
 // Returns the first HIP error met while draining / releasing (the engine is gone either way).
 static hipError_t destroy_engine(zly_engine* e)
@@ -1323,8 +1345,9 @@ struct IngestSlot {
     uint64_t batch = 0;
     int n_reserved = 0, n_committed = 0, n_consumed = 0;
     size_t bytes_used = 0;
-    std::vector<int32_t> w, h;
+    std::vector<int32_t> w, h, fmt;
     std::vector<size_t> off;
+    int n_yuv = 0;                       // frames of a YUV format in the batch
     std::vector<uint8_t> consumed;
     int rc = ZLY_OK;
     std::string err;
@@ -1362,7 +1385,7 @@ static bool ingest_try_open(zly_engine* e, Ingest* g)
     IngestSlot& sl = g->slots[(size_t)(g->next_batch % g->slots.size())];
     if (sl.state != SLOT_FREE) return false;
     sl.state = SLOT_OPEN; sl.batch = g->next_batch++;
-    sl.n_reserved = sl.n_committed = sl.n_consumed = 0; sl.bytes_used = 0; sl.rc = ZLY_OK; sl.err.clear();
+    sl.n_reserved = sl.n_committed = sl.n_consumed = 0; sl.bytes_used = 0; sl.n_yuv = 0; sl.rc = ZLY_OK; sl.err.clear();
     std::fill(sl.consumed.begin(), sl.consumed.end(), (uint8_t)0);
     g->open = (int)(sl.batch % g->slots.size());
     (void)e;
@@ -1389,11 +1412,11 @@ static void ingest_enqueue(zly_engine* e, Ingest* g, IngestSlot& sl)
         HIP_TRY(hipMemcpyAsync(sl.d_stage, sl.h_stage, sl.bytes_used, hipMemcpyHostToDevice, g->copy_stream), ZLY_ERR_INFERENCE);
         HIP_TRY(hipEventRecord(sl.ev_h2d, g->copy_stream), ZLY_ERR_INFERENCE);
         HIP_TRY(hipStreamWaitEvent(e->stream, sl.ev_h2d, 0), ZLY_ERR_INFERENCE);
-        int rc = set_desc(e, n, sl.w.data(), sl.h.data(), sl.off.data(), e->stream);
+        int rc = set_desc(e, n, sl.w.data(), sl.h.data(), sl.off.data(), e->stream, sl.fmt.data());
         if (rc != ZLY_OK) return rc;
         hipStream_t ns = e->stream;
         e->ingest_active = true;
-        rc = run_path(e, n, sl.d_stage, sl.d_slabs, (uint32_t)(sl.batch << 16), e->stream, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns);
+        rc = run_path(e, n, sl.d_stage, sl.d_slabs, (uint32_t)(sl.batch << 16), e->stream, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, sl.n_yuv > 0);
         e->ingest_active = false;
         if (rc != ZLY_OK) return rc;
         // the slabs (n x 2.6 KB) go back on the stream the NMS ran on, right behind it: a download stream of its own would be the fifth
@@ -1502,7 +1525,7 @@ static int ingest_start(zly_engine* e)
              hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming) == hipSuccess;
         if (ok) hipMemset(sl.d_slabs, 0, sb);
-        sl.w.resize((size_t)e->cfg.max_batch); sl.h.resize((size_t)e->cfg.max_batch); sl.off.resize((size_t)e->cfg.max_batch);
+        sl.w.resize((size_t)e->cfg.max_batch); sl.h.resize((size_t)e->cfg.max_batch); sl.fmt.resize((size_t)e->cfg.max_batch); sl.off.resize((size_t)e->cfg.max_batch);
         sl.consumed.resize((size_t)e->cfg.max_batch);
     }
     if (!ok) { ingest_free(e, g); return fail(ZLY_ERR_SYSTEM, "allocation of the staging ring failed"); }
@@ -1548,12 +1571,12 @@ static void ingest_free(zly_engine* e, Ingest* g)
     delete g;                                          // the copy streams are shared by the process and stay
 }
 
-static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket, bool nonblock = false)
+static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket, bool nonblock = false,
+                         int32_t fmt = ZLY_PIX_BGR)
 {
-    if (!bgr || w <= 0 || h <= 0 || nbytes != (size_t)w * (size_t)h * 3u) {
+    if (int rcv = check_frame(fmt, bgr, nbytes, w, h)) {
         with_stats(e, [](zly_stats& st) { st.inference_errors++; });
-        return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: expected " + std::to_string((size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 3u) +
-                                               ", got " + std::to_string(nbytes));
+        return rcv;
     }
     if (!e->ingest.load()) {
         int rc = ingest_start(e);
@@ -1585,7 +1608,8 @@ static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32
             idx = o.n_reserved++;
             off = o.bytes_used;
             o.bytes_used += padded;
-            o.w[(size_t)idx] = w; o.h[(size_t)idx] = h; o.off[(size_t)idx] = off;
+            o.w[(size_t)idx] = w; o.h[(size_t)idx] = h; o.fmt[(size_t)idx] = fmt; o.off[(size_t)idx] = off;
+            if (fmt != ZLY_PIX_BGR) o.n_yuv++;
             *ticket = (o.batch << 16) | (uint64_t)idx;
             if (o.n_reserved == e->cfg.max_batch) ingest_close_open(g);
             break;
@@ -1858,18 +1882,21 @@ int32_t zly_destroy(zly_engine* e)
     return ZLY_OK;
 }
 
+// fmt: per-frame ZLY_PIX_* (null = all BGR)
 static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bgr, const size_t* nbytes,
-                              const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out)
+                              const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out, const int32_t* fmt = nullptr)
 {
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     std::vector<size_t> offs((size_t)n);
     size_t total = 0;
+    bool yuv = false;
     for (int i = 0; i < n; ++i) {
-        if (!bgr[i] || w[i] <= 0 || h[i] <= 0 || nbytes[i] != (size_t)w[i] * (size_t)h[i] * 3u) {
+        const int32_t fi = fmt ? fmt[i] : ZLY_PIX_BGR;
+        if (int rcv = check_frame(fi, bgr[i], nbytes[i], w[i], h[i])) {
             with_stats(e, [](zly_stats& st) { st.inference_errors++; });
-            return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: expected " + std::to_string((size_t)(w[i] > 0 ? w[i] : 0) * (size_t)(h[i] > 0 ? h[i] : 0) * 3u) +
-                                                   ", got " + std::to_string(nbytes[i]));
+            return rcv;
         }
+        yuv = yuv || fi != ZLY_PIX_BGR;
         offs[(size_t)i] = total;
         total += (nbytes[i] + 15) / 16 * 16;
     }
@@ -1884,9 +1911,9 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     for (int i = 0; i < n; ++i) memcpy(e->h_stage + offs[(size_t)i], bgr[i], nbytes[i]);
     SharedGate gl;
     HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, total, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
-    rc = set_desc(e, n, w, h, offs.data(), e->stream);
+    rc = set_desc(e, n, w, h, offs.data(), e->stream, fmt);
     if (rc != ZLY_OK) return rc;
-    rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true);
+    rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, false, nullptr, yuv);
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     const size_t sb = slab_bytes_of(e);
     HIP_TRY(hipMemcpyAsync(e->h_slabs, e->d_slabs, sb * (size_t)n, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
@@ -1907,14 +1934,27 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     return ZLY_OK;
 }
 
+size_t zly_frame_bytes(int32_t fmt, int32_t w, int32_t h)
+{
+    if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
+    if (fmt == ZLY_PIX_BGR) return (size_t)w * (size_t)h * 3u;
+    if (w < 2 || h < 2 || (w & 1) || (h & 1)) return 0;                // 4:2:0: one chroma sample per 2 x 2 block
+    return (size_t)w * (size_t)h * 3u / 2u;
+}
+
 int32_t zly_detect(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, zly_det* out, int32_t cap, int32_t* n_out)
+{
+    return zly_detect_fmt(e, ZLY_PIX_BGR, bgr, nbytes, w, h, out, cap, n_out);
+}
+
+int32_t zly_detect_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, zly_det* out, int32_t cap, int32_t* n_out)
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!out || !n_out || cap < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
     std::lock_guard<std::mutex> lk(e->mu);
     const auto t0 = std::chrono::steady_clock::now();
     const uint8_t* ptrs[1] = {bgr};
-    int rc = detect_host_locked(e, 1, ptrs, &nbytes, &w, &h, out, cap, n_out);
+    int rc = detect_host_locked(e, 1, ptrs, &nbytes, &w, &h, out, cap, n_out, fmt == ZLY_PIX_BGR ? nullptr : &fmt);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     with_stats(e, [&](zly_stats& st) { st.last_detect_ms = ms; });
     return rc;
@@ -1930,18 +1970,38 @@ int32_t zly_detect_batch(zly_engine* e, int32_t n, const uint8_t* const* bgr, co
     return detect_host_locked(e, n, bgr, nbytes, w, h, out, cap, n_out);
 }
 
-int32_t zly_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket)
+int32_t zly_detect_batch_fmt(zly_engine* e, int32_t n, const int32_t* fmt, const uint8_t* const* frames, const size_t* nbytes,
+                             const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out)
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
-    if (!ticket) return fail(ZLY_ERR_INVALID_ARGUMENT, "null ticket");
-    return ingest_submit(e, bgr, nbytes, w, h, ticket);
+    if (!fmt || !frames || !nbytes || !w || !h || !out || !n_out || cap < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    return detect_host_locked(e, n, frames, nbytes, w, h, out, cap, n_out, fmt);
+}
+
+int32_t zly_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket)
+{
+    return zly_submit_fmt(e, ZLY_PIX_BGR, bgr, nbytes, w, h, ticket);
 }
 
 int32_t zly_submit_try(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket)
 {
+    return zly_submit_try_fmt(e, ZLY_PIX_BGR, bgr, nbytes, w, h, ticket);
+}
+
+int32_t zly_submit_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket)
+{
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!ticket) return fail(ZLY_ERR_INVALID_ARGUMENT, "null ticket");
-    return ingest_submit(e, bgr, nbytes, w, h, ticket, true);
+    return ingest_submit(e, frame, nbytes, w, h, ticket, false, fmt);
+}
+
+int32_t zly_submit_try_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!ticket) return fail(ZLY_ERR_INVALID_ARGUMENT, "null ticket");
+    return ingest_submit(e, frame, nbytes, w, h, ticket, true, fmt);
 }
 
 int32_t zly_poll(zly_engine* e, uint64_t ticket)
@@ -1959,20 +2019,27 @@ int32_t zly_wait(zly_engine* e, uint64_t ticket, zly_det* out, int32_t cap, int3
 
 int32_t zly_detect_device(zly_engine* e, int32_t n, const void* d_frames, int32_t w, int32_t h, void* d_slabs, uint32_t frame_tag0, void* stream)
 {
+    return zly_detect_device_fmt(e, ZLY_PIX_BGR, n, d_frames, w, h, d_slabs, frame_tag0, stream);
+}
+
+int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void* d_frames, int32_t w, int32_t h, void* d_slabs, uint32_t frame_tag0, void* stream)
+{
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
-    if (!d_frames || w <= 0 || h <= 0) return fail(ZLY_ERR_INVALID_INPUT, "bad frame pointer or size");
+    if (!fmt_known(fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(fmt));
+    const size_t fb = zly_frame_bytes(fmt, w, h);
+    if (!d_frames || w <= 0 || h <= 0 || fb == 0) return fail(ZLY_ERR_INVALID_INPUT, "bad frame pointer or size");
     if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    std::vector<int32_t> ws((size_t)n, w), hs((size_t)n, h);
+    std::vector<int32_t> ws((size_t)n, w), hs((size_t)n, h), fs((size_t)n, fmt);
     std::vector<size_t> offs((size_t)n);
-    for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * (size_t)w * (size_t)h * 3u;
-    int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s);
+    for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * fb;
+    int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data());
     if (rc != ZLY_OK) return rc;
     hipStream_t ns = s;
-    rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns);
+    rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, fmt != ZLY_PIX_BGR);
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
     e->call_seq++;
@@ -2026,10 +2093,14 @@ int32_t zly_read_slabs(zly_engine* e, int32_t n, void* host_slabs)
 
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw)
 {
+    return zly_preprocess_fmt(e, ZLY_PIX_BGR, bgr, nbytes, w, h, out_nchw);
+}
+
+int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw)
+{
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!out_nchw) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
-    if (!bgr || w <= 0 || h <= 0 || nbytes != (size_t)w * (size_t)h * 3u)
-        return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: expected " + std::to_string((size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 3u) + ", got " + std::to_string(nbytes));
+    if (int rcv = check_frame(fmt, bgr, nbytes, w, h)) return rcv;
     std::lock_guard<std::mutex> lk(e->mu);
     ExclusiveGate gl;                                    // parity / debug entry point: allocations and copies, alone in the process
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
@@ -2042,9 +2113,9 @@ int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t
     memcpy(e->h_stage, bgr, nbytes);
     HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, nbytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
     size_t off0 = 0;
-    rc = set_desc(e, 1, &w, &h, &off0, e->stream);
+    rc = set_desc(e, 1, &w, &h, &off0, e->stream, &fmt);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, fmt != ZLY_PIX_BGR), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
@@ -2331,6 +2402,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
     std::vector<size_t> offs((size_t)n);
     for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * (size_t)w * (size_t)h * 3u;
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream);
+    e->front_yuv = false;                                // BGR frames: the front kernels' BGR instantiations
     if (rc != ZLY_OK) return rc;
     const size_t nops = e->ops.size();
     std::vector<hipEvent_t> ev(nops + 1);

@@ -3,6 +3,7 @@
 // tail lives in kernels_head.hip, preprocess+stem in kernels_stem.hip.)  HBM/LDS-bound element work:
 // 16-byte accesses, no MFMA.
 #include "zly_internal.h"
+#include "yuv_device.h"
 
 namespace zly {
 
@@ -18,8 +19,10 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // Every operation is a single IEEE fp32 op, so the result is bit-identical to the CPU oracle.
 // Two outputs: the engine's NHWC tensor padded to 8 channels (one 16-byte store per pixel in bf16),
 // and optionally the reference's planar fp32 [3][th][tw] layout for the parity entry point.
+// YUV: the instantiation for batches with YUV 4:2:0 frames -- a YUV frame's pixel is converted to the B, G, R bytes of its integer BGR
+// equivalent (yuv_device.h) and then takes exactly the BGR path; the BGR-only instantiation is unchanged.
 // ------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool YUV>
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
                                                          T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
 {
@@ -32,8 +35,16 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     const float scale_h = (float)d.h / (float)th;
     int sy = (int)((float)y * scale_h); if (sy > d.h - 1) sy = d.h - 1;
     int sx = (int)((float)x * scale_w); if (sx > d.w - 1) sx = d.w - 1;
-    const uint8_t* px = src + d.src_off + ((size_t)sy * d.w + sx) * 3;
-    const float b = (float)px[0] / 255.0f, g = (float)px[1] / 255.0f, r = (float)px[2] / 255.0f;
+    float b, g, r;
+    if (YUV && pix_is_yuv(desc_fmt(d.src_off))) {
+        unsigned int yv, uv;
+        yuv_issue(src + desc_off(d.src_off), desc_fmt(d.src_off), d.w, d.h, sx, sy, yv, uv);
+        const unsigned int px = yuv_bgr_word(yv, uv, desc_fmt(d.src_off));
+        b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)(px >> 16) / 255.0f;
+    } else {
+        const uint8_t* px = src + (YUV ? desc_off(d.src_off) : d.src_off) + ((size_t)sy * d.w + sx) * 3;
+        b = (float)px[0] / 255.0f; g = (float)px[1] / 255.0f; r = (float)px[2] / 255.0f;
+    }
     if (out8) {
         T* o = out8 + ((size_t)f * th * tw + idx) * 8;
         o[0] = (T)r; o[1] = (T)g; o[2] = (T)b; o[3] = (T)0.f;
@@ -46,13 +57,16 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
 }
 
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s)
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv)
 {
     dim3 grid((tw * th + 255) / 256, n);
-    if (dtype == ZLY_DTYPE_BF16)
-        hipLaunchKernelGGL(preprocess_kernel<bf16_t>, grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
-    else
-        hipLaunchKernelGGL(preprocess_kernel<float>, grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
+    if (dtype == ZLY_DTYPE_BF16) {
+        if (yuv) hipLaunchKernelGGL((preprocess_kernel<bf16_t, true>), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
+        else hipLaunchKernelGGL((preprocess_kernel<bf16_t, false>), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
+    } else {
+        if (yuv) hipLaunchKernelGGL((preprocess_kernel<float, true>), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
+        else hipLaunchKernelGGL((preprocess_kernel<float, false>), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
+    }
     return hipGetLastError();
 }
 

@@ -14,8 +14,13 @@
 //      for the kernel's lifetime (weight-stationary), activations come from LDS as two 8-byte reads per
 //      fragment (two taps x 4 channels);
 //   4. bias + SiLU, 8-byte NHWC stores: the 4 lanes of a pixel write its 32 bytes contiguously.
+//
+// The YUV = true instantiations of the front kernels (batches with YUV 4:2:0 frames) are compiled in a translation unit of their own,
+// kernels_stem_yuv.hip, which includes this file with ZLY_STEM_YUV_TU defined: instantiated here, next to the BGR ones, they changed the
+// register allocation of the BGR kernels (same resources, different code), and the BGR kernels are to stay exactly as they were.
 #include "zly_internal.h"
 #include "conv_device.h"
+#include "yuv_device.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -43,8 +48,10 @@ __device__ __forceinline__ FrameDesc load_desc(const FrameDesc* p)
 }
 
 // NT = output channel tiles of 16: 1 (YOLOv8n, 16-channel stem: rows in channel order) or 2 (YOLOv8-s, 32 channels: pair-permuted rows, a lane
-// ends with 8 consecutive channels = one 16-byte store); the pixel fragments are read once for both tiles
-template <int NT>
+// ends with 8 consecutive channels = one 16-byte store); the pixel fragments are read once for both tiles.
+// YUV: the instantiation for batches with YUV 4:2:0 frames (yuv_device.h: a YUV frame's pixel becomes its BGR bytes, then the BGR path); it serves
+// the batch's BGR frames as well.  Batches of BGR frames only run YUV = false, the kernel as it was.
+template <int NT, bool YUV>
 __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
 {
     __shared__ __attribute__((aligned(16))) bf16x4 patch[STEM_PH * STEM_PW];
@@ -67,8 +74,9 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
     const FrameDesc d = load_desc(&a.desc[f]);
     const float scale_w = (float)d.w / (float)a.tw;
     const float scale_h = (float)d.h / (float)a.th;
-    const uint8_t* src = a.src + d.src_off;
-    const bool same = (d.w == a.tw) & (d.h == a.th);
+    const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
+    const uint8_t* src = a.src + (YUV ? desc_off(d.src_off) : d.src_off);
+    const bool same = (d.w == a.tw) & (d.h == a.th) & !pix_is_yuv(fmt);
     const size_t frame_bytes = (size_t)d.w * d.h * 3;
     for (int u = tid; u < STEM_PH * STEM_PW; u += 256) {
         const int py = u / STEM_PW, px = u - py * STEM_PW;
@@ -80,13 +88,19 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
                 sy = (int)((float)iy * scale_h); if (sy > d.h - 1) sy = d.h - 1;
                 sx = (int)((float)ix * scale_w); if (sx > d.w - 1) sx = d.w - 1;
             }
+            unsigned int px4;
+            if (YUV && pix_is_yuv(fmt)) {      // wave-uniform: one format per frame
+                unsigned int yv, uv;
+                yuv_issue(src, fmt, d.w, d.h, sx, sy, yv, uv);
+                px4 = yuv_bgr_word(yv, uv, fmt);
+            } else {
             const size_t off = ((size_t)sy * d.w + sx) * 3;
             const uint8_t* q = src + off;
             // one (unaligned) 4-byte load instead of three byte loads -- this kernel is bound by instruction issue; the very
             // last pixel of a frame would read one byte past it and keeps the byte loads
-            unsigned int px4;
             if (off + 4 <= frame_bytes) __builtin_memcpy(&px4, q, 4);                        // B | G<<8 | R<<16 | next B<<24 (amdhsa: unaligned global access is enabled)
             else px4 = (unsigned int)q[0] | ((unsigned int)q[1] << 8) | ((unsigned int)q[2] << 16);
+            }
             // BGR -> RGB; bf16(u8 * (1/255.f)) == bf16(u8 / 255.f) for all 256 values (tests/test_model_spec.py), so the
             // reference's divide (:693) + the bf16 rounding is one v_cvt_f32_ubyte + v_mul + convert, no table
             const float k = 1.0f / 255.0f;
@@ -151,17 +165,29 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
     }
 }
 
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s)
+typedef void (*stem_fused_fn)(const StemArgs);
+typedef void (*stem1_fn)(const Stem1Args);
+#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_DIAG)        // (diagnostic builds, tools/stem_bench.hip: one translation unit)
+// the YUV instantiations, for the launchers in kernels_stem.hip
+stem_fused_fn stem_fused_yuv_kernel(int nt) { return nt == 2 ? stem_fused_kernel<2, true> : stem_fused_kernel<1, true>; }
+#endif
+#ifndef ZLY_STEM_YUV_TU
+stem_fused_fn stem_fused_yuv_kernel(int nt);         // kernels_stem_yuv.hip
+stem1_fn      stem1_yuv_kernel(int nw, int var);
+
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv)
 {
     if (a.Cout != 16 && a.Cout != 32) return hipErrorInvalidValue;         // one or two 16-channel MFMA tiles (YOLOv8n / YOLOv8-s); wider stems use the generic path
     if (a.Cout == 32 && (a.out_cs % 8 || a.out_co % 8)) return hipErrorInvalidValue;
     const int tiles_y = (a.Ho + STEM_TH - 1) / STEM_TH;
-    if (a.Cout == 16) hipLaunchKernelGGL(stem_fused_kernel<1>, dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(stem_fused_kernel<2>, dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    if (yuv) hipLaunchKernelGGL(stem_fused_yuv_kernel(a.Cout == 16 ? 1 : 2), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    else if (a.Cout == 16) hipLaunchKernelGGL((stem_fused_kernel<1, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((stem_fused_kernel<2, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 int stem_tiles_x(int Wo) { return (Wo + STEM_TW - 1) / STEM_TW; }
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // preprocess + model.0 + model.1 as ONE kernel (bf16, 16-channel stem, 32-channel model.1: YOLOv8n).
@@ -206,10 +232,15 @@ __device__ unsigned long long* g_stem_diag = nullptr;            // diagnostic b
 //   read 2 (k-step 1, first half):  kq0 (1,2)  kq1 zero   kq2 (2,2)  kq3 zero            (k-step 1, second half: all zero weights, not read)
 // Round 3's order (tap = s * 8 + kq * 2 + j) put two taps of equal pixel parity into half of the lane groups' pairs: 2-way conflicts on 4 of 8 half-wave
 // reads, and a fourth read for slots whose weights are all zero.
+#ifndef ZLY_STEM_YUV_TU
 static const int STEM1_TAP_SLOT[9] = {0, 2, 5, 4, 6, 8, 1, 3, 12};
 const int* stem1_tap_slot() { return STEM1_TAP_SLOT; }
+#endif
 
-template <int NW, int VAR>
+// YUV: the instantiation for batches with YUV 4:2:0 frames.  A YUV frame never counts as `same` (request size == model size), so it never reaches the
+// BGR quad paths; the per-pixel general path fetches it through yuv_device.h (all byte loads of a thread first, then the conversions).  Batches of
+// BGR frames only run YUV = false, the kernel as it was.
+template <int NW, int VAR, bool YUV>
 __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem_model1_kernel(const Stem1Args a)
 {
     constexpr bool NEWP = VAR >= 1, PERS = VAR >= 2;
@@ -317,7 +348,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
         const int iy0 = 4 * oy1 - 3, ix0 = 4 * ox1 - 3;
         const FrameDesc d = load_desc(&a.st.desc[f]);
         if (!((d.w == a.st.tw) & (d.h == a.st.th))) return;     // resized frame: the general path below does its own loads
-        const uint8_t* src = a.st.src + d.src_off;
+        if (YUV && pix_is_yuv(desc_fmt(d.src_off))) return;     // YUV frame: so does it
+        const uint8_t* src = a.st.src + (YUV ? desc_off(d.src_off) : d.src_off);
         pma = issue_quad(qok[0], qpy[0], qpx[0], iy0, ix0, d, src, pa0, pa1, pa2);
         pmb = issue_quad(qok[1], qpy[1], qpx[1], iy0, ix0, d, src, pb0, pb1, pb2);
     };
@@ -349,8 +381,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
 
     // ---- 1. input patch ------------------------------------------------------------------------------------------
     const FrameDesc d = load_desc(&a.st.desc[f]);
-    const uint8_t* src = a.st.src + d.src_off;
-    const bool same = (d.w == a.st.tw) & (d.h == a.st.th);
+    const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
+    const uint8_t* src = a.st.src + (YUV ? desc_off(d.src_off) : d.src_off);
+    const bool same = (d.w == a.st.tw) & (d.h == a.st.th) & !pix_is_yuv(fmt);
     const size_t frame_bytes = (size_t)d.w * d.h * 3;
     STEMSTAMP(0);
     if (same && NEWP) {
@@ -454,6 +487,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
         const float scale_w = (float)d.w / (float)a.st.tw;
         const float scale_h = (float)d.h / (float)a.st.th;
         unsigned int raw[STEM1_MAXIT];
+        unsigned int rawc[YUV ? STEM1_MAXIT : 1];                   // YUV frames: raw = the Y byte, rawc = U | V << 8
+        const bool yuvf = YUV && pix_is_yuv(fmt);                   // workgroup-uniform
         const int tidg = PERS ? pin_here(tid) : tid;
     #pragma unroll
         for (int k = 0; k < STEM1_MAXIT; ++k) {
@@ -468,12 +503,16 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                         sy = (int)((float)iy * scale_h); if (sy > d.h - 1) sy = d.h - 1;
                         sx = (int)((float)ix * scale_w); if (sx > d.w - 1) sx = d.w - 1;
                     }
+                    if (yuvf) {
+                        yuv_issue(src, fmt, d.w, d.h, sx, sy, raw[k], rawc[k]);
+                    } else {
                     const size_t off = ((size_t)sy * d.w + sx) * 3;
                     const uint8_t* q = src + off;
                     unsigned int px4;
                     if (off + 4 <= frame_bytes) __builtin_memcpy(&px4, q, 4);        // B | G<<8 | R<<16 | next B<<24 (unaligned global access is enabled on amdhsa)
                     else px4 = (unsigned int)q[0] | ((unsigned int)q[1] << 8) | ((unsigned int)q[2] << 16);
                     raw[k] = px4 & 0x00ffffffu;
+                    }
                 }
             }
         }
@@ -484,7 +523,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                 bf16x4 v = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
                 if (!(raw[k] & 0x80000000u)) {
                     const float kk = 1.0f / 255.0f;                  // bf16(u8 * (1/255.f)) == bf16(u8 / 255.f) for all 256 values (tests/test_model_spec.py)
-                    v[0] = (bf16_t)((float)((raw[k] >> 16) & 0xffu) * kk); v[1] = (bf16_t)((float)((raw[k] >> 8) & 0xffu) * kk); v[2] = (bf16_t)((float)(raw[k] & 0xffu) * kk);
+                    unsigned int px = raw[k];
+                    if constexpr (YUV) { if (yuvf) px = yuv_bgr_word(raw[k], rawc[k], fmt); }
+                    v[0] = (bf16_t)((float)((px >> 16) & 0xffu) * kk); v[1] = (bf16_t)((float)((px >> 8) & 0xffu) * kk); v[2] = (bf16_t)((float)(px & 0xffu) * kk);
                 }
                 const int py = div_small_s(u, invPW);
                 patch[u + py * (PW - PWV)] = v;
@@ -651,6 +692,15 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
 }
 
 static constexpr int STEM1_NW = 8;
+#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_DIAG)
+stem1_fn stem1_yuv_kernel(int nw, int var)
+{
+    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, true> : nw == 16 ? stem_model1_kernel<16, 2, true> : stem_model1_kernel<STEM1_NW, 2, true>;
+    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, true> : nw == 16 ? stem_model1_kernel<16, 1, true> : stem_model1_kernel<STEM1_NW, 1, true>;
+    return nw == 12 ? stem_model1_kernel<12, 0, true> : nw == 16 ? stem_model1_kernel<16, 0, true> : stem_model1_kernel<STEM1_NW, 0, true>;
+}
+#endif
+#ifndef ZLY_STEM_YUV_TU
 static size_t stem1_lds_bytes(int th, int tw, int var)
 {
     const size_t RH = 2 * th + 1, RW = 2 * tw + 1, PH = 2 * RH + 1, PW = 2 * RW + 1 + (var >= 1 ? 3 : 0);
@@ -669,22 +719,23 @@ void stem1_plan(int H1, int W1, int* th, int* tw)
     (void)H1;
 }
 
-typedef void (*stem1_fn)(const Stem1Args);
-static stem1_fn pick_stem1(int nw, int var)
+static stem1_fn pick_stem1(int nw, int var, bool yuv)
 {
-    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2> : nw == 16 ? stem_model1_kernel<16, 2> : stem_model1_kernel<STEM1_NW, 2>;
-    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1> : nw == 16 ? stem_model1_kernel<16, 1> : stem_model1_kernel<STEM1_NW, 1>;
-    return nw == 12 ? stem_model1_kernel<12, 0> : nw == 16 ? stem_model1_kernel<16, 0> : stem_model1_kernel<STEM1_NW, 0>;
+    if (yuv) return stem1_yuv_kernel(nw, var);
+    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, false> : nw == 16 ? stem_model1_kernel<16, 2, false> : stem_model1_kernel<STEM1_NW, 2, false>;
+    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, false> : nw == 16 ? stem_model1_kernel<16, 1, false> : stem_model1_kernel<STEM1_NW, 1, false>;
+    return nw == 12 ? stem_model1_kernel<12, 0, false> : nw == 16 ? stem_model1_kernel<16, 0, false> : stem_model1_kernel<STEM1_NW, 0, false>;
 }
 
 static int g_stem1_cus = 256;
 hipError_t stem1_init()
 {
     for (int var = 0; var <= 2; ++var)
-        for (int nw : {STEM1_NW, 12, 16}) {
-            hipError_t r = hipFuncSetAttribute((const void*)pick_stem1(nw, var), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (r != hipSuccess) return r;
-        }
+        for (int nw : {STEM1_NW, 12, 16})
+            for (bool yuv : {false, true}) {
+                hipError_t r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (r != hipSuccess) return r;
+            }
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_stem1_cus = cus;
     return hipSuccess;
@@ -693,7 +744,7 @@ hipError_t stem1_init()
 // a.nw: waves per workgroup (8; 12 / 16 = tuning aid ZLY_STEM1_NW); a.var: 2 = persistent workgroups with the next tile's input bytes in flight (default),
 // 1 = one tile per workgroup, 0 = round 3's staging / tap order as well (ZLY_STEM1_VAR, A/B on one box).  Both are read by the engine once per
 // zly_create, not here (a process-static switch cannot be toggled by a test)
-hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s)
+hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yuv)
 {
     Stem1Args a = a0;
     if (a.st.Cout != 16 || a.TH < 1 || a.TW < 1 || a.out1_cs % 8 || a.out1_co % 8) return hipErrorInvalidValue;
@@ -724,11 +775,13 @@ hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s)
         long long wgs = (long long)g_stem1_cus * (long long)((160 * 1024) / lds < 1 ? 1 : (160 * 1024) / lds);
         if (a.pgrid > 0) wgs = a.pgrid;                                                            // tuning aid ZLY_STEM1_GRID (read by the engine per zly_create)
         if (wgs > total) wgs = total;
-        hipLaunchKernelGGL(pick_stem1(nw, var), dim3((unsigned)wgs), dim3(nw * 64), lds, s, a);
+        hipLaunchKernelGGL(pick_stem1(nw, var, yuv), dim3((unsigned)wgs), dim3(nw * 64), lds, s, a);
     } else {
-        hipLaunchKernelGGL(pick_stem1(nw, var), dim3(a.tiles_x * a.tiles_y, n), dim3(nw * 64), lds, s, a);
+        hipLaunchKernelGGL(pick_stem1(nw, var, yuv), dim3(a.tiles_x * a.tiles_y, n), dim3(nw * 64), lds, s, a);
     }
     return hipGetLastError();
 }
+
+#endif  // !ZLY_STEM_YUV_TU
 
 }  // namespace zly

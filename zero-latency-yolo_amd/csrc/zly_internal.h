@@ -11,9 +11,15 @@ typedef __bf16 bf16_t;
 
 // One frame as the preprocess/decode kernels see it.
 struct FrameDesc {
-    unsigned long long src_off;   // byte offset of the frame's first pixel in the source buffer
+    unsigned long long src_off;   // byte offset of the frame's first pixel in the source buffer; the top byte holds the pixel format (ZLY_PIX_*)
     int w, h;                     // request width / height (REQUEST dims: used for box normalisation too)
 };
+// The pixel format rides in the top byte of FrameDesc::src_off (the descriptor stays 16 bytes, one load).  A BGR frame's top byte is 0, so the
+// BGR-only front-kernel instantiations, which are launched on batches without a YUV frame only, read src_off as the plain offset.
+#define ZLY_DESC_FMT_SHIFT 56
+__host__ __device__ __forceinline__ unsigned long long desc_pack(unsigned long long off, int fmt) { return off | ((unsigned long long)fmt << ZLY_DESC_FMT_SHIFT); }
+__host__ __device__ __forceinline__ unsigned long long desc_off(unsigned long long v) { return v & ((1ull << ZLY_DESC_FMT_SHIFT) - 1); }
+__host__ __device__ __forceinline__ int desc_fmt(unsigned long long v) { return (int)(v >> ZLY_DESC_FMT_SHIFT); }
 
 // Implicit-GEMM convolution launch arguments.  All tensors are NHWC, batch-major; a tensor
 // "view" is a channel slice [co, co+C) of a buffer whose pixels are `cs` elements apart, which is
@@ -110,8 +116,9 @@ hipError_t c2f64_init();
 hipError_t launch_c2f64(int mode, const C2fArgs& a, const C2fPlan& plan, hipStream_t s);
 
 // kernels_misc.hip
+// yuv: the batch holds at least one YUV 4:2:0 frame -> the YUV-capable instantiation of the front kernel (it serves the batch's BGR frames too)
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s);
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv = false);
 hipError_t launch_nchw_to_nhwc8(int dtype, const float* in_nchw, void* out_nhwc8, int n, int tw, int th, hipStream_t s);
 hipError_t launch_sppf_pool(int dtype, void* buf, int cs, int c, int n, int H, int W, hipStream_t s, int six_pass = 0);      // six_pass: sppf_pool_kernel also on maps of <= 16 x 16 pixels (tests / A-B)
 hipError_t launch_tap_to_nchw(int dtype, const void* in, int cs, int co, int C, int H, int W, int idx, float* out, hipStream_t s);
@@ -123,7 +130,7 @@ struct StemArgs {
     void* out; int out_cs, out_co;
     int tw, th, Ho, Wo, Cout, tiles_x;
 };
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s);
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv = false);
 int stem_tiles_x(int Wo);
 // preprocess + model.0 + model.1 in one kernel (the stem map stays in LDS); st.out is only written with dump = 1 (debug taps)
 struct Stem1Args {
@@ -143,7 +150,7 @@ struct Stem1Args {
 };
 void       stem1_plan(int H1, int W1, int* th, int* tw);
 hipError_t stem1_init();
-hipError_t launch_stem_model1(const Stem1Args& a, int n, hipStream_t s);
+hipError_t launch_stem_model1(const Stem1Args& a, int n, hipStream_t s, bool yuv = false);
 const int* stem1_tap_slot();              // [9]: k slot of tap ky * 3 + kx in Stem1Args::wgt0p (weights.h: repack_conv's tap_slot)
 
 // kernels_sppf.hip -- SPPF (cv1 -> three 5x5 max pools -> cv2 over the concat) as one kernel; bf16, hidden width 128, maps of up to 176 pixels

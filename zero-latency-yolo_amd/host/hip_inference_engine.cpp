@@ -11,6 +11,11 @@
 #include <cstring>
 #include <random>
 
+// The format-taking submit calls are referenced weakly: a host build against a C ABI without them (the link-time stub of
+// tests/cpp/test_plugin_stub.cpp) still links, and initialize() refuses a YUV ZLY_INPUT_FORMAT when they are missing.
+#pragma weak zly_submit_fmt
+#pragma weak zly_submit_try_fmt
+
 namespace zero_latency {
 
 namespace {
@@ -31,6 +36,16 @@ ErrorCode toErrorCode(int32_t rc)
         case ZLY_ERR_SYSTEM: return ErrorCode::SYSTEM_ERROR;
         default: return ErrorCode::INFERENCE_ERROR;
     }
+}
+// ZLY_INPUT_FORMAT: bgr (default), nv12, i420 (BT.601), nv12_709, i420_709 -> ZLY_PIX_*, -1 = unknown
+int32_t parseInputFormat(const char* v)
+{
+    if (!v || !*v || std::strcmp(v, "bgr") == 0) return ZLY_PIX_BGR;
+    if (std::strcmp(v, "nv12") == 0) return ZLY_PIX_NV12_BT601;
+    if (std::strcmp(v, "i420") == 0) return ZLY_PIX_I420_BT601;
+    if (std::strcmp(v, "nv12_709") == 0) return ZLY_PIX_NV12_BT709;
+    if (std::strcmp(v, "i420_709") == 0) return ZLY_PIX_I420_BT709;
+    return -1;
 }
 int envInt(const char* name, int fallback)
 {
@@ -60,6 +75,14 @@ Result<void> HipInferenceEngine::initialize()
 {
     if (running_) return Result<void>::ok();
     simulate_ = envInt("ZLY_SIMULATE", 0) != 0;               // explicit opt-in only: a missing or bad model file is an ERROR below, never a silent fake
+    // ZLY_INPUT_FORMAT: requests carry YUV 4:2:0 frames (decoder output) instead of packed BGR; request.data must then hold
+    // zly_frame_bytes(format, width, height) bytes, a request of any other size fails alone with INVALID_INPUT
+    input_format_ = parseInputFormat(std::getenv("ZLY_INPUT_FORMAT"));
+    if (input_format_ < 0)
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_INPUT_FORMAT must be bgr, nv12, i420, nv12_709 or i420_709, got '") +
+                                                                 std::getenv("ZLY_INPUT_FORMAT") + "'");
+    if (input_format_ != ZLY_PIX_BGR && (!zly_submit_fmt || !zly_submit_try_fmt))
+        return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_INPUT_FORMAT: the engine library has no zly_submit_fmt");
     const int ndev = simulate_ ? 0 : std::max(1, envInt("ZLY_NUM_DEVICES", 1));
     const int dev0 = std::max(0, envInt("ZLY_FIRST_DEVICE", 0));
     first_device_ = dev0;
@@ -300,12 +323,16 @@ Result<void> HipInferenceEngine::submitInference(const InferenceRequest& request
             for (size_t k = 0; k < ne && rc == ZLY_PENDING; ++k) {
                 p.slot = (first + k) % ne;
                 p.engine = (*snap)[p.slot];
-                rc = zly_submit_try(p.engine->e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
+                rc = input_format_ == ZLY_PIX_BGR
+                         ? zly_submit_try(p.engine->e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket)
+                         : zly_submit_try_fmt(p.engine->e, input_format_, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
             }
             if (rc == ZLY_PENDING) {
                 p.slot = first;
                 p.engine = (*snap)[first];
-                rc = zly_submit(p.engine->e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
+                rc = input_format_ == ZLY_PIX_BGR
+                         ? zly_submit(p.engine->e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket)
+                         : zly_submit_fmt(p.engine->e, input_format_, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
             }
             if (rc != ZLY_OK) { p.failed = true; p.engine.reset(); }
         }

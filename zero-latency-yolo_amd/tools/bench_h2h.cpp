@@ -2,7 +2,11 @@
 // detections in host memory", config 3: >= 8 submitting host threads), measured natively so that no interpreter sits
 // between the threads and the C ABI.  bench.py runs it as a child process and embeds its JSON line.
 //
-//   zly_h2h_bench <weights.zlyw> <cabi|plugin|lone> <threads> <seconds> <max_batch> [engines [w h]]
+//   zly_h2h_bench <weights.zlyw> <cabi|plugin|lone> <threads> <seconds> <max_batch> [engines [w h [format]]]
+//
+// format (bgr, the default, nv12, i420, nv12_709, i420_709): the requests carry YUV 4:2:0 frames (include/zly.h ZLY_PIX_*), the same
+// synthetic frames put through a float BGR -> YUV transform; cabi submits with zly_submit_fmt, plugin / lone set ZLY_INPUT_FORMAT.
+// Without it the output is unchanged (bench.py --full parses it); with it the JSON line is the same and the format is named on stderr.
 //
 // engines > 1: that many engine instances on the GPU (ZLY_FLAG_SINGLE_CHAIN), submitting thread t feeds engine t % engines; their
 // batches overlap on the device (bench.py --engines)
@@ -44,15 +48,49 @@ struct Lat {
     double pct(double p) { if (ms.empty()) return 0; std::sort(ms.begin(), ms.end()); return ms[std::min(ms.size() - 1, (size_t)(p * ms.size()))]; }
 };
 
+// BGR -> YUV 4:2:0 of format fmt (float, limited range, chroma = mean of each 2 x 2 block): only the content of the requests matters here
+static std::vector<uint8_t> toYuv420(const std::vector<uint8_t>& bgr, int W, int H, int32_t fmt)
+{
+    const bool b709 = fmt == ZLY_PIX_NV12_BT709 || fmt == ZLY_PIX_I420_BT709, nv12 = fmt == ZLY_PIX_NV12_BT601 || fmt == ZLY_PIX_NV12_BT709;
+    const double kr = b709 ? 0.2126 : 0.299, kb = b709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
+    std::vector<uint8_t> out(zly_frame_bytes(fmt, W, H));
+    const size_t q = (size_t)(W / 2) * (H / 2);
+    auto u8 = [](double v) { return (uint8_t)std::min(255.0, std::max(0.0, v + 0.5)); };
+    for (int y = 0; y < H; y += 2)
+        for (int x = 0; x < W; x += 2) {
+            double cb = 0, cr = 0;
+            for (int k = 0; k < 4; ++k) {
+                const uint8_t* p = &bgr[((size_t)(y + k / 2) * W + x + k % 2) * 3];
+                const double l = kr * p[2] + kg * p[1] + kb * p[0];
+                out[(size_t)(y + k / 2) * W + x + k % 2] = u8(16.0 + 219.0 / 255.0 * l);
+                cb += 0.25 * (128.0 + 224.0 / 255.0 * (p[0] - l) / (2.0 * (1.0 - kb)));
+                cr += 0.25 * (128.0 + 224.0 / 255.0 * (p[2] - l) / (2.0 * (1.0 - kr)));
+            }
+            const size_t ci = (size_t)(y / 2) * (W / 2) + x / 2;
+            uint8_t* c = out.data() + (size_t)W * H;
+            if (nv12) { c[2 * ci] = u8(cb); c[2 * ci + 1] = u8(cr); }
+            else { c[ci] = u8(cb); c[q + ci] = u8(cr); }
+        }
+    return out;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 6) { std::fprintf(stderr, "usage: %s weights cabi|plugin threads seconds max_batch [w h]\n", argv[0]); return 2; }
+    if (argc < 6) { std::fprintf(stderr, "usage: %s weights cabi|plugin|lone threads seconds max_batch [engines [w h [format]]]\n", argv[0]); return 2; }
     const std::string weights = argv[1], mode = argv[2];
     const int T = std::max(1, atoi(argv[3]));
     const double seconds = atof(argv[4]);
     const int max_batch = std::max(1, atoi(argv[5]));
     const int E = argc > 6 ? std::max(1, atoi(argv[6])) : 1;
     const int W = argc > 8 ? atoi(argv[7]) : 416, H = argc > 8 ? atoi(argv[8]) : 416;
+    const std::string fmt_name = argc > 9 ? argv[9] : "bgr";
+    const int32_t fmt = fmt_name == "bgr" ? ZLY_PIX_BGR : fmt_name == "nv12" ? ZLY_PIX_NV12_BT601 : fmt_name == "i420" ? ZLY_PIX_I420_BT601
+                      : fmt_name == "nv12_709" ? ZLY_PIX_NV12_BT709 : fmt_name == "i420_709" ? ZLY_PIX_I420_BT709 : -1;
+    if (fmt < 0 || zly_frame_bytes(fmt, W, H) == 0) { std::fprintf(stderr, "bad format '%s' for %dx%d\n", fmt_name.c_str(), W, H); return 2; }
+    if (fmt != ZLY_PIX_BGR) {
+        setenv("ZLY_INPUT_FORMAT", fmt_name.c_str(), 1);        // plugin / lone: read by initialize()
+        std::fprintf(stderr, "format: %s (%zu bytes per frame)\n", fmt_name.c_str(), zly_frame_bytes(fmt, W, H));
+    }
     const size_t fb = (size_t)W * H * 3;
 
     std::vector<std::vector<std::vector<uint8_t>>> frames((size_t)T);
@@ -63,6 +101,7 @@ int main(int argc, char** argv)
             f.resize(fb);
             uint32_t* p = reinterpret_cast<uint32_t*>(f.data());
             for (size_t i = 0; i < fb / 4; ++i) p[i] = rng();
+            if (fmt != ZLY_PIX_BGR) f = toYuv420(f, W, H, fmt);
         }
     }
 
@@ -103,7 +142,7 @@ int main(int argc, char** argv)
                     const auto& f = frames[(size_t)t][k++ & 3];
                     uint64_t ticket = 0;
                     const auto ts = Clock::now();
-                    if (zly_submit(g.e, f.data(), f.size(), W, H, &ticket) != ZLY_OK) { if (errors++ == 0) std::fprintf(stderr, "zly_submit: %s\n", zly_last_error()); break; }
+                    if (zly_submit_fmt(g.e, fmt, f.data(), f.size(), W, H, &ticket) != ZLY_OK) { if (errors++ == 0) std::fprintf(stderr, "zly_submit: %s\n", zly_last_error()); break; }
                     submitted++; g.submitted++;
                     { std::lock_guard<std::mutex> lk(g.qmu); g.q.push_back(Item{ticket, ts}); }
                     g.qcv.notify_one();
@@ -157,7 +196,7 @@ int main(int argc, char** argv)
             std::printf("{\"mode\":\"cabi\",\"threads\":%d,\"engines\":%d,\"max_batch\":%d,\"frame\":\"%dx%d\",\"seconds\":%.3f,\"frames\":%llu,\"frames_per_sec\":%.1f,"
                         "\"pcie_h2d_GBps\":%.2f,\"avg_batch\":%.1f,\"p50_ms\":%.3f,\"p99_ms\":%.3f,\"errors\":%llu,\"detections\":%llu,"
                         "\"avg_preprocess_ms_per_frame\":%.5f,\"avg_forward_ms_per_frame\":%.5f,\"avg_postprocess_ms_per_frame\":%.5f}\n",
-                        T, E, max_batch, W, H, dt, (unsigned long long)(end_completed - warm_completed), fps, fps * (double)fb / 1e9,
+                        T, E, max_batch, W, H, dt, (unsigned long long)(end_completed - warm_completed), fps, fps * (double)zly_frame_bytes(fmt, W, H) / 1e9,
                         batches ? (double)count / (double)batches : 0.0, lat.pct(0.5), lat.pct(0.99),
                         (unsigned long long)errors.load(), (unsigned long long)dets_total.load(),
                         sampled ? pre / (double)sampled : 0.0, sampled ? fwd / (double)sampled : 0.0, sampled ? post / (double)sampled : 0.0);
@@ -253,7 +292,7 @@ int main(int argc, char** argv)
     std::printf("{\"mode\":\"plugin\",\"threads\":%d,\"engines\":%d,\"max_batch\":%d,\"frame\":\"%dx%d\",\"seconds\":%.3f,\"frames\":%llu,\"frames_per_sec\":%.1f,"
                 "\"pcie_h2d_GBps\":%.2f,\"p50_ms\":%.3f,\"p99_ms\":%.3f,\"errors\":%llu,\"detections\":%llu,\"batches\":%s,"
                 "\"avg_preprocessing_time_ms\":%s,\"avg_postprocessing_time_ms\":%s}\n",
-                T, E, max_batch, W, H, dt, (unsigned long long)(end_completed - warm_completed), fps, fps * (double)fb / 1e9, lat.pct(0.5), lat.pct(0.99),
+                T, E, max_batch, W, H, dt, (unsigned long long)(end_completed - warm_completed), fps, fps * (double)zly_frame_bytes(fmt, W, H) / 1e9, lat.pct(0.5), lat.pct(0.99),
                 (unsigned long long)errors.load(), (unsigned long long)dets_total.load(), status["batches"].c_str(),
                 status["avg_preprocessing_time_ms"].c_str(), status["avg_postprocessing_time_ms"].c_str());
     return errors ? 4 : 0;

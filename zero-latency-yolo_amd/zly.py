@@ -31,11 +31,14 @@ FLAG_NO_FUSION = 2
 FLAG_NO_HEAD_TENSOR = 4
 FLAG_ASYNC_NMS = 8
 FLAG_SINGLE_CHAIN = 16
+# pixel formats of a request frame (include/zly.h ZLY_PIX_*): packed BGR, or 8-bit YUV 4:2:0 (limited range) converted in the front kernel
+PIX_BGR, PIX_NV12_BT601, PIX_I420_BT601, PIX_NV12_BT709, PIX_I420_BT709 = 0, 1, 2, 3, 4
 
 # every symbol include/zly.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
     "zly_default_config", "zly_create", "zly_destroy", "zly_last_error", "zly_version",
     "zly_detect", "zly_detect_batch", "zly_submit", "zly_submit_try", "zly_poll", "zly_wait", "zly_detect_device", "zly_slab_bytes", "zly_read_slabs", "zly_sync", "zly_join",
+    "zly_frame_bytes", "zly_detect_fmt", "zly_detect_batch_fmt", "zly_submit_fmt", "zly_submit_try_fmt", "zly_detect_device_fmt", "zly_preprocess_fmt",
     "zly_preprocess", "zly_forward", "zly_head_tensor", "zly_postprocess", "zly_debug_tap",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
@@ -109,6 +112,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_sync.argtypes = [vp]; lib.zly_sync.restype = i32
     lib.zly_join.argtypes = [vp, vp, i32]; lib.zly_join.restype = i32
     lib.zly_preprocess.argtypes = [vp, vp, sz, i32, i32, vp]; lib.zly_preprocess.restype = i32
+    lib.zly_frame_bytes.argtypes = [i32, i32, i32]; lib.zly_frame_bytes.restype = sz
+    lib.zly_detect_fmt.argtypes = [vp, i32, vp, sz, i32, i32, vp, i32, pi32]; lib.zly_detect_fmt.restype = i32
+    lib.zly_detect_batch_fmt.argtypes = [vp, i32, pi32, C.POINTER(vp), C.POINTER(sz), pi32, pi32, vp, i32, pi32]; lib.zly_detect_batch_fmt.restype = i32
+    lib.zly_submit_fmt.argtypes = [vp, i32, vp, sz, i32, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_fmt.restype = i32
+    lib.zly_submit_try_fmt.argtypes = [vp, i32, vp, sz, i32, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_try_fmt.restype = i32
+    lib.zly_detect_device_fmt.argtypes = [vp, i32, i32, vp, i32, i32, vp, u32, vp]; lib.zly_detect_device_fmt.restype = i32
+    lib.zly_preprocess_fmt.argtypes = [vp, i32, vp, sz, i32, i32, vp]; lib.zly_preprocess_fmt.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -125,6 +135,20 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
+
+
+def frame_bytes(fmt: int, w: int, h: int) -> int:
+    """bytes of one w x h frame of format fmt (PIX_*): 3wh for BGR, 3wh/2 for YUV 4:2:0; 0 for an unknown format or invalid sizes (host only)"""
+    return int(load_library().zly_frame_bytes(fmt, w, h))
+
+
+def _dims(frame: np.ndarray, fmt: int, w: Optional[int], h: Optional[int]) -> Tuple[int, int]:
+    """(w, h) of a request: BGR frames carry them in their shape ([h][w][3]); a YUV frame is a flat u8 buffer with explicit w, h"""
+    if fmt == PIX_BGR and frame.ndim == 3:
+        return (w if w is not None else frame.shape[1]), (h if h is not None else frame.shape[0])
+    if w is None or h is None:
+        raise ValueError("a YUV frame (1-D u8 buffer) needs explicit w and h")
+    return w, h
 
 
 def _check(lib, rc: int):
@@ -171,38 +195,62 @@ class Engine:
 
     # -- whole path --------------------------------------------------------------------------------
     def detect(self, frame: np.ndarray, cap: Optional[int] = None, nbytes: Optional[int] = None,
-               w: Optional[int] = None, h: Optional[int] = None) -> Tuple[np.ndarray, int]:
-        """frame: u8 [h][w][3] BGR.  -> (detections[min(n,cap)], n)."""
+               w: Optional[int] = None, h: Optional[int] = None, fmt: int = PIX_BGR) -> Tuple[np.ndarray, int]:
+        """frame: u8 [h][w][3] BGR, or (fmt = PIX_NV12_* / PIX_I420_*) a 1-D u8 YUV 4:2:0 buffer with explicit w, h.
+        -> (detections[min(n,cap)], n)."""
         frame = np.ascontiguousarray(frame, dtype=np.uint8)
-        hh, ww = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (h, w)
-        ww = w if w is not None else ww
-        hh = h if h is not None else hh
+        if fmt == PIX_BGR:
+            hh, ww = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (h, w)
+            ww = w if w is not None else ww
+            hh = h if h is not None else hh
+        else:
+            ww, hh = _dims(frame, fmt, w, h)
         cap = cap or self.max_dets
         out = np.zeros(cap, dtype=DET_DTYPE)
         n = C.c_int32(0)
         nb = frame.nbytes if nbytes is None else nbytes
-        _check(self.lib, self.lib.zly_detect(self.h, frame.ctypes.data, nb, ww, hh, out.ctypes.data, cap, C.byref(n)))
+        if fmt == PIX_BGR:
+            _check(self.lib, self.lib.zly_detect(self.h, frame.ctypes.data, nb, ww, hh, out.ctypes.data, cap, C.byref(n)))
+        else:
+            _check(self.lib, self.lib.zly_detect_fmt(self.h, fmt, frame.ctypes.data, nb, ww, hh, out.ctypes.data, cap, C.byref(n)))
         return out[:min(n.value, cap)], n.value
 
-    def detect_batch(self, frames: Sequence[np.ndarray], cap: Optional[int] = None) -> List[Tuple[np.ndarray, int]]:
+    def detect_batch(self, frames: Sequence[np.ndarray], cap: Optional[int] = None, fmt=None,
+                     ws: Optional[Sequence[int]] = None, hs: Optional[Sequence[int]] = None) -> List[Tuple[np.ndarray, int]]:
+        """fmt: None (all BGR), one PIX_* for every frame, or a list with one per frame (formats may mix);
+        ws / hs: the sizes of the YUV frames (BGR frames carry theirs in their shape)"""
         frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
         n = len(frames)
         cap = cap or self.max_dets
         ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         nbytes = (C.c_size_t * n)(*[f.nbytes for f in frames])
-        ws = (C.c_int32 * n)(*[f.shape[1] for f in frames])
-        hs = (C.c_int32 * n)(*[f.shape[0] for f in frames])
         out = np.zeros((n, cap), dtype=DET_DTYPE)
         n_out = (C.c_int32 * n)()
-        _check(self.lib, self.lib.zly_detect_batch(self.h, n, ptrs, nbytes, ws, hs, out.ctypes.data, cap, n_out))
+        if fmt is None:
+            cws = (C.c_int32 * n)(*[f.shape[1] for f in frames])
+            chs = (C.c_int32 * n)(*[f.shape[0] for f in frames])
+            _check(self.lib, self.lib.zly_detect_batch(self.h, n, ptrs, nbytes, cws, chs, out.ctypes.data, cap, n_out))
+        else:
+            fl = [fmt] * n if isinstance(fmt, int) else list(fmt)
+            dims = [_dims(f, fl[i], None if ws is None else ws[i], None if hs is None else hs[i]) for i, f in enumerate(frames)]
+            cws = (C.c_int32 * n)(*[d[0] for d in dims])
+            chs = (C.c_int32 * n)(*[d[1] for d in dims])
+            cfm = (C.c_int32 * n)(*fl)
+            _check(self.lib, self.lib.zly_detect_batch_fmt(self.h, n, cfm, ptrs, nbytes, cws, chs, out.ctypes.data, cap, n_out))
         return [(out[i, :min(n_out[i], cap)], int(n_out[i])) for i in range(n)]
 
     # -- asynchronous, pipelined host-to-host path ---------------------------------------------------
-    def submit(self, frame: np.ndarray, nbytes: Optional[int] = None) -> int:
+    def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
+               w: Optional[int] = None, h: Optional[int] = None) -> int:
         """copies the frame into the engine's pinned staging ring (on this thread) and returns a ticket"""
         t = C.c_uint64(0)
-        _check(self.lib, self.lib.zly_submit(self.h, frame.ctypes.data, frame.nbytes if nbytes is None else nbytes,
-                                             frame.shape[1], frame.shape[0], C.byref(t)))
+        if fmt == PIX_BGR:
+            _check(self.lib, self.lib.zly_submit(self.h, frame.ctypes.data, frame.nbytes if nbytes is None else nbytes,
+                                                 frame.shape[1], frame.shape[0], C.byref(t)))
+        else:
+            ww, hh = _dims(frame, fmt, w, h)
+            _check(self.lib, self.lib.zly_submit_fmt(self.h, fmt, frame.ctypes.data, frame.nbytes if nbytes is None else nbytes,
+                                                     ww, hh, C.byref(t)))
         return t.value
 
     def poll(self, ticket: int) -> bool:
@@ -218,8 +266,13 @@ class Engine:
         _check(self.lib, self.lib.zly_wait(self.h, ticket, out.ctypes.data, cap, C.byref(n)))
         return out[:min(n.value, cap)], n.value
 
-    def detect_device(self, d_frames_ptr: int, n: int, w: int, h: int, d_slabs_ptr: int = 0, tag0: int = 0, stream: int = 0):
-        _check(self.lib, self.lib.zly_detect_device(self.h, n, d_frames_ptr, w, h, d_slabs_ptr or None, tag0, stream or None))
+    def detect_device(self, d_frames_ptr: int, n: int, w: int, h: int, d_slabs_ptr: int = 0, tag0: int = 0, stream: int = 0,
+                      fmt: int = PIX_BGR):
+        """n frames of format fmt in device memory, frame_bytes(fmt, w, h) apart"""
+        if fmt == PIX_BGR:
+            _check(self.lib, self.lib.zly_detect_device(self.h, n, d_frames_ptr, w, h, d_slabs_ptr or None, tag0, stream or None))
+        else:
+            _check(self.lib, self.lib.zly_detect_device_fmt(self.h, fmt, n, d_frames_ptr, w, h, d_slabs_ptr or None, tag0, stream or None))
 
     def sync(self):
         _check(self.lib, self.lib.zly_sync(self.h))
@@ -234,13 +287,18 @@ class Engine:
         return parse_slabs(raw, n, self.max_dets)
 
     # -- stage level -------------------------------------------------------------------------------
-    def preprocess(self, frame: np.ndarray, nbytes: Optional[int] = None, w: Optional[int] = None, h: Optional[int] = None) -> np.ndarray:
+    def preprocess(self, frame: np.ndarray, nbytes: Optional[int] = None, w: Optional[int] = None, h: Optional[int] = None,
+                   fmt: int = PIX_BGR) -> np.ndarray:
         frame = np.ascontiguousarray(frame, dtype=np.uint8)
-        hh = h if h is not None else frame.shape[0]
-        ww = w if w is not None else frame.shape[1]
         out = np.zeros((3, self.model_h, self.model_w), dtype=np.float32)
         nb = frame.nbytes if nbytes is None else nbytes
-        _check(self.lib, self.lib.zly_preprocess(self.h, frame.ctypes.data, nb, ww, hh, out.ctypes.data))
+        if fmt == PIX_BGR:
+            hh = h if h is not None else frame.shape[0]
+            ww = w if w is not None else frame.shape[1]
+            _check(self.lib, self.lib.zly_preprocess(self.h, frame.ctypes.data, nb, ww, hh, out.ctypes.data))
+        else:
+            ww, hh = _dims(frame, fmt, w, h)
+            _check(self.lib, self.lib.zly_preprocess_fmt(self.h, fmt, frame.ctypes.data, nb, ww, hh, out.ctypes.data))
         return out
 
     def forward(self, images_nchw: np.ndarray) -> np.ndarray:
