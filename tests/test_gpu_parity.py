@@ -859,6 +859,28 @@ def test_deferred_nms_same_slabs(weights_path):
     a.close(); b.close()
 
 
+@pytest.mark.parametrize("flags,env", [(0, {}), (zly.FLAG_SINGLE_CHAIN, {}), (zly.FLAG_NO_FUSION, {}), (0, {"ZLY_SPPF_FUSED": "1"})],
+                         ids=["default", "single_chain", "no_fusion", "sppf_fused"])
+def test_launch_introspection_agrees(weights_path, monkeypatch, flags, env):
+    """op_kernels(), launches() and profile_ops() describe the same launches (bench.py's roofline table reads all three): an op is covered
+    by another op's launch exactly when its kernel name is a parenthesised note, every launch that covers ops covers itself, and the
+    per-launch profile books time on exactly the ops that launch"""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    e = zly.Engine(weights_path, max_batch=64, warmup_runs=0, flags=flags)
+    frames = torch.from_numpy(zm.synth_frames(64, 416, 416, seed=17, rects=False)).cuda()
+    torch.cuda.synchronize()
+    for n in (1, 4, 5, 16, 64):
+        kern, lau = e.op_kernels(n), e.launches(n)
+        ms = e.profile_ops(frames.data_ptr(), n, 416, 416, reps=2)
+        for i, (k, li) in enumerate(zip(kern, lau)):
+            by = li["covered_by"]
+            assert (by != i) == k.startswith("("), (n, i, k, by)
+            assert lau[by]["covered_by"] == by, (n, i, k, by)
+            assert (ms[i] == 0) == (by != i), (n, i, k, float(ms[i]))
+    e.close()
+
+
 def test_latency_path_merged_detect_launches(weights_path, oracle, ref_bf16, monkeypatch):
     """Batch <= 4 (the latency path): the three Detect stem convs run as ONE launch and the six box / class branch convs as another
     (conv_igemm_multi_kernel, blockIdx.z picks the conv).  Every conv output and the detections must be those of the per-conv

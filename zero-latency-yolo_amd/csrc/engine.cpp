@@ -85,8 +85,21 @@ struct Op {
     double wbytes = 0;                 // weight + bias bytes of this op (part of `bytes`)
     double cin_frac = 1.0;             // real / stored input channels (the 3-of-8 channel image, the 80-of-96 channel class branch)
     size_t wsk_w = 0;                  // the 80 -> 80 class-branch convs: weights once more, tiled with cin_store = 80 for conv3x3_wsk_kernel (K packed across taps); 0 = none
-    std::map<int, int> wsk_cache;      // batch size -> does that kernel take the launch
-    std::map<int, ConvLaunch> launch_cache;    // batch size -> kernel shape of the per-conv path (conv_pick_config reads the environment: once per shape, not per launch)
+};
+
+// What one op launches at one batch size: a record of the launch table (resolve_launches)
+enum LaunchKind { LK_NONE, LK_PREPROCESS, LK_STEM, LK_STEM1, LK_CONV, LK_CONV_WSK, LK_MULTI, LK_C2F, LK_PAIR, LK_SPPF_FUSED, LK_SPPF_POOL, LK_HEAD, LK_NMS };
+struct Launch {
+    int kind = LK_NONE;                // LK_NONE: the op's work is done inside the launch of op `covered_by`
+    int covered_by = -1;               // index of the op whose launch does this op's work (the op itself when it launches)
+    bool hbm = true;                   // the op's output reaches HBM (false: it stays in LDS inside a fused kernel; zly_debug_tap)
+    ConvLaunch conv{};                 // conv ops: the per-conv kernel shape, also when a fusion covers the op (zly_forward runs model.0 / model.1 on
+                                       // it; the K-packed launch falls back to it)
+    C2fPlan c2f{};                     // LK_C2F
+    PairPlan pair{};                   // LK_PAIR
+    int multi_ct = 0;                  // LK_MULTI: 3 = the three Detect stems, 2 = the six Detect branch convs
+    int only_level = -1;               // LK_HEAD: -1 = all three levels, else that level only
+    bool pool16 = false;               // LK_SPPF_POOL: sppf_pool16_kernel (else sppf_pool_kernel)
 };
 
 struct Ingest;        // pipelined host-to-host path (zly_submit / zly_wait), below
@@ -149,15 +162,14 @@ struct zly_engine {
     bool stem1 = false;               // ... and model.1 (32 channels) as well: the stem map stays in LDS (kernels_stem.hip: stem_model1_kernel)
     Stem1Args stem1a{};
     bool ingest_active = false;       // set while the pipelined host path (zly_submit) enqueues: see run_path
-    bool last_stem1 = false;          // the most recent call ran it (model.0 then only exists in HBM with ZLY_FLAG_DUMP_LOGITS)
+    bool last_front = false;          // the most recent call launched the front kernel (zly_forward does not: model.0 is then in HBM)
     bool front_yuv = false;           // the current call's batch holds a YUV 4:2:0 frame: its front kernel is the YUV-capable instantiation (set by run_path)
     hipStream_t stream = nullptr;
     hipStream_t side[2] = {nullptr, nullptr};     // P3 / P4 Detect branches (forked from and joined to the main stream)
     hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
     std::map<int, hipGraphExec_t> graphs;   // (batch size, fused front, candidate-buffer parity) -> captured forward+decode
     std::map<int, int> graph_failures;      // failed captures per key (a second failure leaves the shape on eager launches)
-    std::map<long, std::pair<bool, C2fPlan>> c2f_plans;     // (c, mode, n, H, W) -> fused C2f tile plan
-    std::map<long, std::pair<bool, PairPlan>> pair_plans;   // (c, n, H, W) -> fused bottleneck tile plan (or "run unfused")
+    std::map<int, std::vector<Launch>> launches;             // batch size -> what every op launches (resolve_launches)
     int last_n = 0;
 
     // production phase timing: every SAMPLE_EVERY-th call of a detect path is bracketed by four timing events
@@ -179,7 +191,7 @@ struct zly_engine {
     std::atomic<Ingest*> ingest{nullptr};   // created by the first zly_submit (under mu), read lock-free afterwards
 
     // tuning / test switches of the environment, read ONCE at zly_create (they used to be read per launch)
-    struct Switches { bool no_c2f = false, no_det_merge = false, no_tail_split = false, no_lanes = false, nms_general = false, no_sppf = false, no_wsk = false, pool_six_pass = false; int stem1_nw = 0, stem1_var = 1, stem1_grid = 0; std::string ablate; } sw;
+    struct Switches { bool no_c2f = false, no_det_merge = false, no_tail_split = false, no_lanes = false, nms_general = false, no_sppf = false, no_wsk = false, pool_six_pass = false; int stem1_nw = 0, stem1_var = 1, stem1_grid = 0, pair_min_tiles = 32, pair_widths = 48; std::string ablate; } sw;
 
     std::mutex mu;                    // serialises every call that touches engine / device state
     mutable std::mutex stats_mu;      // guards `stats` only, never held across a device call: zly_get_stats cannot wait on a batch
@@ -691,48 +703,6 @@ static bool lanes_active(const zly_engine* e, int n)
     return n >= 16 && !e->sw.no_lanes;                               // ZLY_NO_LANES / ZLY_CU_PART: tuning aid; a CU partition runs one chain
 }
 
-// Fused bottleneck pair for this op at batch n?  Only degenerate launches (a handful of tiles) stay on the per-conv
-// kernels.  Same answer for both ops of a pair.
-static const PairPlan* pair_active(zly_engine* e, const Op& op, int n)
-{
-    if (!op.pair || e->dtype != ZLY_DTYPE_BF16 || (e->cfg.flags & ZLY_FLAG_NO_FUSION)) return nullptr;
-    const Buffer& b = e->bufs[(size_t)(op.pair == 1 ? op.in.buf : op.out.buf)];
-    const long key = (((long)op.pair_c * 4096 + n) * 4096 + b.H) * 4096 + b.W;
-    auto it = e->pair_plans.find(key);
-    if (it == e->pair_plans.end()) {
-        PairPlan pl{};
-        const char* mt = getenv("ZLY_PAIR_MIN_TILES");                 // tuning / tests: force the fused kernel onto small launches
-        const int min_tiles = mt ? atoi(mt) : 32;                       // batch 1 (91 / 234 tiles): one fused launch beats two per-conv launches, 4370 -> 4475 fps
-        const char* pw = getenv("ZLY_PAIR_WIDTHS");                   // bit mask of fused widths (16 | 32 | 64), default 16 | 32
-        const int widths = pw ? atoi(pw) : 48;                          // 64: built and tested, but no faster than two launches (below)
-        const bool ok = (widths & op.pair_c) && pair_plan(op.pair_c, n, b.H, b.W, &pl) && pl.total_tiles >= min_tiles;
-        it = e->pair_plans.emplace(key, std::make_pair(ok, pl)).first;
-    }
-    return it->second.first ? &it->second.second : nullptr;
-}
-
-// Fused C2f kernel for the group led by `L` at batch n?  (plan cached per leader and batch size)
-static const C2fPlan* c2f_active(zly_engine* e, const Op& L, int n)
-{
-    if (!L.c2f_mode || e->dtype != ZLY_DTYPE_BF16 || (e->cfg.flags & ZLY_FLAG_NO_FUSION)) return nullptr;
-    if (e->sw.no_c2f) return nullptr;                                       // ZLY_NO_C2F: tuning / tests
-    const Buffer& b = e->bufs[(size_t)L.c2f_cat];
-    const long key = ((((((long)L.c2f_c * 4 + L.c2f_mode) * 16 + L.c2f_nk1) * 16 + L.c2f_nk2) * 4096 + n) * 4096 + b.H) * 4096 + b.W;   // nk1 / nk2: the LDS layout of the 64-channel kernel depends on them
-    auto it = e->c2f_plans.find(key);
-    if (it == e->c2f_plans.end()) {
-        C2fPlan pl{};
-        const bool ok = c2f_plan(L.c2f_c, L.c2f_mode, L.c2f_nk1, L.c2f_nk2, L.c2f_cout2, n, b.H, b.W, &pl);
-        it = e->c2f_plans.emplace(key, std::make_pair(ok, pl)).first;
-    }
-    return it->second.first ? &it->second.second : nullptr;
-}
-
-// is this op's work done by an active fused C2f kernel launched at another op?
-static bool c2f_covered(zly_engine* e, const Op& op, int n)
-{
-    return op.c2f_leader >= 0 && !op.c2f_mode && c2f_active(e, e->ops[(size_t)op.c2f_leader], n) != nullptr;
-}
-
 // launch arguments of a conv op at batch n
 static ConvArgs make_conv_args(zly_engine* e, const Op& op, int n)
 {
@@ -759,101 +729,140 @@ static ConvArgs make_conv_args(zly_engine* e, const Op& op, int n)
     return a;
 }
 
-// kernel shape of the per-conv path for op at batch n: picked once per (op, batch size) -- conv_pick_config reads ~10 environment
-// switches, which the eager path (partial batches of the pipelined host path) used to do for every conv of every call
-static const ConvLaunch& conv_launch_of(zly_engine* e, const Op& op, int n)
+// the fused SPPF kernel's arguments at batch n: model.9.cv1's input and weights, cv2's weights and output, the block's concat buffer
+static SppfArgs make_sppf_args(const zly_engine* e, int n)
 {
-    Op& mop = const_cast<Op&>(op);
-    auto it = mop.launch_cache.find(n);
-    if (it == mop.launch_cache.end()) {
-        const Buffer& ob = e->bufs[(size_t)op.out.buf];
-        const int cin = op.in.C + (op.in2.buf >= 0 ? op.in2.C : 0);
-        ConvLaunch c;
-        conv_pick_config(e->dtype, op.ks, op.stride, cin, op.cout_pad, n, ob.H, ob.W, &c,
-                         op.in2.buf < 0 && op.res.buf < 0 && op.act && !op.out_f32 && op.cout % 32 == 0,
-                         op.in2.buf < 0 && !op.out_f32 && op.act,
-                         op.in2.buf >= 0 && op.ks == 1 && op.res.buf < 0 && op.act && !op.out_f32 && op.cout % 32 == 0 && op.cout_pad == op.cout);
-        it = mop.launch_cache.emplace(n, c).first;
+    const Op& op = e->ops[(size_t)e->sppf_cv1];
+    const Op& o2 = e->ops[(size_t)e->sppf_cv2];
+    const Buffer& ib = e->bufs[(size_t)op.in.buf];
+    const Buffer& cb = e->bufs[(size_t)op.out.buf];     // the block's concat buffer [y | p1 | p2 | p3]
+    const Buffer& ob2 = e->bufs[(size_t)o2.out.buf];
+    const char* wb = (const char*)e->d_weights;
+    SppfArgs sa{};
+    sa.x = ib.ptr; sa.x_cs = ib.C; sa.x_co = op.in.co; sa.Cin = op.in.C;
+    sa.w1 = wb + op.w_off; sa.b1 = (const float*)(wb + op.b_off);
+    sa.w2 = wb + o2.w_off; sa.b2 = (const float*)(wb + o2.b_off);
+    sa.out = ob2.ptr; sa.out_cs = ob2.C; sa.out_co = o2.out.co; sa.Cout = o2.cout;
+    sa.cat = cb.ptr; sa.cat_cs = cb.C;
+    sa.H = cb.H; sa.W = cb.W; sa.n = n; sa.c = op.cout; sa.split = 0;
+    sa.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
+    return sa;
+}
+
+// What every op launches at batch n, in op order: built once per batch size (under e->mu; run_path builds it before it captures that size) and
+// read by run_op, zly_op_kernel_name, zly_launch_info_at, zly_profile_ops and zly_debug_tap, so that what they report is what runs.
+// It describes the detect paths, whose front kernel covers ops[0..2] (preprocess, model.0, model.1) where the stem is fused; zly_forward,
+// which has no frames, runs model.0 and model.1 as generic convs (run_ops).  Where fusions could claim the same op, the first of these takes it:
+// the front kernel, the fused C2f block (over the bottleneck pair inside it), the fused SPPF, the merged Detect convs, the bottleneck pair, the
+// K-packed class-branch conv, the generic conv.
+static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
+{
+    auto it = e->launches.find(n);
+    if (it != e->launches.end()) return it->second;
+    const bool bf16 = e->dtype == ZLY_DTYPE_BF16, fusion = bf16 && !(e->cfg.flags & ZLY_FLAG_NO_FUSION), dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) != 0;
+    const int nops = (int)e->ops.size();
+    // the fused C2f kernel for the group led by op G (ZLY_NO_C2F: tuning / tests)
+    auto c2f_of = [&](const Op& G, C2fPlan* pl) {
+        if (!G.c2f_mode || !fusion || e->sw.no_c2f) return false;
+        const Buffer& b = e->bufs[(size_t)G.c2f_cat];
+        return c2f_plan(G.c2f_c, G.c2f_mode, G.c2f_nk1, G.c2f_nk2, G.c2f_cout2, n, b.H, b.W, pl);
+    };
+    // the fused bottleneck pair at its first conv A.  Only degenerate launches (a handful of tiles) stay on the per-conv kernels: at batch 1
+    // (91 / 234 tiles) one fused launch beats two per-conv launches, 4370 -> 4475 fps.  Width 64 is built and tested, but no faster than two launches.
+    auto pair_of = [&](const Op& A, PairPlan* pl) {
+        if (A.pair != 1 || !fusion || !(e->sw.pair_widths & A.pair_c)) return false;
+        const Buffer& b = e->bufs[(size_t)A.in.buf];
+        return pair_plan(A.pair_c, n, b.H, b.W, pl) && pl->total_tiles >= e->sw.pair_min_tiles;
+    };
+    // SPPF as one launch at model.9.cv1 (opt-in, ZLY_SPPF_FUSED=1); the pool and cv2 then launch nothing
+    bool sppf = fusion && !e->sw.no_sppf && e->sppf_cv1 >= 0;
+    if (sppf) {
+        const Op& a = e->ops[(size_t)e->sppf_cv1];
+        const Op& b = e->ops[(size_t)e->sppf_cv2];
+        sppf = a.act && b.act && a.res.buf < 0 && b.res.buf < 0 && a.in2.buf < 0 && b.in.C == 4 * a.cout && a.cout_pad == a.cout && b.cout_pad == b.cout &&
+               sppf_fused_ok(make_sppf_args(e, n));
     }
-    return it->second;
-}
-
-// Detect convs merged into two launches on the latency path (conv_igemm_multi_kernel): batch <= 4, no side streams in use
-static bool detect_merge_active(zly_engine* e, int n)
-{
-    if (e->dtype != ZLY_DTYPE_BF16 || e->det_stem[0] < 0 || n > 4 || lanes_active(e, n) || e->sw.no_det_merge) return false;
-    return true;
-}
-// role of op index i in the merged Detect launches: 0 none, 1 covered (no launch), 2 launches the three stems, 3 launches the six branch convs
-static int detect_merge_role(const zly_engine* e, int i)
-{
-    for (int l = 0; l < 3; ++l) {
-        if (i == e->det_stem[l]) return l == 2 ? 2 : 1;
-        if (i == e->det_a[l]) return l == 2 ? 3 : 1;
-        if (i == e->det_b[l]) return 1;
-    }
-    return 0;
-}
-
-// the 80 -> 80 class-branch conv on the K-packed weight-stationary kernel at this batch size?  (decided once per op and batch size)
-static bool wsk_active(zly_engine* e, const Op& op, int n)
-{
-    if (!op.wsk_w || e->sw.no_wsk || e->dtype != ZLY_DTYPE_BF16 || !op.act) return false;
-    Op& mop = const_cast<Op&>(op);
-    auto it = mop.wsk_cache.find(n);
-    if (it == mop.wsk_cache.end()) {
-        const Buffer& ob = e->bufs[(size_t)op.out.buf];
-        it = mop.wsk_cache.emplace(n, conv_wsk_ok(80, op.cout, n, ob.H, ob.W) ? 1 : 0).first;
-    }
-    return it->second != 0;
-}
-
-// SPPF as one launch (kernels_sppf.hip) at the block's first op; the pool and cv2 ops then launch nothing
-static bool sppf_active(const zly_engine* e)
-{
-    if (e->dtype != ZLY_DTYPE_BF16 || e->sppf_cv1 < 0 || (e->cfg.flags & ZLY_FLAG_NO_FUSION) || e->sw.no_sppf) return false;
-    const Op& a = e->ops[(size_t)e->sppf_cv1];
-    const Op& b = e->ops[(size_t)e->sppf_cv2];
-    const Buffer& ob = e->bufs[(size_t)b.out.buf];
-    if (!a.act || !b.act || a.res.buf >= 0 || b.res.buf >= 0 || a.in2.buf >= 0 || b.in.C != 4 * a.cout || a.cout_pad != a.cout || b.cout_pad != b.cout) return false;
-    return sppf_fused_ok(a.in.C, a.cout, b.cout, ob.H, ob.W);
-}
-
-// ops that launch nothing at this batch size (second conv of a fused pair; per-level tail ops when one launch covers all)
-static bool op_is_noop(zly_engine* e, const Op& op, int n)
-{
-    if (op.kind == OP_PREPROCESS) return e->stem_fused;                          // detect paths: inside the stem kernel
-    if (op.kind == OP_CONV && e->stem1 && op.name == "model.1") return true;     // detect paths: computed by stem_model1_kernel (booked on model.0)
-    if (op.kind == OP_CONV && c2f_covered(e, op, n)) return true;
-    if ((op.kind == OP_SPPF || (op.kind == OP_CONV && (int)(&op - e->ops.data()) == e->sppf_cv2)) && sppf_active(e)) return true;
-    if (op.kind == OP_CONV && detect_merge_active(e, n) && detect_merge_role(e, (int)(&op - e->ops.data())) == 1) return true;
-    if (op.kind == OP_CONV && op.pair == 2) return pair_active(e, op, n) != nullptr;
-    if (op.kind == OP_HEAD && op.level != 2) return !lanes_active(e, n) || e->sw.no_tail_split;
-    return false;
-}
-
-// Launch groups (bookkeeping for zly_launch_info_at): index of the op whose launch does op i's work at batch n on the detect paths --
-// i itself when it launches, the fused kernel's leader otherwise.
-static int op_covered_by(zly_engine* e, int i, int n)
-{
-    const Op& op = e->ops[(size_t)i];
-    if (op.kind == OP_PREPROCESS) return e->stem_fused ? 1 : i;
-    if (op.kind == OP_CONV) {
-        if (i == 2 && e->stem1) return 1;
-        if (c2f_covered(e, op, n)) return op.c2f_leader;
-        if (i == e->sppf_cv2 && sppf_active(e)) return e->sppf_cv1;
-        if (detect_merge_active(e, n) && detect_merge_role(e, i) == 1) {
-            for (int l = 0; l < 3; ++l) if (i == e->det_stem[l]) return e->det_stem[2];
-            return e->det_a[2];
+    // the Detect convs as two launches on the latency path (conv_igemm_multi_kernel): batch <= 4, no side streams in use.  The launch of the
+    // three stems is booked on the P5 stem, that of the six branch convs on P5's box-branch conv.
+    const bool merge = bf16 && e->det_stem[0] >= 0 && n <= 4 && !lanes_active(e, n) && !e->sw.no_det_merge;
+    auto merged_at = [&](int i) {
+        for (int l = 0; l < 3; ++l) {
+            if (i == e->det_stem[l]) return e->det_stem[2];
+            if (i == e->det_a[l] || i == e->det_b[l]) return e->det_a[2];
         }
-        if (op.pair == 2 && pair_active(e, op, n)) return i - 1;
-        return i;
+        return -1;
+    };
+    // the Detect tail: one launch per level behind its branch convs when the side streams are in use (+0.3 % at batch 64), else one launch of
+    // all levels at the last tail op
+    const bool tail_split = lanes_active(e, n) && !e->sw.no_tail_split;
+    int tail = -1;
+    for (int i = 0; i < nops; ++i) if (e->ops[(size_t)i].kind == OP_HEAD && e->ops[(size_t)i].level == 2) tail = i;
+
+    std::vector<Launch> t((size_t)nops);
+    for (int i = 0; i < nops; ++i) {
+        const Op& op = e->ops[(size_t)i];
+        Launch& L = t[(size_t)i];
+        L.covered_by = i;
+        auto covered = [&](int by) { L.kind = LK_NONE; L.covered_by = by; };
+        switch (op.kind) {
+        case OP_PREPROCESS:
+            if (e->stem_fused) covered(1);
+            else L.kind = LK_PREPROCESS;
+            break;
+        case OP_SPPF: {
+            const Buffer& b = e->bufs[(size_t)op.in.buf];
+            if (sppf) covered(e->sppf_cv1);
+            else { L.kind = LK_SPPF_POOL; L.pool16 = sppf_pool16_ok(e->dtype, b.C, op.c, n, b.H, b.W, e->sw.pool_six_pass ? 1 : 0); }
+            break;
+        }
+        case OP_HEAD:
+            if (tail_split || op.level == 2) { L.kind = LK_HEAD; L.only_level = tail_split ? op.level : -1; }
+            else covered(tail);
+            break;
+        case OP_NMS:
+            L.kind = LK_NMS;
+            break;
+        case OP_CONV: {
+            const Buffer& ob = e->bufs[(size_t)op.out.buf];
+            const int cin = op.in.C + (op.in2.buf >= 0 ? op.in2.C : 0);
+            conv_pick_config(e->dtype, op.ks, op.stride, cin, op.cout_pad, n, ob.H, ob.W, &L.conv,
+                             op.in2.buf < 0 && op.res.buf < 0 && op.act && !op.out_f32 && op.cout % 32 == 0,
+                             op.in2.buf < 0 && !op.out_f32 && op.act,
+                             op.in2.buf >= 0 && op.ks == 1 && op.res.buf < 0 && op.act && !op.out_f32 && op.cout % 32 == 0 && op.cout_pad == op.cout);
+            C2fPlan cp{};
+            PairPlan pp{};
+            if (i == 1 && e->stem_fused) {
+                L.kind = e->stem1 ? LK_STEM1 : LK_STEM;
+                L.hbm = !e->stem1 || dump;                                  // stem_model1_kernel keeps the stem map in LDS
+            } else if (i == 2 && e->stem1) {
+                covered(1);
+            } else if (op.c2f_leader >= 0 && c2f_of(e->ops[(size_t)op.c2f_leader], &cp)) {
+                if (op.c2f_leader == i) { L.kind = LK_C2F; L.c2f = cp; }
+                else covered(op.c2f_leader);
+                L.hbm = op.c2f_vis == 0 || (op.c2f_vis == 1 && dump);
+            } else if (sppf && i == e->sppf_cv1) {
+                L.kind = LK_SPPF_FUSED;
+                L.hbm = dump;
+            } else if (sppf && i == e->sppf_cv2) {
+                covered(e->sppf_cv1);
+            } else if (merge && merged_at(i) >= 0) {
+                if (merged_at(i) == i) { L.kind = LK_MULTI; L.multi_ct = i == e->det_stem[2] ? 3 : 2; }
+                else covered(merged_at(i));
+            } else if (pair_of(op, &pp)) {
+                L.kind = LK_PAIR; L.pair = pp;
+                L.hbm = false;                                              // the intermediate map stays in LDS
+            } else if (op.pair == 2 && pair_of(e->ops[(size_t)i - 1], &pp)) {
+                covered(i - 1);
+            } else if (op.wsk_w && !e->sw.no_wsk && bf16 && op.act && conv_wsk_ok(80, op.cout, n, ob.H, ob.W)) {
+                L.kind = LK_CONV_WSK;
+            } else {
+                L.kind = LK_CONV;
+            }
+            break;
+        }
+        }
     }
-    if (op.kind == OP_SPPF && sppf_active(e)) return e->sppf_cv1;
-    if (op.kind == OP_HEAD && op_is_noop(e, op, n)) {
-        for (size_t k = 0; k < e->ops.size(); ++k) if (e->ops[k].kind == OP_HEAD && e->ops[k].level == 2) return (int)k;
-    }
-    return i;
+    return e->launches.emplace(n, std::move(t)).first->second;
 }
 
 // channel ranges an op reads / writes, as (buffer, first channel, channels, pixels per frame, scale) records
@@ -890,117 +899,105 @@ static void op_writes(const zly_engine* e, const Op& op, std::vector<IoView>* ou
     }
 }
 
-static hipError_t run_op(zly_engine* e, const Op& op, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s)
+// launches what the launch table says op i launches at batch n (nothing for LK_NONE)
+static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s)
 {
-    switch (op.kind) {
-    case OP_PREPROCESS:
+    const Op& op = e->ops[i];
+    const char* wb = (const char*)e->d_weights;
+    switch (L.kind) {
+    case LK_NONE:
+        return hipSuccess;
+    case LK_PREPROCESS:
         return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front_yuv);
-    case OP_CONV: {
-        const Buffer& ib = e->bufs[(size_t)op.in.buf];
-        if (c2f_covered(e, op, n)) return hipSuccess;               // computed by the fused C2f kernel launched at its leader
-        if (sppf_active(e)) {
-            const int oi = (int)(&op - e->ops.data());
-            if (oi == e->sppf_cv2) return hipSuccess;               // computed by the fused SPPF kernel launched at model.9.cv1
-            if (oi == e->sppf_cv1) {
-                const Op& o2 = e->ops[(size_t)e->sppf_cv2];
-                const Buffer& cb = e->bufs[(size_t)op.out.buf];     // the block's concat buffer [y | p1 | p2 | p3]
-                const Buffer& ob2 = e->bufs[(size_t)o2.out.buf];
-                const char* wb = (const char*)e->d_weights;
-                SppfArgs sa{};
-                sa.x = ib.ptr; sa.x_cs = ib.C; sa.x_co = op.in.co; sa.Cin = op.in.C;
-                sa.w1 = wb + op.w_off; sa.b1 = (const float*)(wb + op.b_off);
-                sa.w2 = wb + o2.w_off; sa.b2 = (const float*)(wb + o2.b_off);
-                sa.out = ob2.ptr; sa.out_cs = ob2.C; sa.out_co = o2.out.co; sa.Cout = o2.cout;
-                sa.cat = cb.ptr; sa.cat_cs = cb.C;
-                sa.H = cb.H; sa.W = cb.W; sa.n = n; sa.c = op.cout; sa.split = 0;
-                sa.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
-                return launch_sppf_fused(sa, s);
-            }
-        }
-        if (detect_merge_active(e, n)) {
-            const int role = detect_merge_role(e, (int)(&op - e->ops.data()));
-            if (role == 1) return hipSuccess;
-            if (role == 2 || role == 3) {
-                ConvArgsMulti m{};
-                for (int l = 0; l < 3; ++l) {
-                    if (role == 2) m.a[m.n++] = make_conv_args(e, e->ops[(size_t)e->det_stem[l]], n);
-                    else { m.a[m.n++] = make_conv_args(e, e->ops[(size_t)e->det_a[l]], n); m.a[m.n++] = make_conv_args(e, e->ops[(size_t)e->det_b[l]], n); }
-                }
-                return launch_conv_multi(m, role == 2 ? 3 : 2, s);
-            }
-        }
-        if (const C2fPlan* pl = c2f_active(e, op, n)) {
-            const Buffer& cb = e->bufs[(size_t)op.c2f_cat];
-            const Buffer& xb = e->bufs[(size_t)op.c2f_x.buf];
-            const Buffer& ob2 = e->bufs[(size_t)op.c2f_out.buf];
-            const char* wb = (const char*)e->d_weights;
-            C2fArgs ca{};
-            ca.x = xb.ptr; ca.x_cs = xb.C; ca.x_co = op.c2f_x.co;
-            if (op.c2f_x2.buf >= 0) {
-                const Buffer& x2 = e->bufs[(size_t)op.c2f_x2.buf];
-                ca.x2 = x2.ptr; ca.x2_cs = x2.C; ca.x2_co = op.c2f_x2.co; ca.split_c = op.c2f_x.C;
-            }
-            ca.w1 = wb + op.c2f_w1; ca.b1 = (const float*)(wb + op.c2f_b1); ca.nk1 = op.c2f_nk1;
-            ca.cat = cb.ptr; ca.cat_cs = cb.C; ca.pair_in_co = op.c2f_in_co; ca.pair_out_co = op.c2f_out_co;
-            ca.wA = wb + op.c2f_wA; ca.bA = (const float*)(wb + op.c2f_bA); ca.wB = wb + op.c2f_wB; ca.bB = (const float*)(wb + op.c2f_bB);
-            ca.res = op.c2f_res;
-            ca.w2 = wb + op.c2f_w2; ca.b2 = (const float*)(wb + op.c2f_b2); ca.nk2 = op.c2f_nk2; ca.Cout2 = op.c2f_cout2;
-            ca.out = ob2.ptr; ca.out_cs = ob2.C; ca.out_co = op.c2f_out.co;
-            ca.H = cb.H; ca.W = cb.W; ca.n = n;
-            ca.TH = pl->th; ca.TW = pl->tw; ca.tiles_x = pl->tiles_x; ca.tiles_y = pl->tiles_y; ca.total_tiles = pl->total_tiles;
-            ca.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
-            if (op.c2f_c == 64 && op.c2f_mid.buf >= 0) { const Buffer& mb = e->bufs[(size_t)op.c2f_mid.buf]; ca.mid = mb.ptr; ca.mid_cs = mb.C; }
-            return launch_c2f(op.c2f_c, op.c2f_mode, ca, *pl, s);
-        }
-        if (op.pair) {
-            const PairPlan* pl = pair_active(e, op, n);
-            if (pl && op.pair == 2) return hipSuccess;             // computed by the pair kernel launched at the first conv
-            if (pl) {
-                const Buffer& pb = e->bufs[(size_t)op.pair_out.buf];
-                PairArgs pa;
-                pa.in = ib.ptr; pa.in_cs = ib.C; pa.in_co = op.in.co;
-                pa.out = pb.ptr; pa.out_cs = pb.C; pa.out_co = op.pair_out.co;
-                pa.wA = (const char*)e->d_weights + op.pair_wA; pa.bA = (const float*)((const char*)e->d_weights + op.pair_bA);
-                pa.wB = (const char*)e->d_weights + op.pair_wB; pa.bB = (const float*)((const char*)e->d_weights + op.pair_bB);
-                pa.H = ib.H; pa.W = ib.W; pa.n = n;
-                pa.TH = pl->th; pa.TW = pl->tw; pa.tiles_x = pl->tiles_x; pa.tiles_y = pl->tiles_y; pa.total_tiles = pl->total_tiles;
-                pa.res = op.pair_res;
-                return launch_pair(op.pair_c, pa, *pl, s);
-            }
-        }
-        ConvArgs a = make_conv_args(e, op, n);
-        if (wsk_active(e, op, n)) {
+    case LK_STEM: {
+        StemArgs st = e->stem;
+        st.src = d_src; st.desc = e->d_desc;
+        return launch_stem_fused(st, n, s, e->front_yuv);
+    }
+    case LK_STEM1: {
+        Stem1Args st = e->stem1a;
+        st.st.src = d_src; st.st.desc = e->d_desc;
+        return launch_stem_model1(st, n, s, e->front_yuv);
+    }
+    case LK_CONV:
+    case LK_CONV_WSK: {
+        const ConvArgs a = make_conv_args(e, op, n);
+        if (L.kind == LK_CONV_WSK) {
             ConvArgs k = a;
             k.Cin = 80; k.K = 9 * 80; k.nk = 23; k.cout_pad = 80;
-            k.wgt = (const char*)e->d_weights + op.wsk_w;
+            k.wgt = wb + op.wsk_w;
             const hipError_t r = launch_conv_wsk(k, s);
             if (r != hipErrorInvalidValue) return r;             // a tensor beyond the kernel's 32-bit offsets takes the generic path below
         }
-        return launch_conv(e->dtype, a, conv_launch_of(e, op, n), s);
+        return launch_conv(e->dtype, a, L.conv, s);
     }
-    case OP_SPPF: {
-        if (sppf_active(e)) return hipSuccess;                       // inside the fused SPPF kernel
+    case LK_MULTI: {
+        ConvArgsMulti m{};
+        for (int l = 0; l < 3; ++l) {
+            if (L.multi_ct == 3) m.a[m.n++] = make_conv_args(e, e->ops[(size_t)e->det_stem[l]], n);
+            else { m.a[m.n++] = make_conv_args(e, e->ops[(size_t)e->det_a[l]], n); m.a[m.n++] = make_conv_args(e, e->ops[(size_t)e->det_b[l]], n); }
+        }
+        return launch_conv_multi(m, L.multi_ct, s);
+    }
+    case LK_C2F: {
+        const C2fPlan* pl = &L.c2f;
+        const Buffer& cb = e->bufs[(size_t)op.c2f_cat];
+        const Buffer& xb = e->bufs[(size_t)op.c2f_x.buf];
+        const Buffer& ob2 = e->bufs[(size_t)op.c2f_out.buf];
+        C2fArgs ca{};
+        ca.x = xb.ptr; ca.x_cs = xb.C; ca.x_co = op.c2f_x.co;
+        if (op.c2f_x2.buf >= 0) {
+            const Buffer& x2 = e->bufs[(size_t)op.c2f_x2.buf];
+            ca.x2 = x2.ptr; ca.x2_cs = x2.C; ca.x2_co = op.c2f_x2.co; ca.split_c = op.c2f_x.C;
+        }
+        ca.w1 = wb + op.c2f_w1; ca.b1 = (const float*)(wb + op.c2f_b1); ca.nk1 = op.c2f_nk1;
+        ca.cat = cb.ptr; ca.cat_cs = cb.C; ca.pair_in_co = op.c2f_in_co; ca.pair_out_co = op.c2f_out_co;
+        ca.wA = wb + op.c2f_wA; ca.bA = (const float*)(wb + op.c2f_bA); ca.wB = wb + op.c2f_wB; ca.bB = (const float*)(wb + op.c2f_bB);
+        ca.res = op.c2f_res;
+        ca.w2 = wb + op.c2f_w2; ca.b2 = (const float*)(wb + op.c2f_b2); ca.nk2 = op.c2f_nk2; ca.Cout2 = op.c2f_cout2;
+        ca.out = ob2.ptr; ca.out_cs = ob2.C; ca.out_co = op.c2f_out.co;
+        ca.H = cb.H; ca.W = cb.W; ca.n = n;
+        ca.TH = pl->th; ca.TW = pl->tw; ca.tiles_x = pl->tiles_x; ca.tiles_y = pl->tiles_y; ca.total_tiles = pl->total_tiles;
+        ca.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
+        if (op.c2f_c == 64 && op.c2f_mid.buf >= 0) { const Buffer& mb = e->bufs[(size_t)op.c2f_mid.buf]; ca.mid = mb.ptr; ca.mid_cs = mb.C; }
+        return launch_c2f(op.c2f_c, op.c2f_mode, ca, *pl, s);
+    }
+    case LK_PAIR: {
+        const PairPlan* pl = &L.pair;
+        const Buffer& ib = e->bufs[(size_t)op.in.buf];
+        const Buffer& pb = e->bufs[(size_t)op.pair_out.buf];
+        PairArgs pa;
+        pa.in = ib.ptr; pa.in_cs = ib.C; pa.in_co = op.in.co;
+        pa.out = pb.ptr; pa.out_cs = pb.C; pa.out_co = op.pair_out.co;
+        pa.wA = wb + op.pair_wA; pa.bA = (const float*)(wb + op.pair_bA);
+        pa.wB = wb + op.pair_wB; pa.bB = (const float*)(wb + op.pair_bB);
+        pa.H = ib.H; pa.W = ib.W; pa.n = n;
+        pa.TH = pl->th; pa.TW = pl->tw; pa.tiles_x = pl->tiles_x; pa.tiles_y = pl->tiles_y; pa.total_tiles = pl->total_tiles;
+        pa.res = op.pair_res;
+        return launch_pair(op.pair_c, pa, *pl, s);
+    }
+    case LK_SPPF_FUSED:
+        return launch_sppf_fused(make_sppf_args(e, n), s);
+    case LK_SPPF_POOL: {
         const Buffer& b = e->bufs[(size_t)op.in.buf];
         return launch_sppf_pool(e->dtype, b.ptr, b.C, op.c, n, b.H, b.W, s, e->sw.pool_six_pass ? 1 : 0);
     }
-    case OP_HEAD: {
+    case LK_HEAD: {
         HeadArgs h = op.head;
-        if (lanes_active(e, n) && !e->sw.no_tail_split) h.only_level = op.level;       // per-level launches (+0.3 % at batch 64)
-        else if (op.level != 2) return hipSuccess;          // the last tail op covers all levels
-        else h.only_level = -1;
+        h.only_level = L.only_level;
         h.head = (e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) ? nullptr : e->d_head; h.desc = e->d_desc; h.conf_thr = e->cfg.conf_thr; h.cand = e->cur_cand; h.cand_count = e->cur_count;
         return launch_head_fused(e->dtype, h, n, s);
     }
-    case OP_NMS:
+    case LK_NMS:
         return launch_nms(e->cur_cand, e->cur_count, e->N, n, e->cfg.iou_thr, e->nc, e->d_scratch,
                           d_slabs_out ? d_slabs_out : e->d_slabs, e->cfg.max_dets, tag0, s, e->sw.nms_general ? 1 : 0);
     }
     return hipErrorInvalidValue;
 }
 
-// ops [first, last) -- the graph-capturable middle of the path is [1, ops.size()-1).  Side-lane ops are
+// ops [first, last) of the launch table `tab` -- the graph-capturable middle of the path is [1, ops.size()-1).  Side-lane ops are
 // launched on the engine's side streams behind a fork event; the Detect tail (OP_HEAD) joins them.
-static hipError_t run_ops(zly_engine* e, size_t first, size_t last, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s)
+static hipError_t run_ops(zly_engine* e, const std::vector<Launch>& tab, size_t first, size_t last, int n, hipStream_t s)
 {
     bool forked[3] = {false, false, false};
     hipError_t r = hipSuccess;
@@ -1035,7 +1032,10 @@ static hipError_t run_ops(zly_engine* e, size_t first, size_t last, int n, const
 #ifdef ZLY_DIAG         // diagnostic build only (libzly_diag.so): a shipped engine cannot be told to skip launches
         if (!e->sw.ablate.empty() && e->sw.ablate.find("," + op.name + ",") != std::string::npos) continue;
 #endif
-        r = run_op(e, op, n, d_src, d_slabs_out, tag0, st);
+        // zly_forward has no frames: the convs the front kernel covers on the detect paths (model.0, model.1) run as generic convs
+        const int by = tab[(size_t)tab[i].covered_by].kind;
+        if (op.kind == OP_CONV && (by == LK_STEM || by == LK_STEM1)) { Launch g = tab[i]; g.kind = LK_CONV; r = run_op(e, i, g, n, nullptr, nullptr, 0, st); }
+        else r = run_op(e, i, tab[i], n, nullptr, nullptr, 0, st);
     }
     if (r == hipSuccess) join_all();
     return r;
@@ -1127,28 +1127,22 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
     }
     e->cur_cand = par ? e->d_cand_alt : e->d_cand;
     e->cur_count = par ? e->d_count_alt : e->d_count;
-    // ops[0] = preprocess, ops[1] = model.0.  On the detect paths of the bf16 engine both are ONE kernel
-    // (kernels_stem.hip); zly_forward (caller-supplied fp32 images) keeps the generic model.0 conv.
-    const bool fused = with_pre && e->stem_fused;
+    // The front kernel -- preprocess, or on the bf16 engine preprocess + model.0 [+ model.1] as ONE kernel (kernels_stem.hip) -- is the
+    // launch of ops[0] or ops[1]; the middle starts at the first op it does not cover.  zly_forward (caller-supplied fp32 images) launches
+    // no front kernel and starts at model.0.
+    const std::vector<Launch>& tab = resolve_launches(e, n);
+    const size_t front = (size_t)tab[0].covered_by;
     size_t first = 1;
     if (sample) HIP_TRY(hipEventRecord(e->ev_t[0], s), ZLY_ERR_INFERENCE);
-    e->last_stem1 = fused && e->stem1;
-    if (fused && e->stem1) {
-        Stem1Args st = e->stem1a;
-        st.st.src = d_src; st.st.desc = e->d_desc;
+    if (with_pre) {
 #ifdef ZLY_DIAG
-        if (e->sw.ablate.find(",stem,") != std::string::npos) { /* ZLY_ABLATE_SKIP=stem (libzly_diag.so only) */ } else
+        if (tab[front].kind == LK_STEM1 && e->sw.ablate.find(",stem,") != std::string::npos) { /* ZLY_ABLATE_SKIP=stem (libzly_diag.so only) */ } else
 #endif
-        HIP_TRY(launch_stem_model1(st, n, s, e->front_yuv), ZLY_ERR_INFERENCE);
-        first = 3;
-    } else if (fused) {
-        StemArgs st = e->stem;
-        st.src = d_src; st.desc = e->d_desc;
-        HIP_TRY(launch_stem_fused(st, n, s, e->front_yuv), ZLY_ERR_INFERENCE);
-        first = 2;
-    } else if (with_pre) {
-        HIP_TRY(run_op(e, e->ops[0], n, d_src, nullptr, 0, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(run_op(e, front, tab[front], n, d_src, nullptr, 0, s), ZLY_ERR_INFERENCE);
+        for (first = front + 1; tab[first].covered_by == (int)front; ++first) {}
     }
+    e->last_front = with_pre;
+    const bool fused = with_pre && front > 0;
     if (sample) HIP_TRY(hipEventRecord(e->ev_t[1], s), ZLY_ERR_INFERENCE);
     // Graph replay.  Graphs are captured at zly_create for batch 1 and max_batch (warm_batch) and, on the synchronous entry points, on the
     // first call of any other batch size.  The pipelined host path (dispatcher threads, several per process) never captures: it replays
@@ -1169,7 +1163,7 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
             ExclusiveGate x;
             hipError_t r = hipStreamBeginCapture(e->stream, hipStreamCaptureModeRelaxed);
             if (r == hipSuccess) {
-                r = run_ops(e, first, nops - 1, n, nullptr, nullptr, 0, e->stream);
+                r = run_ops(e, tab, first, nops - 1, n, e->stream);
                 hipError_t r2 = hipStreamEndCapture(e->stream, &g);
                 if (r == hipSuccess) r = r2;
             }
@@ -1185,7 +1179,7 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
         HIP_TRY(hipGraphLaunch(git->second, s), ZLY_ERR_INFERENCE);
         with_stats(e, [](zly_stats& st) { st.graph_replays++; });
     } else {
-        HIP_TRY(run_ops(e, first, nops - 1, n, nullptr, nullptr, 0, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(run_ops(e, tab, first, nops - 1, n, s), ZLY_ERR_INFERENCE);
         with_stats(e, [](zly_stats& st) { st.eager_batches++; });
     }
     if (sample) HIP_TRY(hipEventRecord(e->ev_t[2], s), ZLY_ERR_INFERENCE);
@@ -1194,11 +1188,11 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
         ns = e->nms_stream;
         HIP_TRY(hipEventRecord(e->ev_head, s), ZLY_ERR_INFERENCE);
         HIP_TRY(hipStreamWaitEvent(e->nms_stream, e->ev_head, 0), ZLY_ERR_INFERENCE);
-        HIP_TRY(run_op(e, e->ops[nops - 1], n, nullptr, d_slabs_out, tag0, e->nms_stream), ZLY_ERR_INFERENCE);
+        HIP_TRY(run_op(e, nops - 1, tab[nops - 1], n, nullptr, d_slabs_out, tag0, e->nms_stream), ZLY_ERR_INFERENCE);
         HIP_TRY(hipEventRecord(e->ev_nms[par], e->nms_stream), ZLY_ERR_INFERENCE);
         e->nms_recorded[par] = true; e->last_async = par; e->parity = par ^ 1;
     } else {
-        HIP_TRY(run_op(e, e->ops[nops - 1], n, nullptr, d_slabs_out, tag0, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(run_op(e, nops - 1, tab[nops - 1], n, nullptr, d_slabs_out, tag0, s), ZLY_ERR_INFERENCE);
     }
     if (sample) {
         HIP_TRY(hipEventRecord(e->ev_t[3], ns), ZLY_ERR_INFERENCE);
@@ -1771,6 +1765,8 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
     if (const char* v = getenv("ZLY_STEM1_NW")) e->sw.stem1_nw = atoi(v);           // tuning aids: waves per workgroup of the front kernel (12 / 16), ...
     if (const char* v = getenv("ZLY_STEM1_GRID")) e->sw.stem1_grid = atoi(v);       // ... workgroups of its persistent grid ...
     if (const char* v = getenv("ZLY_STEM1_VAR")) e->sw.stem1_var = atoi(v);         // ... and 0 = round 3's staging / tap order (A/B on one box)
+    if (const char* v = getenv("ZLY_PAIR_MIN_TILES")) e->sw.pair_min_tiles = atoi(v);   // tuning / tests: force the fused bottleneck pair onto small launches
+    if (const char* v = getenv("ZLY_PAIR_WIDTHS")) e->sw.pair_widths = atoi(v);         // bit mask of fused pair widths (16 | 32 | 64)
     std::string err;
     int rc = load_zlyw(e->weights_path.c_str(), &e->model, &err);        // host only: file parse
     if (rc != ZLY_OK) { delete e; return fail(rc, err); }
@@ -2226,16 +2222,22 @@ int32_t zly_debug_tap(zly_engine* e, const char* name, int32_t idx, float* out, 
         auto jt = e->tap_final.find(name);
         if (it != e->tap_index.end()) {
             const Op& op = e->ops[(size_t)it->second.first];
-            if (e->last_stem1 && op.name == "model.0" && !(e->cfg.flags & ZLY_FLAG_DUMP_LOGITS))
-                return fail(ZLY_ERR_INVALID_ARGUMENT, "tap model.0 stays in LDS inside the fused stem kernel; create the engine with ZLY_FLAG_DUMP_LOGITS (or ZLY_FLAG_NO_FUSION)");
-            if (e->last_n > 0 && op.c2f_leader >= 0 && c2f_active(e, e->ops[(size_t)op.c2f_leader], e->last_n) &&
-                (op.c2f_vis == 2 || (op.c2f_vis == 1 && !(e->cfg.flags & ZLY_FLAG_DUMP_LOGITS))))
+            // where the last call left the op's output: the launch table of its batch size (no call yet: every buffer is in HBM)
+            const std::vector<Launch>* t = e->last_n > 0 ? &resolve_launches(e, e->last_n) : nullptr;
+            const Launch* L = t ? &(*t)[(size_t)it->second.first] : nullptr;
+            switch (L && !L->hbm ? (*t)[(size_t)L->covered_by].kind : LK_NONE) {
+            case LK_STEM1:
+                if (e->last_front)
+                    return fail(ZLY_ERR_INVALID_ARGUMENT, "tap model.0 stays in LDS inside the fused stem kernel; create the engine with ZLY_FLAG_DUMP_LOGITS (or ZLY_FLAG_NO_FUSION)");
+                break;
+            case LK_C2F:
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused C2f kernel at this batch size; create the engine with " +
                                                           (op.c2f_vis == 1 ? "ZLY_FLAG_DUMP_LOGITS or " : "") + "ZLY_FLAG_NO_FUSION");
-            if (it->second.first == e->sppf_cv1 && sppf_active(e) && !(e->cfg.flags & ZLY_FLAG_DUMP_LOGITS))
+            case LK_SPPF_FUSED:
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused SPPF kernel; create the engine with ZLY_FLAG_DUMP_LOGITS or ZLY_FLAG_NO_FUSION");
-            if (op.pair == 1 && e->last_n > 0 && pair_active(e, op, e->last_n))
+            case LK_PAIR:
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused bottleneck kernel at this batch size; create the engine with ZLY_FLAG_NO_FUSION");
+            }
             buf = op.out.buf; co = op.out.co + op.tap_co[(size_t)it->second.second]; C = op.tap_c[(size_t)it->second.second];
             f32 = op.out_f32 != 0;
         } else if (jt != e->tap_final.end()) {
@@ -2281,43 +2283,36 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
 {
     if (!e || !out || cap < 8 || i < 0 || i >= (int32_t)e->ops.size() || n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
     std::lock_guard<std::mutex> lk(e->mu);
+    const std::vector<Launch>& t = resolve_launches(e, n);
+    const Launch& L = t[(size_t)i];
     const Op& op = e->ops[(size_t)i];
     std::string k;
-    switch (op.kind) {
-    case OP_PREPROCESS: k = e->stem_fused ? "(fused into stem_fused_kernel)" : "preprocess_kernel"; break;
-    case OP_SPPF: {
-        const Buffer& pb = e->bufs[(size_t)op.in.buf];
-        k = sppf_active(e) ? "(fused into the SPPF kernel at model.9.cv1)"
-          : (e->dtype == ZLY_DTYPE_BF16 && pb.H <= 16 && pb.W <= 16 && !e->sw.pool_six_pass && n <= 16) ? "sppf_pool16_kernel<DPP row windows, one barrier>" : "sppf_pool_kernel";
+    switch (L.kind) {
+    case LK_NONE:
+        switch (t[(size_t)L.covered_by].kind) {
+        case LK_STEM: case LK_STEM1: k = op.kind == OP_PREPROCESS ? "(fused into stem_fused_kernel)" : "(fused into the previous launch)"; break;
+        case LK_PAIR: k = "(fused into the previous launch)"; break;
+        case LK_C2F: k = "(fused into the C2f kernel at " + e->ops[(size_t)L.covered_by].name + ")"; break;
+        case LK_SPPF_FUSED: k = "(fused into the SPPF kernel at model.9.cv1)"; break;
+        case LK_MULTI: k = "(in a merged Detect launch)"; break;
+        case LK_HEAD: k = "(covered by the last tail launch)"; break;
+        }
         break;
-    }
-    case OP_HEAD: k = op_is_noop(e, op, n) ? "(covered by the last tail launch)" : "head_fused_kernel"; break;
-    case OP_NMS: k = "nms_kernel"; break;
-    case OP_CONV: {
-        if (i == 1 && e->stem1) { k = "stem_model1_kernel (preprocess+model.0+model.1)"; break; }
-        if (i == 2 && e->stem1) { k = "(fused into the previous launch)"; break; }
-        if (i == 1 && e->stem_fused) { k = "stem_fused_kernel"; break; }
-        if (sppf_active(e) && (i == e->sppf_cv1 || i == e->sppf_cv2)) {
-            k = i == e->sppf_cv2 ? std::string("(fused into the SPPF kernel at model.9.cv1)")
-                                 : "sppf_fused_kernel<cv1+3 pools+cv2,SPLIT=" + std::to_string(sppf_split(e->ops[(size_t)e->sppf_cv2].cout, n)) + ">";
-            break;
-        }
-        if (detect_merge_active(e, n) && detect_merge_role(e, i)) {
-            const int role = detect_merge_role(e, i);
-            k = role == 1 ? "(in a merged Detect launch)" : role == 2 ? "conv_igemm_multi_kernel<CT=3> (the 3 Detect stems)" : "conv_igemm_multi_kernel<CT=2> (the 6 Detect branch convs)";
-            break;
-        }
-        if (c2f_covered(e, op, n)) { k = "(fused into the C2f kernel at " + op.c2f_leader_name + ")"; break; }
-        if (c2f_active(e, op, n)) {
-            const C2fPlan* pl = c2f_active(e, op, n);
-            k = "c2f_kernel<C=" + std::to_string(op.c2f_c) + (op.c2f_c == 32 ? ",NW=" + std::to_string(pl->nw) : std::string()) +
-                (op.c2f_mode == 3 ? ",cv1+bottleneck+cv2>" : op.c2f_mode == 1 ? ",cv1+bottleneck>" : ",bottleneck+cv2>");
-            break;
-        }
-        if (op.pair && pair_active(e, op, n)) { k = op.pair == 1 ? "bottleneck_pair_kernel<" + std::to_string(op.pair_c) + ">" : "(fused into the previous launch)"; break; }
-        if (wsk_active(e, op, n)) { k = "conv3x3_wsk_kernel<K=720 packed across taps,5 channel tiles>"; break; }
+    case LK_PREPROCESS: k = "preprocess_kernel"; break;
+    case LK_STEM: k = "stem_fused_kernel"; break;
+    case LK_STEM1: k = "stem_model1_kernel (preprocess+model.0+model.1)"; break;
+    case LK_SPPF_POOL: k = L.pool16 ? "sppf_pool16_kernel<DPP row windows, one barrier>" : "sppf_pool_kernel"; break;
+    case LK_SPPF_FUSED: k = "sppf_fused_kernel<cv1+3 pools+cv2,SPLIT=" + std::to_string(sppf_split(e->ops[(size_t)e->sppf_cv2].cout, n)) + ">"; break;
+    case LK_MULTI: k = L.multi_ct == 3 ? "conv_igemm_multi_kernel<CT=3> (the 3 Detect stems)" : "conv_igemm_multi_kernel<CT=2> (the 6 Detect branch convs)"; break;
+    case LK_C2F:
+        k = "c2f_kernel<C=" + std::to_string(op.c2f_c) + (op.c2f_c == 32 ? ",NW=" + std::to_string(L.c2f.nw) : std::string()) +
+            (op.c2f_mode == 3 ? ",cv1+bottleneck+cv2>" : op.c2f_mode == 1 ? ",cv1+bottleneck>" : ",bottleneck+cv2>");
+        break;
+    case LK_PAIR: k = "bottleneck_pair_kernel<" + std::to_string(op.pair_c) + ">"; break;
+    case LK_CONV_WSK: k = "conv3x3_wsk_kernel<K=720 packed across taps,5 channel tiles>"; break;
+    case LK_CONV: {
         const int cin = op.in.C + (op.in2.buf >= 0 ? op.in2.C : 0);
-        const ConvLaunch c = conv_launch_of(e, op, n);
+        const ConvLaunch& c = L.conv;
         if (c.ws1) k = std::string("conv1x1_ws_kernel<") + (op.in2.buf >= 0 ? "dual-source," : "") + "NK=" + std::to_string(cin / 32) + "," + std::to_string(c.ct) + " channel tiles," + std::to_string(c.pt * 16) + " px>";
         else if (c.ps) k = std::string("conv3x3_ws_kernel<") + (op.stride == 2 ? "S=2," : "") + (c.rowt ? "ROWT," : "") + (c.tpw1 ? "TPW=1," : "TPW=2,") + std::to_string(c.ct) + " channel tiles>";
         else if (c.lds) k = "conv3x3_lds_kernel<S=" + std::to_string(op.stride) + ",CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + (c.wres ? ",wres>" : ">");
@@ -2326,7 +2321,8 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
                  ",CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + ",KSPLIT=" + std::to_string(c.ksplit) + ">";
         break;
     }
-    default: k = "?";
+    case LK_HEAD: k = "head_fused_kernel"; break;
+    case LK_NMS: k = "nms_kernel"; break;
     }
     snprintf(out, cap, "%s", k.c_str());
     return ZLY_OK;
@@ -2338,10 +2334,11 @@ int32_t zly_launch_info_at(zly_engine* e, int32_t i, int32_t n, zly_launch_info*
     std::lock_guard<std::mutex> lk(e->mu);
     memset(out, 0, sizeof *out);
     const int nops = (int)e->ops.size();
-    out->covered_by = op_covered_by(e, i, n);
+    const std::vector<Launch>& t = resolve_launches(e, n);
+    out->covered_by = t[(size_t)i].covered_by;
     if (out->covered_by != i) return ZLY_OK;
     std::vector<char> in_group((size_t)nops, 0);
-    for (int j = 0; j < nops; ++j) in_group[(size_t)j] = op_covered_by(e, j, n) == i ? 1 : 0;
+    for (int j = 0; j < nops; ++j) in_group[(size_t)j] = t[(size_t)j].covered_by == i ? 1 : 0;
     // channel maps per buffer: written inside the group / read outside the group
     std::map<int, std::vector<char>> written_in, read_out, counted_in, counted_out;
     auto chan = [&](std::map<int, std::vector<char>>& m, int buf) -> std::vector<char>& {
@@ -2405,6 +2402,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
     e->front_yuv = false;                                // BGR frames: the front kernels' BGR instantiations
     if (rc != ZLY_OK) return rc;
     const size_t nops = e->ops.size();
+    const std::vector<Launch>& tab = resolve_launches(e, n);
     std::vector<hipEvent_t> ev(nops + 1);
     for (hipEvent_t& x : ev) HIP_TRY(hipEventCreate(&x), ZLY_ERR_SYSTEM);
     std::vector<double> acc(nops, 0.0);
@@ -2420,23 +2418,8 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
             hipError_t hr = hipSuccess;
             // only the idempotent forward ops are repeated: the Detect tail appends candidates and NMS consumes them
             const int reps_i = (e->ops[i].kind == OP_HEAD || e->ops[i].kind == OP_NMS) ? 1 : inner;
-            for (int k = 0; k < reps_i && hr == hipSuccess; ++k) {
-                if (e->stem_fused && i == 0) {
-                    // shipped path: preprocess is part of the stem kernel; its time is booked on ops[1] (model.0)
-                } else if (e->stem1 && i == 1) {
-                    Stem1Args st = e->stem1a;
-                    st.st.src = (const uint8_t*)d_frames; st.st.desc = e->d_desc;
-                    hr = launch_stem_model1(st, n, e->stream);
-                } else if (e->stem1 && i == 2) {
-                    // model.1 ran inside the stem kernel
-                } else if (e->stem_fused && i == 1) {
-                    StemArgs st = e->stem;
-                    st.src = (const uint8_t*)d_frames; st.desc = e->d_desc;
-                    hr = launch_stem_fused(st, n, e->stream);
-                } else {
-                    hr = run_op(e, e->ops[i], n, (const uint8_t*)d_frames, nullptr, 0, e->stream);
-                }
-            }
+            // the detect path's launches: the front kernel's time is booked on the op that launches it, covered ops launch nothing
+            for (int k = 0; k < reps_i && hr == hipSuccess; ++k) hr = run_op(e, i, tab[i], n, (const uint8_t*)d_frames, nullptr, 0, e->stream);
             if (hr != hipSuccess) { rcode = fail(ZLY_ERR_INFERENCE, std::string("profile: ") + hipGetErrorString(hr)); break; }
             hipEventRecord(ev[i + 1], e->stream);
         }
@@ -2445,7 +2428,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
         for (size_t i = 0; i < nops; ++i) {
             float ms = 0.f;
             hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-            if (op_is_noop(e, e->ops[i], n)) ms = 0.f;       // nothing was launched: what the event pair shows is its own cost
+            if (tab[i].kind == LK_NONE) ms = 0.f;            // nothing was launched: what the event pair shows is its own cost
             acc[i] += ms / ((e->ops[i].kind == OP_HEAD || e->ops[i].kind == OP_NMS) ? 1 : inner);
         }
     }
@@ -2460,7 +2443,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
             else st.total_forward_ms += acc[i];
         });
     }
-    e->last_n = n; e->last_stem1 = e->stem1;
+    e->last_n = n; e->last_front = true;
     return ZLY_OK;
 }
 

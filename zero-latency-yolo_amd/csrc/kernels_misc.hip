@@ -243,14 +243,19 @@ __global__ __launch_bounds__(256) void sppf_pool16_kernel(unsigned short* __rest
     }
 }
 
-hipError_t launch_sppf_pool(int dtype, void* buf, int cs, int c, int n, int H, int W, hipStream_t s, int six_pass)
+// small maps in bf16: the one-barrier kernel (six_pass: the engine's ZLY_SPPF_POOL_LDS=1 switch, tests / A-B)
+// Small batches only: at batch 1 the launch is 6.8 us against 8.8 (one barrier instead of six on the latency path); at batch 64 it is 13.7 us against 16.5 in
+// isolation -- both kernels move the map in 16-byte pieces 1 KB apart (an 8-channel slice of a 512-channel NHWC buffer), which is what bounds them
+// there -- and the three-engine step is 0.8 % SLOWER with it (A/B, 3 alternating rounds), so the big batches keep the six-pass kernel.
+bool sppf_pool16_ok(int dtype, int cs, int c, int n, int H, int W, int six_pass)
 {
     constexpr int SPPF_POOL16_MAX_BATCH = 16;
-    // small maps in bf16: the one-barrier kernel (six_pass: the engine's ZLY_SPPF_POOL_LDS=1 switch, tests / A-B)
-    // Small batches only: at batch 1 the launch is 6.8 us against 8.8 (one barrier instead of six on the latency path); at batch 64 it is 13.7 us against 16.5 in
-    // isolation -- both kernels move the map in 16-byte pieces 1 KB apart (an 8-channel slice of a 512-channel NHWC buffer), which is what bounds them
-    // there -- and the three-engine step is 0.8 % SLOWER with it (A/B, 3 alternating rounds), so the big batches keep the six-pass kernel.
-    if (dtype == ZLY_DTYPE_BF16 && H <= 16 && W <= 16 && (c % 8) == 0 && (cs % 8) == 0 && !six_pass && n <= SPPF_POOL16_MAX_BATCH) {
+    return dtype == ZLY_DTYPE_BF16 && H <= 16 && W <= 16 && (c % 8) == 0 && (cs % 8) == 0 && !six_pass && n <= SPPF_POOL16_MAX_BATCH;
+}
+
+hipError_t launch_sppf_pool(int dtype, void* buf, int cs, int c, int n, int H, int W, hipStream_t s, int six_pass)
+{
+    if (sppf_pool16_ok(dtype, cs, c, n, H, W, six_pass)) {
         hipLaunchKernelGGL(sppf_pool16_kernel, dim3(c / 8, n), dim3(256), 0, s, (unsigned short*)buf, cs, c, H, W);
         return hipGetLastError();
     }

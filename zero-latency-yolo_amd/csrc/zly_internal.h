@@ -121,6 +121,7 @@ hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* des
                              void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv = false);
 hipError_t launch_nchw_to_nhwc8(int dtype, const float* in_nchw, void* out_nhwc8, int n, int tw, int th, hipStream_t s);
 hipError_t launch_sppf_pool(int dtype, void* buf, int cs, int c, int n, int H, int W, hipStream_t s, int six_pass = 0);      // six_pass: sppf_pool_kernel also on maps of <= 16 x 16 pixels (tests / A-B)
+bool       sppf_pool16_ok(int dtype, int cs, int c, int n, int H, int W, int six_pass);                        // does launch_sppf_pool take sppf_pool16_kernel?
 hipError_t launch_tap_to_nchw(int dtype, const void* in, int cs, int co, int C, int H, int W, int idx, float* out, hipStream_t s);
 
 // kernels_stem.hip -- preprocess fused into the stem conv (bf16, 16-channel stem)
@@ -164,7 +165,7 @@ struct SppfArgs {
     int split;                                // workgroups per frame (2 / 4), 0 = chosen from n
     int dump;
 };
-bool       sppf_fused_ok(int cin, int c, int cout, int H, int W);
+bool       sppf_fused_ok(const SppfArgs& a);     // does launch_sppf_fused take this launch?
 int        sppf_split(int cout, int n);
 hipError_t sppf_init();
 hipError_t launch_sppf_fused(const SppfArgs& a, hipStream_t s);
