@@ -12,19 +12,20 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wal
 CXX      ?= g++
 PY       ?= python3
 
-KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip
+KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
-OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/engine.o $(OUT)/weights.o
+OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/engine.o $(OUT)/weights.o
 
 all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench oracle weights host
 
 $(OUT):
 	mkdir -p $(OUT)
 
-$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/zly_internal.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h include/zly.h | $(OUT)
+$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/zly_internal.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h $(CSRC)/letterbox_device.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OUT)/kernels_stem_yuv.o: $(CSRC)/kernels_stem.hip
+$(OUT)/kernels_lb.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_head.hip
 
 $(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@

@@ -73,6 +73,33 @@ extern "C" {
                                    each such engine owns exactly one stream, so that up to three of them fit the four hardware queues ROCm gives a process by default
                                    (leave GPU_MAX_HW_QUEUES alone: 8 measured 2x SLOWER on the host-to-host path) */
 #define ZLY_FLAG_NO_FUSION   2   /* run every conv as its own kernel (no fused bottleneck pairs): every zly_debug_tap is then available */
+#define ZLY_FLAG_LETTERBOX    32  /* resize mode of this engine: aspect-preserving bilinear letterbox (what Ultralytics-trained models expect) instead of the
+                                   reference's stretch-nearest resize; boxes come back as true normalised coordinates of the request frame.  Defined below. */
+
+/* Letterbox resize (ZLY_FLAG_LETTERBOX).  Per engine, for a request of w x h and a model of tw x th (model_w x model_h), all in integers:
+ *   Geometry.  If tw*h <= th*w the width binds: nw = tw, nh = max(1, (2*h*tw + w) / (2*w)).  Otherwise nh = th, nw = max(1, (2*w*th + h) / (2*h)).
+ *     (64-bit products, / truncating: round half up.)  pad_x = (tw - nw) >> 1, pad_y = (th - nh) >> 1.  This is Ultralytics' LetterBox
+ *     -- round(w*r), round(dw - 0.1) -- except where h*tw/w is exactly a half, which Python rounds to even: one pixel, on ~2 of 10 000 sizes.
+ *   Sampling: half-pixel centres, 16.16 fixed point, 8-bit weights, in int32.  Per axis with source length S and content length D
+ *     (w, nw or h, nh), for content index d:
+ *       step = ((S << 16) + (D >> 1)) / D
+ *       s    = clamp(d*step + (step >> 1) - 32768, 0, (S-1) << 16)
+ *       i0   = s >> 16;  i1 = min(i0 + 1, S - 1);  a = (s >> 8) & 255
+ *     and per channel of the four taps p00, p01, p10, p11 (row y0|y1, column x0|x1):
+ *       v = (p00*(256-ax)*(256-ay) + p01*ax*(256-ay) + p10*(256-ax)*ay + p11*ax*ay + 32768) >> 16
+ *     v is a byte (255 stays 255).  Everything fits int32 for w, h <= ZLY_LETTERBOX_MAX_DIM; larger requests fail in this mode with
+ *     ZLY_ERR_INVALID_INPUT (and an engine with model_w or model_h above it is refused with ZLY_ERR_INVALID_ARGUMENT).
+ *   Tensor.  Model pixel (x, y) with pad_x <= x < pad_x + nw and pad_y <= y < pad_y + nh holds the B, G, R bytes v of content index
+ *     (x - pad_x, y - pad_y); every other pixel holds 114, 114, 114.  Those bytes then take the stretch path exactly (/255, BGR->RGB, bf16
+ *     rounding in the bf16 engine).  The convolutions' zero padding outside the tw x th tensor is unchanged.
+ *   YUV frames: each of the four taps is first converted to its B, G, R bytes by the formula below, then interpolated as above.
+ *   Boxes.  The head's cx, cy, bw, bh (model pixels) are mapped back with single IEEE fp32 operations (no reciprocal, no contraction):
+ *       x = (cx - (float)pad_x) / (float)nw;  y = (cy - (float)pad_y) / (float)nh;  w = bw / (float)nw;  h = bh / (float)nh
+ *     -- true normalised coordinates of the request frame whatever its size.  Threshold, arg-max, NMS and output order do not change.
+ *   A request with w == tw and h == th has nw = tw, nh = th, no padding, step = 65536, a = 0: the map is the identity.
+ * Every entry point that takes frames honours the mode; the two that take tensors and caller-supplied sizes do not: the Session::Run
+ * stage keeps its model-sized input, and the postProcess stage keeps the stretch mapping (cx / img_w) on every engine. */
+#define ZLY_LETTERBOX_MAX_DIM 16384
 
 /* Pixel formats of a request frame (the *_fmt entry points; the others take ZLY_PIX_BGR).  Planes are tight: no row pitch, no padding.
  *   ZLY_PIX_BGR          packed B,G,R, 3 bytes per pixel: nbytes = w*h*3
@@ -90,7 +117,7 @@ extern "C" {
  *   BT.601   1220542  1673527  -852492  -409993  2116026   (1.164, 1.596, 0.813, 0.391, 2.018 x 2^20)
  *   BT.709   1220945  1879825  -558796  -223607  2215014   (round(c x 2^20) from Kr = 0.2126, Kb = 0.0722, luma x 255/219, chroma x 255/224)
  * Those B,G,R bytes then take the BGR path exactly (resize map, /255, BGR->RGB): a YUV frame gives, bit for bit, what its converted BGR frame
- * gives.  Boxes stay normalised by the request's w, h. */
+ * gives.  Boxes stay normalised by the request's w, h.  (A letterbox engine converts each of its four taps this way, then interpolates.) */
 #define ZLY_PIX_BGR          0
 #define ZLY_PIX_NV12_BT601   1
 #define ZLY_PIX_I420_BT601   2
@@ -171,6 +198,12 @@ const char* zly_version(void);
 /* Bytes of one frame of format fmt (ZLY_PIX_*) and size w x h: w*h*3 for BGR, w*h*3/2 for YUV 4:2:0; 0 for an unknown format or invalid
  * dimensions (w or h < 1; for YUV: odd, or < 2).  Host only: needs no engine and no GPU. */
 size_t  zly_frame_bytes(int32_t fmt, int32_t w, int32_t h);
+
+/* The letterbox geometry of a w x h request in a model_w x model_h model (ZLY_FLAG_LETTERBOX, "Geometry" above): content size nw x nh and its
+ * offset pad_x, pad_y inside the model tensor -- what an integrator needs to map anything else (a crosshair, a mask) between frame and model
+ * space.  ZLY_OK, or ZLY_ERR_INVALID_ARGUMENT for a non-positive size or a null output.  Host only: needs no engine and no GPU. */
+int32_t zly_letterbox_geometry(int32_t w, int32_t h, int32_t model_w, int32_t model_h,
+                               int32_t* nw, int32_t* nh, int32_t* pad_x, int32_t* pad_y);
 
 /* --- whole path ------------------------------------------------------------------------------ */
 /* One frame, synchronous.  bgr: u8 [h][w][3] interleaved BGR in host memory, nbytes must equal

@@ -100,6 +100,7 @@ struct Launch {
     int multi_ct = 0;                  // LK_MULTI: 3 = the three Detect stems, 2 = the six Detect branch convs
     int only_level = -1;               // LK_HEAD: -1 = all three levels, else that level only
     bool pool16 = false;               // LK_SPPF_POOL: sppf_pool16_kernel (else sppf_pool_kernel)
+    bool lb = false;                   // front kernels and LK_HEAD of a letterbox engine (ZLY_FLAG_LETTERBOX): the LB instantiation (kernels_lb.hip)
 };
 
 struct Ingest;        // pipelined host-to-host path (zly_submit / zly_wait), below
@@ -798,11 +799,13 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
     int tail = -1;
     for (int i = 0; i < nops; ++i) if (e->ops[(size_t)i].kind == OP_HEAD && e->ops[(size_t)i].level == 2) tail = i;
 
+    const bool lb = (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0;
     std::vector<Launch> t((size_t)nops);
     for (int i = 0; i < nops; ++i) {
         const Op& op = e->ops[(size_t)i];
         Launch& L = t[(size_t)i];
         L.covered_by = i;
+        L.lb = lb && (op.kind == OP_PREPROCESS || op.kind == OP_HEAD || (i == 1 && e->stem_fused));
         auto covered = [&](int by) { L.kind = LK_NONE; L.covered_by = by; };
         switch (op.kind) {
         case OP_PREPROCESS:
@@ -908,16 +911,16 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
     case LK_NONE:
         return hipSuccess;
     case LK_PREPROCESS:
-        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front_yuv);
+        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front_yuv, L.lb);
     case LK_STEM: {
         StemArgs st = e->stem;
         st.src = d_src; st.desc = e->d_desc;
-        return launch_stem_fused(st, n, s, e->front_yuv);
+        return launch_stem_fused(st, n, s, e->front_yuv, L.lb);
     }
     case LK_STEM1: {
         Stem1Args st = e->stem1a;
         st.st.src = d_src; st.st.desc = e->d_desc;
-        return launch_stem_model1(st, n, s, e->front_yuv);
+        return launch_stem_model1(st, n, s, e->front_yuv, L.lb);
     }
     case LK_CONV:
     case LK_CONV_WSK: {
@@ -985,6 +988,7 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
     case LK_HEAD: {
         HeadArgs h = op.head;
         h.only_level = L.only_level;
+        if (L.lb) { h.lb_tw = e->cfg.model_w; h.lb_th = e->cfg.model_h; }      // boxes are mapped out of the letterbox (the geometry comes from d_desc at run time: no graph key)
         h.head = (e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) ? nullptr : e->d_head; h.desc = e->d_desc; h.conf_thr = e->cfg.conf_thr; h.cand = e->cur_cand; h.cand_count = e->cur_count;
         return launch_head_fused(e->dtype, h, n, s);
     }
@@ -1278,6 +1282,15 @@ static int check_frame(int32_t fmt, const uint8_t* p, size_t nbytes, int32_t w, 
     return ZLY_OK;
 }
 
+// a letterbox engine's fixed-point resize fits int32 for requests of up to ZLY_LETTERBOX_MAX_DIM pixels on a side (include/zly.h)
+static int check_frame_mode(const zly_engine* e, int32_t w, int32_t h)
+{
+    if ((e->cfg.flags & ZLY_FLAG_LETTERBOX) && (w > ZLY_LETTERBOX_MAX_DIM || h > ZLY_LETTERBOX_MAX_DIM))
+        return fail(ZLY_ERR_INVALID_INPUT, "letterbox mode takes frames of at most " + std::to_string(ZLY_LETTERBOX_MAX_DIM) + " pixels on a side, got " +
+                                           std::to_string(w) + " x " + std::to_string(h));
+    return ZLY_OK;
+}
+
 // Returns the first HIP error met while draining / releasing (the engine is gone either way).
 static hipError_t destroy_engine(zly_engine* e)
 {
@@ -1568,7 +1581,9 @@ static void ingest_free(zly_engine* e, Ingest* g)
 static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket, bool nonblock = false,
                          int32_t fmt = ZLY_PIX_BGR)
 {
-    if (int rcv = check_frame(fmt, bgr, nbytes, w, h)) {
+    int rcv = check_frame(fmt, bgr, nbytes, w, h);
+    if (rcv == ZLY_OK) rcv = check_frame_mode(e, w, h);
+    if (rcv != ZLY_OK) {
         with_stats(e, [](zly_stats& st) { st.inference_errors++; });
         return rcv;
     }
@@ -1739,6 +1754,8 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
     if (cfg->max_batch < 1 || cfg->max_dets < 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "max_batch/max_dets must be >= 1");
     if (cfg->max_batch > 65535) return fail(ZLY_ERR_INVALID_ARGUMENT, "max_batch must be <= 65535 (a ticket of the pipelined path carries the frame's index in 16 bits)");
     if (cfg->dtype != ZLY_DTYPE_BF16 && cfg->dtype != ZLY_DTYPE_FP32) return fail(ZLY_ERR_INVALID_ARGUMENT, "dtype must be ZLY_DTYPE_FP32 or ZLY_DTYPE_BF16");
+    if ((cfg->flags & ZLY_FLAG_LETTERBOX) && (cfg->model_w > ZLY_LETTERBOX_MAX_DIM || cfg->model_h > ZLY_LETTERBOX_MAX_DIM))
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "ZLY_FLAG_LETTERBOX: model_w/model_h must be <= " + std::to_string(ZLY_LETTERBOX_MAX_DIM));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(ZLY_ERR_SYSTEM, "no HIP device available: this engine has no CPU fallback");
@@ -1888,7 +1905,9 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     bool yuv = false;
     for (int i = 0; i < n; ++i) {
         const int32_t fi = fmt ? fmt[i] : ZLY_PIX_BGR;
-        if (int rcv = check_frame(fi, bgr[i], nbytes[i], w[i], h[i])) {
+        int rcv = check_frame(fi, bgr[i], nbytes[i], w[i], h[i]);
+        if (rcv == ZLY_OK) rcv = check_frame_mode(e, w[i], h[i]);
+        if (rcv != ZLY_OK) {
             with_stats(e, [](zly_stats& st) { st.inference_errors++; });
             return rcv;
         }
@@ -1936,6 +1955,19 @@ size_t zly_frame_bytes(int32_t fmt, int32_t w, int32_t h)
     if (fmt == ZLY_PIX_BGR) return (size_t)w * (size_t)h * 3u;
     if (w < 2 || h < 2 || (w & 1) || (h & 1)) return 0;                // 4:2:0: one chroma sample per 2 x 2 block
     return (size_t)w * (size_t)h * 3u / 2u;
+}
+
+int32_t zly_letterbox_geometry(int32_t w, int32_t h, int32_t model_w, int32_t model_h, int32_t* nw, int32_t* nh, int32_t* pad_x, int32_t* pad_y)
+{
+    if (w < 1 || h < 1 || model_w < 1 || model_h < 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_letterbox_geometry: sizes must be positive");
+    if (!nw || !nh || !pad_x || !pad_y) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    const int64_t W = w, H = h, TW = model_w, TH = model_h;
+    int64_t cw, ch;
+    if (TW * H <= TH * W) { cw = TW; ch = std::max<int64_t>(1, (2 * H * TW + W) / (2 * W)); }      // the width binds
+    else                  { ch = TH; cw = std::max<int64_t>(1, (2 * W * TH + H) / (2 * H)); }
+    *nw = (int32_t)cw; *nh = (int32_t)ch;
+    *pad_x = (int32_t)((TW - cw) >> 1); *pad_y = (int32_t)((TH - ch) >> 1);
+    return ZLY_OK;
 }
 
 int32_t zly_detect(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, zly_det* out, int32_t cap, int32_t* n_out)
@@ -2025,6 +2057,7 @@ int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void*
     const size_t fb = zly_frame_bytes(fmt, w, h);
     if (!d_frames || w <= 0 || h <= 0 || fb == 0) return fail(ZLY_ERR_INVALID_INPUT, "bad frame pointer or size");
     if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    if (int rcm = check_frame_mode(e, w, h)) return rcm;
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
@@ -2097,6 +2130,7 @@ int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!out_nchw) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
     if (int rcv = check_frame(fmt, bgr, nbytes, w, h)) return rcv;
+    if (int rcm = check_frame_mode(e, w, h)) return rcm;
     std::lock_guard<std::mutex> lk(e->mu);
     ExclusiveGate gl;                                    // parity / debug entry point: allocations and copies, alone in the process
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
@@ -2111,7 +2145,8 @@ int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_
     size_t off0 = 0;
     rc = set_desc(e, 1, &w, &h, &off0, e->stream, &fmt);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, fmt != ZLY_PIX_BGR), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, fmt != ZLY_PIX_BGR,
+                              (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
@@ -2298,9 +2333,9 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
         case LK_HEAD: k = "(covered by the last tail launch)"; break;
         }
         break;
-    case LK_PREPROCESS: k = "preprocess_kernel"; break;
-    case LK_STEM: k = "stem_fused_kernel"; break;
-    case LK_STEM1: k = "stem_model1_kernel (preprocess+model.0+model.1)"; break;
+    case LK_PREPROCESS: k = L.lb ? "preprocess_kernel<LB> (letterbox)" : "preprocess_kernel"; break;
+    case LK_STEM: k = L.lb ? "stem_fused_kernel<LB> (letterbox)" : "stem_fused_kernel"; break;
+    case LK_STEM1: k = L.lb ? "stem_model1_kernel<LB> (letterbox preprocess+model.0+model.1)" : "stem_model1_kernel (preprocess+model.0+model.1)"; break;
     case LK_SPPF_POOL: k = L.pool16 ? "sppf_pool16_kernel<DPP row windows, one barrier>" : "sppf_pool_kernel"; break;
     case LK_SPPF_FUSED: k = "sppf_fused_kernel<cv1+3 pools+cv2,SPLIT=" + std::to_string(sppf_split(e->ops[(size_t)e->sppf_cv2].cout, n)) + ">"; break;
     case LK_MULTI: k = L.multi_ct == 3 ? "conv_igemm_multi_kernel<CT=3> (the 3 Detect stems)" : "conv_igemm_multi_kernel<CT=2> (the 6 Detect branch convs)"; break;
@@ -2321,7 +2356,7 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
                  ",CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + ",KSPLIT=" + std::to_string(c.ksplit) + ">";
         break;
     }
-    case LK_HEAD: k = "head_fused_kernel"; break;
+    case LK_HEAD: k = L.lb ? "head_fused_kernel<LB> (letterbox box mapping)" : "head_fused_kernel"; break;
     case LK_NMS: k = "nms_kernel"; break;
     }
     snprintf(out, cap, "%s", k.c_str());
@@ -2391,7 +2426,8 @@ int32_t zly_launch_info_at(zly_engine* e, int32_t i, int32_t n, zly_launch_info*
 int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t w, int32_t h, int32_t reps, float* ms_out)
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
-    if (!d_frames || !ms_out || reps < 1 || n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
+    if (!d_frames || !ms_out || reps < 1 || n < 1 || n > e->cfg.max_batch || w < 1 || h < 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
+    if (int rcm = check_frame_mode(e, w, h)) return rcm;
     std::lock_guard<std::mutex> lk(e->mu);
     ExclusiveGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);

@@ -9,6 +9,7 @@
 // round trip through HBM.  decode here and decode_kernel (kernels_post.hip, used by zly_postprocess)
 // apply the same comparisons to the same fp32 values, so both give the same candidates.
 #include "zly_internal.h"
+#include "letterbox_device.h"
 #include <algorithm>
 #include <math.h>
 
@@ -55,7 +56,9 @@ template <> __device__ __forceinline__ float h_div<bf16_t>(float a, float b) { r
 // logit(conf_thr) - 1e-2, none can reach the confidence threshold (the margin is four orders of magnitude above the error of
 // v_exp / v_rcp), and the box loads, the box GEMM, the DFL and the 80 sigmoids per anchor are skipped -- ~4 of 5 tiles on a detector that
 // passes ~1.5 % of its anchors.  Tiles that are not skipped run the full arithmetic, so the candidates are exactly the same.
-template <typename T, int CTC>
+// LB: the instantiation of a letterbox engine (include/zly.h ZLY_FLAG_LETTERBOX): a surviving anchor's box is mapped out of the letterbox -- its
+// geometry recomputed from the frame descriptor, for survivors only -- instead of divided by the request size.  Compiled in kernels_lb.hip.
+template <typename T, int CTC, bool LB = false>
 __global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(const HeadArgs a)
 {
     typedef typename HFrag<T>::type F;
@@ -294,7 +297,12 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(const HeadA
                 if (slot < a.N_total) {
                     const FrameDesc d = a.desc[f];
                     Cand c;
+                    if constexpr (LB) {
+                        const LbGeom g = lb_geometry(d.w, d.h, a.lb_tw, a.lb_th);
+                        c.x = (cx - (float)g.pad_x) / (float)g.nw; c.y = (cy - (float)g.pad_y) / (float)g.nh; c.w = bw / (float)g.nw; c.h = bh / (float)g.nh;
+                    } else {
                     c.x = cx / (float)d.w; c.y = cy / (float)d.h; c.w = bw / (float)d.w; c.h = bh / (float)d.h;
+                    }
                     c.conf = best; c.cls = cls; c.anchor = L.anchor_off + an; c.pad_ = 0;
                     a.cand[(size_t)f * a.N_total + slot] = c;
                 }
@@ -304,16 +312,22 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(const HeadA
 }
 
 typedef void (*head_fn)(const HeadArgs);
-template <typename T> static head_fn pick_head(int ctc) {
+template <typename T, bool LB> static head_fn pick_head(int ctc) {
     switch (ctc) {
-        case 1: return head_fused_kernel<T, 1>;
-        case 2: return head_fused_kernel<T, 2>;
-        case 3: return head_fused_kernel<T, 3>;
-        case 4: return head_fused_kernel<T, 4>;
-        case 5: return head_fused_kernel<T, 5>;
+        case 1: return head_fused_kernel<T, 1, LB>;
+        case 2: return head_fused_kernel<T, 2, LB>;
+        case 3: return head_fused_kernel<T, 3, LB>;
+        case 4: return head_fused_kernel<T, 4, LB>;
+        case 5: return head_fused_kernel<T, 5, LB>;
     }
     return nullptr;
 }
+#if defined(ZLY_LB_TU) || defined(ZLY_HEAD_DIAG)              // (diagnostic builds, tools/head_bench.hip: one translation unit)
+// the letterbox instantiations, for the launcher in kernels_head.hip
+head_fn head_fused_lb_kernel(int dtype, int ctc) { return dtype == ZLY_DTYPE_BF16 ? pick_head<bf16_t, true>(ctc) : pick_head<float, true>(ctc); }
+#endif
+#ifndef ZLY_LB_TU
+head_fn head_fused_lb_kernel(int dtype, int ctc);          // kernels_lb.hip
 
 hipError_t launch_head_fused(int dtype, const HeadArgs& a0, int n, hipStream_t s)
 {
@@ -323,7 +337,7 @@ hipError_t launch_head_fused(int dtype, const HeadArgs& a0, int n, hipStream_t s
     const double thr = (double)a.conf_thr;
     a.skip_logit = thr <= 0.0 ? -3.0e38f : (thr >= 1.0 ? 15.0f : (float)(log(thr / (1.0 - thr)) - 1e-2));
     const int ctc = (a.nc + 15) / 16;
-    head_fn fn = dtype == ZLY_DTYPE_BF16 ? pick_head<bf16_t>(ctc) : pick_head<float>(ctc);
+    head_fn fn = a.lb_tw > 0 ? head_fused_lb_kernel(dtype, ctc) : dtype == ZLY_DTYPE_BF16 ? pick_head<bf16_t, false>(ctc) : pick_head<float, false>(ctc);
     if (!fn) return hipErrorInvalidValue;                  // nc > 80 is not supported by this kernel
     if (a.only_level > 2) return hipErrorInvalidValue;
     size_t lds = 0;
@@ -340,5 +354,6 @@ hipError_t launch_head_fused(int dtype, const HeadArgs& a0, int n, hipStream_t s
     hipLaunchKernelGGL(fn, dim3(blocks, n), dim3(HEAD_WAVES * 64), lds, s, a);
     return hipGetLastError();
 }
+#endif  // !ZLY_LB_TU
 
 }  // namespace zly

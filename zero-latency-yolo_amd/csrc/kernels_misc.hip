@@ -4,6 +4,7 @@
 // 16-byte accesses, no MFMA.
 #include "zly_internal.h"
 #include "yuv_device.h"
+#include "letterbox_device.h"
 
 namespace zly {
 
@@ -21,8 +22,10 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // and optionally the reference's planar fp32 [3][th][tw] layout for the parity entry point.
 // YUV: the instantiation for batches with YUV 4:2:0 frames -- a YUV frame's pixel is converted to the B, G, R bytes of its integer BGR
 // equivalent (yuv_device.h) and then takes exactly the BGR path; the BGR-only instantiation is unchanged.
+// LB: the instantiation of a letterbox engine (ZLY_FLAG_LETTERBOX, letterbox_device.h): the fetch is the padding test + the bilinear blend of four
+// taps instead of the nearest-neighbour pick; the bytes it yields take the same path.  Compiled in kernels_lb.hip (ZLY_LB_TU), not here.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool YUV>
+template <typename T, bool YUV, bool LB = false>
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
                                                          T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
 {
@@ -36,6 +39,14 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     int sy = (int)((float)y * scale_h); if (sy > d.h - 1) sy = d.h - 1;
     int sx = (int)((float)x * scale_w); if (sx > d.w - 1) sx = d.w - 1;
     float b, g, r;
+    if constexpr (LB) {
+        const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
+        const LbFrame lf = lb_frame(d.w, d.h, tw, th);
+        LbTaps taps;
+        lb_issue<YUV>(src + (YUV ? desc_off(d.src_off) : d.src_off), fmt, lf, x, y, taps);
+        const unsigned int px = lb_blend<YUV>(taps, fmt);
+        b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)((px >> 16) & 0xffu) / 255.0f;
+    } else
     if (YUV && pix_is_yuv(desc_fmt(d.src_off))) {
         unsigned int yv, uv;
         yuv_issue(src + desc_off(d.src_off), desc_fmt(d.src_off), d.w, d.h, sx, sy, yv, uv);
@@ -56,10 +67,25 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     }
 }
 
+typedef void (*preprocess_bf16_fn)(const uint8_t*, const FrameDesc*, bf16_t*, float*, int, int);
+typedef void (*preprocess_f32_fn)(const uint8_t*, const FrameDesc*, float*, float*, int, int);
+#ifdef ZLY_LB_TU
+// the letterbox instantiations, for the launcher in kernels_misc.hip
+preprocess_bf16_fn preprocess_lb_bf16_kernel(bool yuv) { return yuv ? preprocess_kernel<bf16_t, true, true> : preprocess_kernel<bf16_t, false, true>; }
+preprocess_f32_fn  preprocess_lb_f32_kernel(bool yuv) { return yuv ? preprocess_kernel<float, true, true> : preprocess_kernel<float, false, true>; }
+#else
+preprocess_bf16_fn preprocess_lb_bf16_kernel(bool yuv);      // kernels_lb.hip
+preprocess_f32_fn  preprocess_lb_f32_kernel(bool yuv);
+
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv)
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv, bool lb)
 {
     dim3 grid((tw * th + 255) / 256, n);
+    if (lb) {
+        if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(preprocess_lb_bf16_kernel(yuv), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
+        else hipLaunchKernelGGL(preprocess_lb_f32_kernel(yuv), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
+        return hipGetLastError();
+    }
     if (dtype == ZLY_DTYPE_BF16) {
         if (yuv) hipLaunchKernelGGL((preprocess_kernel<bf16_t, true>), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
         else hipLaunchKernelGGL((preprocess_kernel<bf16_t, false>), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
@@ -69,7 +95,9 @@ hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* des
     }
     return hipGetLastError();
 }
+#endif  // !ZLY_LB_TU
 
+#ifndef ZLY_LB_TU
 // fp32 planar [n][3][th][tw] (the "images" tensor of onnx_engine.cpp:560-569) -> engine NHWC8
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const float* __restrict__ in, T* __restrict__ out8, int hw)
@@ -295,5 +323,7 @@ hipError_t launch_tap_to_nchw(int dtype, const void* in, int cs, int co, int C, 
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
+
+#endif  // !ZLY_LB_TU
 
 }  // namespace zly

@@ -18,9 +18,14 @@
 // The YUV = true instantiations of the front kernels (batches with YUV 4:2:0 frames) are compiled in a translation unit of their own,
 // kernels_stem_yuv.hip, which includes this file with ZLY_STEM_YUV_TU defined: instantiated here, next to the BGR ones, they changed the
 // register allocation of the BGR kernels (same resources, different code), and the BGR kernels are to stay exactly as they were.
+// The LB = true instantiations (letterbox engines, ZLY_FLAG_LETTERBOX) live in kernels_lb.hip for the same reason (ZLY_STEM_LB_TU).
 #include "zly_internal.h"
 #include "conv_device.h"
 #include "yuv_device.h"
+#include "letterbox_device.h"
+#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_LB_TU)
+#define ZLY_STEM_SIDE_TU 1                 // a translation unit of instantiations only: no launchers, no tables
+#endif
 #include <stdlib.h>
 #include <type_traits>
 
@@ -51,7 +56,9 @@ __device__ __forceinline__ FrameDesc load_desc(const FrameDesc* p)
 // ends with 8 consecutive channels = one 16-byte store); the pixel fragments are read once for both tiles.
 // YUV: the instantiation for batches with YUV 4:2:0 frames (yuv_device.h: a YUV frame's pixel becomes its BGR bytes, then the BGR path); it serves
 // the batch's BGR frames as well.  Batches of BGR frames only run YUV = false, the kernel as it was.
-template <int NT, bool YUV>
+// LB: the instantiation of a letterbox engine (letterbox_device.h): a frame that is not model-sized BGR is fetched as padding / a four-tap bilinear
+// blend instead of the nearest-neighbour pick.  Every other engine runs LB = false, the kernel as it was.
+template <int NT, bool YUV, bool LB = false>
 __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
 {
     __shared__ __attribute__((aligned(16))) bf16x4 patch[STEM_PH * STEM_PW];
@@ -78,18 +85,26 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
     const uint8_t* src = a.src + (YUV ? desc_off(d.src_off) : d.src_off);
     const bool same = (d.w == a.tw) & (d.h == a.th) & !pix_is_yuv(fmt);
     const size_t frame_bytes = (size_t)d.w * d.h * 3;
+    LbFrame lf;
+    if constexpr (LB) lf = lb_frame(d.w, d.h, a.tw, a.th);
     for (int u = tid; u < STEM_PH * STEM_PW; u += 256) {
         const int py = u / STEM_PW, px = u - py * STEM_PW;
         const int iy = iy0 + py, ix = ix0 + px;
         bf16x4 v = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
         if ((unsigned)iy < (unsigned)a.th && (unsigned)ix < (unsigned)a.tw) {
             int sy = iy, sx = ix;
-            if (!same) {       // request size == model size: the nearest-neighbour map is the identity (wave-uniform branch)
+            if (!LB && !same) {       // request size == model size: the nearest-neighbour map is the identity (wave-uniform branch)
                 sy = (int)((float)iy * scale_h); if (sy > d.h - 1) sy = d.h - 1;
                 sx = (int)((float)ix * scale_w); if (sx > d.w - 1) sx = d.w - 1;
             }
             unsigned int px4;
-            if (YUV && pix_is_yuv(fmt)) {      // wave-uniform: one format per frame
+            if (LB && !same) {         // (a model-sized BGR frame: the letterbox map is the identity too)
+                if constexpr (LB) {
+                    LbTaps taps;
+                    lb_issue<YUV>(src, fmt, lf, ix, iy, taps);
+                    px4 = lb_blend<YUV>(taps, fmt);
+                }
+            } else if (YUV && pix_is_yuv(fmt)) {      // wave-uniform: one format per frame
                 unsigned int yv, uv;
                 yuv_issue(src, fmt, d.w, d.h, sx, sy, yv, uv);
                 px4 = yuv_bgr_word(yv, uv, fmt);
@@ -171,16 +186,27 @@ typedef void (*stem1_fn)(const Stem1Args);
 // the YUV instantiations, for the launchers in kernels_stem.hip
 stem_fused_fn stem_fused_yuv_kernel(int nt) { return nt == 2 ? stem_fused_kernel<2, true> : stem_fused_kernel<1, true>; }
 #endif
-#ifndef ZLY_STEM_YUV_TU
+#if defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_DIAG)
+// the letterbox instantiations
+stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv)
+{
+    if (yuv) return nt == 2 ? stem_fused_kernel<2, true, true> : stem_fused_kernel<1, true, true>;
+    return nt == 2 ? stem_fused_kernel<2, false, true> : stem_fused_kernel<1, false, true>;
+}
+#endif
+#ifndef ZLY_STEM_SIDE_TU
 stem_fused_fn stem_fused_yuv_kernel(int nt);         // kernels_stem_yuv.hip
 stem1_fn      stem1_yuv_kernel(int nw, int var);
+stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv);         // kernels_lb.hip
+stem1_fn      stem1_lb_kernel(int nw, int var, bool yuv);
 
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv)
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv, bool lb)
 {
     if (a.Cout != 16 && a.Cout != 32) return hipErrorInvalidValue;         // one or two 16-channel MFMA tiles (YOLOv8n / YOLOv8-s); wider stems use the generic path
     if (a.Cout == 32 && (a.out_cs % 8 || a.out_co % 8)) return hipErrorInvalidValue;
     const int tiles_y = (a.Ho + STEM_TH - 1) / STEM_TH;
-    if (yuv) hipLaunchKernelGGL(stem_fused_yuv_kernel(a.Cout == 16 ? 1 : 2), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    if (lb) hipLaunchKernelGGL(stem_fused_lb_kernel(a.Cout == 16 ? 1 : 2, yuv), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    else if (yuv) hipLaunchKernelGGL(stem_fused_yuv_kernel(a.Cout == 16 ? 1 : 2), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else if (a.Cout == 16) hipLaunchKernelGGL((stem_fused_kernel<1, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((stem_fused_kernel<2, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -232,7 +258,7 @@ __device__ unsigned long long* g_stem_diag = nullptr;            // diagnostic b
 //   read 2 (k-step 1, first half):  kq0 (1,2)  kq1 zero   kq2 (2,2)  kq3 zero            (k-step 1, second half: all zero weights, not read)
 // Round 3's order (tap = s * 8 + kq * 2 + j) put two taps of equal pixel parity into half of the lane groups' pairs: 2-way conflicts on 4 of 8 half-wave
 // reads, and a fourth read for slots whose weights are all zero.
-#ifndef ZLY_STEM_YUV_TU
+#ifndef ZLY_STEM_SIDE_TU
 static const int STEM1_TAP_SLOT[9] = {0, 2, 5, 4, 6, 8, 1, 3, 12};
 const int* stem1_tap_slot() { return STEM1_TAP_SLOT; }
 #endif
@@ -240,7 +266,9 @@ const int* stem1_tap_slot() { return STEM1_TAP_SLOT; }
 // YUV: the instantiation for batches with YUV 4:2:0 frames.  A YUV frame never counts as `same` (request size == model size), so it never reaches the
 // BGR quad paths; the per-pixel general path fetches it through yuv_device.h (all byte loads of a thread first, then the conversions).  Batches of
 // BGR frames only run YUV = false, the kernel as it was.
-template <int NW, int VAR, bool YUV>
+// LB: the instantiation of a letterbox engine.  Model-sized BGR frames keep the quad paths (the letterbox map is the identity for them); every other
+// frame takes the letterbox general path below.  Every other engine runs LB = false, the kernel as it was.
+template <int NW, int VAR, bool YUV, bool LB = false>
 __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem_model1_kernel(const Stem1Args a)
 {
     constexpr bool NEWP = VAR >= 1, PERS = VAR >= 2;
@@ -481,6 +509,42 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                 }
             }
         }
+    } else if constexpr (LB) {
+        // Letterbox: a patch pixel is zero (outside the model-sized image), grey (the letterbox padding: no loads) or the blend of four taps.  A
+        // pixel's taps are four dwords (BGR: two 8-byte loads) + its weights, so the thread's STEM1_MAXIT pixels go in groups of LB_GROUP whose
+        // loads are issued before the group's first blend.  The persistent variant runs at its register limit as it is (125 of 128 VGPRs without
+        // this path): one pixel per group there, or the kernel spills; the others take four.
+        const LbFrame lf = lb_frame(d.w, d.h, a.st.tw, a.st.th);
+        constexpr int LB_GROUP = PERS ? 1 : 4, LB_OUT = -2;
+        const int tidg = PERS ? pin_here(tid) : tid;
+    #pragma unroll
+        for (int k0 = 0; k0 < STEM1_MAXIT; k0 += LB_GROUP) {
+            LbTaps tp[LB_GROUP];
+    #pragma unroll
+            for (int j = 0; j < LB_GROUP; ++j) {
+                const int u = tidg + (k0 + j) * NW * 64;
+                tp[j].m = LB_OUT;
+                if (u < PH * PWV) {
+                    const int py = div_small_s(u, invPW), px = u - py * PWV;
+                    const int iy = iy0 + py, ix = ix0 + px;
+                    if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) lb_issue<YUV>(src, fmt, lf, ix, iy, tp[j]);
+                }
+            }
+    #pragma unroll
+            for (int j = 0; j < LB_GROUP; ++j) {
+                const int u = tidg + (k0 + j) * NW * 64;
+                if (u < PH * PWV) {
+                    bf16x4 v = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+                    if (tp[j].m != LB_OUT) {
+                        const float kk = 1.0f / 255.0f;
+                        const unsigned int px = lb_blend<YUV>(tp[j], fmt);
+                        v[0] = (bf16_t)((float)((px >> 16) & 0xffu) * kk); v[1] = (bf16_t)((float)((px >> 8) & 0xffu) * kk); v[2] = (bf16_t)((float)(px & 0xffu) * kk);
+                    }
+                    const int py = div_small_s(u, invPW);
+                    patch[u + py * (PW - PWV)] = v;
+                }
+            }
+        }
     } else {
         // all of a thread's loads are issued before the first conversion (the loop below is fully unrolled: STEM1_MAXIT pixels per thread):
         // with one load per loop iteration every iteration exposed a full memory round trip, ~6 us of the ~12 us a tile took
@@ -700,7 +764,16 @@ stem1_fn stem1_yuv_kernel(int nw, int var)
     return nw == 12 ? stem_model1_kernel<12, 0, true> : nw == 16 ? stem_model1_kernel<16, 0, true> : stem_model1_kernel<STEM1_NW, 0, true>;
 }
 #endif
-#ifndef ZLY_STEM_YUV_TU
+#if defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_DIAG)
+template <bool YUV> static stem1_fn stem1_lb_pick(int nw, int var)
+{
+    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, YUV, true> : nw == 16 ? stem_model1_kernel<16, 2, YUV, true> : stem_model1_kernel<STEM1_NW, 2, YUV, true>;
+    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, YUV, true> : nw == 16 ? stem_model1_kernel<16, 1, YUV, true> : stem_model1_kernel<STEM1_NW, 1, YUV, true>;
+    return nw == 12 ? stem_model1_kernel<12, 0, YUV, true> : nw == 16 ? stem_model1_kernel<16, 0, YUV, true> : stem_model1_kernel<STEM1_NW, 0, YUV, true>;
+}
+stem1_fn stem1_lb_kernel(int nw, int var, bool yuv) { return yuv ? stem1_lb_pick<true>(nw, var) : stem1_lb_pick<false>(nw, var); }
+#endif
+#ifndef ZLY_STEM_SIDE_TU
 static size_t stem1_lds_bytes(int th, int tw, int var)
 {
     const size_t RH = 2 * th + 1, RW = 2 * tw + 1, PH = 2 * RH + 1, PW = 2 * RW + 1 + (var >= 1 ? 3 : 0);
@@ -719,8 +792,9 @@ void stem1_plan(int H1, int W1, int* th, int* tw)
     (void)H1;
 }
 
-static stem1_fn pick_stem1(int nw, int var, bool yuv)
+static stem1_fn pick_stem1(int nw, int var, bool yuv, bool lb = false)
 {
+    if (lb) return stem1_lb_kernel(nw, var, yuv);
     if (yuv) return stem1_yuv_kernel(nw, var);
     if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, false> : nw == 16 ? stem_model1_kernel<16, 2, false> : stem_model1_kernel<STEM1_NW, 2, false>;
     if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, false> : nw == 16 ? stem_model1_kernel<16, 1, false> : stem_model1_kernel<STEM1_NW, 1, false>;
@@ -732,10 +806,11 @@ hipError_t stem1_init()
 {
     for (int var = 0; var <= 2; ++var)
         for (int nw : {STEM1_NW, 12, 16})
-            for (bool yuv : {false, true}) {
-                hipError_t r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (r != hipSuccess) return r;
-            }
+            for (bool yuv : {false, true})
+                for (bool lb : {false, true}) {
+                    hipError_t r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv, lb), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                    if (r != hipSuccess) return r;
+                }
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_stem1_cus = cus;
     return hipSuccess;
@@ -744,7 +819,7 @@ hipError_t stem1_init()
 // a.nw: waves per workgroup (8; 12 / 16 = tuning aid ZLY_STEM1_NW); a.var: 2 = persistent workgroups with the next tile's input bytes in flight (default),
 // 1 = one tile per workgroup, 0 = round 3's staging / tap order as well (ZLY_STEM1_VAR, A/B on one box).  Both are read by the engine once per
 // zly_create, not here (a process-static switch cannot be toggled by a test)
-hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yuv)
+hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yuv, bool lb)
 {
     Stem1Args a = a0;
     if (a.st.Cout != 16 || a.TH < 1 || a.TW < 1 || a.out1_cs % 8 || a.out1_co % 8) return hipErrorInvalidValue;
@@ -775,13 +850,13 @@ hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yu
         long long wgs = (long long)g_stem1_cus * (long long)((160 * 1024) / lds < 1 ? 1 : (160 * 1024) / lds);
         if (a.pgrid > 0) wgs = a.pgrid;                                                            // tuning aid ZLY_STEM1_GRID (read by the engine per zly_create)
         if (wgs > total) wgs = total;
-        hipLaunchKernelGGL(pick_stem1(nw, var, yuv), dim3((unsigned)wgs), dim3(nw * 64), lds, s, a);
+        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb), dim3((unsigned)wgs), dim3(nw * 64), lds, s, a);
     } else {
-        hipLaunchKernelGGL(pick_stem1(nw, var, yuv), dim3(a.tiles_x * a.tiles_y, n), dim3(nw * 64), lds, s, a);
+        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb), dim3(a.tiles_x * a.tiles_y, n), dim3(nw * 64), lds, s, a);
     }
     return hipGetLastError();
 }
 
-#endif  // !ZLY_STEM_YUV_TU
+#endif  // !ZLY_STEM_SIDE_TU
 
 }  // namespace zly

@@ -117,8 +117,9 @@ hipError_t launch_c2f64(int mode, const C2fArgs& a, const C2fPlan& plan, hipStre
 
 // kernels_misc.hip
 // yuv: the batch holds at least one YUV 4:2:0 frame -> the YUV-capable instantiation of the front kernel (it serves the batch's BGR frames too)
+// lb: a letterbox engine (ZLY_FLAG_LETTERBOX) -> the letterbox instantiations of the front kernels and of the Detect tail (kernels_lb.hip)
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv = false);
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv = false, bool lb = false);
 hipError_t launch_nchw_to_nhwc8(int dtype, const float* in_nchw, void* out_nhwc8, int n, int tw, int th, hipStream_t s);
 hipError_t launch_sppf_pool(int dtype, void* buf, int cs, int c, int n, int H, int W, hipStream_t s, int six_pass = 0);      // six_pass: sppf_pool_kernel also on maps of <= 16 x 16 pixels (tests / A-B)
 bool       sppf_pool16_ok(int dtype, int cs, int c, int n, int H, int W, int six_pass);                        // does launch_sppf_pool take sppf_pool16_kernel?
@@ -131,7 +132,7 @@ struct StemArgs {
     void* out; int out_cs, out_co;
     int tw, th, Ho, Wo, Cout, tiles_x;
 };
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv = false);
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv = false, bool lb = false);
 int stem_tiles_x(int Wo);
 // preprocess + model.0 + model.1 in one kernel (the stem map stays in LDS); st.out is only written with dump = 1 (debug taps)
 struct Stem1Args {
@@ -151,7 +152,7 @@ struct Stem1Args {
 };
 void       stem1_plan(int H1, int W1, int* th, int* tw);
 hipError_t stem1_init();
-hipError_t launch_stem_model1(const Stem1Args& a, int n, hipStream_t s, bool yuv = false);
+hipError_t launch_stem_model1(const Stem1Args& a, int n, hipStream_t s, bool yuv = false, bool lb = false);
 const int* stem1_tap_slot();              // [9]: k slot of tap ky * 3 + kx in Stem1Args::wgt0p (weights.h: repack_conv's tap_slot)
 
 // kernels_sppf.hip -- SPPF (cv1 -> three 5x5 max pools -> cv2 over the concat) as one kernel; bf16, hidden width 128, maps of up to 176 pixels
@@ -193,6 +194,7 @@ struct HeadArgs {
     int diag;                                 // diagnostic builds only (tools/head_bench.hip); 0 in the product
     struct Cand* cand; int* cand_count;
     int buf32;                                // set by launch_head_fused: every level's branch tensors are below 2 GiB -> fragments by buffer loads (lane mask as an out-of-range offset)
+    int lb_tw, lb_th;                         // letterbox engine: the model size (boxes are mapped out of the letterbox, kernels_lb.hip's instantiations); 0 = stretch
 };
 hipError_t launch_head_fused(int dtype, const HeadArgs& a, int n, hipStream_t s);
 

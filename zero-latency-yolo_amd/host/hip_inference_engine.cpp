@@ -47,6 +47,13 @@ int32_t parseInputFormat(const char* v)
     if (std::strcmp(v, "i420_709") == 0) return ZLY_PIX_I420_BT709;
     return -1;
 }
+// ZLY_RESIZE: stretch (default: the reference's nearest-neighbour stretch), letterbox (ZLY_FLAG_LETTERBOX) -> 0 / 1, -1 = unknown
+int parseResizeMode(const char* v)
+{
+    if (!v || !*v || std::strcmp(v, "stretch") == 0) return 0;
+    if (std::strcmp(v, "letterbox") == 0) return 1;
+    return -1;
+}
 int envInt(const char* name, int fallback)
 {
     const char* v = std::getenv(name);
@@ -83,6 +90,12 @@ Result<void> HipInferenceEngine::initialize()
                                                                  std::getenv("ZLY_INPUT_FORMAT") + "'");
     if (input_format_ != ZLY_PIX_BGR && (!zly_submit_fmt || !zly_submit_try_fmt))
         return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_INPUT_FORMAT: the engine library has no zly_submit_fmt");
+    // ZLY_RESIZE: how every engine of this plugin (a hot reload's new ones included) fits a request into the model's input: the reference's
+    // stretch, or the aspect-preserving letterbox an Ultralytics-trained model expects (boxes then are normalised to the request frame itself)
+    const int resize = parseResizeMode(std::getenv("ZLY_RESIZE"));
+    if (resize < 0)
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_RESIZE must be stretch or letterbox, got '") + std::getenv("ZLY_RESIZE") + "'");
+    letterbox_ = resize == 1;
     const int ndev = simulate_ ? 0 : std::max(1, envInt("ZLY_NUM_DEVICES", 1));
     const int dev0 = std::max(0, envInt("ZLY_FIRST_DEVICE", 0));
     first_device_ = dev0;
@@ -152,7 +165,7 @@ std::shared_ptr<HipInferenceEngine::EngineHandle> HipInferenceEngine::createEngi
     c.warmup_runs = 3;                                   // onnx_engine.cpp:919-954
     c.use_graph = 1;
     // the server only consumes detections; one engine per GPU: NMS of a batch runs beside the next one; several: one chain each
-    c.flags = ZLY_FLAG_NO_HEAD_TENSOR | (engines_per_gpu_ > 1 ? ZLY_FLAG_SINGLE_CHAIN : ZLY_FLAG_ASYNC_NMS);
+    c.flags = ZLY_FLAG_NO_HEAD_TENSOR | (engines_per_gpu_ > 1 ? ZLY_FLAG_SINGLE_CHAIN : ZLY_FLAG_ASYNC_NMS) | (letterbox_ ? ZLY_FLAG_LETTERBOX : 0);
     zly_engine* e = nullptr;
     *rc = zly_create(&c, &e);
     if (*rc != ZLY_OK) { *msg = zly_last_error(); return nullptr; }
@@ -522,6 +535,7 @@ std::unordered_map<std::string, std::string> HipInferenceEngine::getStatus() con
     s["inference_errors"] = std::to_string(inference_errors_.load());
     s["dropped_frames"] = std::to_string(dropped_frames_.load());
     s["dynamic_batching"] = "enabled";
+    s["resize_mode"] = letterbox_ ? "letterbox" : "stretch";
     double avg = 0, p99 = 0;
     {
         std::lock_guard<std::mutex> lk(stats_mutex_);

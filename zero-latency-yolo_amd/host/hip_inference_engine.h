@@ -94,6 +94,7 @@ private:
     int first_device_ = 0;
     int engines_per_gpu_ = 1;
     int32_t input_format_ = 0;                             // ZLY_INPUT_FORMAT (read by initialize()): ZLY_PIX_* of every request's data (0 = BGR)
+    bool letterbox_ = false;                               // ZLY_RESIZE=letterbox (read by initialize()): every engine is created with ZLY_FLAG_LETTERBOX
     std::thread monitor_, completer_, reaper_;
     // Engines replaced by a hot reload are destroyed on the reaper thread: zly_destroy drains the engine's streams and takes the process-wide
     // exclusive gate, which must never stall callback delivery (the completion thread) or a submitting thread.

@@ -31,6 +31,8 @@ FLAG_NO_FUSION = 2
 FLAG_NO_HEAD_TENSOR = 4
 FLAG_ASYNC_NMS = 8
 FLAG_SINGLE_CHAIN = 16
+FLAG_LETTERBOX = 32          # per-engine resize mode: aspect-preserving bilinear letterbox (include/zly.h), boxes normalised to the request frame
+LETTERBOX_MAX_DIM = 16384    # largest request side (and model side) of a letterbox engine
 # pixel formats of a request frame (include/zly.h ZLY_PIX_*): packed BGR, or 8-bit YUV 4:2:0 (limited range) converted in the front kernel
 PIX_BGR, PIX_NV12_BT601, PIX_I420_BT601, PIX_NV12_BT709, PIX_I420_BT709 = 0, 1, 2, 3, 4
 
@@ -38,7 +40,7 @@ PIX_BGR, PIX_NV12_BT601, PIX_I420_BT601, PIX_NV12_BT709, PIX_I420_BT709 = 0, 1, 
 SYMBOLS = [
     "zly_default_config", "zly_create", "zly_destroy", "zly_last_error", "zly_version",
     "zly_detect", "zly_detect_batch", "zly_submit", "zly_submit_try", "zly_poll", "zly_wait", "zly_detect_device", "zly_slab_bytes", "zly_read_slabs", "zly_sync", "zly_join",
-    "zly_frame_bytes", "zly_detect_fmt", "zly_detect_batch_fmt", "zly_submit_fmt", "zly_submit_try_fmt", "zly_detect_device_fmt", "zly_preprocess_fmt",
+    "zly_frame_bytes", "zly_letterbox_geometry", "zly_detect_fmt", "zly_detect_batch_fmt", "zly_submit_fmt", "zly_submit_try_fmt", "zly_detect_device_fmt", "zly_preprocess_fmt",
     "zly_preprocess", "zly_forward", "zly_head_tensor", "zly_postprocess", "zly_debug_tap",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
@@ -113,6 +115,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_join.argtypes = [vp, vp, i32]; lib.zly_join.restype = i32
     lib.zly_preprocess.argtypes = [vp, vp, sz, i32, i32, vp]; lib.zly_preprocess.restype = i32
     lib.zly_frame_bytes.argtypes = [i32, i32, i32]; lib.zly_frame_bytes.restype = sz
+    lib.zly_letterbox_geometry.argtypes = [i32, i32, i32, i32, pi32, pi32, pi32, pi32]; lib.zly_letterbox_geometry.restype = i32
     lib.zly_detect_fmt.argtypes = [vp, i32, vp, sz, i32, i32, vp, i32, pi32]; lib.zly_detect_fmt.restype = i32
     lib.zly_detect_batch_fmt.argtypes = [vp, i32, pi32, C.POINTER(vp), C.POINTER(sz), pi32, pi32, vp, i32, pi32]; lib.zly_detect_batch_fmt.restype = i32
     lib.zly_submit_fmt.argtypes = [vp, i32, vp, sz, i32, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_fmt.restype = i32
@@ -140,6 +143,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 def frame_bytes(fmt: int, w: int, h: int) -> int:
     """bytes of one w x h frame of format fmt (PIX_*): 3wh for BGR, 3wh/2 for YUV 4:2:0; 0 for an unknown format or invalid sizes (host only)"""
     return int(load_library().zly_frame_bytes(fmt, w, h))
+
+
+def letterbox_geometry(w: int, h: int, model_w: int, model_h: int) -> Tuple[int, int, int, int]:
+    """(nw, nh, pad_x, pad_y): where a w x h request lands in the model_w x model_h tensor of a FLAG_LETTERBOX engine (host only)"""
+    lib = load_library()
+    o = [C.c_int32() for _ in range(4)]
+    _check(lib, lib.zly_letterbox_geometry(w, h, model_w, model_h, *[C.byref(x) for x in o]))
+    return tuple(int(x.value) for x in o)
 
 
 def _dims(frame: np.ndarray, fmt: int, w: Optional[int], h: Optional[int]) -> Tuple[int, int]:
