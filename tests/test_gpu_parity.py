@@ -390,7 +390,7 @@ def test_throughput_kernels_on_ragged_maps(weights_path, oracle, monkeypatch, w,
     want = ref.forward(torch.from_numpy(x)).numpy()
     e = zly.Engine(weights_path, model_w=w, model_h=h, max_batch=n, warmup_runs=0, flags=zly.FLAG_DUMP_LOGITS)
     # the switches must really have selected what the case is about (as process-static variables they were fixed by the first engine
-    # of the pytest process and these cases never switched kernels); the engine reads them per zly_create / per picked shape now
+    # of the pytest process and these cases never switched kernels); the engine reads them once, at zly_create
     kn = " | ".join(e.op_kernels(n))
     if "ZLY_NO_WS" in env:
         assert "conv3x3_ws_kernel<TPW" not in kn and "conv3x3_ws_kernel<ROWT" not in kn, kn
@@ -406,6 +406,11 @@ def test_throughput_kernels_on_ragged_maps(weights_path, oracle, monkeypatch, w,
     if "ZLY_NO_WS_S2" in env:
         assert "conv3x3_ws_kernel<S=2" not in kn, kn
     if env.get("ZLY_WS1") == "0":
+        assert "conv1x1_ws_kernel" not in kn, kn
+    # the forced fall-backs are planned as the kernels that run: the table names no weight-stationary kernel that would fall back at launch
+    if "ZLY_WS_MAX_BYTES" in env:
+        assert "conv3x3_ws_kernel<" not in kn, kn
+    if "ZLY_WS1_MAX_BYTES" in env:
         assert "conv1x1_ws_kernel" not in kn, kn
     if "ZLY_C2F64" in env:
         assert "c2f_kernel<C=64" in kn, kn

@@ -20,6 +20,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <string.h>
 #include <stdio.h>
@@ -93,8 +94,8 @@ struct Launch {
     int kind = LK_NONE;                // LK_NONE: the op's work is done inside the launch of op `covered_by`
     int covered_by = -1;               // index of the op whose launch does this op's work (the op itself when it launches)
     bool hbm = true;                   // the op's output reaches HBM (false: it stays in LDS inside a fused kernel; zly_debug_tap)
-    ConvLaunch conv{};                 // conv ops: the per-conv kernel shape, also when a fusion covers the op (zly_forward runs model.0 / model.1 on
-                                       // it; the K-packed launch falls back to it)
+    ConvPlan conv{};                   // conv ops: the per-conv launch (conv_plan), also when a fusion covers the op (zly_forward runs model.0 / model.1 on it)
+    WskPlan wsk{};                     // LK_CONV_WSK
     C2fPlan c2f{};                     // LK_C2F
     PairPlan pair{};                   // LK_PAIR
     int multi_ct = 0;                  // LK_MULTI: 3 = the three Detect stems, 2 = the six Detect branch convs
@@ -191,8 +192,7 @@ struct zly_engine {
     uint32_t cu_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::atomic<Ingest*> ingest{nullptr};   // created by the first zly_submit (under mu), read lock-free afterwards
 
-    // tuning / test switches of the environment, read ONCE at zly_create (they used to be read per launch)
-    struct Switches { bool no_c2f = false, no_det_merge = false, no_tail_split = false, no_lanes = false, nms_general = false, no_sppf = false, no_wsk = false, pool_six_pass = false; int stem1_nw = 0, stem1_var = 1, stem1_grid = 0, pair_min_tiles = 32, pair_widths = 48; std::string ablate; } sw;
+    Switches sw;                      // tuning / test switches of the environment, read ONCE at zly_create (read_switches; the list: zly_internal.h)
 
     std::mutex mu;                    // serialises every call that touches engine / device state
     mutable std::mutex stats_mu;      // guards `stats` only, never held across a device call: zly_get_stats cannot wait on a batch
@@ -204,6 +204,76 @@ namespace zly {
 static size_t slab_bytes_of(const zly_engine* e) { return sizeof(zly_slab_header) + (size_t)e->cfg.max_dets * sizeof(zly_det); }
 
 template <typename F> static void with_stats(zly_engine* e, F&& f) { std::lock_guard<std::mutex> lk(e->stats_mu); f(e->stats); }
+
+// The environment's tuning / test switches (zly_internal.h: Switches is the list).  The ONLY place that reads the environment: zly_create calls it
+// once, before the plan is built, and everything that plans or launches gets the record -- an engine never looks at the environment again.
+static void read_switches(Switches* sw)
+{
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    auto num = [](const char* name, auto* out) { if (const char* v = getenv(name)) *out = (std::remove_pointer_t<decltype(out)>)atoll(v); };
+    *sw = Switches();
+    if (const char* cp = getenv("ZLY_CU_PART")) {
+        int pi = 0, pn = 1;
+        if (sscanf(cp, "%d/%d", &pi, &pn) == 2 && pn >= 1 && pn <= 8 && pi >= 0 && pi < pn) { sw->cu_part_i = pi; sw->cu_part_n = pn; sw->num_cus = 256 / pn; }
+    }
+    sw->no_lanes = on("ZLY_NO_LANES") || on("ZLY_CU_PART");           // a CU partition runs one chain
+    sw->no_c2f = on("ZLY_NO_C2F");
+    sw->no_det_merge = on("ZLY_NO_DET_MERGE");
+    sw->no_tail_split = on("ZLY_NO_TAIL_SPLIT");
+    sw->sppf_fused = on("ZLY_SPPF_FUSED");
+    sw->pool_six_pass = on("ZLY_SPPF_POOL_LDS");
+    sw->no_wsk = on("ZLY_NO_WSK");
+    sw->nms_general = on("ZLY_NMS_GENERAL");
+    sw->no_cout_pad = on("ZLY_NO_COUT_PAD");
+    sw->no_cin_pad = on("ZLY_NO_CIN_PAD");
+    sw->no_stem1 = on("ZLY_NO_STEM1");
+    num("ZLY_STEM1_NW", &sw->stem1_nw);
+    num("ZLY_STEM1_VAR", &sw->stem1_var);
+    num("ZLY_STEM1_GRID", &sw->stem1_grid);
+    num("ZLY_STEM1_TW", &sw->stem1_tw);
+    num("ZLY_STEM1_TH", &sw->stem1_th);
+    sw->stem1_keep_tiles = on("ZLY_STEM1_TW") || on("ZLY_STEM1_TH") || on("ZLY_STEM1_BIG_TILES");
+    num("ZLY_PAIR_MIN_TILES", &sw->pair_min_tiles);
+    num("ZLY_PAIR_WIDTHS", &sw->pair_widths);
+    auto num_nonempty = [&](const char* name, int* out) { const char* v = getenv(name); if (v && *v) *out = atoi(v); };
+    num_nonempty("ZLY_STAGE_SLOTS", &sw->stage_slots);
+    num_nonempty("ZLY_STAGE_MB", &sw->stage_mb);
+    num_nonempty("ZLY_INFLIGHT", &sw->inflight);
+    { int d = 0; num_nonempty("ZLY_D2H_STREAM", &d); sw->d2h_stream = d != 0; }
+    num("ZLY_PROFILE_INNER", &sw->profile_inner);
+    if (sw->profile_inner < 1) sw->profile_inner = 1;
+#ifdef ZLY_DIAG
+    if (const char* v = getenv("ZLY_ABLATE_SKIP")) sw->ablate = std::string(",") + v + ",";       // result-changing: compiled into libzly_diag.so only (tools/ablate_launches.sh)
+#endif
+    sw->no_stream = on("ZLY_NO_STREAM");
+    sw->stream_ct2 = on("ZLY_STREAM_CT2");
+    num("ZLY_STREAM_MAX_NK", &sw->stream_max_nk);
+    num("ZLY_STREAM_MIN_GROUPS", &sw->stream_min_groups);
+    num("ZLY_STREAM_WGS", &sw->stream_wgs);
+    num("ZLY_WS1", &sw->ws1_mode);
+    sw->ws1_no_dual = on("ZLY_WS1_NO_DUAL");
+    num("ZLY_WS1_MIN_PX", &sw->ws1_min_px);
+    sw->ws1_max_bytes = on("ZLY_WS1_MAX_BYTES");
+    sw->no_ws = on("ZLY_NO_WS");
+    sw->no_ws_s2 = on("ZLY_NO_WS_S2");
+    sw->no_ws_s2_c32 = on("ZLY_NO_WS_S2_C32");
+    sw->ws_rowt = on("ZLY_WS_ROWT");
+    num("ZLY_WS_TPW1_MAXCT", &sw->ws_tpw1_maxct);
+    num("ZLY_WS_MIN_TILES", &sw->ws_min_tiles);
+    num("ZLY_WS_MAX_BYTES", &sw->ws_max_bytes);
+    sw->no_wres = on("ZLY_NO_WRES");
+    num("ZLY_WRES_MAXCHUNKS", &sw->wres_maxchunks);
+    sw->lds_s2_pt1 = on("ZLY_LDS_S2_PT1");
+    num("ZLY_LDS_MIN_TILES", &sw->lds_min_tiles);
+    num("ZLY_LDS_WGS_PER_CU", &sw->lds_wgs_per_cu);
+    num("ZLY_DIRECT_PT4_MIN", &sw->direct_pt4_min);
+    num("ZLY_DIRECT_PT2_MIN", &sw->direct_pt2_min);
+    num("ZLY_DIRECT_KSPLIT_NK", &sw->direct_ksplit_nk);
+    num("ZLY_C2F32_NW", &sw->c2f32_nw);
+    num("ZLY_C2F_LDS_KB", &sw->c2f_lds_kb);
+    if (const char* ft = getenv("ZLY_C2F_TILE")) { int th = 0, tw = 0; if (sscanf(ft, "%d,%d", &th, &tw) == 2) { sw->c2f_tile_th = th; sw->c2f_tile_tw = tw; } }
+    sw->c2f64 = on("ZLY_C2F64");
+}
 
 // ------------------------------------------------------------------------------------------------
 // plan
@@ -259,7 +329,7 @@ struct PlanBuilder {
         // 5 channel tiles (the 80-channel Detect class branch) suit no kernel's channel blocking: CT = 5 needs more registers than
         // two waves per SIMD leave.  One whole zero tile is appended instead (6 tiles = 2 blocks of CT = 3); its outputs are never
         // stored (channel >= Cout) -- 20 % more MFMAs on these layers, but the LDS-tiled kernel instead of the direct one.
-        if (e->dtype == ZLY_DTYPE_BF16 && op.ks == 3 && op.cout_pad == 80 && cin_total % 32 == 0 && getenv("ZLY_NO_COUT_PAD") == nullptr) {
+        if (e->dtype == ZLY_DTYPE_BF16 && op.ks == 3 && op.cout_pad == 80 && cin_total % 32 == 0 && !e->sw.no_cout_pad) {
             w.resize(w.size() + (size_t)op.nk * 1024, 0);
             b.resize(b.size() + 16, 0.0f);
             op.cout_pad = 96;
@@ -456,7 +526,7 @@ static int build_plan_host(zly_engine* e, PlanState* ps, std::string* err)
     if (e->stem_fused) ok = ok && pb.pack_only("model.0", 4, &stem_w, &stem_b, &stem_nk, ch[0] == 32) && stem_nk == 2;
     ok = ok && pb.conv({"model.1"}, View{a0, 0, ch[0]}, View{a1, 0, ch[1]});
     size_t m1_w = 0, m1_b = 0, stem_w0p = 0;
-    e->stem1 = e->stem_fused && ch[0] == 16 && ch[1] == 32 && !(e->cfg.flags & ZLY_FLAG_NO_FUSION) && getenv("ZLY_NO_STEM1") == nullptr && ok;
+    e->stem1 = e->stem_fused && ch[0] == 16 && ch[1] == 32 && !(e->cfg.flags & ZLY_FLAG_NO_FUSION) && !e->sw.no_stem1 && ok;
     if (e->stem1) {
         // model.1 in the fused kernel's tiling: one 16x16x16 MFMA per tap (k = ci), pair-permuted rows, bias in channel order
         const ConvRec* r = m.find("model.1");
@@ -521,7 +591,7 @@ static int build_plan_host(zly_engine* e, PlanState* ps, std::string* err)
         const std::string L = std::to_string(l);
         // the class branch's 80 channels are stored as 96 (16 zero channels, never written) so that its second 3x3 conv has
         // Cin % 32 == 0 and takes the LDS-tiled kernel; the padded k-steps carry zero weights
-        const int c3s = (e->dtype == ZLY_DTYPE_BF16 && c3 % 32 != 0 && c2 % 32 == 0 && getenv("ZLY_NO_CIN_PAD") == nullptr) ? (c3 + 31) / 32 * 32 : c3;
+        const int c3s = (e->dtype == ZLY_DTYPE_BF16 && c3 % 32 != 0 && c2 % 32 == 0 && !e->sw.no_cin_pad) ? (c3 + 31) / 32 * 32 : c3;
         const int hd1 = pb.add_buffer("detect." + L + ".stem", fh[l], fw[l], c2 + c3s);
         const int hb2 = pb.add_buffer("detect." + L + ".box2", fh[l], fw[l], c2);
         const int hc2 = pb.add_buffer("detect." + L + ".cls2", fh[l], fw[l], c3);
@@ -672,12 +742,12 @@ static int build_plan_device(zly_engine* e, PlanState* ps, std::string* err)
         s1.w1 = (const char*)e->d_weights + m1_w; s1.b1 = (const float*)((const char*)e->d_weights + m1_b);
         s1.out1 = e->bufs[(size_t)a1].ptr; s1.out1_cs = ch[1]; s1.out1_co = 0;
         s1.H1 = H4; s1.W1 = W4;
-        stem1_plan(H4, W4, &s1.TH, &s1.TW);
+        stem1_plan(H4, W4, e->sw, &s1.TH, &s1.TW);
         s1.tiles_x = (W4 + s1.TW - 1) / s1.TW; s1.tiles_y = (H4 + s1.TH - 1) / s1.TH;
         s1.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
         s1.wgt0p = (const char*)e->d_weights + stem_w0p;
         s1.nw = e->sw.stem1_nw; s1.var = e->sw.stem1_var; s1.pgrid = e->sw.stem1_grid;
-        s1.small_tiles = (getenv("ZLY_STEM1_TW") || getenv("ZLY_STEM1_TH") || getenv("ZLY_STEM1_BIG_TILES")) ? 0 : 1;      // tuning aids given: keep the planned shape at every batch size
+        s1.small_tiles = e->sw.stem1_keep_tiles ? 0 : 1;
     }
     for (Op& op : e->ops) {
         if (op.kind != OP_HEAD) continue;
@@ -730,6 +800,15 @@ static ConvArgs make_conv_args(zly_engine* e, const Op& op, int n)
     return a;
 }
 
+// ... and of an 80 -> 80 class-branch conv as the K-packed kernel sees it: 80 of the 96 stored input channels, weights tiled with cin_store = 80
+static ConvArgs make_wsk_args(zly_engine* e, const Op& op, int n)
+{
+    ConvArgs k = make_conv_args(e, op, n);
+    k.Cin = 80; k.K = 9 * 80; k.nk = 23; k.cout_pad = 80;
+    k.wgt = (const char*)e->d_weights + op.wsk_w;
+    return k;
+}
+
 // the fused SPPF kernel's arguments at batch n: model.9.cv1's input and weights, cv2's weights and output, the block's concat buffer
 static SppfArgs make_sppf_args(const zly_engine* e, int n)
 {
@@ -745,7 +824,7 @@ static SppfArgs make_sppf_args(const zly_engine* e, int n)
     sa.w2 = wb + o2.w_off; sa.b2 = (const float*)(wb + o2.b_off);
     sa.out = ob2.ptr; sa.out_cs = ob2.C; sa.out_co = o2.out.co; sa.Cout = o2.cout;
     sa.cat = cb.ptr; sa.cat_cs = cb.C;
-    sa.H = cb.H; sa.W = cb.W; sa.n = n; sa.c = op.cout; sa.split = 0;
+    sa.H = cb.H; sa.W = cb.W; sa.n = n; sa.c = op.cout; sa.split = sppf_split(o2.cout, n, e->sw);
     sa.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
     return sa;
 }
@@ -766,17 +845,17 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
     auto c2f_of = [&](const Op& G, C2fPlan* pl) {
         if (!G.c2f_mode || !fusion || e->sw.no_c2f) return false;
         const Buffer& b = e->bufs[(size_t)G.c2f_cat];
-        return c2f_plan(G.c2f_c, G.c2f_mode, G.c2f_nk1, G.c2f_nk2, G.c2f_cout2, n, b.H, b.W, pl);
+        return c2f_plan(G.c2f_c, G.c2f_mode, G.c2f_nk1, G.c2f_nk2, G.c2f_cout2, n, b.H, b.W, e->sw, pl);
     };
     // the fused bottleneck pair at its first conv A.  Only degenerate launches (a handful of tiles) stay on the per-conv kernels: at batch 1
     // (91 / 234 tiles) one fused launch beats two per-conv launches, 4370 -> 4475 fps.  Width 64 is built and tested, but no faster than two launches.
     auto pair_of = [&](const Op& A, PairPlan* pl) {
         if (A.pair != 1 || !fusion || !(e->sw.pair_widths & A.pair_c)) return false;
         const Buffer& b = e->bufs[(size_t)A.in.buf];
-        return pair_plan(A.pair_c, n, b.H, b.W, pl) && pl->total_tiles >= e->sw.pair_min_tiles;
+        return pair_plan(A.pair_c, n, b.H, b.W, e->sw, pl) && pl->total_tiles >= e->sw.pair_min_tiles;
     };
     // SPPF as one launch at model.9.cv1 (opt-in, ZLY_SPPF_FUSED=1); the pool and cv2 then launch nothing
-    bool sppf = fusion && !e->sw.no_sppf && e->sppf_cv1 >= 0;
+    bool sppf = fusion && e->sw.sppf_fused && e->sppf_cv1 >= 0;
     if (sppf) {
         const Op& a = e->ops[(size_t)e->sppf_cv1];
         const Op& b = e->ops[(size_t)e->sppf_cv2];
@@ -826,12 +905,7 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
             L.kind = LK_NMS;
             break;
         case OP_CONV: {
-            const Buffer& ob = e->bufs[(size_t)op.out.buf];
-            const int cin = op.in.C + (op.in2.buf >= 0 ? op.in2.C : 0);
-            conv_pick_config(e->dtype, op.ks, op.stride, cin, op.cout_pad, n, ob.H, ob.W, &L.conv,
-                             op.in2.buf < 0 && op.res.buf < 0 && op.act && !op.out_f32 && op.cout % 32 == 0,
-                             op.in2.buf < 0 && !op.out_f32 && op.act,
-                             op.in2.buf >= 0 && op.ks == 1 && op.res.buf < 0 && op.act && !op.out_f32 && op.cout % 32 == 0 && op.cout_pad == op.cout);
+            conv_plan(e->dtype, op.ks, make_conv_args(e, op, n), e->sw, &L.conv);
             C2fPlan cp{};
             PairPlan pp{};
             if (i == 1 && e->stem_fused) {
@@ -856,7 +930,7 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
                 L.hbm = false;                                              // the intermediate map stays in LDS
             } else if (op.pair == 2 && pair_of(e->ops[(size_t)i - 1], &pp)) {
                 covered(i - 1);
-            } else if (op.wsk_w && !e->sw.no_wsk && bf16 && op.act && conv_wsk_ok(80, op.cout, n, ob.H, ob.W)) {
+            } else if (op.wsk_w && !e->sw.no_wsk && bf16 && conv_wsk_ok(make_wsk_args(e, op, n), e->sw, &L.wsk)) {
                 L.kind = LK_CONV_WSK;
             } else {
                 L.kind = LK_CONV;
@@ -923,17 +997,9 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
         return launch_stem_model1(st, n, s, e->front_yuv, L.lb);
     }
     case LK_CONV:
-    case LK_CONV_WSK: {
-        const ConvArgs a = make_conv_args(e, op, n);
-        if (L.kind == LK_CONV_WSK) {
-            ConvArgs k = a;
-            k.Cin = 80; k.K = 9 * 80; k.nk = 23; k.cout_pad = 80;
-            k.wgt = wb + op.wsk_w;
-            const hipError_t r = launch_conv_wsk(k, s);
-            if (r != hipErrorInvalidValue) return r;             // a tensor beyond the kernel's 32-bit offsets takes the generic path below
-        }
-        return launch_conv(e->dtype, a, L.conv, s);
-    }
+        return launch_conv(make_conv_args(e, op, n), L.conv, s);
+    case LK_CONV_WSK:
+        return launch_conv_wsk(make_wsk_args(e, op, n), L.wsk, s);
     case LK_MULTI: {
         ConvArgsMulti m{};
         for (int l = 0; l < 3; ++l) {
@@ -1384,8 +1450,6 @@ struct Ingest {
 // compute stream stalled A for a whole 33 MB transfer.  Uploads of different engines share the PCIe link anyway.
 static hipStream_t g_h2d_stream[16] = {}, g_d2h_stream[16] = {};
 
-static int env_int(const char* name, int fallback) { const char* v = getenv(name); return (v && *v) ? atoi(v) : fallback; }
-
 // under ing->mu: make the next ring slot the open one if it is free
 static bool ingest_try_open(zly_engine* e, Ingest* g)
 {
@@ -1510,16 +1574,16 @@ static int ingest_start(zly_engine* e)
     // six slots (round 4; four before): two batches on the device, one filling, and three whose results wait for their consumer.  A host that delivers results
     // in submission order across several engines (the plugin) consumes an engine's finished batch only when the other engines' earlier frames are back as
     // well; with four slots that wait reached the submitters as back-pressure (plugin 78 - 91 k frames/s from run to run; six: 93 k beside the C ABI's 96 k)
-    const int S = std::max(3, std::min(16, env_int("ZLY_STAGE_SLOTS", 6)));
+    const int S = std::max(3, std::min(16, e->sw.stage_slots));
     const size_t frame = (size_t)e->cfg.model_w * e->cfg.model_h * 3;
     size_t bytes = (size_t)((double)e->cfg.max_batch * (double)frame * 1.25);
     if (bytes < (8u << 20)) bytes = 8u << 20;
-    if (env_int("ZLY_STAGE_MB", 0) > 0) bytes = (size_t)env_int("ZLY_STAGE_MB", 0) << 20;
+    if (e->sw.stage_mb > 0) bytes = (size_t)e->sw.stage_mb << 20;
     g->slot_bytes = (bytes + 4095) / 4096 * 4096;
-    g->depth = std::max(1, std::min(S - 2, env_int("ZLY_INFLIGHT", 2)));
+    g->depth = std::max(1, std::min(S - 2, e->sw.inflight));
     g->slots.resize((size_t)S);
     const int dv = e->dev & 15;
-    g->use_d2h_stream = env_int("ZLY_D2H_STREAM", 0) != 0;
+    g->use_d2h_stream = e->sw.d2h_stream;
     bool ok = (g_h2d_stream[dv] || hipStreamCreateWithFlags(&g_h2d_stream[dv], hipStreamNonBlocking) == hipSuccess) &&
               (!g->use_d2h_stream || g_d2h_stream[dv] || hipStreamCreateWithFlags(&g_d2h_stream[dv], hipStreamNonBlocking) == hipSuccess);
     g->copy_stream = g_h2d_stream[dv]; g->d2h_stream = g_d2h_stream[dv];
@@ -1768,22 +1832,7 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
     e->dev = cfg->device;
     e->dtype = cfg->dtype;
     e->esz = cfg->dtype == ZLY_DTYPE_BF16 ? 2 : 4;
-    e->sw.no_c2f = getenv("ZLY_NO_C2F") != nullptr;
-#ifdef ZLY_DIAG
-    if (const char* v = getenv("ZLY_ABLATE_SKIP")) e->sw.ablate = std::string(",") + v + ",";       // result-changing: compiled into libzly_diag.so only (tools/ablate_launches.sh)
-#endif
-    e->sw.no_det_merge = getenv("ZLY_NO_DET_MERGE") != nullptr;
-    e->sw.no_tail_split = getenv("ZLY_NO_TAIL_SPLIT") != nullptr;
-    e->sw.no_lanes = getenv("ZLY_NO_LANES") != nullptr || getenv("ZLY_CU_PART") != nullptr;
-    e->sw.no_sppf = getenv("ZLY_SPPF_FUSED") == nullptr;                         // the fused SPPF kernel is OPT-IN (ZLY_SPPF_FUSED=1): parity-green, 36 -> ~24 us in isolation at batch 64, but the step gets 0.5 % slower
-    e->sw.pool_six_pass = getenv("ZLY_SPPF_POOL_LDS") != nullptr;                 // tuning / tests: SPPF's pools on the six-pass LDS kernel also on small maps
-    e->sw.no_wsk = getenv("ZLY_NO_WSK") != nullptr;                               // tuning / tests: the class-branch convs on the LDS-tiled kernel (96-channel padding)
-    e->sw.nms_general = getenv("ZLY_NMS_GENERAL") != nullptr;                     // tests / A-B: every frame on NMS's eight-wave path
-    if (const char* v = getenv("ZLY_STEM1_NW")) e->sw.stem1_nw = atoi(v);           // tuning aids: waves per workgroup of the front kernel (12 / 16), ...
-    if (const char* v = getenv("ZLY_STEM1_GRID")) e->sw.stem1_grid = atoi(v);       // ... workgroups of its persistent grid ...
-    if (const char* v = getenv("ZLY_STEM1_VAR")) e->sw.stem1_var = atoi(v);         // ... and 0 = round 3's staging / tap order (A/B on one box)
-    if (const char* v = getenv("ZLY_PAIR_MIN_TILES")) e->sw.pair_min_tiles = atoi(v);   // tuning / tests: force the fused bottleneck pair onto small launches
-    if (const char* v = getenv("ZLY_PAIR_WIDTHS")) e->sw.pair_widths = atoi(v);         // bit mask of fused pair widths (16 | 32 | 64)
+    read_switches(&e->sw);
     std::string err;
     int rc = load_zlyw(e->weights_path.c_str(), &e->model, &err);        // host only: file parse
     if (rc != ZLY_OK) { delete e; return fail(rc, err); }
@@ -1805,15 +1854,9 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
         // ZLY_CU_PART="i/n": this engine's streams only use the i-th of n equal slices of the chip's compute units (spatial
         // partitioning: several engines run side by side, the launch-latency-bound small-map layers of one beside the
         // bandwidth-bound layers of another).  Experiment switch: see DESIGN.md section 5.
-        if (const char* cp = getenv("ZLY_CU_PART")) {
-            int pi = 0, pn = 1;
-            if (sscanf(cp, "%d/%d", &pi, &pn) == 2 && pn >= 1 && pn <= 8 && pi >= 0 && pi < pn) {
-                e->cu_part_n = pn;
-                const int per = 256 / pn;
-                for (int b = pi * per; b < (pi + 1) * per; ++b) e->cu_mask[b / 32] |= 1u << (b % 32);
-                set_num_cus(per);
-            }
-        }
+        e->cu_part_n = e->sw.cu_part_n;
+        if (e->cu_part_n > 1)
+            for (int b = e->sw.cu_part_i * e->sw.num_cus; b < (e->sw.cu_part_i + 1) * e->sw.num_cus; ++b) e->cu_mask[b / 32] |= 1u << (b % 32);
         auto make_stream = [&](hipStream_t* st) {
             if (e->cu_part_n > 1) return hipExtStreamCreateWithCUMask(st, 8, e->cu_mask) == hipSuccess;
             return hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess;
@@ -2337,7 +2380,7 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
     case LK_STEM: k = L.lb ? "stem_fused_kernel<LB> (letterbox)" : "stem_fused_kernel"; break;
     case LK_STEM1: k = L.lb ? "stem_model1_kernel<LB> (letterbox preprocess+model.0+model.1)" : "stem_model1_kernel (preprocess+model.0+model.1)"; break;
     case LK_SPPF_POOL: k = L.pool16 ? "sppf_pool16_kernel<DPP row windows, one barrier>" : "sppf_pool_kernel"; break;
-    case LK_SPPF_FUSED: k = "sppf_fused_kernel<cv1+3 pools+cv2,SPLIT=" + std::to_string(sppf_split(e->ops[(size_t)e->sppf_cv2].cout, n)) + ">"; break;
+    case LK_SPPF_FUSED: k = "sppf_fused_kernel<cv1+3 pools+cv2,SPLIT=" + std::to_string(sppf_split(e->ops[(size_t)e->sppf_cv2].cout, n, e->sw)) + ">"; break;
     case LK_MULTI: k = L.multi_ct == 3 ? "conv_igemm_multi_kernel<CT=3> (the 3 Detect stems)" : "conv_igemm_multi_kernel<CT=2> (the 6 Detect branch convs)"; break;
     case LK_C2F:
         k = "c2f_kernel<C=" + std::to_string(op.c2f_c) + (op.c2f_c == 32 ? ",NW=" + std::to_string(L.c2f.nw) : std::string()) +
@@ -2347,13 +2390,15 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
     case LK_CONV_WSK: k = "conv3x3_wsk_kernel<K=720 packed across taps,5 channel tiles>"; break;
     case LK_CONV: {
         const int cin = op.in.C + (op.in2.buf >= 0 ? op.in2.C : 0);
-        const ConvLaunch& c = L.conv;
-        if (c.ws1) k = std::string("conv1x1_ws_kernel<") + (op.in2.buf >= 0 ? "dual-source," : "") + "NK=" + std::to_string(cin / 32) + "," + std::to_string(c.ct) + " channel tiles," + std::to_string(c.pt * 16) + " px>";
-        else if (c.ps) k = std::string("conv3x3_ws_kernel<") + (op.stride == 2 ? "S=2," : "") + (c.rowt ? "ROWT," : "") + (c.tpw1 ? "TPW=1," : "TPW=2,") + std::to_string(c.ct) + " channel tiles>";
-        else if (c.lds) k = "conv3x3_lds_kernel<S=" + std::to_string(op.stride) + ",CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + (c.wres ? ",wres>" : ">");
-        else if (c.stream) k = "conv1x1_stream_kernel<CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + ",NK=" + std::to_string((cin + 31) / 32) + ">";
-        else k = std::string("conv_igemm_kernel<") + (op.ks == 1 ? (op.in2.buf >= 0 ? "1x1 dual-source" : "1x1") : (c.fastk ? "3x3" : "3x3 generic-K")) +
+        const ConvPlan& c = L.conv;
+        switch (c.kind) {
+        case CONV_WS1: k = std::string("conv1x1_ws_kernel<") + (op.in2.buf >= 0 ? "dual-source," : "") + "NK=" + std::to_string(cin / 32) + "," + std::to_string(c.ct) + " channel tiles," + std::to_string(c.pt * 16) + " px>"; break;
+        case CONV_WS: k = std::string("conv3x3_ws_kernel<") + (op.stride == 2 ? "S=2," : "") + (c.rowt ? "ROWT," : "") + (c.tpw1 ? "TPW=1," : "TPW=2,") + std::to_string(c.ct) + " channel tiles>"; break;
+        case CONV_LDS: k = "conv3x3_lds_kernel<S=" + std::to_string(op.stride) + ",CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + (c.wres ? ",wres>" : ">"); break;
+        case CONV_STREAM: k = "conv1x1_stream_kernel<CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + ",NK=" + std::to_string((cin + 31) / 32) + ">"; break;
+        default: k = std::string("conv_igemm_kernel<") + (op.ks == 1 ? (op.in2.buf >= 0 ? "1x1 dual-source" : "1x1") : (c.fastk ? "3x3" : "3x3 generic-K")) +
                  ",CT=" + std::to_string(c.ct) + ",PT=" + std::to_string(c.pt) + ",KSPLIT=" + std::to_string(c.ksplit) + ">";
+        }
         break;
     }
     case LK_HEAD: k = L.lb ? "head_fused_kernel<LB> (letterbox box mapping)" : "head_fused_kernel"; break;
@@ -2446,8 +2491,10 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
     // ZLY_PROFILE_INNER=k: every op is launched k times back to back between its two events, and the time is
     // divided by k -- the in-sequence cost of a launch (kernel + boundary) without the ~5 us that an event pair
     // per launch adds; used to study the batch-1 path, where most kernels are shorter than that
-    int inner = 1;
-    if (const char* v = getenv("ZLY_PROFILE_INNER")) inner = atoi(v) > 0 ? atoi(v) : 1;
+    // (read per call, not per engine: bench.py changes it between two calls on one engine)
+    Switches now;
+    read_switches(&now);
+    const int inner = now.profile_inner;
     for (int r = 0; r < reps && rcode == ZLY_OK; ++r) {
         hipEventRecord(ev[0], e->stream);
         for (size_t i = 0; i < nops; ++i) {

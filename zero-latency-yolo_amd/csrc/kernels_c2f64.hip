@@ -403,14 +403,14 @@ static const C64Variant* c64_pick(int mode, int nk1, int nk2)
 
 // tile shape: TW + 2 <= 16 (a region row is one MFMA pixel tile), phase A <= 3 and phase D <= 2 pixel tiles per wave, LDS budget; among those
 // the least (rounds of tiles over the CUs) x (MFMAs on the busiest wave per tile + a fixed per-tile cost: weight loads, barriers)
-bool c2f64_plan(int mode, int nk1, int nk2, int cout2, int n, int H, int W, C2fPlan* plan)
+bool c2f64_plan(int mode, int nk1, int nk2, int cout2, int n, int H, int W, const Switches& sw, C2fPlan* plan)
 {
     const C64Variant* v = c64_pick(mode, nk1, nk2);
     // OFF unless ZLY_C2F64 is set: measured (profiles/r03_c2f64_*): model.12 62 -> 57 us, model.18 59 -> 42, model.6 88 -> 56 at batch 64, but
     // the step with three engines gets SLOWER (0.676 -> 0.695 ms): one 121-142 KB workgroup per CU for 40-57 us keeps the other chains' kernels
     // off the CU, which the four short launches it replaces did not; batch 1: 0.205 -> 0.225 ms (35 workgroups of 4 x 6 pixels, 17 us each)
-    if (!v || ((mode & 2) && cout2 != 128) || !getenv("ZLY_C2F64")) return false;
-    const int ncu = num_cus();
+    if (!v || ((mode & 2) && cout2 != 128) || !sw.c2f64) return false;
+    const int ncu = sw.num_cus;
     double best = 1e30;
     for (int th = 4; th <= 16; ++th)
         for (int tw = 6; tw <= 14; ++tw) {

@@ -223,7 +223,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a)
         int ox, oy, b;
         if constexpr (KSPLIT > 1) {
             // split-K form (small M by construction): (b, oy, ox) by reciprocal multiplies -- exact for m < 2^20 and maps of < 2^10 pixels a side, which
-            // launch_conv checks -- instead of two emulated 32-bit divisions in front of the first load of a ~3 us launch
+            // the planner checks (plan_direct) -- instead of two emulated 32-bit divisions in front of the first load of a ~3 us launch
             const int r = (int)(((float)mm + 0.5f) * a.inv_wo);
             ox = mm - r * a.Wo;
             b = (int)(((float)r + 0.5f) * a.inv_ho);
@@ -253,7 +253,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a)
     const T* __restrict__ wp = static_cast<const T*>(a.wgt) +
                                (size_t)(blockIdx.y * CT) * a.nk * WTILE + lane * EPL;
 
-    // split-K form: inputs through buffer resources (32-bit byte offsets: launch_conv sends tensors of 2 GiB or more to the KSPLIT = 1 shapes)
+    // split-K form: inputs through buffer resources (32-bit byte offsets: the planner sends tensors of 2 GiB or more to the KSPLIT = 1 shapes)
     const __amdgpu_buffer_rsrc_t rin1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(in), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rin2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(in2 ? in2 : in), 0, 0x7fffffff, 0x00020000);
     (void)rin1; (void)rin2;
@@ -591,35 +591,19 @@ static conv_stream_fn pick_stream(int ct, int pt, int nk)
     return nullptr;
 }
 
-// Fragment reads of the tap loop are software-pipelined ZLY_TAPS_DEPTH taps ahead of the MFMAs that consume them
-// (statically indexed fragment sets) and pinned with sched_barrier.  Left to itself hipcc issues each tap's
-// ds_reads 1-2 instructions before its MFMAs with lgkmcnt(0/1) waits in between.  Measured with the stamped
-// build (tools/diag_lds.hip): tap phase 2100 -> 1700 cycles per item at depth 1; depth 2 costs VGPRs (occupancy)
-// for no further gain; 0 = compiler schedule.
-#ifndef ZLY_TAPS_DEPTH
-#define ZLY_TAPS_DEPTH 1
-#endif
 #ifndef ZLY_LDS_MIN_WAVES
 #define ZLY_LDS_MIN_WAVES 2      // waves per SIMD the register allocation must allow (= resident workgroups per CU of this 4-wave kernel)
 #endif
-#ifndef ZLY_LDS_WDMA
-#define ZLY_LDS_WDMA 1           // per-item weight tiles go global -> LDS by LDS-DMA (buffer_load ... lds): no register round trip, no ds_write;
-                                 // 186 -> 133 registers for the CT=4 x PT=2 variant (3 resident workgroups per CU), +3 % on the whole step.  0 = through registers
-#endif
-#ifndef ZLY_LDS_DEPTH
-#define ZLY_LDS_DEPTH 1          // items of global loads in flight ahead of the one being computed.  2 (a second register set,
-                                 // +48..60 VGPRs) was needed while the kernel ran one workgroup per CU; with two or three resident
-                                 // workgroups covering each other it measures the same (tools/diag_lds.hip, -DZLY_LDS_DEPTH=2)
-#endif
-#ifndef ZLY_TAPS_PIN
-#define ZLY_TAPS_PIN 1
-#endif
-#if ZLY_TAPS_DEPTH > 0
+// The 9 taps of one staged chunk.  Fragment reads are software-pipelined one tap ahead of the MFMAs that consume them (statically
+// indexed fragment sets) and pinned with sched_barrier.  What the variants that are no longer built measured (tools/diag_lds.hip):
+//   * the compiler's own schedule (each tap's ds_reads 1-2 instructions before its MFMAs, lgkmcnt(0/1) waits in between): tap phase
+//     2100 cycles per item against 1700 for this one; the same pipeline without the sched_barriers fell back to that schedule;
+//   * two taps ahead: more VGPRs (occupancy) for no further gain.
 template <int CT, int PT, int S, int PW, int PITCH>
 __device__ __forceinline__ void taps_mma(const unsigned char* lpatch, const unsigned char* lw, int lane, int row0, int p, int kq,
                                          f32x4 (&acc)[CT][PT])
 {
-    constexpr int D = ZLY_TAPS_DEPTH;
+    constexpr int D = 1;
     bf16x8 wf[D + 1][CT], af[D + 1][PT];
     const unsigned char* wl = lw + lane * 16;
     const unsigned char* al = lpatch + ((row0 * S) * PW + p * S) * PITCH + kq * 16;
@@ -635,19 +619,14 @@ __device__ __forceinline__ void taps_mma(const unsigned char* lpatch, const unsi
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
         if (t + D < 9) rd(t + D, wf[(t + D) % (D + 1)], af[(t + D) % (D + 1)]);
-#if ZLY_TAPS_PIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int cc = 0; cc < CT; ++cc)
 #pragma unroll
             for (int i = 0; i < PT; ++i) acc[cc][i] = mma_step(wf[t % (D + 1)][cc], af[t % (D + 1)][i], acc[cc][i]);
-#if ZLY_TAPS_PIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
     }
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // 3x3 convolution, LDS-tiled (bf16, Cin % 32 == 0, pad 1, stride S): the throughput kernel.
@@ -659,9 +638,15 @@ __device__ __forceinline__ void taps_mma(const unsigned char* lpatch, const unsi
 //     conflict-free for the ds_read_b128 fragment pattern (tests/lds_pitch.py), zero-filled outside the frame
 //   * the 9 x CT weight tiles (1 KiB each, already in MFMA lane order)                     -> LDS
 // once, and all 9 taps x CT x PT MFMAs of the 4 waves read their fragments from LDS.
-// Workgroups are persistent over (tile, chunk) items: the global loads of item i+1 are issued into
-// registers before the MFMAs of item i and written to LDS after them (one LDS buffer, so two
-// workgroups fit per CU and cover each other's barriers).
+// Workgroups are persistent over (tile, chunk) items: the patch loads of item i+1 are issued into
+// registers before the MFMAs of item i and written to LDS after them (one LDS buffer, so two or three
+// workgroups fit per CU and cover each other's barriers).  The weight tiles of item i+1 go global -> LDS
+// by LDS-DMA (buffer_load ... lds: no register round trip, no ds_write) behind the taps of item i, or
+// stay resident for the whole launch (wres).  Variants that are no longer built:
+//   * weights staged through registers like the patch: 186 instead of 133 registers for CT=4 x PT=2 (two
+//     instead of three resident workgroups per CU), the whole step 3 % slower;
+//   * a second register set, i.e. two items of global loads in flight (+48..60 VGPRs): needed while the
+//     kernel ran one workgroup per CU; with two or three covering each other it measured the same.
 // ------------------------------------------------------------------------------------------------
 
 template <int S, int PT> struct LdsGeom {
@@ -679,7 +664,7 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
     constexpr int NPU = G::PH * G::PW * 4;            // 16-byte units in the patch chunk
     constexpr int NPU_T = (NPU + 255) / 256;
     constexpr int NWU = 9 * CT * 64;                  // 16-byte units in the weight chunk
-    constexpr int NWU_T = (NWU + 255) / 256;
+    constexpr int NWU_T = (NWU + 255) / 256;          // ... per thread (resident weights only)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* lpatch = smem;
     unsigned char* lw = smem + G::PATCH_BYTES;
@@ -713,7 +698,6 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
     // 2/3 of the bytes staged per item (staging costs ~1/64 + 1/79 cycles per byte per CU): with them resident a
     // 64 -> 64 layer runs as 2 channel blocks of CT = 2 that stage 17 KB per item instead of one block staging 54 KB.
     const bool w_once = wres != 0;
-    bool w_staged = w_once;
     if (w_once) {
         for (int c = 0; c < nchunks; ++c) {
             const bf16_t* wc = wbase + c * 512;
@@ -724,6 +708,8 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
             }
         }
     }
+    // (rw: the register set the weights went through before LDS-DMA.  Nothing reads or writes it any more; the parameter stays because without
+    // it hipcc swaps two scalar moves of the item loop in 11 of the 20 variants, and this kernel's code is kept instruction for instruction.)
     auto stage_load = [&](int tl, int c, u32x4 (&rp)[NPU_T], u32x4 (&rw)[NWU_T]) {
         const int b = tl / tiles_per_img;
         const int r = tl - b * tiles_per_img;
@@ -738,23 +724,12 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
                 v = *reinterpret_cast<const u32x4*>(inb + usrc[i]);
             rp[i] = v;
         }
-        if (w_once || ZLY_LDS_WDMA) return;                   // weights are resident / moved by LDS-DMA
-        const bf16_t* wc = wbase + c * 512;
-#pragma unroll
-        for (int i = 0; i < NWU_T; ++i) rw[i] = *reinterpret_cast<const u32x4*>(wc + uwsrc[i]);
     };
-    auto stage_store = [&](const u32x4 (&rp)[NPU_T], const u32x4 (&rw)[NWU_T]) {
+    auto stage_store = [&](const u32x4 (&rp)[NPU_T]) {
 #pragma unroll
         for (int i = 0; i < NPU_T; ++i) {
             const int u = tid + i * 256;
             if (u < NPU) *reinterpret_cast<u32x4*>(lpatch + (u >> 2) * PITCH + (u & 3) * 16) = rp[i];
-        }
-        if ((w_once && w_staged) || ZLY_LDS_WDMA) return;
-        w_staged = true;
-#pragma unroll
-        for (int i = 0; i < NWU_T; ++i) {
-            const int u = tid + i * 256;
-            if (u < NWU) *reinterpret_cast<u32x4*>(lw + u * 16) = rw[i];
         }
     };
 
@@ -764,7 +739,6 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
 #pragma unroll
         for (int t = 0; t < PT; ++t) acc[c][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#if ZLY_LDS_WDMA
     // LDS-DMA of one chunk's weight tiles: tile ti = tap * CT + ct is one contiguous KiB in lane order on both sides; wave w
     // moves tiles w, w+4, ...; completion is the wave's vmcnt, visibility the workgroup barrier that follows
     const __amdgpu_buffer_rsrc_t rwgt = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(wbase), 0, (unsigned)(CT * a.nk * 1024), 0x00020000);
@@ -779,7 +753,6 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
             }
         }
     };
-#endif
     f32x4 biasr[CT];
     load_bias<CT>(a, blockIdx.y * CT, kq, biasr);
     const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)((size_t)a.M * a.out_cs * 2), 0x00020000);
@@ -792,38 +765,15 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
 #endif
     // 9 taps of one staged chunk; the epilogue runs after a tile's last chunk
     bool dma_next_valid = false; int dma_next_c = 0;
-    (void)dma_next_valid; (void)dma_next_c;
     auto compute = [&](int tl, int c) {
-#if ZLY_TAPS_DEPTH > 0
         taps_mma<CT, PT, S, PW, PITCH>(lpatch, w_once ? lw + (size_t)c * (NWU * 16) : lw, lane, wave * PT, p, kq, acc);
-#else
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int ky = t / 3, kx = t - ky * 3;
-            bf16x8 wf[CT], af[PT];
-#pragma unroll
-            for (int cc = 0; cc < CT; ++cc)
-                wf[cc] = *reinterpret_cast<const bf16x8*>((w_once ? lw + (size_t)c * (NWU * 16) : lw) + (t * CT + cc) * 1024 + lane * 16);
-#pragma unroll
-            for (int i = 0; i < PT; ++i) {
-                const int row = wave * PT + i;
-                af[i] = *reinterpret_cast<const bf16x8*>(lpatch + ((row * S + ky) * PW + p * S + kx) * PITCH + kq * 16);
-            }
-#pragma unroll
-            for (int cc = 0; cc < CT; ++cc)
-#pragma unroll
-                for (int i = 0; i < PT; ++i) acc[cc][i] = mma_step(wf[cc], af[i], acc[cc][i]);
-        }
-#endif
 #ifdef ZLY_DIAG
         ZPHASE(3);
 #endif
-#if ZLY_LDS_WDMA
         if (!w_once) {
             __syncthreads();                                   // every wave is done reading this item's weights and patch
             if (dma_next_valid) dma_weights(dma_next_c);       // the next item's weights land during the epilogue / patch store
         }
-#endif
         if (c != nchunks - 1) return;
         // epilogue for tile tl (see epilogue_px)
         const int b = tl / tiles_per_img;
@@ -841,21 +791,14 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
         }
     };
 
-    // item stream of this workgroup: (tile, chunk) with tile = blockIdx.x + k * gridDim.x; two items are
-    // always in flight in registers (sets A and B) ahead of the one being computed from LDS
+    // item stream of this workgroup: (tile, chunk) with tile = blockIdx.x + k * gridDim.x; the patch of the next item is
+    // in flight in registers while the current one is computed from LDS
     auto advance = [&](int& tl, int& c) { if (++c == nchunks) { c = 0; tl += gridDim.x; } };
     int t0 = blockIdx.x, c0 = 0;                 // item being computed
     if (t0 >= total_tiles) return;
     int t1 = t0, c1 = c0; advance(t1, c1);       // next item
-    int t2 = t1, c2 = c1; advance(t2, c2);       // the one after
-#if ZLY_LDS_DEPTH == 1
-    u32x4 rpA[NPU_T], rwA[NWU_T];
-    stage_load(t0, c0, rpA, rwA);
-#else
-    u32x4 rpA[NPU_T], rwA[NWU_T], rpB[NPU_T], rwB[NWU_T];
-    stage_load(t0, c0, rpA, rwA);
-    if (t1 < total_tiles) stage_load(t1, c1, rpB, rwB);
-#endif
+    u32x4 rp[NPU_T], rw[NWU_T];
+    stage_load(t0, c0, rp, rw);
 #ifdef ZLY_DIAG
     // diagnostic build only (tools/diag_lds.hip): per-wave cycle sums of the phases of an item, written to the
     // buffer passed in a.in2 (unused by 3x3 convs): [store+wait, barrier, load issue, taps+epilogue, barrier, items]
@@ -866,28 +809,19 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
 #else
 #define ZPHASE(k) do { } while (0)
 #endif
-#if ZLY_LDS_DEPTH == 1
-#if ZLY_LDS_WDMA
     if (!w_once) dma_weights(c0);
-#endif
     while (true) {
-        stage_store(rpA, rwA);
-#if ZLY_LDS_WDMA
+        stage_store(rp);
         if (!w_once) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this item's weight DMA (and whatever was issued after it) has landed
-#endif
         ZPHASE(0);
         __syncthreads();
         ZPHASE(1);
-        if (t1 < total_tiles) stage_load(t1, c1, rpA, rwA);
+        if (t1 < total_tiles) stage_load(t1, c1, rp, rw);
         ZPHASE(2);
         dma_next_valid = t1 < total_tiles; dma_next_c = c1;
         compute(t0, c0);
         ZPHASE(5);
-#if ZLY_LDS_WDMA
         if (w_once) __syncthreads();                           // (the DMA path has its barrier between the taps and the epilogue)
-#else
-        __syncthreads();
-#endif
         ZPHASE(4);
 #ifdef ZLY_DIAG
         ++ditems;
@@ -895,43 +829,6 @@ __global__ __launch_bounds__(256, ZLY_LDS_MIN_WAVES) void conv3x3_lds_kernel(con
         if (t1 >= total_tiles) break;
         t0 = t1; c0 = c1; advance(t1, c1);
     }
-#else
-    while (true) {
-        // ---- item (t0,c0) from set A ----
-        stage_store(rpA, rwA);
-        ZPHASE(0);
-        __syncthreads();
-        ZPHASE(1);
-        if (t2 < total_tiles) stage_load(t2, c2, rpA, rwA);
-        ZPHASE(2);
-        compute(t0, c0);
-        ZPHASE(5);
-        __syncthreads();
-        ZPHASE(4);
-#ifdef ZLY_DIAG
-        ++ditems;
-#endif
-        if (t1 >= total_tiles) break;
-        // ---- item (t1,c1) from set B ----
-        int t3 = t2, c3 = c2; advance(t3, c3);
-        stage_store(rpB, rwB);
-        ZPHASE(0);
-        __syncthreads();
-        ZPHASE(1);
-        if (t3 < total_tiles) stage_load(t3, c3, rpB, rwB);
-        ZPHASE(2);
-        compute(t1, c1);
-        ZPHASE(5);
-        __syncthreads();
-        ZPHASE(4);
-#ifdef ZLY_DIAG
-        ++ditems;
-#endif
-        if (t2 >= total_tiles) break;
-        t0 = t2; c0 = c2; t1 = t3; c1 = c3;
-        t2 = t1; c2 = c1; advance(t2, c2);
-    }
-#endif
 #ifdef ZLY_DIAG
     if (lane == 0 && a.in2) {
         unsigned long long* o = (unsigned long long*)a.in2 + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 16;
@@ -984,7 +881,6 @@ static size_t lds_bytes(int stride, int pt, int ct, int wchunks = 1) {
 //     (256 VGPRs per lane, <= 80 KB LDS); an odd tile count (the 64 -> 144 Detect stem: 9 tiles) runs its last tile as a second launch of
 //     the TPW = 1 form (1 x 4 waves).
 // ------------------------------------------------------------------------------------------------
-struct WsGeom { int TH, TW, tiles_x, tiles_y, total_tiles, pitch, nchunks, nwc, nwp; };
 #ifdef ZLY_WS_DIAG
 __device__ unsigned long long* g_ws_diag = nullptr;              // diagnostic build only (tools/ws_bench.hip): per-wave phase cycle sums
 #endif
@@ -1180,7 +1076,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ws_kernel(const ConvArgs a, co
                 for (int c = 0; c < TPW; ++c) {
                     o[c] = acc[h2][c] + biasr[c];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) o[c][r] = silu<bf16_t>(o[c][r]);      // always SiLU here: launch_conv sends a conv without activation elsewhere (a run-time select cost one v_cndmask per value: 16 per pair)
+                    for (int r = 0; r < 4; ++r) o[c][r] = silu<bf16_t>(o[c][r]);      // always SiLU here: the planner sends a conv without activation elsewhere (a run-time select cost one v_cndmask per value: 16 per pair)
                 }
                 if (TPW == 2) {
                     f32x4 lo = o[0], hi = o[TPW - 1];
@@ -1364,7 +1260,7 @@ __global__ __launch_bounds__(320, 3) void conv3x3_wsk_kernel(const ConvArgs a, c
             for (int h2 = 0; h2 < 2; ++h2) {
                 f32x4 o = acc[h2] + biasr;
 #pragma unroll
-                for (int r2 = 0; r2 < 4; ++r2) o[r2] = silu<bf16_t>(o[r2]);       // launch_conv_wsk refuses a conv without activation
+                for (int r2 = 0; r2 < 4; ++r2) o[r2] = silu<bf16_t>(o[r2]);       // conv_wsk_ok refuses a conv without activation
                 const bf16x4 wv = to_bf16x4(o);
                 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, wv), rout, ob[h2], 0, 0);
@@ -1399,7 +1295,7 @@ __global__ __launch_bounds__(320, 3) void conv3x3_wsk_kernel(const ConvArgs a, c
 // one lane group (pieces 10 p: all even slots of the 256-byte bank row) and 8 of its neighbour, whose offset is ONE piece further -- the next piece of the
 // same tap, or, where a k-step straddles two taps, piece 0 of the next pixel, which in an unpadded row is again exactly one piece on.  (First version:
 // 160 + 32 = 192 bytes = 12 pieces: 12 p mod 16 has period 4, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.51, no faster than the LDS-tiled kernel.)
-static bool wsk_plan(int H, int W, int cin, int n, WsGeom* g)
+static bool wsk_plan(int H, int W, int cin, int n, int ncu, WsGeom* g)
 {
     const int pitch = cin * 2;
     long best = -1;
@@ -1410,7 +1306,7 @@ static bool wsk_plan(int H, int W, int cin, int n, WsGeom* g)
             if (lds > 64 * 1024) continue;
             const int tx = (W + tw - 1) / tw, ty = (H + th - 1) / th;
             const long tiles = (long)tx * ty * n;
-            const long rounds = (tiles + 2 * num_cus() - 1) / (2 * num_cus());
+            const long rounds = (tiles + 2 * ncu - 1) / (2 * ncu);
             const long key = rounds * ((th * tw + 15) / 16 * 16 + 64) * 4096 + ph * pw;
             if (best < 0 || key < best) { best = key; g->TH = th; g->TW = tw; g->tiles_x = tx; g->tiles_y = ty; }
         }
@@ -1419,29 +1315,29 @@ static bool wsk_plan(int H, int W, int cin, int n, WsGeom* g)
     return true;
 }
 
-// may this conv take it?  (3x3 stride 1, 80 real input channels, 80 output channels, enough pixels for the persistent grid, tiles that cover the map well)
-bool conv_wsk_ok(int cin, int cout, int n, int Ho, int Wo)
+// does launch_conv_wsk take this launch?  3x3 stride 1 with SiLU, 80 real input channels as 23 packed k-steps, 80 output channels, single source, no residual,
+// aligned views, tensors within 32-bit byte offsets, enough pixels for the persistent grid, tiles that cover the map well.  Fills the plan if so.
+bool conv_wsk_ok(const ConvArgs& a, const Switches& sw, WskPlan* plan)
 {
-    if (cin != 80 || cout != 80) return false;
-    WsGeom g{};
-    if (!wsk_plan(Ho, Wo, cin, n, &g)) return false;
-    const double util = (double)Ho * Wo / ((double)g.tiles_x * g.tiles_y * g.TH * g.TW);
-    const char* mt = getenv("ZLY_WS_MIN_TILES");
-    return util >= 0.7 && (long)n * Ho * Wo >= (mt ? atol(mt) : 64) * 169L;
-}
-
-hipError_t launch_conv_wsk(const ConvArgs& a, hipStream_t s)
-{
-    WsGeom g{};
+    if (a.Cin != 80 || a.Cout != 80 || a.nk != 23 || a.stride != 1 || a.pad != 1 || a.in2 || a.res || a.out_f32 || !a.act || a.in_cs % 8 || a.in_co % 8 || a.out_cs % 4 || a.out_co % 4) return false;
+    if ((size_t)a.M * (size_t)std::max(a.in_cs, a.out_cs) * 2 >= ((size_t)1 << 31)) return false;        // 32-bit buffer offsets
     const int n = a.M / (a.Ho * a.Wo);
-    if (a.Cin != 80 || a.Cout != 80 || a.nk != 23 || a.stride != 1 || a.pad != 1 || a.in2 || a.res || a.out_f32 || !a.act || a.in_cs % 8 || a.in_co % 8 || a.out_cs % 4 || a.out_co % 4 ||
-        !wsk_plan(a.Ho, a.Wo, a.Cin, n, &g)) return hipErrorInvalidValue;
-    if ((size_t)a.M * (size_t)std::max(a.in_cs, a.out_cs) * 2 >= ((size_t)1 << 31)) return hipErrorInvalidValue;        // 32-bit buffer offsets (the caller falls back)
+    WsGeom g{};
+    if (!wsk_plan(a.Ho, a.Wo, a.Cin, n, sw.num_cus, &g)) return false;
+    const double util = (double)a.Ho * a.Wo / ((double)g.tiles_x * g.tiles_y * g.TH * g.TW);
+    if (util < 0.7 || (long)n * a.Ho * a.Wo < sw.ws_min_tiles * 169L) return false;
     g.total_tiles = g.tiles_x * g.tiles_y * n;
     g.nwc = 5; g.nwp = 1;
-    const size_t lds = ((size_t)(g.TH + 2) * (g.TW + 8) * g.pitch + 1023) / 1024 * 1024;
-    const int gx = g.total_tiles < 2 * num_cus() ? g.total_tiles : 2 * num_cus();
-    hipLaunchKernelGGL(conv3x3_wsk_kernel<23>, dim3(gx), dim3(320), lds, s, a, g);
+    plan->g = g;
+    plan->lds = (unsigned)(((size_t)(g.TH + 2) * (g.TW + 8) * g.pitch + 1023) / 1024 * 1024);
+    plan->gx = (unsigned)(g.total_tiles < 2 * sw.num_cus ? g.total_tiles : 2 * sw.num_cus);
+    return true;
+}
+
+hipError_t launch_conv_wsk(const ConvArgs& a, const WskPlan& plan, hipStream_t s)
+{
+    if (a.Cin != 80 || a.nk != 23 || plan.gx < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(conv3x3_wsk_kernel<23>, dim3(plan.gx), dim3(320), plan.lds, s, a, plan.g);
     return hipGetLastError();
 }
 
@@ -1463,7 +1359,7 @@ static constexpr int WS_LDS_MAX = 64 * 1024;        // two resident workgroups p
 
 // tile shape: among the shapes whose patch lets two workgroups be resident per CU, the one with the least work on the busiest workgroup --
 // rounds of tiles over the 2 x 256 resident workgroups x (pixels of a tile + a fixed per-tile cost); 768 tiles of 9 x 26 lose to 1024 of 13 x 13
-static bool ws_plan(int H, int W, int cin, int n, WsGeom* g, int stride = 1)
+static bool ws_plan(int H, int W, int cin, int n, int ncu, WsGeom* g, int stride = 1)
 {
     if (!pick_ws(cin, 2, false, false, stride)) return false;
     const int pitch = cin * 2 + (stride == 2 ? 16 : 32);
@@ -1475,7 +1371,7 @@ static bool ws_plan(int H, int W, int cin, int n, WsGeom* g, int stride = 1)
             if (lds > WS_LDS_MAX) continue;
             const int tx = (W + tw - 1) / tw, ty = (H + th - 1) / th;
             const long tiles = (long)tx * ty * n;
-            const long rounds = (tiles + 2 * num_cus() - 1) / (2 * num_cus());
+            const long rounds = (tiles + 2 * ncu - 1) / (2 * ncu);
             const long key = rounds * ((th * tw + 15) / 16 * 16 + 64) * 4096 + ph * pw;
             if (best < 0 || key < best) { best = key; g->TH = th; g->TW = tw; g->tiles_x = tx; g->tiles_y = ty; }
         }
@@ -1517,8 +1413,6 @@ hipError_t ws_init()
 // epilogue of one pair beside the MFMAs of the next, no barrier inside a tile).  Workgroup = 4 waves = NWC channel groups x NWP pixel
 // groups; blockIdx.y = block of NWC x TPW channel tiles; persistent over pixel tiles, two workgroups per CU.
 // ------------------------------------------------------------------------------------------------
-struct Ws1Geom { int npx, total_tiles, pitch, nwc, nwp; };
-
 template <int TPW, int NK, bool DUAL = false>
 __global__ __launch_bounds__(256, 2) void conv1x1_ws_kernel(const ConvArgs a, const Ws1Geom g)
 {
@@ -1686,7 +1580,7 @@ static conv_ws1_fn pick_ws1(int tpw, int nk, bool dual = false)
 static int ws1_tpw(int nk) { return nk <= 16 ? 2 : 1; }
 
 // pixel tile: as many pixels as 64 KB of LDS hold (two workgroups per CU), fewer while the launch has less than two workgroups per CU
-static bool ws1_plan(int cin, int cout_pad, int M, Ws1Geom* g, int* ny, bool dual = false)
+static bool ws1_plan(int cin, int cout_pad, int M, int ncu, Ws1Geom* g, int* ny, bool dual = false)
 {
     const int nk = cin / 32, tpw = ws1_tpw(nk);
     if (cin % 32 || !pick_ws1(tpw, nk, dual)) return false;
@@ -1705,7 +1599,7 @@ static bool ws1_plan(int cin, int cout_pad, int M, Ws1Geom* g, int* ny, bool dua
     long best = -1;
     for (int npx = 16 * g->nwp; npx <= npx_max; npx += 16) {
         const long tiles = (long)((M + npx - 1) / npx) * *ny;
-        const long rounds = (tiles + 2L * num_cus() - 1) / (2L * num_cus());
+        const long rounds = (tiles + 2L * ncu - 1) / (2L * ncu);
         const long key = rounds * (npx + 128);
         if (best < 0 || key < best) { best = key; g->npx = npx; }
     }
@@ -1724,11 +1618,11 @@ hipError_t ws1_init()
     return hipSuccess;
 }
 
-static int g_num_cus = 256;
-int num_cus() { return g_num_cus; }
-void set_num_cus(int n) { g_num_cus = n < 1 ? 1 : (n > 256 ? 256 : n); }
+// resident workgroups per CU of conv3x3_lds_kernel, [stride][ct][pt][resident weight chunks] (registers: 94..243 per lane, LDS 35..80 KB -> 2..4):
+// asked from the runtime by conv_init, read by plan_lds -- the persistent grid is exactly what is resident
+static int g_lds_occ[3][6][5][3];
 
-// dynamic LDS above 64 KiB needs an opt-in per kernel; done once, outside any stream capture
+// dynamic LDS above 64 KiB needs an opt-in per kernel; done once, outside any stream capture (zly_create runs it alone in the process)
 hipError_t conv_init()
 {
     { hipError_t r = ws_init(); if (r != hipSuccess) return r; }
@@ -1744,6 +1638,17 @@ hipError_t conv_init()
             if (r != hipSuccess) return r;
         }
     }
+    static bool occ_done = false;
+    if (occ_done) return hipSuccess;
+    for (int stride = 1; stride <= 2; ++stride)
+        for (int ct = 2; ct <= 5; ++ct)
+            for (int pt = 1; pt <= (stride == 1 ? 4 : 2); pt *= 2)
+                for (int wch = 0; wch <= (stride == 1 ? 2 : 0); ++wch) {       // 0 = one chunk's weights per item, 1 / 2 = that many chunks resident
+                    int o = 0;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)pick_lds(stride, pt, ct), 256, lds_bytes(stride, pt, ct, wch ? wch : 1)) != hipSuccess || o < 1) o = 2;
+                    g_lds_occ[stride][ct][pt][wch] = o > 4 ? 4 : o;
+                }
+    occ_done = true;
     return hipSuccess;
 }
 
@@ -1770,19 +1675,82 @@ static conv_fn pick_mode(int mode, int ct) {
     return nullptr;
 }
 
-void conv_pick_direct(int dtype, int ks, int cin, int cout_pad, int M, ConvLaunch* cfg);
-
 int conv_kstep(int dtype) { return dtype == ZLY_DTYPE_BF16 ? Frag<bf16_t>::KSTEP : Frag<float>::KSTEP; }
 
-// Tile shape per launch.  The chip has 256 CUs; a launch wants >= ~2 workgroups per CU.
+// ------------------------------------------------------------------------------------------------
+// The planner: which kernel a conv launches, in which shape, on which grid.  conv_plan tries the kernels in order; each plan_* below answers
+// "does this kernel take the launch?" from the launch's own arguments (shape, alignment, tensor sizes) and, if so, fills the whole plan.
+// The chip has 256 CUs; a launch wants >= ~2 workgroups per CU.
+// ------------------------------------------------------------------------------------------------
+
+// the direct kernel (always takes the launch).  Tile shape:
 //   large M (batch 64, shallow layers): PT = 4 / 2 pixel tiles per wave amortise the weight fragments;
 //   small M (batch 1, deep layers): PT = 1, fewer channel tiles per wave and 4-way split-K, so that
 //   even the 13x13 layers put a few hundred workgroups on the chip.
-// LDS-tiled 3x3 kernel when the launch is big enough to fill the chip with TH x 16 tiles
-static bool pick_lds_config(int stride, int cin, int cout_pad, int n, int Ho, int Wo, ConvLaunch* cfg)
+static void direct_shape(int dtype, int ks, int cin, int cout_pad, int M, const Switches& sw, ConvPlan* p)
 {
-    if (cin % 32 != 0) return false;
+    const int kstep = conv_kstep(dtype);
+    p->fastk = (ks == 3 && cin % kstep == 0) ? 1 : 0;
+    p->ksplit = 1;
     const int ntiles = cout_pad / 16;
+    static const int pref[5] = {4, 5, 3, 2, 1};
+    p->ct = 1;
+    for (int i = 0; i < 5; ++i)
+        if (ntiles % pref[i] == 0) { p->ct = pref[i]; break; }
+    if (dtype != ZLY_DTYPE_BF16) { p->pt = 2; return; }            // fp32 = verification mode: one shape
+    const long ytiles = ntiles / p->ct;
+    const long wgs_pt4 = ((long)(M + 255) / 256) * ytiles;
+    const long wgs_pt2 = ((long)(M + 127) / 128) * ytiles;
+    const long wgs_pt1 = ((long)(M + 63) / 64) * ytiles;
+    const int nk = (ks * ks * cin + kstep - 1) / kstep;
+    const bool force_split = nk >= sw.direct_ksplit_nk;              // tuning aid: K-heavy launches take the 4-way split-K shape whatever their size
+    if (!force_split) {
+        if (wgs_pt4 >= sw.direct_pt4_min && p->ct <= 4) { p->pt = 4; return; }       // CT=5 x PT=4 would need > 200 VGPRs
+        if (wgs_pt2 >= sw.direct_pt2_min) { p->pt = 2; return; }                     // 1024 before: the K-heavy 1x1 layers at 26x26 re-read their weights per 16 pixels (+0.8 %)
+    }
+    p->pt = 1;
+    if (!force_split && (wgs_pt1 >= 512 || nk < 4)) return;
+    p->ksplit = 4;                                                   // workgroup = one 16-pixel tile
+    long wgs = ((long)(M + 15) / 16) * ytiles;
+    while (wgs < 256 && p->ct > 1) {                                 // still thin: fewer channel tiles per wave
+        int nct = p->ct - 1;
+        while (nct > 1 && ntiles % nct != 0) --nct;
+        p->ct = nct;
+        wgs = ((long)(M + 15) / 16) * (ntiles / p->ct);
+    }
+}
+static void plan_direct(int dtype, int ks, const ConvArgs& a, const Switches& sw, ConvPlan* p)
+{
+    *p = ConvPlan{};
+    p->kind = CONV_DIRECT;
+    direct_shape(dtype, ks, a.Cin, a.cout_pad, a.M, sw, p);
+    if (ks == 1 && (a.stride != 1 || a.pad != 0)) return;          // the 1x1 paths assume input pixel = output pixel: no kernel, launch_conv refuses
+    // the split-K kernel reads its inputs through 32-bit buffer offsets and splits (b, y, x) by reciprocal multiplies: an input tensor of 2 GiB or more, 2^20
+    // pixels or a map of 1024 pixels a side (never a latency-path launch) takes the one-pass shape
+    const size_t in_bytes = (size_t)(a.M / (a.Ho * a.Wo)) * a.H * a.W * (size_t)std::max(a.in_cs, a.in2 ? a.in2_cs : 0) * 2;
+    if (p->ksplit == 4 && !(in_bytes < ((size_t)1 << 31) && a.M < (1 << 20) && a.Wo < 1024 && a.Ho < 1024)) p->ksplit = 1;
+    const int mode = ks == 1 ? 0 : (p->fastk ? 1 : 2);
+    conv_fn fn = nullptr;
+    if (dtype == ZLY_DTYPE_BF16) {
+        if (p->ksplit == 4)   fn = pick_mode<bf16_t, 1, 4>(mode, p->ct);
+        else if (p->pt == 1)  fn = pick_mode<bf16_t, 1, 1>(mode, p->ct);
+        else if (p->pt == 2)  fn = pick_mode<bf16_t, 2, 1>(mode, p->ct);
+        else                  fn = pick_mode<bf16_t, 4, 1>(mode, p->ct);
+    } else {
+        fn = pick_mode<float, 2, 1>(mode, p->ct);
+    }
+    p->fn[0] = (const void*)fn;
+    const int px_per_wg = p->ksplit == 4 ? 16 * p->pt : 64 * p->pt;
+    p->gx = (unsigned)((a.M + px_per_wg - 1) / px_per_wg);
+    p->gy = (unsigned)(a.cout_pad / (16 * p->ct));
+}
+
+// LDS-tiled 3x3 kernel when the launch is big enough to fill the chip with TH x 16 tiles
+static bool plan_lds(const ConvArgs& a, const Switches& sw, ConvPlan* p)
+{
+    const int stride = a.stride, cin = a.Cin, Ho = a.Ho, Wo = a.Wo, n = a.M / (a.Ho * a.Wo);
+    if (cin % 32 != 0 || stride < 1 || stride > 2 || a.pad != 1) return false;
+    const int ntiles = a.cout_pad / 16;
     int ct = 0;
     static const int pref[4] = {4, 5, 3, 2};
     for (int i = 0; i < 4; ++i)
@@ -1792,303 +1760,217 @@ static bool pick_lds_config(int stride, int cin, int cout_pad, int n, int Ho, in
     // Cin = 64 with CT = 3 (the 64 -> 144 Detect stems, 54 KB for both chunks) residency won 12 % while weights went through
     // registers; since they go by LDS-DMA the per-item copy is cheap and three resident workgroups beat two with resident
     // weights (ZLY_WRES_MAXCHUNKS=2 restores it).  Halving CT to make 64 -> 64 resident was always slower (37 vs 32 us).
-    cfg->wres = 0;
-    const char* nr = getenv("ZLY_NO_WRES");
-    const char* wm = getenv("ZLY_WRES_MAXCHUNKS");                   // tuning aid
-    if (stride == 1 && cin <= 32 * (wm ? atoi(wm) : 1) && !nr) {
+    int wres = 0;
+    if (stride == 1 && cin <= 32 * sw.wres_maxchunks && cin <= 64 && !sw.no_wres) {     // (two chunks at most: what conv_init opts in and asks the occupancy for)
         static const int rpref[4] = {4, 3, 2, 5};
         for (int i = 0; i < 4; ++i) {
             const int c = rpref[i];
-            if (ntiles % c == 0 && c >= ct && (size_t)(cin / 32) * 9 * c * 1024 + LdsGeom<1, 2>::PATCH_BYTES <= 80 * 1024) { ct = c; cfg->wres = 1; break; }
+            if (ntiles % c == 0 && c >= ct && (size_t)(cin / 32) * 9 * c * 1024 + LdsGeom<1, 2>::PATCH_BYTES <= 80 * 1024) { ct = c; wres = 1; break; }
         }
     }
     const int ytiles = ntiles / ct;
     const int tx = (Wo + 15) / 16;
     // stride 2 (round 3): 8-row tiles where they still leave enough work items for the persistent grid (model.5 25.1 -> 21.6 us, model.7 23.6 -> 21.1;
     // model.19's 256 items stay on 4-row tiles)
-    int pt = stride == 1 ? 2 : (((long)n * ((Wo + 15) / 16) * ((Ho + 7) / 8) * (ntiles / ct) >= 384 && !getenv("ZLY_LDS_S2_PT1")) ? 2 : 1);
+    int pt = stride == 1 ? 2 : (((long)n * ((Wo + 15) / 16) * ((Ho + 7) / 8) * (ntiles / ct) >= 384 && !sw.lds_s2_pt1) ? 2 : 1);
     if (stride == 1 && ct == 2 && (long)n * tx * ((Ho + 15) / 16) * ytiles >= 2048) pt = 4;   // plenty of tiles, few channels: bigger tiles (VGPR budget)
     if (stride == 1 && Ho <= 14) pt = 1;                                            // 13-row maps: 4 x 4 rows
     if (ct == 5 && (pt > 1 || stride == 2)) { if (stride == 2) return false; pt = 1; }  // those variants do not fit 256 registers (2 waves per SIMD) without spilling
-    const long tiles = (long)n * tx * ((Ho + 4 * pt - 1) / (4 * pt));
-    const char* lm = getenv("ZLY_LDS_MIN_TILES");                                   // tuning / tests: force the LDS kernel onto small launches
-    if (tiles * ytiles < (lm ? atol(lm) : 384)) return false;                       // too small: direct kernel
-    cfg->lds = 1; cfg->ct = ct; cfg->pt = pt; cfg->ksplit = 1; cfg->fastk = 1;
+    const int tiles_y = (Ho + 4 * pt - 1) / (4 * pt);
+    const long tiles = (long)n * tx * tiles_y;
+    if (tiles * ytiles < sw.lds_min_tiles) return false;                            // too small: direct kernel
+    conv_lds_fn fn = pick_lds(stride, pt, ct);
+    if (!fn) return false;
+    *p = ConvPlan{};
+    p->kind = CONV_LDS; p->ct = ct; p->pt = pt; p->ksplit = 1; p->fastk = 1; p->wres = wres;
+    p->fn[0] = (const void*)fn;
+    p->tiles_x = tx; p->tiles_per_img = tx * tiles_y; p->total_tiles = (int)tiles;
+    const int wch = wres ? cin / 32 : 0;
+    p->lds = (unsigned)lds_bytes(stride, pt, ct, wch ? wch : 1);
+    int occ = g_lds_occ[stride][ct][pt][wch];
+    if (occ < 1) occ = 2;                                  // conv_init has not run (a diagnostic tool): what the kernel's launch bounds guarantee
+    // never more workgroups than are resident: a persistent workgroup that has to wait for a slot runs a whole round alone
+    const int max_wgs = (sw.lds_wgs_per_cu ? sw.lds_wgs_per_cu : occ) * sw.num_cus;
+    int gx = (int)tiles;
+    if (gx * ytiles > max_wgs) gx = max_wgs / ytiles;
+    if (gx > (int)tiles) gx = (int)tiles;
+    p->gx = (unsigned)gx; p->gy = (unsigned)ytiles;
     return true;
 }
 
 // streaming 1x1 kernel: single-source pointwise convs with enough pixels to keep persistent waves busy
-static bool pick_stream_config(int cin, int cout_pad, int M, ConvLaunch* cfg)
+static bool plan_stream(const ConvArgs& a, const Switches& sw, ConvPlan* p)
 {
-    const int nk = (cin + 31) / 32;
-    const int ntiles = cout_pad / 16;
+    const int nk = (a.Cin + 31) / 32;
+    const int ntiles = a.cout_pad / 16;
     int ct = 0, pt = 0;
     if (nk <= 2 && ntiles == 2) { ct = 2; pt = 4; }
     else if (nk <= 4 && ntiles % 4 == 0) { ct = 4; pt = 2; }
     // 192 / 256 input channels (round 3): 64 output channels per wave (CT = 4) -- with CT = 2 the four channel blocks of a 128-channel layer
     // each read the whole input: model.12.cv2 17.7 -> 15.1 us, model.18.cv1 / cv2 16.7 -> 14.5.  256 input channels go to the direct kernel,
     // which is faster still there (model.6.cv2 21.1 -> 16.9 us, model.8.cv1 15.3 -> 13.3).  ZLY_STREAM_CT2 restores the old shapes (tests).
-    else if (nk == 6 && ntiles % 4 == 0 && !getenv("ZLY_STREAM_CT2")) { ct = 4; pt = 1; }
-    else if (nk == 8 && !getenv("ZLY_STREAM_CT2")) return false;
+    else if (nk == 6 && ntiles % 4 == 0 && !sw.stream_ct2) { ct = 4; pt = 1; }
+    else if (nk == 8 && !sw.stream_ct2) return false;
     else if ((nk == 6 || nk == 8) && ntiles % 2 == 0) { ct = 2; pt = 1; }
-    if (!ct || !pick_stream(ct, pt, nk)) return false;
-    if (const char* mx = getenv("ZLY_STREAM_MAX_NK")) { if (nk > atoi(mx)) return false; }          // tuning aid
-    const char* mg = getenv("ZLY_STREAM_MIN_GROUPS");                     // tuning / tests: force the streaming kernel onto small launches
-    if ((long)M / (16 * pt) * (ntiles / ct) < (mg ? atol(mg) : 4096)) return false;   // too few pixel groups to keep persistent waves busy
-    cfg->stream = 1; cfg->ct = ct; cfg->pt = pt; cfg->ksplit = 1; cfg->fastk = 0; cfg->lds = 0;
+    conv_stream_fn fn = ct ? pick_stream(ct, pt, nk) : nullptr;
+    if (!fn || nk > sw.stream_max_nk) return false;
+    if ((long)a.M / (16 * pt) * (ntiles / ct) < sw.stream_min_groups) return false;   // too few pixel groups to keep persistent waves busy
+    if (a.in2 || a.res || nk > a.nk || !a.act || a.out_f32 || a.Cout % 32 || a.in_cs % 8 || a.in_co % 8 || a.out_cs % 8 || a.out_co % 8) return false;
+    *p = ConvPlan{};
+    p->kind = CONV_STREAM; p->ct = ct; p->pt = pt; p->ksplit = 1;
+    p->fn[0] = (const void*)fn;
+    const int ytiles = a.cout_pad / (16 * ct);
+    p->ngroups = (a.M + 16 * pt - 1) / (16 * pt);
+    int gx = (p->ngroups + 3) / 4;
+    const int wgs = sw.stream_wgs > 0 ? sw.stream_wgs : (ct == 4 && pt == 1 ? 2 : 4) * sw.num_cus;      // the 64-channel shapes hold 2 workgroups per CU (189-239 VGPRs)
+    const int cap = wgs / ytiles > 0 ? wgs / ytiles : 1;
+    if (gx > cap) gx = cap;
+    p->gx = (unsigned)gx; p->gy = (unsigned)ytiles;
     return true;
 }
 
-// weight-stationary 3x3 kernel: stride-1 layers with Cin = 64 and 32 / 64 / 128 (+ 16) output channels on maps its tiles cover well, with
-// enough tiles to fill the chip
-static bool pick_ws_config(int stride, int cin, int cout_pad, int n, int Ho, int Wo, ConvLaunch* cfg)
+// weight-stationary 3x3 kernel: stride-1 layers with Cin = 64 and 32 / 64 / 128 (+ 16) output channels (stride 2: 32 / 64 input channels, an even number
+// of output tiles, no residual) on maps its tiles cover well, with enough tiles to fill the chip.  Its addresses are 32-bit byte offsets into buffer
+// resources (and 0x80000000 the out-of-range sentinel): a launch it would take whose tensors reach 2 GiB (YOLOv8-s 640 x 640 crosses it near batch 440;
+// ZLY_WS_MAX_BYTES lowers the bound for tests) is planned as the LDS-tiled / direct kernel, which address with 64 bits.
+static bool plan_ws(const ConvArgs& a, const Switches& sw, ConvPlan* p)
 {
-    const bool off = getenv("ZLY_NO_WS") != nullptr;               // tuning / tests (read per picked shape = once per engine, op and batch size: Op::launch_cache)
-    const int even = cout_pad / 16 / 2 * 2;                         // tiles of the TPW = 2 launch; an odd last tile goes to a TPW = 1 launch
-    if (off || cout_pad % 16 || (even != 2 && even != 4 && even != 8)) return false;
-    if (stride == 2 && (cout_pad / 16 != even || getenv("ZLY_NO_WS_S2"))) return false;      // tuning / tests
+    const int stride = a.stride, cin = a.Cin, cout_pad = a.cout_pad, Ho = a.Ho, Wo = a.Wo, n = a.M / (a.Ho * a.Wo);
+    const int ntiles = cout_pad / 16, even = ntiles / 2 * 2;        // tiles of the TPW = 2 launch; an odd last tile goes to a TPW = 1 launch
+    if (sw.no_ws || cout_pad % 16 || (even != 2 && even != 4 && even != 8)) return false;
+    if (stride == 2 && (ntiles != even || a.res || sw.no_ws_s2)) return false;
     // 32 input channels at stride 2 are all patch DMA and no MFMA work: taken on maps up to 200k output pixels only (model.3 at 416 x 416: 23.2 -> 21.2 us;
     // YOLOv8-s' 320 -> 160 map at batch 32, 819k pixels: 68 -> 75 us)
-    if (stride == 2 && cin == 32 && ((long)n * Ho * Wo >= 200000 || getenv("ZLY_NO_WS_S2_C32"))) return false;
+    if (stride == 2 && cin == 32 && ((long)n * Ho * Wo >= 200000 || sw.no_ws_s2_c32)) return false;
     if (stride != 1 && stride != 2) return false;
+    if (a.pad != 1 || a.in2 || a.out_f32 || !a.act || a.nk != 9 * cin / 32 || a.in_cs % 8 || a.in_co % 8) return false;
     WsGeom g{};
-    if (!ws_plan(Ho, Wo, cin, n, &g, stride)) return false;
+    if (!ws_plan(Ho, Wo, cin, n, sw.num_cus, &g, stride)) return false;
     // enough pixels to give each of the 512 resident workgroups a ~13 x 13 tile (the tile planner would happily cut a small launch into
     // tiny tiles): below that the launch belongs to the latency-path kernels
     const double util = (double)Ho * Wo / ((double)g.tiles_x * g.tiles_y * g.TH * g.TW);
-    const char* mt = getenv("ZLY_WS_MIN_TILES");
-    if (util < 0.7 || (long)n * Ho * Wo < (mt ? atol(mt) : 64) * 169L) return false;     // 64 x 169 pixels (batch 16 at 26 x 26) up: batch 16 +2.8 %, batch 32 +6 % on one engine; 256 before
-    cfg->ps = 1; cfg->ct = cout_pad / 16; cfg->pt = 4; cfg->ksplit = 1; cfg->fastk = 1;
-    cfg->rowt = (stride == 1 && getenv("ZLY_WS_ROWT") != nullptr && g.TW + 2 <= 16) ? 1 : 0;      // experiment: one MFMA tile per output row, kx taps by DPP shifts
-    {   // 64 -> 64 on small pixel tiles (the 26 x 26 maps: 7 x 13 tiles = 6 column tiles): 4 waves x ONE tile instead of 2 tile pairs x 2 pixel groups.  In the
-        // pair form a wave there has three column tiles = two rounds of its software pipeline (MFMAs of a pair beside the epilogue of the one before), mostly
-        // fill and drain: 6.7 k cycles for 1.7 k of MFMA issue (profiles/r03_ws_kernel_phase_stamps_v4.txt).  With one tile per wave it walks all six column
-        // tiles (three rounds) for the same MFMAs: 12.5 -> 11.3 us per launch, step +1.9 % (nine launches).  On 13 x 13 tiles (11 column tiles) the pair form
-        // wins (P3 box branch 23.3 vs 25.7 us: twice the fragment reads).  ZLY_WS_TPW1_MAXCT: tuning / tests (0 = never).
-        const char* t1 = getenv("ZLY_WS_TPW1_MAXCT");
-        cfg->tpw1 = (cin == 64 && cout_pad == 64 && (g.TH * g.TW + 15) / 16 <= (t1 ? atoi(t1) : 6)) ? 1 : 0;
+    if (util < 0.7 || (long)n * Ho * Wo < sw.ws_min_tiles * 169L) return false;     // 64 x 169 pixels (batch 16 at 26 x 26) up: batch 16 +2.8 %, batch 32 +6 % on one engine; 256 before
+    const size_t widest = std::max(std::max((size_t)n * a.H * a.W * (size_t)a.in_cs, (size_t)a.M * (size_t)a.out_cs), a.res ? (size_t)a.M * (size_t)a.res_cs : (size_t)0) * 2;
+    if (widest >= sw.ws_max_bytes) {
+        if (!plan_lds(a, sw, p)) plan_direct(ZLY_DTYPE_BF16, 3, a, sw, p);
+        return true;
     }
+    *p = ConvPlan{};
+    p->kind = CONV_WS; p->ct = ntiles; p->pt = 4; p->ksplit = 1; p->fastk = 1;
+    p->rowt = (stride == 1 && sw.ws_rowt && g.TW + 2 <= 16) ? 1 : 0;
+    // 64 -> 64 on small pixel tiles (the 26 x 26 maps: 7 x 13 tiles = 6 column tiles): 4 waves x ONE tile instead of 2 tile pairs x 2 pixel groups.  In the
+    // pair form a wave there has three column tiles = two rounds of its software pipeline (MFMAs of a pair beside the epilogue of the one before), mostly
+    // fill and drain: 6.7 k cycles for 1.7 k of MFMA issue (profiles/r03_ws_kernel_phase_stamps_v4.txt).  With one tile per wave it walks all six column
+    // tiles (three rounds) for the same MFMAs: 12.5 -> 11.3 us per launch, step +1.9 % (nine launches).  On 13 x 13 tiles (11 column tiles) the pair form
+    // wins (P3 box branch 23.3 vs 25.7 us: twice the fragment reads).
+    p->tpw1 = (cin == 64 && cout_pad == 64 && (g.TH * g.TW + 15) / 16 <= sw.ws_tpw1_maxct) ? 1 : 0;
+    g.total_tiles = g.tiles_x * g.tiles_y * n;
+    p->lds = (unsigned)(stride == 2 ? ((size_t)(2 * g.TH + 1) * (g.TW + 8 * ((g.TW + 8) / 8)) * g.pitch + 1023) / 1024 * 1024
+                                    : ((size_t)(g.TH + 2) * (g.TW + 8) * g.pitch + 1023) / 1024 * 1024);
+    p->gx = (unsigned)(g.total_tiles < 2 * sw.num_cus ? g.total_tiles : 2 * sw.num_cus);      // persistent: two resident workgroups per CU
+    p->gy = 1;
+    const bool res = a.res != nullptr;
+    if (p->tpw1) {                                                 // 4 waves x one tile, every wave walks all column tiles of the pixel tile
+        g.nwc = 4; g.nwp = 1; p->tiles0 = ntiles;
+        p->fn[0] = (const void*)(stride == 2 ? pick_ws(cin, 1, false, false, 2) : pick_ws(cin, 1, res));
+    } else {                                                       // the even tiles: 4 waves = (even / 2) channel groups x pixel groups
+        g.nwc = even / 2; g.nwp = 4 / g.nwc; p->tiles0 = even;
+        p->fn[0] = (const void*)(stride == 2 ? pick_ws(cin, 2, false, false, 2) : pick_ws(cin, 2, res, p->rowt != 0));
+        // the odd last tile (pair-permuted rows cover the even tiles only, so it is a plain 16-channel conv of its own): 1 x 4 waves
+        if (stride == 1 && ntiles > even && a.Cout > even * 16) p->fn[1] = (const void*)pick_ws(cin, 1, res);
+    }
+    p->ws = g;
     return true;
 }
 
-// weight-stationary 1x1 kernel: single-source pointwise convs with at least four k-steps and enough pixels for the persistent grid
-static bool pick_ws1_config(int cin, int cout_pad, int M, ConvLaunch* cfg, bool dual = false)
+// weight-stationary 1x1 kernel: pointwise convs (single source, or the Upsample + Concat pair) with at least four k-steps and enough pixels for the
+// persistent grid.  32-bit byte offsets, as plan_ws: a launch it would take whose tensors reach 2 GiB (ZLY_WS1_MAX_BYTES: every one, for tests) is
+// planned as the direct kernel.
+static bool plan_ws1(const ConvArgs& a, const Switches& sw, ConvPlan* p)
 {
+    const bool dual = a.in2 != nullptr;
     Ws1Geom g{};
     int ny = 0;
-    if (cin < 128 || !ws1_plan(cin, cout_pad, M, &g, &ny, dual)) return false;
-    const char* mm = getenv("ZLY_WS1_MIN_PX");                      // tuning / tests: force the kernel onto small launches
-    if (M < (mm ? atol(mm) : 2048)) return false;
-    cfg->ws1 = 1; cfg->ct = cout_pad / 16; cfg->pt = g.npx / 16; cfg->ksplit = 1; cfg->fastk = getenv("ZLY_WS1_MAX_BYTES") ? 1 : 0; cfg->lds = 0; cfg->stream = 0;
+    if (a.Cin < 128 || !ws1_plan(a.Cin, a.cout_pad, a.M, sw.num_cus, &g, &ny, dual) || a.M < sw.ws1_min_px) return false;
+    if (a.stride != 1 || a.pad != 0 || a.res || !a.act || a.out_f32 || a.nk != a.Cin / 32 || a.Cout % 32 || a.cout_pad != a.Cout ||
+        a.in_cs % 8 || a.in_co % 8 || a.out_cs % 8 || a.out_co % 8) return false;
+    if (dual && (a.in2_cs % 8 || a.in2_co % 8 || a.split_c % 8 || a.split_c <= 0 || a.split_c >= a.Cin || (a.H & 1) || (a.W & 1) || a.M % (a.H * a.W))) return false;
+    const size_t widest = (size_t)a.M * (size_t)std::max(std::max(a.in_cs, a.out_cs), dual ? a.in2_cs : 0) * 2;
+    if (sw.ws1_max_bytes || widest >= ((size_t)1 << 31)) { plan_direct(ZLY_DTYPE_BF16, 1, a, sw, p); return true; }
+    *p = ConvPlan{};
+    p->kind = CONV_WS1; p->ct = a.cout_pad / 16; p->pt = g.npx / 16; p->ksplit = 1;
+    p->fn[0] = (const void*)pick_ws1(ws1_tpw(a.nk), a.nk, dual);
+    p->ws1 = g;
+    p->lds = (unsigned)(((size_t)g.npx * g.pitch + 1023) / 1024 * 1024);
+    int gx = 2 * sw.num_cus / ny;                                  // persistent: two resident workgroups per CU
+    if (gx < 1) gx = 1;
+    if (gx > g.total_tiles) gx = g.total_tiles;
+    p->gx = (unsigned)gx; p->gy = (unsigned)ny;
     return true;
 }
 
-void conv_pick_config(int dtype, int ks, int stride, int cin, int cout_pad, int n, int Ho, int Wo, ConvLaunch* cfg, bool streamable, bool plain, bool dual)
+void conv_plan(int dtype, int ks, const ConvArgs& a, const Switches& sw, ConvPlan* p)
 {
-    const int M = n * Ho * Wo;
-    cfg->ks = ks; cfg->lds = 0; cfg->stream = 0; cfg->wres = 0; cfg->ps = 0; cfg->ws1 = 0; cfg->rowt = 0; cfg->tpw1 = 0;
-    const bool no_stream = getenv("ZLY_NO_STREAM") != nullptr;             // tuning / tests
-    // ZLY_WS1 (tuning / tests): 0 = never the weight-stationary 1x1 kernel, 1 = for the shapes the streaming kernel does not take, 2 = before it
-    const char* w1 = getenv("ZLY_WS1");
-    const int ws1_mode = w1 ? atoi(w1) : 1;
-    const bool ws1_ok = dtype == ZLY_DTYPE_BF16 && ks == 1 && stride == 1 && streamable && ws1_mode > 0;
-    if (dual) {             // Upsample + Concat input, otherwise "streamable": the weight-stationary kernel or the direct one
-        if (dtype == ZLY_DTYPE_BF16 && ks == 1 && stride == 1 && ws1_mode > 0 && !getenv("ZLY_WS1_NO_DUAL") && pick_ws1_config(cin, cout_pad, M, cfg, true)) return;
-        conv_pick_direct(dtype, ks, cin, cout_pad, M, cfg);
+    const bool bf16 = dtype == ZLY_DTYPE_BF16, pointwise = bf16 && ks == 1 && a.stride == 1 && a.pad == 0;
+    const bool streamable = !a.in2 && !a.res && a.act && !a.out_f32 && a.Cout % 32 == 0;      // single source, no residual, SiLU, bf16 output
+    if (a.in2 && ks == 1 && !a.res && a.act && !a.out_f32 && a.Cout % 32 == 0 && a.cout_pad == a.Cout) {
+        // Upsample + Concat input, otherwise "streamable": the weight-stationary kernel or the direct one
+        if (pointwise && sw.ws1_mode > 0 && !sw.ws1_no_dual && plan_ws1(a, sw, p)) return;
+        plan_direct(dtype, ks, a, sw, p);
         return;
     }
+    const bool ws1_ok = pointwise && streamable && sw.ws1_mode > 0;
     // before the streaming kernel: on request, and on the largest maps (YOLOv8-s 640 x 640 P3, 205k pixels: 31 -> 27 and 35 -> 31 us)
-    if (ws1_ok && (ws1_mode == 2 || M >= 131072) && pick_ws1_config(cin, cout_pad, M, cfg)) return;
-    if (dtype == ZLY_DTYPE_BF16 && ks == 1 && stride == 1 && streamable && !no_stream && pick_stream_config(cin, cout_pad, M, cfg)) return;
-    if (ws1_ok && pick_ws1_config(cin, cout_pad, M, cfg)) return;
-    if (dtype == ZLY_DTYPE_BF16 && ks == 3 && plain && pick_ws_config(stride, cin, cout_pad, n, Ho, Wo, cfg)) return;
-    if (dtype == ZLY_DTYPE_BF16 && ks == 3 && pick_lds_config(stride, cin, cout_pad, n, Ho, Wo, cfg)) return;
-    conv_pick_direct(dtype, ks, cin, cout_pad, M, cfg);
+    if (ws1_ok && (sw.ws1_mode == 2 || a.M >= 131072) && plan_ws1(a, sw, p)) return;
+    if (pointwise && streamable && !sw.no_stream && plan_stream(a, sw, p)) return;
+    if (ws1_ok && plan_ws1(a, sw, p)) return;
+    if (bf16 && ks == 3 && plan_ws(a, sw, p)) return;
+    if (bf16 && ks == 3 && plan_lds(a, sw, p)) return;
+    plan_direct(dtype, ks, a, sw, p);
 }
 
-void conv_pick_direct(int dtype, int ks, int cin, int cout_pad, int M, ConvLaunch* cfg)
+// launches what the plan says; the only argument it fills is the split-K kernel's pair of reciprocals
+hipError_t launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s)
 {
-    const int kstep = conv_kstep(dtype);
-    cfg->ks = ks; cfg->stream = 0; cfg->wres = 0; cfg->ps = 0; cfg->ws1 = 0; cfg->rowt = 0; cfg->tpw1 = 0;
-    cfg->fastk = (ks == 3 && cin % kstep == 0) ? 1 : 0;
-    cfg->ksplit = 1;
-    const int ntiles = cout_pad / 16;
-    static const int pref[5] = {4, 5, 3, 2, 1};
-    cfg->ct = 1;
-    for (int i = 0; i < 5; ++i)
-        if (ntiles % pref[i] == 0) { cfg->ct = pref[i]; break; }
-    cfg->lds = 0;
-    if (dtype != ZLY_DTYPE_BF16) { cfg->pt = 2; return; }           // fp32 = verification mode: one shape
-    const long ytiles = ntiles / cfg->ct;
-    const long wgs_pt4 = ((long)(M + 255) / 256) * ytiles;
-    const long wgs_pt2 = ((long)(M + 127) / 128) * ytiles;
-    const long wgs_pt1 = ((long)(M + 63) / 64) * ytiles;
-    const char* e4 = getenv("ZLY_DIRECT_PT4_MIN");                       // tuning aids
-    const char* e2 = getenv("ZLY_DIRECT_PT2_MIN");
-    const int nk = (ks * ks * cin + kstep - 1) / kstep;
-    const char* fk = getenv("ZLY_DIRECT_KSPLIT_NK");                   // tuning aid: K-heavy launches take the 4-way split-K shape whatever their size
-    const bool force_split = fk && nk >= atoi(fk);
-    if (!force_split) {
-        if (wgs_pt4 >= (e4 ? atol(e4) : 1024) && cfg->ct <= 4) { cfg->pt = 4; return; }       // CT=5 x PT=4 would need > 200 VGPRs
-        if (wgs_pt2 >= (e2 ? atol(e2) : 512)) { cfg->pt = 2; return; }                      // 1024 before: the K-heavy 1x1 layers at 26x26 re-read their weights per 16 pixels (+0.8 %)
-    }
-    cfg->pt = 1;
-    if (!force_split && (wgs_pt1 >= 512 || nk < 4)) return;
-    cfg->ksplit = 4;                                                 // workgroup = one 16-pixel tile
-    long wgs = ((long)(M + 15) / 16) * ytiles;
-    while (wgs < 256 && cfg->ct > 1) {                               // still thin: fewer channel tiles per wave
-        int nct = cfg->ct - 1;
-        while (nct > 1 && ntiles % nct != 0) --nct;
-        cfg->ct = nct;
-        wgs = ((long)(M + 15) / 16) * (ntiles / cfg->ct);
-    }
-}
-
-hipError_t launch_conv(int dtype, const ConvArgs& a, const ConvLaunch& cfg, hipStream_t s)
-{
-    if (cfg.ws1) {                                                 // weight-stationary 1x1 kernel
-        Ws1Geom g{};
-        int ny = 0;
-        const bool dual = a.in2 != nullptr;
-        if (dtype != ZLY_DTYPE_BF16 || cfg.ks != 1 || a.stride != 1 || a.pad != 0 || a.res || !a.act || a.out_f32 || a.Cin % 32 || a.nk != a.Cin / 32 ||
-            a.Cout % 32 || a.cout_pad != a.Cout || a.in_cs % 8 || a.in_co % 8 || a.out_cs % 8 || a.out_co % 8 || !ws1_plan(a.Cin, a.cout_pad, a.M, &g, &ny, dual)) return hipErrorInvalidValue;
-        if (dual && (a.in2_cs % 8 || a.in2_co % 8 || a.split_c % 8 || a.split_c <= 0 || a.split_c >= a.Cin || (a.H & 1) || (a.W & 1) || a.M % (a.H * a.W))) return hipErrorInvalidValue;
-        // 32-bit byte offsets into the buffer resources: a tensor beyond 2 GiB (batch x map x channels far above any configuration run here)
-        // takes the direct kernel's 64-bit addressing instead
-        const size_t widest = (size_t)a.M * (size_t)std::max(std::max(a.in_cs, a.out_cs), dual ? a.in2_cs : 0) * 2;
-        if (cfg.fastk || widest >= ((size_t)1 << 31)) {             // cfg.fastk: ZLY_WS1_MAX_BYTES was set when the shape was picked (tests: force the fall-back)
-            ConvLaunch d{};
-            conv_pick_direct(dtype, 1, a.Cin, a.cout_pad, a.M, &d);
-            return launch_conv(dtype, a, d, s);
-        }
-        const size_t lds = ((size_t)g.npx * g.pitch + 1023) / 1024 * 1024;
-        int gx = 2 * num_cus() / ny;                               // persistent: two resident workgroups per CU
-        if (gx < 1) gx = 1;
-        if (gx > g.total_tiles) gx = g.total_tiles;
-        hipLaunchKernelGGL(pick_ws1(ws1_tpw(a.nk), a.nk, dual), dim3(gx, ny), dim3(256), lds, s, a, g);
-        return hipGetLastError();
-    }
-    if (cfg.ps) {                                                  // weight-stationary 3x3 kernel
-        WsGeom g{};
-        const int ntiles = a.cout_pad / 16, even = ntiles / 2 * 2;
-        if (dtype != ZLY_DTYPE_BF16 || !pick_ws(a.Cin, 2, false, false, a.stride) || a.pad != 1 || a.in2 || a.out_f32 || !a.act || a.nk != 9 * a.Cin / 32 ||
-            a.in_cs % 8 || a.in_co % 8 || (even != 2 && even != 4 && even != 8) || !ws_plan(a.Ho, a.Wo, a.Cin, a.M / (a.Ho * a.Wo), &g, a.stride)) return hipErrorInvalidValue;
-        if (a.stride == 2 && (a.res || ntiles != even)) return hipErrorInvalidValue;
-        // 32-bit byte offsets into the buffer resources (and 0x80000000 as the out-of-range sentinel): a tensor of 2 GiB or more takes the LDS-tiled /
-        // direct kernels' 64-bit addressing instead (YOLOv8-s 640 x 640 crosses it near batch 440).  ZLY_WS_MAX_BYTES forces it (tests).
-        {
-            const size_t widest = std::max(std::max((size_t)a.M / ((size_t)a.Ho * a.Wo) * a.H * a.W * (size_t)a.in_cs, (size_t)a.M * (size_t)a.out_cs), a.res ? (size_t)a.M * (size_t)a.res_cs : (size_t)0) * 2;
-            const char* mb = getenv("ZLY_WS_MAX_BYTES");
-            if (widest >= (mb ? (size_t)atoll(mb) : ((size_t)1 << 31))) {
-                ConvLaunch d{};
-                if (!pick_lds_config(a.stride, a.Cin, a.cout_pad, a.M / (a.Ho * a.Wo), a.Ho, a.Wo, &d)) conv_pick_direct(dtype, 3, a.Cin, a.cout_pad, a.M, &d);
-                d.ks = 3;
-                return launch_conv(dtype, a, d, s);
-            }
-        }
-        const int n = a.M / (a.Ho * a.Wo);
-        g.total_tiles = g.tiles_x * g.tiles_y * n;
-        const size_t lds = a.stride == 2 ? ((size_t)(2 * g.TH + 1) * (g.TW + 8 * ((g.TW + 8) / 8)) * g.pitch + 1023) / 1024 * 1024
-                                         : ((size_t)(g.TH + 2) * (g.TW + 8) * g.pitch + 1023) / 1024 * 1024;
-        const int gx = g.total_tiles < 2 * num_cus() ? g.total_tiles : 2 * num_cus();      // persistent: two resident workgroups per CU
-        // the even tiles: 4 waves = (even / 2) channel groups x pixel groups
+    if (!p.fn[0] || p.gx < 1 || p.gy < 1) return hipErrorInvalidValue;
+    const dim3 grid(p.gx, p.gy, 1);
+    switch (p.kind) {
+    case CONV_WS1:
+        hipLaunchKernelGGL(reinterpret_cast<conv_ws1_fn>(const_cast<void*>(p.fn[0])), grid, dim3(256), p.lds, s, a, p.ws1);
+        break;
+    case CONV_WS: {
         ConvArgs m = a;
-        m.cout_pad = even * 16;
-        m.Cout = a.Cout < even * 16 ? a.Cout : even * 16;
-        g.nwc = even / 2; g.nwp = 4 / g.nwc;
-        if (cfg.tpw1 && ntiles == 4 && a.Cin == 64) {
-            // 64 output channels as 4 waves x ONE tile (every wave walks all column tiles of the pixel tile) instead of 2 tile pairs x 2 pixel groups: on
-            // small pixel tiles a wave of the pair form has two or three column tiles -- one or two rounds of its software pipeline, mostly fill and drain
-            g.nwc = 4; g.nwp = 1;
-            if (a.stride == 2) hipLaunchKernelGGL(pick_ws(a.Cin, 1, false, false, 2), dim3(gx), dim3(256), lds, s, a, g);
-            else               hipLaunchKernelGGL(pick_ws(a.Cin, 1, a.res != nullptr), dim3(gx), dim3(256), lds, s, a, g);
-            return hipGetLastError();
-        }
-        if (a.stride == 2) {
-            hipLaunchKernelGGL(pick_ws(a.Cin, 2, false, false, 2), dim3(gx), dim3(256), lds, s, m, g);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL(pick_ws(a.Cin, 2, a.res != nullptr, cfg.rowt != 0 && a.Cin == 64 && g.TW + 2 <= 16), dim3(gx), dim3(256), lds, s, m, g);
-        if (ntiles > even && a.Cout > even * 16) {
-            // the odd last tile (pair-permuted rows cover the even tiles only, so it is a plain 16-channel conv of its own): 1 x 4 waves
+        m.cout_pad = p.tiles0 * 16;
+        m.Cout = a.Cout < p.tiles0 * 16 ? a.Cout : p.tiles0 * 16;
+        hipLaunchKernelGGL(reinterpret_cast<conv_ws_fn>(const_cast<void*>(p.fn[0])), grid, dim3(256), p.lds, s, m, p.ws);
+        if (p.fn[1]) {                                             // the odd last tile: 1 x 4 waves
             ConvArgs r = a;
-            r.wgt = static_cast<const char*>(a.wgt) + (size_t)even * a.nk * 1024;
-            r.bias = a.bias + even * 16;
-            r.out_co = a.out_co + even * 16;
-            if (a.res) r.res_co = a.res_co + even * 16;
-            r.Cout = a.Cout - even * 16; r.cout_pad = 16;
+            r.wgt = static_cast<const char*>(a.wgt) + (size_t)p.tiles0 * a.nk * 1024;
+            r.bias = a.bias + p.tiles0 * 16;
+            r.out_co = a.out_co + p.tiles0 * 16;
+            if (a.res) r.res_co = a.res_co + p.tiles0 * 16;
+            r.Cout = a.Cout - p.tiles0 * 16; r.cout_pad = 16;
+            WsGeom g = p.ws;
             g.nwc = 1; g.nwp = 4;
-            hipLaunchKernelGGL(pick_ws(a.Cin, 1, a.res != nullptr), dim3(gx), dim3(256), lds, s, r, g);
+            hipLaunchKernelGGL(reinterpret_cast<conv_ws_fn>(const_cast<void*>(p.fn[1])), grid, dim3(256), p.lds, s, r, g);
         }
-        return hipGetLastError();
+        break;
     }
-    if (cfg.lds) {
-        conv_lds_fn fn = pick_lds(a.stride, cfg.pt, cfg.ct);
-        if (!fn || dtype != ZLY_DTYPE_BF16) return hipErrorInvalidValue;
-        const int cout_pad = a.cout_pad;
-        const int ytiles = cout_pad / (16 * cfg.ct);
-        const int th = 4 * cfg.pt;
-        const int tiles_x = (a.Wo + 15) / 16, tiles_y = (a.Ho + th - 1) / th;
-        const int n = a.M / (a.Ho * a.Wo);
-        const int tiles_per_img = tiles_x * tiles_y, total = tiles_per_img * n;
-        int gx = total;
-        const int nchunks = a.Cin / 32;
-        if (cfg.wres && (a.stride != 1 || nchunks > 2)) return hipErrorInvalidValue;
-        if (a.stride < 1 || a.stride > 2 || cfg.ct > 5 || cfg.pt > 4) return hipErrorInvalidValue;
-        // resident workgroups per CU for this variant and LDS size, asked from the runtime once (registers: 94..243 per
-        // lane, LDS 35..80 KB -> 2..4); the persistent grid is exactly what is resident
-        static int occ_cache[3][6][5][3];                  // [stride][ct][pt][wres chunks] -> blocks per CU
-        int& occ = occ_cache[a.stride][cfg.ct][cfg.pt][cfg.wres ? a.Cin / 32 : 0];
-        if (occ == 0) {
-            int o = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)fn, 256, lds_bytes(a.stride, cfg.pt, cfg.ct, cfg.wres ? a.Cin / 32 : 1)) != hipSuccess || o < 1) o = 2;
-            occ = o > 4 ? 4 : o;
-        }
-        const char* wv = getenv("ZLY_LDS_WGS_PER_CU");       // tuning aid: force
-        const int max_wgs = (wv ? atoi(wv) : occ) * num_cus();
-        if (gx * ytiles > max_wgs) gx = max_wgs / ytiles;  // never more than are resident: a persistent workgroup
-        if (gx > total) gx = total;                        // that has to wait for a slot runs a whole round alone
-        hipLaunchKernelGGL(fn, dim3(gx, ytiles, 1), dim3(256), lds_bytes(a.stride, cfg.pt, cfg.ct, cfg.wres ? nchunks : 1), s, a, tiles_x, tiles_per_img, total, cfg.wres);
-        return hipGetLastError();
+    case CONV_LDS:
+        hipLaunchKernelGGL(reinterpret_cast<conv_lds_fn>(const_cast<void*>(p.fn[0])), grid, dim3(256), p.lds, s, a, p.tiles_x, p.tiles_per_img, p.total_tiles, p.wres);
+        break;
+    case CONV_STREAM:
+        hipLaunchKernelGGL(reinterpret_cast<conv_stream_fn>(const_cast<void*>(p.fn[0])), grid, dim3(256), 0, s, a, p.ngroups);
+        break;
+    case CONV_DIRECT: {
+        ConvArgs b = a;
+        b.inv_wo = 1.0f / (float)a.Wo; b.inv_ho = 1.0f / (float)a.Ho;
+        hipLaunchKernelGGL(reinterpret_cast<conv_fn>(const_cast<void*>(p.fn[0])), grid, dim3(256), 0, s, b);
+        break;
     }
-    if (cfg.ks == 1 && (a.stride != 1 || a.pad != 0)) return hipErrorInvalidValue;      // the 1x1 paths assume input pixel = output pixel
-    if (cfg.stream) {
-        const int nk = (a.Cin + 31) / 32;
-        conv_stream_fn sf = pick_stream(cfg.ct, cfg.pt, nk);
-        if (!sf || dtype != ZLY_DTYPE_BF16 || a.in2 || a.res || nk > a.nk || !a.act || a.out_f32 || a.Cout % 32 || a.in_cs % 8 || a.in_co % 8 || a.out_cs % 8 || a.out_co % 8)
-            return hipErrorInvalidValue;
-        const int cout_pad = a.cout_pad;
-        const int ytiles = cout_pad / (16 * cfg.ct);
-        const int ngroups = (a.M + 16 * cfg.pt - 1) / (16 * cfg.pt);
-        int gx = (ngroups + 3) / 4;
-        const char* sw = getenv("ZLY_STREAM_WGS");         // tuning / tests: total persistent workgroups (default ~4 per CU)
-        const int wgs = sw && atoi(sw) > 0 ? atoi(sw) : (cfg.ct == 4 && cfg.pt == 1 ? 2 : 4) * num_cus();      // the 64-channel shapes hold 2 workgroups per CU (189-239 VGPRs)
-        const int cap = wgs / ytiles > 0 ? wgs / ytiles : 1;
-        if (gx > cap) gx = cap;
-        hipLaunchKernelGGL(sf, dim3(gx, ytiles, 1), dim3(256), 0, s, a, ngroups);
-        return hipGetLastError();
+    default:
+        return hipErrorInvalidValue;
     }
-    const int mode = cfg.ks == 1 ? 0 : (cfg.fastk ? 1 : 2);
-    conv_fn fn = nullptr;
-    // the split-K kernel reads its inputs through 32-bit buffer offsets: an input tensor of 2 GiB or more (never a latency-path launch) takes the one-pass shape
-    const size_t in_bytes = (size_t)(a.M / (a.Ho * a.Wo)) * a.H * a.W * (size_t)std::max(a.in_cs, a.in2 ? a.in2_cs : 0) * 2;
-    const bool split = cfg.ksplit == 4 && in_bytes < ((size_t)1 << 31) && a.M < (1 << 20) && a.Wo < 1024 && a.Ho < 1024;
-    if (dtype == ZLY_DTYPE_BF16) {
-        if (split)             fn = pick_mode<bf16_t, 1, 4>(mode, cfg.ct);
-        else if (cfg.pt == 1)  fn = pick_mode<bf16_t, 1, 1>(mode, cfg.ct);
-        else if (cfg.pt == 2)  fn = pick_mode<bf16_t, 2, 1>(mode, cfg.ct);
-        else                   fn = pick_mode<bf16_t, 4, 1>(mode, cfg.ct);
-    } else {
-        fn = pick_mode<float, 2, 1>(mode, cfg.ct);
-    }
-    if (!fn) return hipErrorInvalidValue;
-    const int cout_pad = a.cout_pad;
-    const int ytiles = cout_pad / (16 * cfg.ct);
-    const int px_per_wg = split ? 16 * cfg.pt : 64 * cfg.pt;
-    dim3 grid((a.M + px_per_wg - 1) / px_per_wg, ytiles, 1);
-    ConvArgs b = a;
-    b.inv_wo = 1.0f / (float)a.Wo; b.inv_ho = 1.0f / (float)a.Ho;
-    hipLaunchKernelGGL(fn, grid, dim3(256), 0, s, b);
     return hipGetLastError();
 }
 

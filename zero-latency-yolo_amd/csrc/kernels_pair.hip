@@ -636,10 +636,10 @@ static size_t pair_lds_bytes(int c, int th, int tw)
 
 // Tile shape for an H x W map and n frames: minimise (rounds of tiles over the 256 CUs) x (16-pixel tile rounds of the
 // two convs over the workgroup's waves + a fixed per-tile cost), subject to the LDS budget and the staging registers.
-bool pair_plan(int c, int n, int H, int W, PairPlan* plan)
+bool pair_plan(int c, int n, int H, int W, const Switches& sw, PairPlan* plan)
 {
     if (c != 16 && c != 32 && c != 64) return false;
-    const int ncu = num_cus(), nw = pair_nw(c);
+    const int ncu = sw.num_cus, nw = pair_nw(c);
     double best = 1e30;
     for (int th = 4; th <= 32; ++th) {
         for (int tw = 8; tw <= 64; ++tw) {
@@ -673,12 +673,10 @@ hipError_t pair_init()
 static constexpr int C2F_NW16 = 16, C2F_NW32 = 8, C2F_NLD = 4;
 // waves per workgroup of the 32-channel kernel: 16 (128 VGPRs, biases in LDS: four waves per SIMD hide the fragment-read and epilogue latencies
 // behind each other -- neither the vector nor the matrix pipe was half busy with two) except for the front half, which spills at 128 and keeps 8
-// (read where the plan is made -- c2f_plan, cached per engine and shape -- and carried in C2fPlan::nw: as a process-static it could not be switched by a test)
-static int c2f_nw32(int mode)
+// (decided where the plan is made -- c2f_plan, once per engine and batch size -- and carried in C2fPlan::nw)
+static int c2f_nw32(int mode, const Switches& sw)
 {
-    const char* fv = getenv("ZLY_C2F32_NW");                                                   // tuning / tests: 8 or 16 for every mode
-    const int forced = fv ? atoi(fv) : 0;
-    if (forced == 8 || forced == 16) return forced;
+    if (sw.c2f32_nw == 8 || sw.c2f32_nw == 16) return sw.c2f32_nw;                            // tuning / tests: 8 or 16 for every mode
     return mode == 1 ? C2F_NW32 : 16;          // measured at batch 64: back half 40.7 -> 30.2 us, whole block (model.15) 55.9 -> 44.9 us; the front half spills at 128 VGPRs (30.5 -> 34 us)
 }
 static size_t c2f_lds_bytes(int c, int mode, int nk1, int nk2, int cout2, int th, int tw)
@@ -694,21 +692,21 @@ static size_t c2f_lds_bytes(int c, int mode, int nk1, int nk2, int cout2, int th
 }
 
 typedef void (*c2f_fn)(const C2fArgs);
-static c2f_fn pick_c2f(int c, int mode, int nk1);
+static c2f_fn pick_c2f(int c, int mode, int nk1, int nw32);
 
 // tile shape: rounds of tiles over the CUs x (16-pixel tile rounds of the phases over the workgroup's waves + a fixed cost), LDS budget
-bool c2f_plan(int c, int mode, int nk1, int nk2, int cout2, int n, int H, int W, C2fPlan* plan)
+bool c2f_plan(int c, int mode, int nk1, int nk2, int cout2, int n, int H, int W, const Switches& sw, C2fPlan* plan)
 {
-    if (c == 64 && mode >= 1 && mode <= 3) return c2f64_plan(mode, nk1, nk2, cout2, n, H, W, plan);
-    if ((c != 16 && c != 32) || mode < 1 || mode > 3 || !pick_c2f(c, mode, nk1)) return false;
+    if (c == 64 && mode >= 1 && mode <= 3) return c2f64_plan(mode, nk1, nk2, cout2, n, H, W, sw, plan);
+    if ((c != 16 && c != 32) || mode < 1 || mode > 3 || !pick_c2f(c, mode, nk1, c2f_nw32(mode, sw))) return false;
     if ((mode & 2) && nk2 != (mode == 2 ? 4 : 3)) return false;          // concat of 3 (one bottleneck) or 4 (back half of two) sources
-    const int ncu = num_cus(), nw = c == 16 ? C2F_NW16 : c2f_nw32(mode);
+    const int ncu = sw.num_cus, nw = c == 16 ? C2F_NW16 : c2f_nw32(mode, sw);
+    const size_t lds_cap = sw.c2f_lds_kb ? (size_t)sw.c2f_lds_kb * 1024 : (size_t)PAIR_LDS_MAX;      // tuning aid
     double best = 1e30;
     for (int th = 4; th <= 32; ++th) {
         for (int tw = 8; tw <= 64; ++tw) {
-            const size_t lds_cap = getenv("ZLY_C2F_LDS_KB") ? (size_t)atoi(getenv("ZLY_C2F_LDS_KB")) * 1024 : (size_t)PAIR_LDS_MAX;    // tuning aid
             if (c2f_lds_bytes(c, mode, nk1, nk2, cout2, th, tw) > lds_cap) continue;
-            if (const char* ft = getenv("ZLY_C2F_TILE")) { int fth = 0, ftw = 0; if (sscanf(ft, "%d,%d", &fth, &ftw) == 2 && (fth != th || ftw != tw)) continue; }    // tuning aid: only this shape
+            if (sw.c2f_tile_th && (sw.c2f_tile_th != th || sw.c2f_tile_tw != tw)) continue;      // tuning aid: only this shape
             if (!(mode & 1) && (th + 4) * (tw + 4) * (c / 8) > nw * 64 * C2F_NLD) continue;
             const int tx = (W + tw - 1) / tw, ty = (H + th - 1) / th;
             const long tiles = (long)n * tx * ty;
@@ -744,7 +742,6 @@ static c2f_fn pick_c2f(int c, int mode, int nk1, int nw32)
 {
     return c == 16 ? pick_c2f_c<16, C2F_NW16>(mode, nk1) : nw32 == 16 ? pick_c2f_c<32, 16>(mode, nk1) : pick_c2f_c<32, C2F_NW32>(mode, nk1);
 }
-static c2f_fn pick_c2f(int c, int mode, int nk1) { return pick_c2f(c, mode, nk1, c2f_nw32(mode)); }
 
 hipError_t c2f_init()
 {

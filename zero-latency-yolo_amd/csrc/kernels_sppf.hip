@@ -275,9 +275,7 @@ static sppf_fn pick_sppf(int nk1, int np2)
 }
 
 // workgroups per frame (by cv2 output channels): 4 while that leaves the launch at or below one workgroup per CU, else 2
-int sppf_split(int cout, int n) { return (cout / 4) % 64 == 0 && (long)n * 4 <= (long)num_cus() ? 4 : 2; }      // (one workgroup per CU: 146 KB of LDS)
-
-static int sppf_split_of(const SppfArgs& a) { return a.split == 2 || a.split == 4 ? a.split : sppf_split(a.Cout, a.n); }
+int sppf_split(int cout, int n, const Switches& sw) { return (cout / 4) % 64 == 0 && (long)n * 4 <= (long)sw.num_cus ? 4 : 2; }      // (one workgroup per CU: 146 KB of LDS)
 
 // does the fused kernel take this launch?  (YOLOv8n: 256 -> 128 -> 256 on maps of up to 176 pixels -- 13 x 13 at 416 x 416; everything else takes the
 // three-launch path: at 640 x 640 three 400-pixel maps of 128 channels do not fit one CU's LDS.)  Also 16-byte aligned views and 32-bit offsets.
@@ -285,9 +283,9 @@ bool sppf_fused_ok(const SppfArgs& a)
 {
     if (a.c != SPPF_C || a.Cin != 256 || a.Cout % 128 != 0 || a.Cout > 256 || a.H * a.W > SPPF_MAXPX || a.H < 3 || a.W < 3) return false;
     if (sppf_lds_bytes(a.Cin, a.H * a.W) > 160 * 1024) return false;
-    if (a.x_cs % 8 || a.x_co % 8 || a.out_cs % 8 || a.out_co % 8 || a.cat_cs % 8 || a.n < 1) return false;
+    if (a.x_cs % 8 || a.x_co % 8 || a.out_cs % 8 || a.out_co % 8 || a.cat_cs % 8 || a.n < 1 || (a.split != 2 && a.split != 4)) return false;
     if ((size_t)a.n * a.H * a.W * (size_t)std::max(a.x_cs, std::max(a.out_cs, a.cat_cs)) * 2 >= ((size_t)1 << 31)) return false;      // 32-bit offsets
-    return pick_sppf(a.Cin / 32, a.Cout / sppf_split_of(a) / 32) != nullptr;
+    return pick_sppf(a.Cin / 32, a.Cout / a.split / 32) != nullptr;
 }
 
 hipError_t sppf_init()
@@ -302,8 +300,7 @@ hipError_t sppf_init()
 hipError_t launch_sppf_fused(const SppfArgs& a, hipStream_t s)
 {
     if (!sppf_fused_ok(a)) return hipErrorInvalidValue;
-    const int split = sppf_split_of(a);
-    hipLaunchKernelGGL(pick_sppf(a.Cin / 32, a.Cout / split / 32), dim3(split, a.n), dim3(SPPF_NW * 64), sppf_lds_bytes(a.Cin, a.H * a.W), s, a);
+    hipLaunchKernelGGL(pick_sppf(a.Cin / 32, a.Cout / a.split / 32), dim3(a.split, a.n), dim3(SPPF_NW * 64), sppf_lds_bytes(a.Cin, a.H * a.W), s, a);
     return hipGetLastError();
 }
 

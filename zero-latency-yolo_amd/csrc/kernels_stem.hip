@@ -781,14 +781,14 @@ static size_t stem1_lds_bytes(int th, int tw, int var)
 }
 
 // tile shape: the widest TW <= 26 that divides the map width if there is one (104 -> 26, 160 -> 20), TH = 8
-void stem1_plan(int H1, int W1, int* th, int* tw)
+void stem1_plan(int H1, int W1, const Switches& sw, int* th, int* tw)
 {
     *th = 8;
     *tw = 26;
     for (int c = 26; c >= 13; --c)
         if (W1 % c == 0) { *tw = c; break; }
-    if (const char* v = getenv("ZLY_STEM1_TW")) { if (atoi(v) >= 8 && atoi(v) <= 26) *tw = atoi(v); }      // tuning aids
-    if (const char* v = getenv("ZLY_STEM1_TH")) { if (atoi(v) >= 2 && atoi(v) <= 8) *th = atoi(v); }
+    if (sw.stem1_tw >= 8 && sw.stem1_tw <= 26) *tw = sw.stem1_tw;      // tuning aids
+    if (sw.stem1_th >= 2 && sw.stem1_th <= 8) *th = sw.stem1_th;
     (void)H1;
 }
 

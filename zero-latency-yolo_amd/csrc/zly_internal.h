@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <string>
 #include "zly.h"
 
 namespace zly {
@@ -55,25 +56,98 @@ struct ConvArgs {
     int out_f32;                  // 1 = write fp32 regardless of the activation dtype
 };
 
-struct ConvLaunch { int ks, ct, pt, fastk, ksplit, lds, stream, wres, ps, ws1, rowt, tpw1; };   // rowt: weight-stationary 3x3 kernel's row-tile form (ZLY_WS_ROWT, read when the shape is picked)
 struct ConvArgsMulti { ConvArgs a[6]; int n; };       // independent convs of one launch (conv_igemm_multi_kernel)
 hipError_t launch_conv_multi(const ConvArgsMulti& m, int ct, hipStream_t s);
 
-// compute units the engine's streams may use: 256 (whole chip), or the size of its CU partition (engine.cpp: ZLY_CU_PART).  The
-// persistent grids of the conv kernels are sized from it (a persistent workgroup that waits for a slot runs a whole round alone).
-int  num_cus();
-void set_num_cus(int n);
+// Every tuning / test switch of the environment, with its default.  THE list of the switches: an engine reads them once, at zly_create
+// (engine.cpp: read_switches), and hands the record to whoever plans a launch; nothing else in csrc/ looks at the environment.
+struct Switches {
+    int  num_cus = 256;             // compute units the engine's streams may use: the whole chip, or the size of its partition (ZLY_CU_PART).  Persistent grids are
+                                    // sized from it (a persistent workgroup that waits for a slot runs a whole round alone)
+    // ---- engine ----
+    int  cu_part_i = 0, cu_part_n = 1;  // ZLY_CU_PART="i/n": the engine's streams use the i-th of n equal slices of the chip's compute units
+    bool no_lanes = false;          // ZLY_NO_LANES (or ZLY_CU_PART given): no Detect branches on side streams
+    bool no_c2f = false;            // ZLY_NO_C2F: no fused C2f kernel
+    bool no_det_merge = false;      // ZLY_NO_DET_MERGE: the Detect convs as launches of their own at batch <= 4 too
+    bool no_tail_split = false;     // ZLY_NO_TAIL_SPLIT: one Detect tail launch for all levels also with side streams
+    bool sppf_fused = false;        // ZLY_SPPF_FUSED: the fused SPPF kernel (opt-in: 36 -> ~24 us in isolation at batch 64, but the step gets 0.5 % slower)
+    bool pool_six_pass = false;     // ZLY_SPPF_POOL_LDS: SPPF's pools on the six-pass LDS kernel also on small maps
+    bool no_wsk = false;            // ZLY_NO_WSK: the class-branch convs on the LDS-tiled kernel (96-channel padding)
+    bool nms_general = false;       // ZLY_NMS_GENERAL: every frame on NMS's eight-wave path
+    bool no_cout_pad = false;       // ZLY_NO_COUT_PAD: no sixth, all-zero output tile for the 80-channel 3x3 convs
+    bool no_cin_pad = false;        // ZLY_NO_CIN_PAD: the class branch's input not stored as a multiple of 32 channels
+    bool no_stem1 = false;          // ZLY_NO_STEM1: model.1 not fused into the front kernel
+    int  stem1_nw = 0;              // ZLY_STEM1_NW: waves per workgroup of the front kernel (12 / 16; 0 = its default)
+    int  stem1_var = 1;             // ZLY_STEM1_VAR: 2 = persistent workgroups + input prefetch, 1 = one tile per workgroup, 0 = round 3's staging / tap order
+    int  stem1_grid = 0;            // ZLY_STEM1_GRID: workgroups of the persistent grid (0 = as many as stay resident)
+    int  stem1_tw = 0, stem1_th = 0;    // ZLY_STEM1_TW (8..26) / ZLY_STEM1_TH (2..8): the front kernel's tile (0 = planned)
+    bool stem1_keep_tiles = false;  // ZLY_STEM1_TW, ZLY_STEM1_TH or ZLY_STEM1_BIG_TILES given: the planned tile at every batch size (no halving for small batches)
+    int  pair_min_tiles = 32;       // ZLY_PAIR_MIN_TILES: fewest tiles for which a bottleneck runs as the fused pair
+    int  pair_widths = 48;          // ZLY_PAIR_WIDTHS: bit mask of fused pair widths (16 | 32 | 64)
+    int  stage_slots = 6;           // ZLY_STAGE_SLOTS: ring slots of the pipelined host path (3..16)
+    int  stage_mb = 0;              // ZLY_STAGE_MB: bytes per slot in MiB (0 = 1.25 batches)
+    int  inflight = 2;              // ZLY_INFLIGHT: batches on the device at once
+    bool d2h_stream = false;        // ZLY_D2H_STREAM: result download on a stream of its own
+    int  profile_inner = 1;         // ZLY_PROFILE_INNER: launches per event pair in zly_profile_ops (which reads it per call: bench.py changes it between two calls)
+    std::string ablate;             // ZLY_ABLATE_SKIP: ops to leave out, ",name,name," (result-changing: libzly_diag.so only)
+    // ---- generic convs (kernels_conv.hip: conv_plan) ----
+    bool no_stream = false;         // ZLY_NO_STREAM: never the streaming 1x1 kernel
+    bool stream_ct2 = false;        // ZLY_STREAM_CT2: 192 / 256 input channels on its CT = 2 shapes
+    int  stream_max_nk = 1 << 30;   // ZLY_STREAM_MAX_NK: most k-steps it takes
+    long stream_min_groups = 4096;  // ZLY_STREAM_MIN_GROUPS: fewest pixel groups it takes
+    int  stream_wgs = 0;            // ZLY_STREAM_WGS: its persistent workgroups in all (0 = 4, or 2, per CU)
+    int  ws1_mode = 1;              // ZLY_WS1: 0 = never the weight-stationary 1x1 kernel, 1 = for the shapes the streaming kernel does not take, 2 = before it
+    bool ws1_no_dual = false;       // ZLY_WS1_NO_DUAL: not for the Upsample + Concat inputs
+    long ws1_min_px = 2048;         // ZLY_WS1_MIN_PX: fewest pixels it takes
+    bool ws1_max_bytes = false;     // ZLY_WS1_MAX_BYTES: plan its shapes as tensors beyond 32-bit offsets are (the direct kernel)
+    bool no_ws = false;             // ZLY_NO_WS: never the weight-stationary 3x3 kernel
+    bool no_ws_s2 = false;          // ZLY_NO_WS_S2: not for stride 2
+    bool no_ws_s2_c32 = false;      // ZLY_NO_WS_S2_C32: not for stride 2 with 32 input channels
+    bool ws_rowt = false;           // ZLY_WS_ROWT: its row-tile form (one MFMA tile per output row, kx taps by DPP shifts)
+    int  ws_tpw1_maxct = 6;         // ZLY_WS_TPW1_MAXCT: 64 -> 64 as 4 waves x one tile on pixel tiles of up to this many column tiles (0 = never)
+    long ws_min_tiles = 64;         // ZLY_WS_MIN_TILES: fewest 13 x 13 tiles' worth of pixels it (and the K-packed kernel) takes
+    size_t ws_max_bytes = (size_t)1 << 31;  // ZLY_WS_MAX_BYTES: tensors of this size or more take the LDS-tiled / direct kernel (32-bit offsets; tests lower it)
+    bool no_wres = false;           // ZLY_NO_WRES: LDS-tiled kernel without resident weights
+    int  wres_maxchunks = 1;        // ZLY_WRES_MAXCHUNKS: most 32-channel chunks whose weights stay resident
+    bool lds_s2_pt1 = false;        // ZLY_LDS_S2_PT1: 4-row tiles at stride 2
+    long lds_min_tiles = 384;       // ZLY_LDS_MIN_TILES: fewest work items it takes
+    int  lds_wgs_per_cu = 0;        // ZLY_LDS_WGS_PER_CU: its persistent workgroups per CU (0 = as many as are resident)
+    long direct_pt4_min = 1024, direct_pt2_min = 512;   // ZLY_DIRECT_PT4_MIN / ZLY_DIRECT_PT2_MIN: fewest workgroups for 4 / 2 pixel tiles per wave
+    int  direct_ksplit_nk = 1 << 30;    // ZLY_DIRECT_KSPLIT_NK: launches with this many k-steps or more take the 4-way split-K shape whatever their size
+    // ---- fused C2f (kernels_pair.hip, kernels_c2f64.hip) ----
+    int  c2f32_nw = 0;              // ZLY_C2F32_NW: 8 or 16 waves per workgroup of the 32-channel kernel in every mode (0 = per mode)
+    int  c2f_lds_kb = 0;            // ZLY_C2F_LDS_KB: LDS budget of a tile in KiB (0 = 160)
+    int  c2f_tile_th = 0, c2f_tile_tw = 0;  // ZLY_C2F_TILE="th,tw": only this tile shape (0 = planned)
+    bool c2f64 = false;             // ZLY_C2F64: the fused 64-channel C2f kernel (opt-in: faster per launch, slower per step with three engines)
+};
 
 // kernels_conv.hip
-hipError_t launch_conv(int dtype, const ConvArgs& a, const ConvLaunch& cfg, hipStream_t s);
-void       conv_pick_config(int dtype, int ks, int stride, int cin, int cout_pad, int n, int Ho, int Wo, ConvLaunch* cfg,
-                            bool streamable = false,    // single source, no residual, SiLU, bf16 output, Cout % 32 == 0
-                            bool plain = false,         // single source, activation dtype output: may take the weight-stationary 3x3 kernel
-                            bool dual = false);         // 1x1 with the fused Upsample + Concat input, otherwise as `streamable`: may take the weight-stationary 1x1 kernel
+// A conv launch, resolved: which kernel, its shape parameters, geometry, grid and dynamic LDS.  conv_plan decides everything (also that a tensor
+// beyond a kernel's 32-bit offsets takes another kernel); launch_conv only launches.
+enum ConvKind { CONV_DIRECT, CONV_LDS, CONV_STREAM, CONV_WS, CONV_WS1 };       // conv_igemm_kernel, conv3x3_lds_kernel, conv1x1_stream_kernel, conv3x3_ws_kernel, conv1x1_ws_kernel
+struct WsGeom { int TH, TW, tiles_x, tiles_y, total_tiles, pitch, nchunks, nwc, nwp; };
+struct Ws1Geom { int npx, total_tiles, pitch, nwc, nwp; };
+struct ConvPlan {
+    int kind;                       // ConvKind
+    int ct, pt, ksplit;             // channel tiles / pixel tiles per wave (CONV_WS1: pixel tiles per workgroup); split-K ways
+    int fastk;                      // 3x3 with K a multiple of the k-step
+    int wres, rowt, tpw1;           // CONV_LDS: resident weights; CONV_WS: row-tile form, 64 -> 64 as 4 waves x one tile
+    const void* fn[2];              // kernel(s); fn[1]: CONV_WS's second launch for an odd last channel tile, else null
+    unsigned gx, gy;                // grid (256 threads per workgroup)
+    unsigned lds;                   // dynamic LDS bytes
+    int tiles_x, tiles_per_img, total_tiles;    // CONV_LDS
+    int ngroups;                    // CONV_STREAM
+    int tiles0;                     // CONV_WS: channel tiles the first launch covers
+    WsGeom ws;                      // CONV_WS (of the first launch)
+    Ws1Geom ws1;                    // CONV_WS1
+};
+void       conv_plan(int dtype, int ks, const ConvArgs& a, const Switches& sw, ConvPlan* plan);
+hipError_t launch_conv(const ConvArgs& a, const ConvPlan& plan, hipStream_t s);
 hipError_t conv_init();
 // the 80 -> 80 class-branch convs: weight-stationary with K packed across taps (kernels_conv.hip: conv3x3_wsk_kernel); weights tiled with cin_store = 80
-bool       conv_wsk_ok(int cin, int cout, int n, int Ho, int Wo);
-hipError_t launch_conv_wsk(const ConvArgs& a, hipStream_t s);
+struct WskPlan { WsGeom g; unsigned gx, lds; };
+bool       conv_wsk_ok(const ConvArgs& a, const Switches& sw, WskPlan* plan);     // does launch_conv_wsk take this launch?  (fills the plan if so)
+hipError_t launch_conv_wsk(const ConvArgs& a, const WskPlan& plan, hipStream_t s);
 int        conv_kstep(int dtype);
 
 // kernels_pair.hip -- a C2f bottleneck (two 3x3 convs, c -> c -> c, optional shortcut) as one kernel; bf16, c = 16 / 32
@@ -87,7 +161,7 @@ struct PairArgs {
     int res;                                  // 1 = add x to the output (after the activation)
 };
 struct PairPlan { int th, tw, tiles_x, tiles_y, total_tiles, grid, lds_bytes; };
-bool       pair_plan(int c, int n, int H, int W, PairPlan* plan);
+bool       pair_plan(int c, int n, int H, int W, const Switches& sw, PairPlan* plan);
 hipError_t pair_init();
 hipError_t launch_pair(int c, const PairArgs& a, const PairPlan& plan, hipStream_t s);
 
@@ -107,11 +181,11 @@ struct C2fArgs {
     void* mid; int mid_cs;                    // c = 64 with dump: the bottleneck's intermediate map (its first conv's output buffer of the unfused path)
 };
 struct C2fPlan { int th, tw, tiles_x, tiles_y, total_tiles, grid, lds_bytes, nw; };      // nw: waves per workgroup the plan was made for
-bool       c2f_plan(int c, int mode, int nk1, int nk2, int cout2, int n, int H, int W, C2fPlan* plan);
+bool       c2f_plan(int c, int mode, int nk1, int nk2, int cout2, int n, int H, int W, const Switches& sw, C2fPlan* plan);
 hipError_t c2f_init();
 hipError_t launch_c2f(int c, int mode, const C2fArgs& a, const C2fPlan& plan, hipStream_t s);
 // kernels_c2f64.hip -- the same for c = 64 (c2f64_kernel: 3x3 weights in registers, 1x1 weights streamed through LDS); reached through c2f_plan / launch_c2f
-bool       c2f64_plan(int mode, int nk1, int nk2, int cout2, int n, int H, int W, C2fPlan* plan);
+bool       c2f64_plan(int mode, int nk1, int nk2, int cout2, int n, int H, int W, const Switches& sw, C2fPlan* plan);
 hipError_t c2f64_init();
 hipError_t launch_c2f64(int mode, const C2fArgs& a, const C2fPlan& plan, hipStream_t s);
 
@@ -150,7 +224,7 @@ struct Stem1Args {
     float inv_pw, inv_rw, inv_tw, inv_qb;     // 1 / patch row pitch, 1 / region width, 1 / tile width, 1 / quad blocks per patch row
     const void* wgt0p;                        // stem weights in the tap order of the conflict-free fragment reads (kernels_stem.hip: STEM1_TAP_SLOT)
 };
-void       stem1_plan(int H1, int W1, int* th, int* tw);
+void       stem1_plan(int H1, int W1, const Switches& sw, int* th, int* tw);
 hipError_t stem1_init();
 hipError_t launch_stem_model1(const Stem1Args& a, int n, hipStream_t s, bool yuv = false, bool lb = false);
 const int* stem1_tap_slot();              // [9]: k slot of tap ky * 3 + kx in Stem1Args::wgt0p (weights.h: repack_conv's tap_slot)
@@ -163,11 +237,11 @@ struct SppfArgs {
     void* out; int out_cs, out_co, Cout;
     void* cat; int cat_cs;                    // the block's concat buffer in HBM: written only with dump (debug taps)
     int H, W, n, c;
-    int split;                                // workgroups per frame (2 / 4), 0 = chosen from n
+    int split;                                // workgroups per frame (2 / 4: sppf_split)
     int dump;
 };
 bool       sppf_fused_ok(const SppfArgs& a);     // does launch_sppf_fused take this launch?
-int        sppf_split(int cout, int n);
+int        sppf_split(int cout, int n, const Switches& sw);
 hipError_t sppf_init();
 hipError_t launch_sppf_fused(const SppfArgs& a, hipStream_t s);
 

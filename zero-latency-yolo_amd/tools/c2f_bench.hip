@@ -8,8 +8,7 @@
 #include <string.h>
 #include <vector>
 namespace zly {
-int num_cus() { return 256; }
-bool c2f64_plan(int, int, int, int, int, int, int, C2fPlan*) { return false; }
+bool c2f64_plan(int, int, int, int, int, int, int, const Switches&, C2fPlan*) { return false; }
 hipError_t c2f64_init() { return hipSuccess; }
 hipError_t launch_c2f64(int, const C2fArgs&, const C2fPlan&, hipStream_t) { return hipErrorInvalidValue; }
 }
@@ -27,7 +26,7 @@ static void run(const char* name, int c, int mode, int n, int H, int W, int cin,
 {
     const int nk1 = cin / 32, nk2 = nmaps;
     C2fPlan pl{};
-    if (!c2f_plan(c, mode, nk1, nk2, cout2, n, H, W, &pl)) { printf("%s: no plan\n", name); return; }
+    if (!c2f_plan(c, mode, nk1, nk2, cout2, n, H, W, Switches(), &pl)) { printf("%s: no plan\n", name); return; }
     C2fArgs a; memset(&a, 0, sizeof a);
     const size_t px = (size_t)n * H * W;
     if (dual) { a.x = dalloc_rand(px / 4 * 128, 1, 0x3c00, 0x1ff); a.x_cs = 128; a.x2 = dalloc_rand(px * 64, 2, 0x3c00, 0x1ff); a.x2_cs = 64; a.split_c = 128; }

@@ -7,7 +7,6 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-namespace zly { int num_cus() { return 256; } }
 using namespace zly;
 
 static void* dalloc_rand(size_t elems, unsigned seed, unsigned short base, unsigned mask)
@@ -22,7 +21,9 @@ static void run(const char* name, int mode, int n, int H, int W, int cin, bool d
 {
     const int nk1 = cin / 32, nk2 = 2 * nmaps;
     C2fPlan pl{};
-    if (!c2f64_plan(mode, nk1, nk2, 128, n, H, W, &pl)) { printf("%s: no plan\n", name); return; }
+    Switches sw;
+    sw.c2f64 = true;                       // the kernel is opt-in (ZLY_C2F64)
+    if (!c2f64_plan(mode, nk1, nk2, 128, n, H, W, sw, &pl)) { printf("%s: no plan\n", name); return; }
     C2fArgs a; memset(&a, 0, sizeof a);
     const size_t px = (size_t)n * H * W;
     if (dual) { a.x = dalloc_rand(px / 4 * 256, 1, 0x3c00, 0x1ff); a.x_cs = 256; a.x2 = dalloc_rand(px * 128, 2, 0x3c00, 0x1ff); a.x2_cs = 128; a.split_c = 256; }

@@ -25,8 +25,8 @@ static void run(const char* name, int H, int W, int Cin, int Cout, int ks, int s
     a.in = din; a.in_cs = Cin; a.H = H; a.W = W; a.Cin = Cin; a.wgt = dw; a.bias = dbias;
     a.out = dout; a.out_cs = cout_pad; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.cout_pad = cout_pad; a.stride = stride; a.pad = ks / 2;
     a.K = ks * ks * Cin; a.nk = nk; a.M = n * Ho * Wo; a.act = 1;
-    ConvLaunch cfg{};
-    conv_pick_direct(ZLY_DTYPE_BF16, ks, Cin, cout_pad, a.M, &cfg);
+    ConvPlan cfg{};
+    plan_direct(ZLY_DTYPE_BF16, ks, a, Switches(), &cfg);
     if (cfg.ksplit != 4) { printf("%-34s not a split-K shape (ct %d pt %d)\n", name, cfg.ct, cfg.pt); return; }
     const int gx = (a.M + 15) / 16, gy = cout_pad / (16 * cfg.ct);
     const size_t nw = (size_t)gx * gy * 4;
@@ -36,7 +36,7 @@ static void run(const char* name, int H, int W, int Cin, int Cout, int ks, int s
     const int N = 40;
     hipGraph_t gr; hipGraphExec_t ge;
     (void)hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    for (int i = 0; i < N; ++i) if (launch_conv(ZLY_DTYPE_BF16, a, cfg, st) != hipSuccess) { printf("%s: launch failed\n", name); return; }
+    for (int i = 0; i < N; ++i) if (launch_conv(a, cfg, st) != hipSuccess) { printf("%s: launch failed\n", name); return; }
     (void)hipStreamEndCapture(st, &gr);
     (void)hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0);
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);

@@ -7,7 +7,6 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-namespace zly { int num_cus() { return 256; } }
 using namespace zly;
 
 static void* dalloc_bf16(size_t elems, unsigned seed)

@@ -23,21 +23,20 @@ static void run(const char* name, int n, int H, int W, int Cin, int Cout)
     a.in = din; a.in_cs = Cin; a.H = H; a.W = W; a.Cin = Cin; a.wgt = dw; a.bias = dbias;
     a.out = dout; a.out_cs = Cout; a.Ho = H; a.Wo = W; a.Cout = Cout; a.cout_pad = cout_pad; a.stride = 1; a.pad = 1;
     a.K = 9 * Cin; a.nk = nk; a.M = n * H * W; a.act = 1;
-    WsGeom g{};
-    if (!ws_plan(H, W, Cin, n, &g)) { printf("%s: no plan\n", name); return; }
-    g.total_tiles = g.tiles_x * g.tiles_y * n;
-    const size_t lds = ((size_t)(g.TH + 2) * (g.TW + 8) * g.pitch + 1023) / 1024 * 1024;
-    const int gx = g.total_tiles < 512 ? g.total_tiles : 512;
+    conv_init();
+    ConvPlan cfg{};
+    if (!plan_ws(a, Switches(), &cfg) || cfg.kind != CONV_WS) { printf("%s: no plan\n", name); return; }
+    const WsGeom g = cfg.ws;
+    const size_t lds = cfg.lds;
+    const int gx = (int)cfg.gx;
     const size_t nw = (size_t)gx * 4;
     hipMalloc((void**)&ddbg, nw * 64); hipMemset(ddbg, 0, nw * 64);
     hipMemcpyToSymbol(HIP_SYMBOL(g_ws_diag), &ddbg, sizeof ddbg);
-    ws_init();
-    ConvLaunch cfg{}; cfg.ps = 1;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     float ms = 0, best = 1e9f;
     for (int rep = 0; rep < 30; ++rep) {
         hipEventRecord(e0, 0);
-        launch_conv(ZLY_DTYPE_BF16, a, cfg, 0);
+        launch_conv(a, cfg, 0);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         hipEventElapsedTime(&ms, e0, e1);
         if (rep >= 10 && ms < best) best = ms;
