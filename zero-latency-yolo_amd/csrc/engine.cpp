@@ -54,7 +54,9 @@ enum OpKind { OP_PREPROCESS = 0, OP_CONV = 1, OP_SPPF = 2, OP_HEAD = 4, OP_NMS =
 struct Op {
     int kind = 0;
     std::string name;
-    // conv
+    int lane = 0;                      // 0 = main stream; 1, 2 = Detect-branch streams that run beside the neck
+    int level = 0;                     // OP_HEAD: the Detect level the tail op stands for
+    // conv (OP_SPPF: `in` = the hidden-width slice of the block's concat buffer that the pools read)
     View in{-1, 0, 0}, out{-1, 0, 0}, res{-1, 0, 0};
     View in2{-1, 0, 0};                // 1x1 convs: second (full-size) source of a fused Upsample+Concat input; `in` is then half-size
     int ks = 1, stride = 1, act = 0, out_f32 = 0;
@@ -63,29 +65,67 @@ struct Op {
     std::vector<std::string> taps;     // conv names whose outputs this op produces (for zly_debug_tap)
     std::vector<int> tap_co;           // channel offset of each tap inside `out`
     std::vector<int> tap_c;
-    // sppf / upsample / head
-    int c = 0;                         // sppf: hidden width; upsample: channels
-    int level = 0, stride_px = 0, anchor_off = 0;
-    int lane = 0;                      // 0 = main stream; 1, 2 = Detect-branch streams that run beside the neck
-    // fused bottleneck pair (kernels_pair.hip): pair = 1 on a bottleneck's first 3x3 conv (it then carries what the
-    // kernel needs of the second one), 2 on the second (a no-op when the pair kernel ran); 0 otherwise
-    int pair = 0, pair_c = 0, pair_res = 0;
-    View pair_out{-1, 0, 0};
-    size_t pair_wA = 0, pair_bA = 0, pair_wB = 0, pair_bB = 0;
-    // fused C2f block (kernels_pair.hip: c2f_kernel): c2f_mode != 0 on the op that launches it (cv1, or the second bottleneck's first
-    // conv for the back half of a two-bottleneck C2f); the ops it covers carry the leader's name and launch nothing when it is active
-    int c2f_mode = 0, c2f_c = 0, c2f_res = 0, c2f_cat = -1, c2f_in_co = 0, c2f_out_co = 0, c2f_nk1 = 0, c2f_nk2 = 0, c2f_cout2 = 0;
-    View c2f_x{-1, 0, 0}, c2f_x2{-1, 0, 0}, c2f_out{-1, 0, 0}, c2f_mid{-1, 0, 0};
-    size_t c2f_w1 = 0, c2f_b1 = 0, c2f_wA = 0, c2f_bA = 0, c2f_wB = 0, c2f_bB = 0, c2f_w2 = 0, c2f_b2 = 0;
-    std::string c2f_leader_name;       // covered ops (and the leader itself)
-    int c2f_leader = -1;               // index of the leader op (resolved after the ops are ordered)
-    int c2f_vis = 0;                   // this op's output with the fused kernel: 0 = in HBM, 1 = only with ZLY_FLAG_DUMP_LOGITS, 2 = stays in LDS
-    HeadArgs head{};                   // OP_HEAD: fused Detect tail
-    int head_box[3] = {-1, -1, -1}, head_cls[3] = {-1, -1, -1};     // OP_HEAD: buffers the tail reads per level (launch-group bookkeeping)
+    size_t wsk_w = 0;                  // the 80 -> 80 class-branch convs: weights once more, tiled with cin_store = 80 for conv3x3_wsk_kernel (K packed across taps); 0 = none
+    int pair = -1;                     // index of the PairGroup this conv is a member of (its first or second conv), -1 = none
+    int c2f = -1;                      // index of the C2fGroup that covers this conv, -1 = none
     double flops = 0, bytes = 0;
     double wbytes = 0;                 // weight + bias bytes of this op (part of `bytes`)
     double cin_frac = 1.0;             // real / stored input channels (the 3-of-8 channel image, the 80-of-96 channel class branch)
-    size_t wsk_w = 0;                  // the 80 -> 80 class-branch convs: weights once more, tiled with cin_store = 80 for conv3x3_wsk_kernel (K packed across taps); 0 = none
+};
+
+// fused bottleneck pair (kernels_pair.hip): a bottleneck's two 3x3 convs as one launch at the first one; the second is a no-op when the pair kernel ran
+struct PairGroup {
+    int first = -1, second = -1;       // member ops
+    int c = 0, res = 0;                // width; 1 = shortcut
+    View out{-1, 0, 0};                // the second conv's output
+    size_t wA = 0, bA = 0, wB = 0, bB = 0;     // the pair kernel's operands (for c = 16 its own weight tiling: one tap per 16x16x16 MFMA k-step)
+};
+
+// fused C2f block (kernels_pair.hip: c2f_kernel) around one bottleneck: launched at `leader` (cv1, or the second bottleneck's first conv for the back
+// half of a two-bottleneck C2f); the other members launch nothing when it is active
+struct C2fGroup {
+    struct Member { int op, vis; };    // vis: the op's output with the fused kernel: 0 = in HBM, 1 = only with ZLY_FLAG_DUMP_LOGITS, 2 = stays in LDS
+    int leader = -1;
+    std::vector<Member> members;       // the leader included
+    int mode = 0, c = 0, res = 0, cat = -1;    // mode bit 0 = cv1 in front, bit 1 = cv2 behind; width; shortcut; the block's concat buffer
+    int pair = -1;                     // the PairGroup of the bottleneck it wraps (its weights and channel offsets inside cat)
+    View x{-1, 0, 0}, x2{-1, 0, 0}, out{-1, 0, 0};
+    View mid{-1, 0, 0};                // c = 64: the 64-channel kernel can dump the bottleneck's intermediate map (debug taps)
+    size_t w1 = 0, b1 = 0, w2 = 0, b2 = 0;
+    int nk1 = 0, nk2 = 0, cout2 = 0;
+    int vis_of(int op) const { for (const Member& m : members) if (m.op == op) return m.vis; return 0; }
+};
+
+// fused Detect tail (kernels_head.hip): the final 1x1 convs + DFL + sigmoid + decode of all three levels.  One record per engine; the three
+// tail ops (one per level) only say which level a launch stands for.
+struct DetectTail {
+    HeadArgs args{};                   // the launch template: the weight / activation pointers are set once the blob and the buffers are on the device
+    int op[3] = {-1, -1, -1};          // the tail op of each level
+    int box[3] = {-1, -1, -1}, cls[3] = {-1, -1, -1}, logits[3] = {-1, -1, -1};     // buffers the tail reads / (ZLY_FLAG_DUMP_LOGITS) writes per level
+    size_t wb[3] = {}, bb[3] = {}, wc[3] = {}, bc[3] = {};                          // final 1x1 weights / biases in the weight blob
+};
+
+// The model plan: everything build_plan derives from the model file, the config and the switches, with no device call.  Weights are offsets into
+// `blob` and tensors are indices into `bufs`; upload_plan allocates, uploads and turns them into pointers.
+struct Plan {
+    int nc = 0, N = 0;                 // classes, anchors of all levels
+    std::vector<Buffer> bufs;
+    std::vector<Op> ops;               // in launch order
+    std::vector<PairGroup> pairs;
+    std::vector<C2fGroup> c2fs;
+    DetectTail tail;
+    int in_buf = -1;
+    std::map<std::string, std::pair<int, int>> tap_index;   // conv name -> (op index, tap slot)
+    std::map<std::string, std::pair<int, int>> tap_final;   // final Detect convs -> (logits buffer, channel offset)
+    bool stem_fused = false;          // bf16 + 16-channel stem: preprocess and model.0 are one kernel on the detect paths
+    bool stem1 = false;               // ... and model.1 (32 channels) as well: the stem map stays in LDS (kernels_stem.hip: stem_model1_kernel)
+    size_t stem_w = 0, stem_b = 0, m1_w = 0, m1_b = 0, stem_w0p = 0;     // the front kernels' weight tilings in the blob
+    int stem_out = -1, m1_out = -1;   // the buffers of model.0 / model.1
+    int sppf_cv1 = -1, sppf_pool = -1, sppf_cv2 = -1;     // op indices of the SPPF block (model.9): one launch where kernels_sppf.hip covers the shape
+    int det_stem[3] = {-1, -1, -1}, det_a[3] = {-1, -1, -1}, det_b[3] = {-1, -1, -1};   // op indices of the Detect convs (stem, box .1, class .1) per level
+    bool det_merge_ok = false;        // all three levels suit the shared kernel shape of the merged Detect launches (latency path)
+    int join_at = -1;                 // the op in front of which the side streams are joined (the P5 Detect stem)
+    std::vector<uint8_t> blob;        // host image of the device weight blob: built outside the exclusive gate, released after upload
 };
 
 // What one op launches at one batch size: a record of the launch table (resolve_launches)
@@ -110,20 +150,13 @@ struct Ingest;        // pipelined host-to-host path (zly_submit / zly_wait), be
 
 using namespace zly;
 
-struct zly_engine {
+struct zly_engine : Plan {
     zly_config cfg;
     std::string weights_path;
     int dev = 0;
     int dtype = ZLY_DTYPE_BF16;
     size_t esz = 2;
     ModelFile model;
-    int nc = 0, N = 0;
-    int lvl_h[3], lvl_w[3];
-    std::vector<Buffer> bufs;
-    std::vector<Op> ops;
-    int in_buf = -1;
-    std::map<std::string, std::pair<int, int>> tap_index;   // conv name -> (op index, tap slot)
-    std::map<std::string, std::pair<int, int>> tap_final;   // final Detect convs -> (logits buffer, channel offset)
 
     void* d_weights = nullptr;
     float* d_head = nullptr;          // [max_batch][4+nc][N]
@@ -159,9 +192,7 @@ struct zly_engine {
     float* d_scratch_f32 = nullptr;   // stage-level entry points
     size_t scratch_f32_elems = 0;
 
-    bool stem_fused = false;          // bf16 + 16-channel stem: preprocess and model.0 are one kernel on the detect paths
-    StemArgs stem{};
-    bool stem1 = false;               // ... and model.1 (32 channels) as well: the stem map stays in LDS (kernels_stem.hip: stem_model1_kernel)
+    StemArgs stem{};                  // stem_fused / stem1 (Plan): the front kernels' launch templates
     Stem1Args stem1a{};
     bool ingest_active = false;       // set while the pipelined host path (zly_submit) enqueues: see run_path
     bool last_front = false;          // the most recent call launched the front kernel (zly_forward does not: model.0 is then in HBM)
@@ -186,8 +217,6 @@ struct zly_engine {
     // per GPU) or with deferred NMS
     hipEvent_t ev_call[2] = {nullptr, nullptr};
     uint64_t call_seq = 0;
-    int det_stem[3] = {-1, -1, -1}, det_a[3] = {-1, -1, -1}, det_b[3] = {-1, -1, -1};   // op indices of the Detect convs (stem, box .1, class .1) per level
-    int sppf_cv1 = -1, sppf_pool = -1, sppf_cv2 = -1;     // op indices of the SPPF block (model.9): one launch where kernels_sppf.hip covers the shape
     int cu_part_n = 1;                // ZLY_CU_PART: number of CU partitions (1 = whole chip)
     uint32_t cu_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::atomic<Ingest*> ingest{nullptr};   // created by the first zly_submit (under mu), read lock-free afterwards
@@ -279,45 +308,70 @@ static void read_switches(Switches* sw)
 // plan
 // ------------------------------------------------------------------------------------------------
 struct PlanBuilder {
-    zly_engine* e;
-    std::vector<uint8_t> blob;         // host image of the device weight blob
+    Plan* p;
+    const ModelFile& model;
+    const zly_config& cfg;
+    const int dtype;
+    const Switches& sw;
+    const size_t esz;
+    const int kstep;
     std::string err;
-    int kstep;
 
+    bool bf16() const { return dtype == ZLY_DTYPE_BF16; }
+    bool fail(const std::string& msg) { err = msg; return false; }
     int add_buffer(const std::string& name, int H, int W, int C, bool f32 = false) {
         Buffer b;
         b.name = name; b.H = H; b.W = W; b.C = C; b.f32 = f32;
-        e->bufs.push_back(b);
-        return (int)e->bufs.size() - 1;
+        p->bufs.push_back(b);
+        return (int)p->bufs.size() - 1;
     }
-    size_t append(const void* p, size_t bytes) {
+    int add_op(const Op& op) { p->ops.push_back(op); return (int)p->ops.size() - 1; }
+    size_t append(const void* d, size_t bytes) {
+        std::vector<uint8_t>& blob = p->blob;
         size_t off = (blob.size() + 255) / 256 * 256;
         blob.resize(off + bytes);
-        memcpy(blob.data() + off, p, bytes);
+        memcpy(blob.data() + off, d, bytes);
         return off;
     }
-    bool conv(const std::vector<std::string>& names, View in, View out, View res = View{-1, 0, 0}, bool out_f32 = false, View in2 = View{-1, 0, 0}) {
+    const ConvRec* find(const std::string& name) {
+        const ConvRec* r = model.find(name);
+        if (!r) err = "conv missing from model file: " + name;
+        return r;
+    }
+    // one conv's weights in a tiling of their own (the tilings of the fused kernels), appended to the blob
+    void pack(const ConvRec* r, int cin_store, int ks, bool pair_rows, int epl, const int* tap_slot, size_t* w_off, size_t* b_off, int* nk, int* cout_pad) {
+        std::vector<uint8_t> w;
+        std::vector<float> b;
+        int cout = 0;
+        repack_conv({r}, cin_store, ks, bf16(), &w, &b, &cout, cout_pad, nk, pair_rows, epl, tap_slot);
+        *w_off = append(w.data(), w.size());
+        if (b_off) *b_off = append(b.data(), b.size() * sizeof(float));
+    }
+    // the conv op of `names` (several convs of one input = one launch); returns its op index, -1 on error
+    int conv(const std::vector<std::string>& names, View in, View out, View res = View{-1, 0, 0}, bool out_f32 = false, View in2 = View{-1, 0, 0}, int lane = 0) {
         std::vector<const ConvRec*> srcs;
         for (const std::string& n : names) {
-            const ConvRec* r = e->model.find(n);
-            if (!r) { err = "conv missing from model file: " + n; return false; }
+            const ConvRec* r = find(n);
+            if (!r) return -1;
             srcs.push_back(r);
         }
+        auto bad = [&](const char* what) { err = what + names[0]; return -1; };
         const ConvRec* r0 = srcs[0];
         for (const ConvRec* r : srcs)
-            if (r->cin != r0->cin || r->k != r0->k || r->stride != r0->stride || r->act != r0->act) { err = "cannot fuse " + names[0]; return false; }
-        const Buffer& ib = e->bufs[(size_t)in.buf];
-        const Buffer& ob = e->bufs[(size_t)out.buf];
-        const int epl = e->dtype == ZLY_DTYPE_BF16 ? 8 : 4;
+            if (r->cin != r0->cin || r->k != r0->k || r->stride != r0->stride || r->act != r0->act) return bad("cannot fuse ");
+        const Buffer& ib = p->bufs[(size_t)in.buf];
+        const Buffer& ob = p->bufs[(size_t)out.buf];
+        const int epl = bf16() ? 8 : 4;
         const int cin_total = in.C + (in2.buf >= 0 ? in2.C : 0);
-        if (cin_total < r0->cin || in.C % epl != 0 || in.co % epl != 0 || ib.C % epl != 0 || in.co + in.C > ib.C) { err = "bad input view for " + names[0]; return false; }
+        if (cin_total < r0->cin || in.C % epl != 0 || in.co % epl != 0 || ib.C % epl != 0 || in.co + in.C > ib.C) return bad("bad input view for ");
         if (in2.buf >= 0) {
-            const Buffer& i2 = e->bufs[(size_t)in2.buf];
+            const Buffer& i2 = p->bufs[(size_t)in2.buf];
             if (r0->k != 1 || in.C % kstep != 0 || in2.C % epl != 0 || in2.co % epl != 0 || i2.C % epl != 0 || in2.co + in2.C > i2.C ||
-                i2.H != ob.H || i2.W != ob.W || ib.H * 2 != ob.H || ib.W * 2 != ob.W) { err = "bad upsample+concat input for " + names[0]; return false; }
+                i2.H != ob.H || i2.W != ob.W || ib.H * 2 != ob.H || ib.W * 2 != ob.W) return bad("bad upsample+concat input for ");
         }
         Op op;
         op.kind = OP_CONV;
+        op.lane = lane;
         op.name = names[0];
         for (size_t i = 1; i < names.size(); ++i) op.name += "+" + names[i];
         if (op.name.size() > 47) op.name.resize(47);
@@ -325,20 +379,20 @@ struct PlanBuilder {
         op.ks = r0->k; op.stride = r0->stride; op.act = r0->act; op.out_f32 = out_f32 ? 1 : 0;
         std::vector<uint8_t> w;
         std::vector<float> b;
-        repack_conv(srcs, cin_total, kstep, e->dtype == ZLY_DTYPE_BF16, &w, &b, &op.cout, &op.cout_pad, &op.nk, true);
+        repack_conv(srcs, cin_total, kstep, bf16(), &w, &b, &op.cout, &op.cout_pad, &op.nk, true);
         // 5 channel tiles (the 80-channel Detect class branch) suit no kernel's channel blocking: CT = 5 needs more registers than
         // two waves per SIMD leave.  One whole zero tile is appended instead (6 tiles = 2 blocks of CT = 3); its outputs are never
         // stored (channel >= Cout) -- 20 % more MFMAs on these layers, but the LDS-tiled kernel instead of the direct one.
-        if (e->dtype == ZLY_DTYPE_BF16 && op.ks == 3 && op.cout_pad == 80 && cin_total % 32 == 0 && !e->sw.no_cout_pad) {
+        if (bf16() && op.ks == 3 && op.cout_pad == 80 && cin_total % 32 == 0 && !sw.no_cout_pad) {
             w.resize(w.size() + (size_t)op.nk * 1024, 0);
             b.resize(b.size() + 16, 0.0f);
             op.cout_pad = 96;
         }
-        if (out.C != op.cout || out.co % 4 != 0 || ob.C % 4 != 0 || out.co + out.C > ob.C) { err = "bad output view for " + names[0]; return false; }
-        if (out_f32 != ob.f32) { err = "output dtype mismatch for " + names[0]; return false; }
+        if (out.C != op.cout || out.co % 4 != 0 || ob.C % 4 != 0 || out.co + out.C > ob.C) return bad("bad output view for ");
+        if (out_f32 != ob.f32) return bad("output dtype mismatch for ");
         const int Ho = ob.H, Wo = ob.W;
         const int Hin = in2.buf >= 0 ? ib.H * 2 : ib.H, Win = in2.buf >= 0 ? ib.W * 2 : ib.W;
-        if (Ho != (Hin + 2 * (op.ks / 2) - op.ks) / op.stride + 1 || Wo != (Win + 2 * (op.ks / 2) - op.ks) / op.stride + 1) { err = "spatial mismatch for " + names[0]; return false; }
+        if (Ho != (Hin + 2 * (op.ks / 2) - op.ks) / op.stride + 1 || Wo != (Win + 2 * (op.ks / 2) - op.ks) / op.stride + 1) return bad("spatial mismatch for ");
         op.K = op.ks * op.ks * cin_total;
         op.w_off = append(w.data(), w.size());
         op.b_off = append(b.data(), b.size() * sizeof(float));
@@ -350,156 +404,186 @@ struct PlanBuilder {
             macs += (double)Ho * Wo * srcs[i]->cout * srcs[i]->cin * op.ks * op.ks;
         }
         op.flops = 2.0 * macs;
-        const double osz = out_f32 ? 4.0 : (double)e->esz;
+        const double osz = out_f32 ? 4.0 : (double)esz;
         op.cin_frac = (double)r0->cin / cin_total;
-        op.wbytes = (double)op.cout * r0->cin * op.ks * op.ks * e->esz + (double)op.cout * 4.0;
-        op.bytes = ((double)ib.H * ib.W * in.C + (in2.buf >= 0 ? (double)Ho * Wo * in2.C : 0.0)) * e->esz * op.cin_frac + (double)Ho * Wo * op.cout * osz +
-                   op.wbytes + (res.buf >= 0 ? (double)Ho * Wo * op.cout * e->esz : 0.0);
-        e->ops.push_back(op);
-        for (size_t i = 0; i < names.size(); ++i) e->tap_index[names[i]] = std::make_pair((int)e->ops.size() - 1, (int)i);
-        return true;
+        op.wbytes = (double)op.cout * r0->cin * op.ks * op.ks * esz + (double)op.cout * 4.0;
+        op.bytes = ((double)ib.H * ib.W * in.C + (in2.buf >= 0 ? (double)Ho * Wo * in2.C : 0.0)) * esz * op.cin_frac + (double)Ho * Wo * op.cout * osz +
+                   op.wbytes + (res.buf >= 0 ? (double)Ho * Wo * op.cout * esz : 0.0);
+        const int idx = add_op(op);
+        for (size_t i = 0; i < names.size(); ++i) p->tap_index[names[i]] = std::make_pair(idx, (int)i);
+        return idx;
     }
-    // repack + upload the weights of a conv that is executed inside another kernel (fused Detect tail)
-    bool pack_only(const std::string& name, int cin_store, size_t* w_off, size_t* b_off, int* nk, bool pair_rows = false) {
-        const ConvRec* r = e->model.find(name);
-        if (!r) { err = "conv missing from model file: " + name; return false; }
-        std::vector<uint8_t> w;
-        std::vector<float> b;
-        int cout = 0, cout_pad = 0;
-        repack_conv({r}, cin_store, kstep, e->dtype == ZLY_DTYPE_BF16, &w, &b, &cout, &cout_pad, nk, pair_rows);
-        *w_off = append(w.data(), w.size());
-        *b_off = append(b.data(), b.size() * sizeof(float));
-        return true;
-    }
-    // The two convs just added are a bottleneck's 3x3 pair: when the fused kernel covers this width, the first op
-    // also carries the pair kernel's operands (for c = 16 its own weight tiling: one tap per 16x16x16 MFMA k-step).
-    bool mark_pair(const std::string& m, int c, bool shortcut) {
-        if (e->dtype != ZLY_DTYPE_BF16 || (c != 16 && c != 32 && c != 64) || e->ops.size() < 2) return true;
-        Op& B = e->ops[e->ops.size() - 1];
-        Op& A = e->ops[e->ops.size() - 2];
+    // Ops a and b are a bottleneck's 3x3 pair: when the fused kernel covers this width, a PairGroup holds the pair kernel's operands
+    // (for c = 16 its own weight tiling: one tap per 16x16x16 MFMA k-step).
+    bool mark_pair(const std::string& m, int a, int b, int c, bool shortcut) {
+        if (!bf16() || (c != 16 && c != 32 && c != 64)) return true;
+        Op& A = p->ops[(size_t)a];
+        Op& B = p->ops[(size_t)b];
         if (A.ks != 3 || B.ks != 3 || A.stride != 1 || B.stride != 1 || !A.act || !B.act || A.cout != c || B.cout != c) return true;
-        if (A.in.co % 8 || B.out.co % 8 || e->bufs[(size_t)A.in.buf].C % 8 || e->bufs[(size_t)B.out.buf].C % 8) return true;
-        A.pair = 1; B.pair = 2; A.pair_c = B.pair_c = c; A.pair_res = shortcut ? 1 : 0;
-        A.pair_out = B.out;
-        if (c >= 32) { A.pair_wA = A.w_off; A.pair_bA = A.b_off; A.pair_wB = B.w_off; A.pair_bB = B.b_off; return true; }
-        const char* names[2] = {".cv1", ".cv2"};
-        size_t* wo[2] = {&A.pair_wA, &A.pair_wB};
-        size_t* bo[2] = {&A.pair_bA, &A.pair_bB};
-        for (int k = 0; k < 2; ++k) {
-            const ConvRec* r = e->model.find(m + names[k]);
-            if (!r) { err = "conv missing from model file: " + m + names[k]; return false; }
-            std::vector<uint8_t> w;
-            std::vector<float> b;
-            int cout = 0, cout_pad = 0, nk = 0;
-            repack_conv({r}, c, 16, true, &w, &b, &cout, &cout_pad, &nk, false, 4);
-            if (nk != 9 || cout_pad != 16) { err = "internal: pair weight tiling for " + m; return false; }
-            *wo[k] = append(w.data(), w.size());
-            *bo[k] = append(b.data(), b.size() * sizeof(float));
+        if (A.in.co % 8 || B.out.co % 8 || p->bufs[(size_t)A.in.buf].C % 8 || p->bufs[(size_t)B.out.buf].C % 8) return true;
+        PairGroup g;
+        g.first = a; g.second = b; g.c = c; g.res = shortcut ? 1 : 0;
+        g.out = B.out;
+        g.wA = A.w_off; g.bA = A.b_off; g.wB = B.w_off; g.bB = B.b_off;
+        if (c == 16) {
+            const char* names[2] = {".cv1", ".cv2"};
+            size_t* wo[2] = {&g.wA, &g.wB};
+            size_t* bo[2] = {&g.bA, &g.bB};
+            for (int k = 0; k < 2; ++k) {
+                const ConvRec* r = find(m + names[k]);
+                if (!r) return false;
+                int cout_pad = 0, nk = 0;
+                pack(r, c, 16, false, 4, nullptr, wo[k], bo[k], &nk, &cout_pad);
+                if (nk != 9 || cout_pad != 16) return fail("internal: pair weight tiling for " + m);
+            }
         }
+        A.pair = B.pair = (int)p->pairs.size();
+        p->pairs.push_back(g);
         return true;
     }
     // C2f(c1 -> c2, n bottlenecks): cv1 writes [0,2c) of the concat buffer, bottleneck i reads
     // [(1+i)c,(2+i)c) and writes [(2+i)c,(3+i)c), cv2 reads all (2+n)c channels.
-    bool c2f(const std::string& p, View in, View out, int n, bool shortcut, int H, int W, View in2 = View{-1, 0, 0}) {
+    bool c2f(const std::string& pfx, View in, View out, int n, bool shortcut, int H, int W, View in2 = View{-1, 0, 0}) {
         const int c = out.C / 2;
-        const int cat = add_buffer(p + ".cat", H, W, (2 + n) * c);
-        if (!conv({p + ".cv1"}, in, View{cat, 0, 2 * c}, View{-1, 0, 0}, false, in2)) return false;
+        const int cat = add_buffer(pfx + ".cat", H, W, (2 + n) * c);
+        const int cv1 = conv({pfx + ".cv1"}, in, View{cat, 0, 2 * c}, View{-1, 0, 0}, false, in2);
+        if (cv1 < 0) return false;
         for (int i = 0; i < n; ++i) {
             const View src{cat, (1 + i) * c, c};
-            const std::string m = p + ".m." + std::to_string(i);
+            const std::string m = pfx + ".m." + std::to_string(i);
             const int tmp = add_buffer(m + ".tmp", H, W, c);
-            if (!conv({m + ".cv1"}, src, View{tmp, 0, c})) return false;
-            if (!conv({m + ".cv2"}, View{tmp, 0, c}, View{cat, (2 + i) * c, c}, shortcut ? src : View{-1, 0, 0})) return false;
-            if (!mark_pair(m, c, shortcut)) return false;
+            const int a = conv({m + ".cv1"}, src, View{tmp, 0, c});
+            const int b = a < 0 ? -1 : conv({m + ".cv2"}, View{tmp, 0, c}, View{cat, (2 + i) * c, c}, shortcut ? src : View{-1, 0, 0});
+            if (b < 0 || !mark_pair(m, a, b, c, shortcut)) return false;
         }
-        if (!conv({p + ".cv2"}, View{cat, 0, (2 + n) * c}, out)) return false;
-        return mark_c2f(p, cat, c, n, shortcut, in, in2, out);
+        const int cv2 = conv({pfx + ".cv2"}, View{cat, 0, (2 + n) * c}, out);
+        return cv2 >= 0 && mark_c2f(pfx, cv1, cv2, cat, c, n, shortcut, in, in2, out);
     }
-    // The 2 + 2n ops just added are a C2f block: annotate the fused kernel's launch groups (n = 1: the whole block; n = 2: front half
-    // = cv1 + first bottleneck, back half = second bottleneck + cv2).  Weight tilings are shared with the per-conv kernels where the
-    // layout is the same (C = 32); the 16-channel block gets its own cv1 (rows in channel order) and cv2 (k-steps of 16) tilings.
-    bool mark_c2f(const std::string& p, int cat, int c, int n, bool shortcut, View in, View in2, View out) {
-        if (e->dtype != ZLY_DTYPE_BF16 || (c != 16 && c != 32 && c != 64) || (n != 1 && n != 2) || (e->cfg.flags & ZLY_FLAG_NO_FUSION)) return true;
-        const size_t base = e->ops.size() - (size_t)(2 + 2 * n);
-        Op& cv1 = e->ops[base];
-        Op& cv2 = e->ops[e->ops.size() - 1];
+    // Ops [cv1, cv2] are a C2f block: its fused kernel's launch groups (n = 1: the whole block; n = 2: front half = cv1 + first bottleneck,
+    // back half = second bottleneck + cv2).  Weight tilings are shared with the per-conv kernels where the layout is the same (C = 32); the
+    // 16-channel block gets its own cv1 (rows in channel order) and cv2 (k-steps of 16) tilings.
+    bool mark_c2f(const std::string& pfx, int cv1, int cv2, int cat, int c, int n, bool shortcut, View in, View in2, View out) {
+        if (!bf16() || (c != 16 && c != 32 && c != 64) || (n != 1 && n != 2) || (cfg.flags & ZLY_FLAG_NO_FUSION)) return true;
+        const Op& o1 = p->ops[(size_t)cv1];
+        const Op& o2 = p->ops[(size_t)cv2];
         const int cin = in.C + (in2.buf >= 0 ? in2.C : 0);
-        if (cin % 32 != 0 || cv2.cout != 2 * c || cv1.cout != 2 * c || !cv1.act || !cv2.act) return true;
-        for (int i = 0; i < n; ++i) if (e->ops[base + 1 + 2 * (size_t)i].pair != 1) return true;       // mark_pair declined
-        size_t w1 = cv1.w_off, b1 = cv1.b_off, w2 = cv2.w_off, b2 = cv2.b_off;
-        int nk1 = cv1.nk, nk2 = cv2.nk;
+        if (cin % 32 != 0 || o2.cout != 2 * c || o1.cout != 2 * c || !o1.act || !o2.act) return true;
+        for (int i = 0; i < n; ++i) if (p->ops[(size_t)cv1 + 1 + 2 * (size_t)i].pair < 0) return true;       // mark_pair declined
+        C2fGroup g;
+        g.c = c; g.res = shortcut ? 1 : 0; g.cat = cat;
+        g.x = in; g.x2 = in2; g.out = out;
+        g.w1 = o1.w_off; g.b1 = o1.b_off; g.nk1 = o1.nk; g.w2 = o2.w_off; g.b2 = o2.b_off; g.nk2 = o2.nk; g.cout2 = o2.cout;
         if (c == 16) {
-            const ConvRec* r1 = e->model.find(p + ".cv1");
-            const ConvRec* r2 = e->model.find(p + ".cv2");
-            std::vector<uint8_t> w;
-            std::vector<float> b;
-            int cout = 0, cout_pad = 0;
-            repack_conv({r1}, cin, 32, true, &w, &b, &cout, &cout_pad, &nk1, false);
-            w1 = append(w.data(), w.size()); b1 = append(b.data(), b.size() * sizeof(float));
-            repack_conv({r2}, (2 + n) * c, 16, true, &w, &b, &cout, &cout_pad, &nk2, true, 4);
-            w2 = append(w.data(), w.size()); b2 = append(b.data(), b.size() * sizeof(float));
+            int cout_pad = 0;
+            pack(model.find(pfx + ".cv1"), cin, 32, false, 0, nullptr, &g.w1, &g.b1, &g.nk1, &cout_pad);
+            pack(model.find(pfx + ".cv2"), (2 + n) * c, 16, true, 4, nullptr, &g.w2, &g.b2, &g.nk2, &cout_pad);
         }
-        if (nk2 != (c == 64 ? 2 : 1) * (2 + n)) return true;            // cv2's k-steps: one per source map (c = 16 / 32), two per map of 64 channels
-        auto fill = [&](Op& L, int mode, const Op& A) {
-            L.c2f_mode = mode; L.c2f_c = c; L.c2f_res = shortcut ? 1 : 0; L.c2f_cat = cat;
-            L.c2f_in_co = A.in.co; L.c2f_out_co = A.pair_out.co;
-            L.c2f_x = in; L.c2f_x2 = in2; L.c2f_out = out;
-            L.c2f_w1 = w1; L.c2f_b1 = b1; L.c2f_nk1 = nk1; L.c2f_w2 = w2; L.c2f_b2 = b2; L.c2f_nk2 = nk2; L.c2f_cout2 = cv2.cout;
-            L.c2f_wA = A.pair_wA; L.c2f_bA = A.pair_bA; L.c2f_wB = A.pair_wB; L.c2f_bB = A.pair_bB;
-            L.c2f_leader_name = L.name;
-            if (c == 64) L.c2f_mid = A.out;                      // the 64-channel kernel can dump the bottleneck's intermediate map (debug taps)
+        if (g.nk2 != (c == 64 ? 2 : 1) * (2 + n)) return true;            // cv2's k-steps: one per source map (c = 16 / 32), two per map of 64 channels
+        // one group, led by its first member, around the bottleneck whose first conv is op a
+        auto group = [&](int mode, int a, std::initializer_list<C2fGroup::Member> members) {
+            g.mode = mode; g.pair = p->ops[(size_t)a].pair; g.leader = members.begin()->op; g.members = members;
+            if (c == 64) g.mid = p->ops[(size_t)a].out;
+            for (const C2fGroup::Member& m : members) p->ops[(size_t)m.op].c2f = (int)p->c2fs.size();
+            p->c2fs.push_back(g);
         };
-        if (n == 1) {
-            Op& A = e->ops[base + 1];
-            fill(cv1, 3, A);
-            cv1.c2f_vis = 1;
-            A.c2f_leader_name = cv1.name; A.c2f_vis = c == 64 ? 1 : 2;
-            e->ops[base + 2].c2f_leader_name = cv1.name; e->ops[base + 2].c2f_vis = 1;
-            cv2.c2f_leader_name = cv1.name; cv2.c2f_vis = 0;
-        } else {
-            Op& A0 = e->ops[base + 1];
-            Op& A1 = e->ops[base + 3];
-            fill(cv1, 1, A0);
-            cv1.c2f_vis = 0;
-            A0.c2f_leader_name = cv1.name; A0.c2f_vis = c == 64 ? 1 : 2;
-            e->ops[base + 2].c2f_leader_name = cv1.name; e->ops[base + 2].c2f_vis = 0;
-            fill(A1, 2, A1);
-            A1.c2f_vis = c == 64 ? 1 : 2;
-            e->ops[base + 4].c2f_leader_name = A1.name; e->ops[base + 4].c2f_vis = 1;
-            cv2.c2f_leader_name = A1.name; cv2.c2f_vis = 0;
+        const int mid_vis = c == 64 ? 1 : 2;
+        if (n == 1) group(3, cv1 + 1, {{cv1, 1}, {cv1 + 1, mid_vis}, {cv1 + 2, 1}, {cv2, 0}});
+        else {
+            group(1, cv1 + 1, {{cv1, 0}, {cv1 + 1, mid_vis}, {cv1 + 2, 0}});
+            group(2, cv1 + 3, {{cv1 + 3, mid_vis}, {cv1 + 4, 1}, {cv2, 0}});
         }
+        return true;
+    }
+    // One Detect level right behind the C2f that feeds it: the two branches' first 3x3 convs read the same tensor and are one launch, then each
+    // branch's second conv, then the level's tail op.  P3 and P4 only depend on model.15 / model.18: on side streams (lanes 1, 2) they run, inside
+    // the captured graph, BESIDE the rest of the neck (model.16-21) instead of after it.  These launches are latency/issue-bound and leave most
+    // of the chip idle, so the overlap is nearly free.
+    bool detect_level(int l, View feat, int c2, int c3, const Op& tail_total) {
+        const std::string L = std::to_string(l);
+        const int lane = l == 0 ? 1 : (l == 1 ? 2 : 0);
+        DetectTail& t = p->tail;
+        HeadLevel& hl = t.args.lv[l];
+        // the class branch's 80 channels are stored as 96 (16 zero channels, never written) so that its second 3x3 conv has
+        // Cin % 32 == 0 and takes the LDS-tiled kernel; the padded k-steps carry zero weights
+        const int c3s = (bf16() && c3 % 32 != 0 && c2 % 32 == 0 && !sw.no_cin_pad) ? (c3 + 31) / 32 * 32 : c3;
+        const int hd1 = add_buffer("detect." + L + ".stem", hl.H, hl.W, c2 + c3s);
+        t.box[l] = add_buffer("detect." + L + ".box2", hl.H, hl.W, c2);
+        t.cls[l] = add_buffer("detect." + L + ".cls2", hl.H, hl.W, c3);
+        t.logits[l] = add_buffer("detect." + L + ".logits", hl.H, hl.W, hl.logits_cs, true);
+        const View none{-1, 0, 0};
+        const int s = p->det_stem[l] = conv({"model.22.cv2." + L + ".0", "model.22.cv3." + L + ".0"}, feat, View{hd1, 0, c2 + c3}, none, false, none, lane);
+        const int a = p->det_a[l] = s < 0 ? -1 : conv({"model.22.cv2." + L + ".1"}, View{hd1, 0, c2}, View{t.box[l], 0, c2}, none, false, none, lane);
+        const int b = p->det_b[l] = a < 0 ? -1 : conv({"model.22.cv3." + L + ".1"}, View{hd1, c2, c3s}, View{t.cls[l], 0, c3}, none, false, none, lane);
+        if (b < 0) return false;
+        if (l == 2) p->join_at = s;
+        if (bf16() && c3 == 80 && c3s >= 80) {
+            // the same conv for conv3x3_wsk_kernel: k = tap * 80 + c without channel padding (23 k-steps instead of 27), plain tile rows, no zero output tile
+            const ConvRec* r = model.find("model.22.cv3." + L + ".1");
+            size_t w_off = 0;
+            int cout_pad = 0, nk = 0;
+            pack(r, 80, kstep, false, 0, nullptr, &w_off, nullptr, &nk, &cout_pad);
+            if (nk == 23 && cout_pad == 80 && r->k == 3 && r->stride == 1) p->ops[(size_t)b].wsk_w = w_off;
+        }
+        // the final 1x1 convs run inside the fused tail: weights only
+        const ConvRec* rb = find("model.22.cv2." + L + ".2");
+        const ConvRec* rc = rb ? find("model.22.cv3." + L + ".2") : nullptr;
+        if (!rc) return false;
+        int cout_pad = 0;
+        pack(rb, c2, kstep, false, 0, nullptr, &t.wb[l], &t.bb[l], &hl.nkb, &cout_pad);
+        pack(rc, c3, kstep, false, 0, nullptr, &t.wc[l], &t.bc[l], &hl.nkc, &cout_pad);
+        // the fused tail holds a branch's fragments in HEAD_KMAX k-steps of registers (launch_head_fused refuses more): refuse the model here, at load
+        if (hl.nkb > HEAD_KMAX || hl.nkc > HEAD_KMAX)
+            return fail("Detect branch too wide for the fused tail: " + std::to_string(c2) + " / " + std::to_string(c3) + " channels = " + std::to_string(hl.nkb) + " / " +
+                        std::to_string(hl.nkc) + " k-steps, at most " + std::to_string(HEAD_KMAX) + (bf16() ? " in bf16" : " in fp32"));
+        p->tap_final["model.22.cv2." + L + ".2"] = std::make_pair(t.logits[l], 0);
+        p->tap_final["model.22.cv3." + L + ".2"] = std::make_pair(t.logits[l], 64);
+        // the merged launches of the latency path: all three levels must suit the shared kernel shape
+        const Op& S = p->ops[(size_t)s];
+        const Op& A = p->ops[(size_t)a];
+        const Op& Bc = p->ops[(size_t)b];
+        p->det_merge_ok = p->det_merge_ok && S.ks == 3 && A.ks == 3 && Bc.ks == 3 && S.stride == 1 && S.in.C % 32 == 0 && A.in.C % 32 == 0 && Bc.in.C % 32 == 0 &&
+                          S.cout_pad % 48 == 0 && A.cout_pad % 32 == 0 && Bc.cout_pad % 32 == 0 && S.in2.buf < 0 && S.res.buf < 0 && A.res.buf < 0 && Bc.res.buf < 0;
+        // Three tail ops, one per level.  From batch 16 up each is its own launch right behind its level's branch convs (P3 and
+        // P4 on the side streams, i.e. beside the neck) and only the small P5 launch is left at the end of the step; below
+        // that the first two are skipped and the last one covers all levels in a single launch (fewest launches).
+        Op op;
+        op.kind = OP_HEAD; op.lane = lane; op.level = l;
+        op.name = std::string("detect.tail.P") + std::to_string(3 + l) + (l == 2 ? " (all levels below batch 16)" : "");
+        const double share = (double)hl.hw / (double)p->N;
+        op.flops = tail_total.flops * share; op.bytes = tail_total.bytes * share; op.wbytes = tail_total.wbytes * share;
+        t.op[l] = add_op(op);
         return true;
     }
 };
 
-// build_plan runs in two halves: the HOST half -- the op list and every weight repack into a host image of the device blob -- needs no
-// device call and runs before zly_create takes the process-wide exclusive gate; the DEVICE half (hipMalloc / hipMemcpy, pointers into the blob) runs
+// The plan is made in two halves: build_plan -- the op list and every weight repack into a host image of the device blob -- needs no
+// device call and runs before zly_create takes the process-wide exclusive gate; upload_plan (hipMalloc / hipMemcpy, pointers into the blob) runs
 // under it.  A hot reload builds its new engines beside running ones: their enqueue sections now stall for the allocations only, not for the repack.
-struct PendingLevel { size_t wb, bb, wc, bc; int hb2, hc2, hout; };
-struct PlanState {
-    std::vector<uint8_t> blob;
-    size_t stem_w = 0, stem_b = 0, m1_w = 0, m1_b = 0, stem_w0p = 0;
-    int a0 = -1, a1 = -1;
-    PendingLevel pend[3] = {};
-};
-
-static int build_plan_host(zly_engine* e, PlanState* ps, std::string* err)
+// The ops are emitted in launch order: the main chain, each Detect level behind the C2f that feeds it, NMS last.
+static int build_plan(const ModelFile& m, const zly_config& cfg, int dtype, const Switches& sw, Plan* plan, std::string* err)
 {
-    PlanBuilder pb;
-    pb.e = e;
-    pb.kstep = conv_kstep(e->dtype);
-    const ModelFile& m = e->model;
-    const int W = e->cfg.model_w, H = e->cfg.model_h;
+    const size_t esz = dtype == ZLY_DTYPE_BF16 ? 2 : 4;
+    PlanBuilder pb{plan, m, cfg, dtype, sw, esz, conv_kstep(dtype), std::string()};
+    Plan* const p = plan;
+    const int W = cfg.model_w, H = cfg.model_h;
     const int* ch = m.ch;
     const int* nb = m.n_c2f;
-    if (m.reg_max != 16) { *err = "only reg_max = 16 is supported"; return ZLY_ERR_MODEL_LOAD; }
+    auto refuse = [&](const std::string& msg) { *err = msg; return (int)ZLY_ERR_MODEL_LOAD; };
+    if (m.reg_max != 16) return refuse("only reg_max = 16 is supported");
     for (int i = 0; i < 5; ++i)
-        if (ch[i] % 16 != 0) { *err = "channel widths must be multiples of 16"; return ZLY_ERR_MODEL_LOAD; }
+        if (ch[i] % 16 != 0) return refuse("channel widths must be multiples of 16");
+    const int c2 = std::max(16, std::max(ch[2] / 4, 4 * m.reg_max));
+    const int c3 = std::max(ch[2], std::min(m.nc, 100));
+    if (m.nc > 80) return refuse("nc > 80 is not supported by the fused Detect kernel");
+    // the class branch's stored width is c3 itself: for 65 <= nc <= 79 (YOLOv8n) its pixel rows would not be whole 16-channel
+    // tiles, and no conv epilogue nor the Detect tail's 16-byte fragment loads is written for that
+    if (c3 % 16 != 0) return refuse("Detect class-branch width max(ch[2], nc) = " + std::to_string(c3) + " is not a multiple of 16 (nc = " + std::to_string(m.nc) + ")");
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+    p->nc = m.nc;
 
-    e->in_buf = pb.add_buffer("images", H, W, 8);
-    const int a0 = pb.add_buffer("model.0", H2, W2, ch[0]);
-    const int a1 = pb.add_buffer("model.1", H4, W4, ch[1]);
+    p->in_buf = pb.add_buffer("images", H, W, 8);
+    const int a0 = p->stem_out = pb.add_buffer("model.0", H2, W2, ch[0]);
+    const int a1 = p->m1_out = pb.add_buffer("model.1", H4, W4, ch[1]);
     const int a2 = pb.add_buffer("model.2", H4, W4, ch[1]);
     const int a3 = pb.add_buffer("model.3", H8, W8, ch[2]);
     const int cat14 = pb.add_buffer("cat14[up(12),4]", H8, W8, ch[3] + ch[2]);
@@ -514,213 +598,91 @@ static int build_plan_host(zly_engine* e, PlanState* ps, std::string* err)
     const int a18 = pb.add_buffer("model.18", H16, W16, ch[3]);
     const int a21 = pb.add_buffer("model.21", H32, W32, ch[4]);
 
+    // The Detect tail's geometry and its three-level accounting, of which each tail op reports its level's share: they need only c2, c3, nc and the map sizes
+    const int fh[3] = {H8, H16, H32}, fw[3] = {W8, W16, W32};
+    HeadArgs& head = p->tail.args;
+    Op tail_total;
+    p->N = fh[0] * fw[0] + fh[1] * fw[1] + fh[2] * fw[2];
+    int anchor_off = 0, block0 = 0;
+    for (int l = 0; l < 3; ++l) {
+        HeadLevel& hl = head.lv[l];
+        hl.box_cs = c2; hl.cls_cs = c3; hl.box_cin = c2; hl.cls_cin = c3;
+        hl.H = fh[l]; hl.W = fw[l]; hl.hw = fh[l] * fw[l]; hl.stride_px = 8 << l; hl.anchor_off = anchor_off; hl.block0 = block0;
+        hl.logits_cs = 64 + (m.nc + 3) / 4 * 4;
+        block0 += (hl.hw + HEAD_GROUP - 1) / HEAD_GROUP;
+        anchor_off += hl.hw;
+        const double macs = (double)hl.hw * (c2 * 64.0 + (double)c3 * m.nc);
+        tail_total.flops += 2.0 * macs;
+        // algorithmic bytes: both branch activations in, the weights, and -- only when the engine materialises it -- the fp32 head tensor out
+        tail_total.bytes += (double)hl.hw * ((c2 + c3) * (double)esz + ((cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) ? 0.0 : (4 + m.nc) * 4.0)) + (c2 * 64.0 + (double)c3 * m.nc) * esz;
+        tail_total.wbytes += (c2 * 64.0 + (double)c3 * m.nc) * esz;
+    }
+    head.nc = m.nc; head.N_total = p->N; head.total_blocks = block0; head.only_level = -1;
+    p->det_merge_ok = pb.bf16();
+
     Op pre; pre.kind = OP_PREPROCESS; pre.name = "preprocess";
-    pre.bytes = (double)W * H * 3 + (double)W * H * 3 * e->esz;          // algorithmic: u8 frame in, the 3-channel tensor out (stored as 8 channels)
-    e->ops.push_back(pre);
+    pre.bytes = (double)W * H * 3 + (double)W * H * 3 * esz;          // algorithmic: u8 frame in, the 3-channel tensor out (stored as 8 channels)
+    pb.add_op(pre);
 
     bool ok = true;
-    ok = ok && pb.conv({"model.0"}, View{e->in_buf, 0, 8}, View{a0, 0, ch[0]});
-    size_t stem_w = 0, stem_b = 0;
-    int stem_nk = 0;
-    e->stem_fused = e->dtype == ZLY_DTYPE_BF16 && (ch[0] == 16 || ch[0] == 32);          // YOLOv8n / YOLOv8-s stems: preprocess + model.0 in one kernel
-    if (e->stem_fused) ok = ok && pb.pack_only("model.0", 4, &stem_w, &stem_b, &stem_nk, ch[0] == 32) && stem_nk == 2;
-    ok = ok && pb.conv({"model.1"}, View{a0, 0, ch[0]}, View{a1, 0, ch[1]});
-    size_t m1_w = 0, m1_b = 0, stem_w0p = 0;
-    e->stem1 = e->stem_fused && ch[0] == 16 && ch[1] == 32 && !(e->cfg.flags & ZLY_FLAG_NO_FUSION) && !e->sw.no_stem1 && ok;
-    if (e->stem1) {
+    ok = ok && pb.conv({"model.0"}, View{p->in_buf, 0, 8}, View{a0, 0, ch[0]}) >= 0;
+    p->stem_fused = pb.bf16() && (ch[0] == 16 || ch[0] == 32);          // YOLOv8n / YOLOv8-s stems: preprocess + model.0 in one kernel
+    if (ok && p->stem_fused) {
+        int nk = 0, cout_pad = 0;
+        pb.pack(m.find("model.0"), 4, pb.kstep, ch[0] == 32, 0, nullptr, &p->stem_w, &p->stem_b, &nk, &cout_pad);
+        ok = nk == 2;
+    }
+    ok = ok && pb.conv({"model.1"}, View{a0, 0, ch[0]}, View{a1, 0, ch[1]}) >= 0;
+    p->stem1 = p->stem_fused && ch[0] == 16 && ch[1] == 32 && !(cfg.flags & ZLY_FLAG_NO_FUSION) && !sw.no_stem1 && ok;
+    if (p->stem1) {
         // model.1 in the fused kernel's tiling: one 16x16x16 MFMA per tap (k = ci), pair-permuted rows, bias in channel order
         const ConvRec* r = m.find("model.1");
-        std::vector<uint8_t> w;
-        std::vector<float> b;
-        int cout = 0, cout_pad = 0, nk = 0;
-        repack_conv({r}, ch[0], 16, true, &w, &b, &cout, &cout_pad, &nk, true, 4);
-        if (nk != 9 || cout_pad != 32 || r->k != 3 || r->stride != 2) e->stem1 = false;
-        else { m1_w = pb.append(w.data(), w.size()); m1_b = pb.append(b.data(), b.size() * sizeof(float)); }
+        int cout_pad = 0, nk = 0;
+        pb.pack(r, ch[0], 16, true, 4, nullptr, &p->m1_w, &p->m1_b, &nk, &cout_pad);
+        if (nk != 9 || cout_pad != 32 || r->k != 3 || r->stride != 2) p->stem1 = false;
+    }
+    if (p->stem1) {
         // the stem's weights once more in the tap order of the fused kernel's conflict-free fragment reads (kernels_stem.hip: STEM1_TAP_SLOT)
-        if (e->stem1) {
-            const ConvRec* r0 = m.find("model.0");
-            int nk0 = 0;
-            repack_conv({r0}, 4, pb.kstep, true, &w, &b, &cout, &cout_pad, &nk0, false, 0, stem1_tap_slot());
-            if (nk0 != 2 || cout_pad != 16) e->stem1 = false;
-            else stem_w0p = pb.append(w.data(), w.size());
-        }
+        int cout_pad = 0, nk0 = 0;
+        pb.pack(m.find("model.0"), 4, pb.kstep, false, 0, stem1_tap_slot(), &p->stem_w0p, nullptr, &nk0, &cout_pad);
+        if (nk0 != 2 || cout_pad != 16) p->stem1 = false;
     }
     ok = ok && pb.c2f("model.2", View{a1, 0, ch[1]}, View{a2, 0, ch[1]}, nb[0], true, H4, W4);
-    ok = ok && pb.conv({"model.3"}, View{a2, 0, ch[1]}, View{a3, 0, ch[2]});
+    ok = ok && pb.conv({"model.3"}, View{a2, 0, ch[1]}, View{a3, 0, ch[2]}) >= 0;
     ok = ok && pb.c2f("model.4", View{a3, 0, ch[2]}, View{cat14, ch[3], ch[2]}, nb[1], true, H8, W8);          // P3 -> cat14
-    ok = ok && pb.conv({"model.5"}, View{cat14, ch[3], ch[2]}, View{a5, 0, ch[3]});
+    ok = ok && pb.conv({"model.5"}, View{cat14, ch[3], ch[2]}, View{a5, 0, ch[3]}) >= 0;
     ok = ok && pb.c2f("model.6", View{a5, 0, ch[3]}, View{cat11, ch[4], ch[3]}, nb[2], true, H16, W16);        // P4 -> cat11
-    ok = ok && pb.conv({"model.7"}, View{cat11, ch[4], ch[3]}, View{a7, 0, ch[4]});
+    ok = ok && pb.conv({"model.7"}, View{cat11, ch[4], ch[3]}, View{a7, 0, ch[4]}) >= 0;
     ok = ok && pb.c2f("model.8", View{a7, 0, ch[4]}, View{a8, 0, ch[4]}, nb[3], true, H32, W32);
     // SPPF
-    ok = ok && pb.conv({"model.9.cv1"}, View{a8, 0, ch[4]}, View{spp, 0, ch[4] / 2});
+    ok = ok && (p->sppf_cv1 = pb.conv({"model.9.cv1"}, View{a8, 0, ch[4]}, View{spp, 0, ch[4] / 2})) >= 0;
     if (ok) {
-        Op p; p.kind = OP_SPPF; p.name = "model.9.pool"; p.in = View{spp, 0, ch[4] / 2}; p.c = ch[4] / 2;
-        p.bytes = (double)H32 * W32 * (ch[4] / 2) * 4 * e->esz;
-        e->ops.push_back(p);
+        Op pool; pool.kind = OP_SPPF; pool.name = "model.9.pool"; pool.in = View{spp, 0, ch[4] / 2};
+        pool.bytes = (double)H32 * W32 * (ch[4] / 2) * 4 * esz;
+        p->sppf_pool = pb.add_op(pool);
     }
-    ok = ok && pb.conv({"model.9.cv2"}, View{spp, 0, 2 * ch[4]}, View{cat20, ch[3], ch[4]});                     // P5 -> cat20
+    ok = ok && (p->sppf_cv2 = pb.conv({"model.9.cv2"}, View{spp, 0, 2 * ch[4]}, View{cat20, ch[3], ch[4]})) >= 0;               // P5 -> cat20
     // neck, top-down.  Upsample(x2, nearest) + Concat are fused into the consumer: model.12.cv1 / model.15.cv1 read
     // their first channels from the half-size tensor at (y>>1, x>>1) and the rest from the skip tensor.
     ok = ok && pb.c2f("model.12", View{cat20, ch[3], ch[4]}, View{cat17, ch[2], ch[3]}, nb[4], false, H16, W16, View{cat11, ch[4], ch[3]});
     ok = ok && pb.c2f("model.15", View{cat17, ch[2], ch[3]}, View{a15, 0, ch[2]}, nb[5], false, H8, W8, View{cat14, ch[3], ch[2]});
+    ok = ok && pb.detect_level(0, View{a15, 0, ch[2]}, c2, c3, tail_total);
     // neck, bottom-up
-    ok = ok && pb.conv({"model.16"}, View{a15, 0, ch[2]}, View{cat17, 0, ch[2]});
+    ok = ok && pb.conv({"model.16"}, View{a15, 0, ch[2]}, View{cat17, 0, ch[2]}) >= 0;
     ok = ok && pb.c2f("model.18", View{cat17, 0, ch[2] + ch[3]}, View{a18, 0, ch[3]}, nb[6], false, H16, W16);
-    ok = ok && pb.conv({"model.19"}, View{a18, 0, ch[3]}, View{cat20, 0, ch[3]});
+    ok = ok && pb.detect_level(1, View{a18, 0, ch[3]}, c2, c3, tail_total);
+    ok = ok && pb.conv({"model.19"}, View{a18, 0, ch[3]}, View{cat20, 0, ch[3]}) >= 0;
     ok = ok && pb.c2f("model.21", View{cat20, 0, ch[3] + ch[4]}, View{a21, 0, ch[4]}, nb[7], false, H32, W32);
-    // Detect: per level, the two branches' first 3x3 convs read the same tensor and are one launch
-    const int c2 = std::max(16, std::max(ch[2] / 4, 4 * m.reg_max));
-    const int c3 = std::max(ch[2], std::min(m.nc, 100));
-    const int feats[3] = {a15, a18, a21};
-    const int fch[3] = {ch[2], ch[3], ch[4]};
-    const int fh[3] = {H8, H16, H32}, fw[3] = {W8, W16, W32};
-    const int ncp = (m.nc + 3) / 4 * 4;
-    int anchor_off = 0;
-    e->N = fh[0] * fw[0] + fh[1] * fw[1] + fh[2] * fw[2];
-    if (m.nc > 80) { *err = "nc > 80 is not supported by the fused Detect kernel"; return ZLY_ERR_MODEL_LOAD; }
-    // the class branch's stored width is c3 itself: for 65 <= nc <= 79 (YOLOv8n) its pixel rows would not be whole 16-channel
-    // tiles, and no conv epilogue nor the Detect tail's 16-byte fragment loads is written for that
-    if (c3 % 16 != 0) { *err = "Detect class-branch width max(ch[2], nc) = " + std::to_string(c3) + " is not a multiple of 16 (nc = " + std::to_string(m.nc) + ")"; return ZLY_ERR_MODEL_LOAD; }
-    Op hd;
-    hd.kind = OP_HEAD; hd.name = "detect.tail(1x1 convs+DFL+sigmoid+decode)";
-    if (hd.name.size() > 47) hd.name.resize(47);
-    PendingLevel (&pend)[3] = ps->pend;
-    int block0 = 0;
-    for (int l = 0; l < 3 && ok; ++l) {
-        const std::string L = std::to_string(l);
-        // the class branch's 80 channels are stored as 96 (16 zero channels, never written) so that its second 3x3 conv has
-        // Cin % 32 == 0 and takes the LDS-tiled kernel; the padded k-steps carry zero weights
-        const int c3s = (e->dtype == ZLY_DTYPE_BF16 && c3 % 32 != 0 && c2 % 32 == 0 && !e->sw.no_cin_pad) ? (c3 + 31) / 32 * 32 : c3;
-        const int hd1 = pb.add_buffer("detect." + L + ".stem", fh[l], fw[l], c2 + c3s);
-        const int hb2 = pb.add_buffer("detect." + L + ".box2", fh[l], fw[l], c2);
-        const int hc2 = pb.add_buffer("detect." + L + ".cls2", fh[l], fw[l], c3);
-        const int hout = pb.add_buffer("detect." + L + ".logits", fh[l], fw[l], 64 + ncp, true);
-        ok = ok && pb.conv({"model.22.cv2." + L + ".0", "model.22.cv3." + L + ".0"}, View{feats[l], 0, fch[l]}, View{hd1, 0, c2 + c3});
-        ok = ok && pb.conv({"model.22.cv2." + L + ".1"}, View{hd1, 0, c2}, View{hb2, 0, c2});
-        ok = ok && pb.conv({"model.22.cv3." + L + ".1"}, View{hd1, c2, c3s}, View{hc2, 0, c3});
-        if (ok && e->dtype == ZLY_DTYPE_BF16 && c3 == 80 && c3s >= 80) {
-            // the same conv for conv3x3_wsk_kernel: k = tap * 80 + c without channel padding (23 k-steps instead of 27), plain tile rows, no zero output tile
-            const ConvRec* r = m.find("model.22.cv3." + L + ".1");
-            std::vector<uint8_t> w;
-            std::vector<float> b;
-            int cout = 0, cout_pad = 0, nk = 0;
-            repack_conv({r}, 80, pb.kstep, true, &w, &b, &cout, &cout_pad, &nk, false);
-            if (nk == 23 && cout_pad == 80 && r->k == 3 && r->stride == 1) e->ops.back().wsk_w = pb.append(w.data(), w.size());
-        }
-        HeadLevel& hl = hd.head.lv[l];
-        ok = ok && pb.pack_only("model.22.cv2." + L + ".2", c2, &pend[l].wb, &pend[l].bb, &hl.nkb);
-        ok = ok && pb.pack_only("model.22.cv3." + L + ".2", c3, &pend[l].wc, &pend[l].bc, &hl.nkc);
-        // the fused tail holds a branch's fragments in HEAD_KMAX k-steps of registers (launch_head_fused refuses more): refuse the model here, at load
-        if (ok && (hl.nkb > HEAD_KMAX || hl.nkc > HEAD_KMAX)) {
-            *err = "Detect branch too wide for the fused tail: " + std::to_string(c2) + " / " + std::to_string(c3) + " channels = " + std::to_string(hl.nkb) + " / " +
-                   std::to_string(hl.nkc) + " k-steps, at most " + std::to_string(HEAD_KMAX) + (e->dtype == ZLY_DTYPE_BF16 ? " in bf16" : " in fp32");
-            return ZLY_ERR_MODEL_LOAD;
-        }
-        pend[l].hb2 = hb2; pend[l].hc2 = hc2; pend[l].hout = hout;
-        hl.box_cs = c2; hl.cls_cs = c3; hl.box_cin = c2; hl.cls_cin = c3;
-        hl.H = fh[l]; hl.W = fw[l]; hl.hw = fh[l] * fw[l]; hl.stride_px = 8 << l; hl.anchor_off = anchor_off; hl.block0 = block0;
-        hl.logits_cs = 64 + ncp;
-        block0 += (hl.hw + HEAD_GROUP - 1) / HEAD_GROUP;
-        const double macs = (double)hl.hw * (c2 * 64.0 + (double)c3 * m.nc);
-        hd.flops += 2.0 * macs;
-        // algorithmic bytes: both branch activations in, the weights, and -- only when the engine materialises it -- the fp32 head tensor out
-        hd.bytes += (double)hl.hw * ((c2 + c3) * (double)e->esz + ((e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) ? 0.0 : (4 + m.nc) * 4.0)) + (c2 * 64.0 + (double)c3 * m.nc) * e->esz;
-        hd.wbytes += (c2 * 64.0 + (double)c3 * m.nc) * e->esz;
-        hd.head_box[l] = hb2; hd.head_cls[l] = hc2;
-        e->tap_final[std::string("model.22.cv2.") + L + ".2"] = std::make_pair(hout, 0);
-        e->tap_final[std::string("model.22.cv3.") + L + ".2"] = std::make_pair(hout, 64);
-        e->lvl_h[l] = fh[l]; e->lvl_w[l] = fw[l];
-        anchor_off += fh[l] * fw[l];
-    }
-    hd.head.nc = m.nc; hd.head.N_total = e->N; hd.head.total_blocks = block0; hd.head.only_level = -1;
-    // Three tail ops, one per level.  From batch 16 up each is its own launch right behind its level's branch convs (P3 and
-    // P4 on the side streams, i.e. beside the neck) and only the small P5 launch is left at the end of the step; below
-    // that the first two are skipped and the last one covers all levels in a single launch (fewest launches).
-    for (int l = 0; l < 3 && ok; ++l) {
-        Op t = hd;
-        t.level = l;
-        t.name = std::string("detect.tail.P") + std::to_string(3 + l) + (l == 2 ? " (all levels below batch 16)" : "");
-        const double share = (double)hd.head.lv[l].hw / (double)e->N;
-        t.flops = hd.flops * share; t.bytes = hd.bytes * share; t.wbytes = hd.wbytes * share;
-        e->ops.push_back(t);
-    }
-    if (!ok) { *err = pb.err; return ZLY_ERR_MODEL_LOAD; }
-    Op nm; nm.kind = OP_NMS; nm.name = "nms"; e->ops.push_back(nm);
-
-    // The Detect branches of P3 and P4 only depend on model.15 / model.18: issue them right behind their
-    // producer on side streams (lanes 1, 2) so that, inside the captured graph, they run BESIDE the rest of
-    // the neck (model.16-21) instead of after it.  These launches are latency/issue-bound and leave most of
-    // the chip idle, so the overlap is nearly free.  The tail op joins all lanes.
-    {
-        std::vector<Op> main_ops, lane_ops[3];
-        for (Op& op : e->ops) {
-            int lane = 0;
-            if (op.kind == OP_CONV && op.name.rfind("model.22.cv", 0) == 0) {
-                const int lvl = op.name[13] - '0';                 // "model.22.cvX.L...": L is character 13
-                lane = lvl == 0 ? 1 : (lvl == 1 ? 2 : 0);
-            }
-            if (op.kind == OP_HEAD) lane = op.level == 0 ? 1 : (op.level == 1 ? 2 : 0);
-            op.lane = lane;
-            (lane == 0 ? main_ops : lane_ops[lane]).push_back(op);
-        }
-        std::vector<Op> ordered;
-        for (Op& op : main_ops) {
-            ordered.push_back(op);
-            if (op.kind == OP_CONV && op.name == "model.15.cv2") for (Op& x : lane_ops[1]) ordered.push_back(x);
-            if (op.kind == OP_CONV && op.name == "model.18.cv2") for (Op& x : lane_ops[2]) ordered.push_back(x);
-        }
-        if (ordered.size() != e->ops.size()) { *err = "internal: op reordering lost ops"; return ZLY_ERR_MODEL_LOAD; }
-        e->ops.swap(ordered);
-        e->tap_index.clear();
-        for (size_t i = 0; i < e->ops.size(); ++i)
-            for (size_t k = 0; k < e->ops[i].taps.size(); ++k) e->tap_index[e->ops[i].taps[k]] = std::make_pair((int)i, (int)k);
-        std::map<std::string, int> by_name;
-        for (size_t i = 0; i < e->ops.size(); ++i) by_name[e->ops[i].name] = (int)i;
-        for (Op& op : e->ops)
-            if (!op.c2f_leader_name.empty()) op.c2f_leader = by_name[op.c2f_leader_name];
-        if (by_name.count("model.9.cv1") && by_name.count("model.9.pool") && by_name.count("model.9.cv2")) {
-            e->sppf_cv1 = by_name["model.9.cv1"]; e->sppf_pool = by_name["model.9.pool"]; e->sppf_cv2 = by_name["model.9.cv2"];
-        }
-        // Detect convs, for the merged launches of the latency path: all three levels must suit the shared kernel shape
-        bool det_ok = e->dtype == ZLY_DTYPE_BF16;
-        for (int l = 0; l < 3 && det_ok; ++l) {
-            const std::string L = std::to_string(l);
-            for (size_t i = 0; i < e->ops.size(); ++i) {
-                const Op& op = e->ops[i];
-                if (op.kind != OP_CONV) continue;
-                if (op.name.rfind("model.22.cv2." + L + ".0", 0) == 0) e->det_stem[l] = (int)i;
-                if (op.name == "model.22.cv2." + L + ".1") e->det_a[l] = (int)i;
-                if (op.name == "model.22.cv3." + L + ".1") e->det_b[l] = (int)i;
-            }
-            det_ok = e->det_stem[l] >= 0 && e->det_a[l] >= 0 && e->det_b[l] >= 0;
-            if (det_ok) {
-                const Op& S = e->ops[(size_t)e->det_stem[l]];
-                const Op& A = e->ops[(size_t)e->det_a[l]];
-                const Op& Bc = e->ops[(size_t)e->det_b[l]];
-                det_ok = S.ks == 3 && A.ks == 3 && Bc.ks == 3 && S.stride == 1 && S.in.C % 32 == 0 && A.in.C % 32 == 0 && Bc.in.C % 32 == 0 &&
-                         S.cout_pad % 48 == 0 && A.cout_pad % 32 == 0 && Bc.cout_pad % 32 == 0 && S.in2.buf < 0 && S.res.buf < 0 && A.res.buf < 0 && Bc.res.buf < 0;
-            }
-        }
-        if (!det_ok) e->det_stem[0] = -1;
-    }
-
-    ps->blob.swap(pb.blob);
-    ps->stem_w = stem_w; ps->stem_b = stem_b; ps->m1_w = m1_w; ps->m1_b = m1_b; ps->stem_w0p = stem_w0p; ps->a0 = a0; ps->a1 = a1;
+    ok = ok && pb.detect_level(2, View{a21, 0, ch[4]}, c2, c3, tail_total);
+    if (!ok) return refuse(pb.err);
+    Op nm; nm.kind = OP_NMS; nm.name = "nms"; pb.add_op(nm);
     return ZLY_OK;
 }
 
-static int build_plan_device(zly_engine* e, PlanState* ps, std::string* err)
+// the device half: allocates the buffers, uploads the weight blob and turns the plan's offsets and buffer indices into the pointers of the launch templates
+static int upload_plan(zly_engine* e, std::string* err)
 {
-    const ModelFile& m = e->model;
     const int W = e->cfg.model_w, H = e->cfg.model_h;
-    const int* ch = m.ch;
-    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
-    const size_t stem_w = ps->stem_w, stem_b = ps->stem_b, m1_w = ps->m1_w, m1_b = ps->m1_b, stem_w0p = ps->stem_w0p;
-    const int a0 = ps->a0, a1 = ps->a1;
-    const PendingLevel (&pend)[3] = ps->pend;
-    struct { std::vector<uint8_t>& blob; } pb{ps->blob};
-    // device allocations
     const int B = e->cfg.max_batch;
     for (Buffer& b : e->bufs) {
         if (b.elems_per_frame() * (size_t)B >= (1ull << 31)) { *err = "activation buffer " + b.name + " exceeds 2^31 elements: lower max_batch"; return ZLY_ERR_INVALID_ARGUMENT; }
@@ -728,37 +690,39 @@ static int build_plan_device(zly_engine* e, PlanState* ps, std::string* err)
         if (hipMalloc(&b.ptr, bytes) != hipSuccess) { *err = "hipMalloc failed for " + b.name; return ZLY_ERR_SYSTEM; }
         hipMemset(b.ptr, 0, bytes);
     }
-    if (hipMalloc(&e->d_weights, pb.blob.size()) != hipSuccess) { *err = "hipMalloc failed for weights"; return ZLY_ERR_SYSTEM; }
-    if (hipMemcpy(e->d_weights, pb.blob.data(), pb.blob.size(), hipMemcpyHostToDevice) != hipSuccess) { *err = "weight upload failed"; return ZLY_ERR_SYSTEM; }
+    if (hipMalloc(&e->d_weights, e->blob.size()) != hipSuccess) { *err = "hipMalloc failed for weights"; return ZLY_ERR_SYSTEM; }
+    if (hipMemcpy(e->d_weights, e->blob.data(), e->blob.size(), hipMemcpyHostToDevice) != hipSuccess) { *err = "weight upload failed"; return ZLY_ERR_SYSTEM; }
+    e->blob = std::vector<uint8_t>();                    // the host image of the weight blob is on the device now
+    const char* wb = (const char*)e->d_weights;
     if (e->stem_fused) {
+        const Buffer& ob = e->bufs[(size_t)e->stem_out];
         StemArgs& st = e->stem;
-        st.wgt = (const char*)e->d_weights + stem_w; st.bias = (const float*)((const char*)e->d_weights + stem_b);
-        st.out = e->bufs[(size_t)a0].ptr; st.out_cs = ch[0]; st.out_co = 0;
-        st.tw = W; st.th = H; st.Ho = H2; st.Wo = W2; st.Cout = ch[0]; st.tiles_x = stem_tiles_x(W2);
+        st.wgt = wb + e->stem_w; st.bias = (const float*)(wb + e->stem_b);
+        st.out = ob.ptr; st.out_cs = ob.C; st.out_co = 0;
+        st.tw = W; st.th = H; st.Ho = ob.H; st.Wo = ob.W; st.Cout = ob.C; st.tiles_x = stem_tiles_x(ob.W);
     }
     if (e->stem1) {
+        const Buffer& ob = e->bufs[(size_t)e->m1_out];
         Stem1Args& s1 = e->stem1a;
         s1.st = e->stem;
-        s1.w1 = (const char*)e->d_weights + m1_w; s1.b1 = (const float*)((const char*)e->d_weights + m1_b);
-        s1.out1 = e->bufs[(size_t)a1].ptr; s1.out1_cs = ch[1]; s1.out1_co = 0;
-        s1.H1 = H4; s1.W1 = W4;
-        stem1_plan(H4, W4, e->sw, &s1.TH, &s1.TW);
-        s1.tiles_x = (W4 + s1.TW - 1) / s1.TW; s1.tiles_y = (H4 + s1.TH - 1) / s1.TH;
+        s1.w1 = wb + e->m1_w; s1.b1 = (const float*)(wb + e->m1_b);
+        s1.out1 = ob.ptr; s1.out1_cs = ob.C; s1.out1_co = 0;
+        s1.H1 = ob.H; s1.W1 = ob.W;
+        stem1_plan(ob.H, ob.W, e->sw, &s1.TH, &s1.TW);
+        s1.tiles_x = (ob.W + s1.TW - 1) / s1.TW; s1.tiles_y = (ob.H + s1.TH - 1) / s1.TH;
         s1.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
-        s1.wgt0p = (const char*)e->d_weights + stem_w0p;
+        s1.wgt0p = wb + e->stem_w0p;
         s1.nw = e->sw.stem1_nw; s1.var = e->sw.stem1_var; s1.pgrid = e->sw.stem1_grid;
         s1.small_tiles = e->sw.stem1_keep_tiles ? 0 : 1;
     }
-    for (Op& op : e->ops) {
-        if (op.kind != OP_HEAD) continue;
-        for (int l = 0; l < 3; ++l) {
-            HeadLevel& hl = op.head.lv[l];
-            hl.box_in = e->bufs[(size_t)pend[l].hb2].ptr;
-            hl.cls_in = e->bufs[(size_t)pend[l].hc2].ptr;
-            hl.wb = (const char*)e->d_weights + pend[l].wb; hl.bb = (const float*)((const char*)e->d_weights + pend[l].bb);
-            hl.wc = (const char*)e->d_weights + pend[l].wc; hl.bc = (const float*)((const char*)e->d_weights + pend[l].bc);
-            hl.logits = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? (float*)e->bufs[(size_t)pend[l].hout].ptr : nullptr;
-        }
+    DetectTail& t = e->tail;
+    for (int l = 0; l < 3; ++l) {
+        HeadLevel& hl = t.args.lv[l];
+        hl.box_in = e->bufs[(size_t)t.box[l]].ptr;
+        hl.cls_in = e->bufs[(size_t)t.cls[l]].ptr;
+        hl.wb = wb + t.wb[l]; hl.bb = (const float*)(wb + t.bb[l]);
+        hl.wc = wb + t.wc[l]; hl.bc = (const float*)(wb + t.bc[l]);
+        hl.logits = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? (float*)e->bufs[(size_t)t.logits[l]].ptr : nullptr;
     }
     return ZLY_OK;
 }
@@ -829,6 +793,51 @@ static SppfArgs make_sppf_args(const zly_engine* e, int n)
     return sa;
 }
 
+// the fused bottleneck pair's arguments at batch n, on the tiling of plan pl
+static PairArgs make_pair_args(const zly_engine* e, const PairGroup& g, const PairPlan& pl, int n)
+{
+    const Op& A = e->ops[(size_t)g.first];
+    const Buffer& ib = e->bufs[(size_t)A.in.buf];
+    const Buffer& ob = e->bufs[(size_t)g.out.buf];
+    const char* wb = (const char*)e->d_weights;
+    PairArgs pa;
+    pa.in = ib.ptr; pa.in_cs = ib.C; pa.in_co = A.in.co;
+    pa.out = ob.ptr; pa.out_cs = ob.C; pa.out_co = g.out.co;
+    pa.wA = wb + g.wA; pa.bA = (const float*)(wb + g.bA);
+    pa.wB = wb + g.wB; pa.bB = (const float*)(wb + g.bB);
+    pa.H = ib.H; pa.W = ib.W; pa.n = n;
+    pa.TH = pl.th; pa.TW = pl.tw; pa.tiles_x = pl.tiles_x; pa.tiles_y = pl.tiles_y; pa.total_tiles = pl.total_tiles;
+    pa.res = g.res;
+    return pa;
+}
+
+// the fused C2f kernel's arguments at batch n, on the tiling of plan pl: the block's input(s), concat buffer and output, cv1 / cv2 and the bottleneck's pair
+static C2fArgs make_c2f_args(const zly_engine* e, const C2fGroup& g, const C2fPlan& pl, int n)
+{
+    const PairGroup& pg = e->pairs[(size_t)g.pair];
+    const Buffer& cb = e->bufs[(size_t)g.cat];
+    const Buffer& xb = e->bufs[(size_t)g.x.buf];
+    const Buffer& ob = e->bufs[(size_t)g.out.buf];
+    const char* wb = (const char*)e->d_weights;
+    C2fArgs ca{};
+    ca.x = xb.ptr; ca.x_cs = xb.C; ca.x_co = g.x.co;
+    if (g.x2.buf >= 0) {
+        const Buffer& x2 = e->bufs[(size_t)g.x2.buf];
+        ca.x2 = x2.ptr; ca.x2_cs = x2.C; ca.x2_co = g.x2.co; ca.split_c = g.x.C;
+    }
+    ca.w1 = wb + g.w1; ca.b1 = (const float*)(wb + g.b1); ca.nk1 = g.nk1;
+    ca.cat = cb.ptr; ca.cat_cs = cb.C; ca.pair_in_co = e->ops[(size_t)pg.first].in.co; ca.pair_out_co = pg.out.co;
+    ca.wA = wb + pg.wA; ca.bA = (const float*)(wb + pg.bA); ca.wB = wb + pg.wB; ca.bB = (const float*)(wb + pg.bB);
+    ca.res = g.res;
+    ca.w2 = wb + g.w2; ca.b2 = (const float*)(wb + g.b2); ca.nk2 = g.nk2; ca.Cout2 = g.cout2;
+    ca.out = ob.ptr; ca.out_cs = ob.C; ca.out_co = g.out.co;
+    ca.H = cb.H; ca.W = cb.W; ca.n = n;
+    ca.TH = pl.th; ca.TW = pl.tw; ca.tiles_x = pl.tiles_x; ca.tiles_y = pl.tiles_y; ca.total_tiles = pl.total_tiles;
+    ca.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
+    if (g.c == 64 && g.mid.buf >= 0) { const Buffer& mb = e->bufs[(size_t)g.mid.buf]; ca.mid = mb.ptr; ca.mid_cs = mb.C; }
+    return ca;
+}
+
 // What every op launches at batch n, in op order: built once per batch size (under e->mu; run_path builds it before it captures that size) and
 // read by run_op, zly_op_kernel_name, zly_launch_info_at, zly_profile_ops and zly_debug_tap, so that what they report is what runs.
 // It describes the detect paths, whose front kernel covers ops[0..2] (preprocess, model.0, model.1) where the stem is fused; zly_forward,
@@ -841,18 +850,21 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
     if (it != e->launches.end()) return it->second;
     const bool bf16 = e->dtype == ZLY_DTYPE_BF16, fusion = bf16 && !(e->cfg.flags & ZLY_FLAG_NO_FUSION), dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) != 0;
     const int nops = (int)e->ops.size();
-    // the fused C2f kernel for the group led by op G (ZLY_NO_C2F: tuning / tests)
-    auto c2f_of = [&](const Op& G, C2fPlan* pl) {
-        if (!G.c2f_mode || !fusion || e->sw.no_c2f) return false;
-        const Buffer& b = e->bufs[(size_t)G.c2f_cat];
-        return c2f_plan(G.c2f_c, G.c2f_mode, G.c2f_nk1, G.c2f_nk2, G.c2f_cout2, n, b.H, b.W, e->sw, pl);
+    // the fused C2f kernel for group g (ZLY_NO_C2F: tuning / tests)
+    auto c2f_of = [&](const C2fGroup& g, C2fPlan* pl) {
+        if (!fusion || e->sw.no_c2f) return false;
+        const Buffer& b = e->bufs[(size_t)g.cat];
+        return c2f_plan(g.c, g.mode, g.nk1, g.nk2, g.cout2, n, b.H, b.W, e->sw, pl);
     };
-    // the fused bottleneck pair at its first conv A.  Only degenerate launches (a handful of tiles) stay on the per-conv kernels: at batch 1
+    // the fused bottleneck pair at its first conv, op a.  Only degenerate launches (a handful of tiles) stay on the per-conv kernels: at batch 1
     // (91 / 234 tiles) one fused launch beats two per-conv launches, 4370 -> 4475 fps.  Width 64 is built and tested, but no faster than two launches.
-    auto pair_of = [&](const Op& A, PairPlan* pl) {
-        if (A.pair != 1 || !fusion || !(e->sw.pair_widths & A.pair_c)) return false;
+    auto pair_of = [&](int a, PairPlan* pl) {
+        const Op& A = e->ops[(size_t)a];
+        if (A.pair < 0 || !fusion) return false;
+        const PairGroup& g = e->pairs[(size_t)A.pair];
+        if (g.first != a || !(e->sw.pair_widths & g.c)) return false;
         const Buffer& b = e->bufs[(size_t)A.in.buf];
-        return pair_plan(A.pair_c, n, b.H, b.W, e->sw, pl) && pl->total_tiles >= e->sw.pair_min_tiles;
+        return pair_plan(g.c, n, b.H, b.W, e->sw, pl) && pl->total_tiles >= e->sw.pair_min_tiles;
     };
     // SPPF as one launch at model.9.cv1 (opt-in, ZLY_SPPF_FUSED=1); the pool and cv2 then launch nothing
     bool sppf = fusion && e->sw.sppf_fused && e->sppf_cv1 >= 0;
@@ -864,7 +876,7 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
     }
     // the Detect convs as two launches on the latency path (conv_igemm_multi_kernel): batch <= 4, no side streams in use.  The launch of the
     // three stems is booked on the P5 stem, that of the six branch convs on P5's box-branch conv.
-    const bool merge = bf16 && e->det_stem[0] >= 0 && n <= 4 && !lanes_active(e, n) && !e->sw.no_det_merge;
+    const bool merge = bf16 && e->det_merge_ok && n <= 4 && !lanes_active(e, n) && !e->sw.no_det_merge;
     auto merged_at = [&](int i) {
         for (int l = 0; l < 3; ++l) {
             if (i == e->det_stem[l]) return e->det_stem[2];
@@ -875,8 +887,7 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
     // the Detect tail: one launch per level behind its branch convs when the side streams are in use (+0.3 % at batch 64), else one launch of
     // all levels at the last tail op
     const bool tail_split = lanes_active(e, n) && !e->sw.no_tail_split;
-    int tail = -1;
-    for (int i = 0; i < nops; ++i) if (e->ops[(size_t)i].kind == OP_HEAD && e->ops[(size_t)i].level == 2) tail = i;
+    const int tail = e->tail.op[2];
 
     const bool lb = (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0;
     std::vector<Launch> t((size_t)nops);
@@ -894,7 +905,7 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
         case OP_SPPF: {
             const Buffer& b = e->bufs[(size_t)op.in.buf];
             if (sppf) covered(e->sppf_cv1);
-            else { L.kind = LK_SPPF_POOL; L.pool16 = sppf_pool16_ok(e->dtype, b.C, op.c, n, b.H, b.W, e->sw.pool_six_pass ? 1 : 0); }
+            else { L.kind = LK_SPPF_POOL; L.pool16 = sppf_pool16_ok(e->dtype, b.C, op.in.C, n, b.H, b.W, e->sw.pool_six_pass ? 1 : 0); }
             break;
         }
         case OP_HEAD:
@@ -913,10 +924,11 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
                 L.hbm = !e->stem1 || dump;                                  // stem_model1_kernel keeps the stem map in LDS
             } else if (i == 2 && e->stem1) {
                 covered(1);
-            } else if (op.c2f_leader >= 0 && c2f_of(e->ops[(size_t)op.c2f_leader], &cp)) {
-                if (op.c2f_leader == i) { L.kind = LK_C2F; L.c2f = cp; }
-                else covered(op.c2f_leader);
-                L.hbm = op.c2f_vis == 0 || (op.c2f_vis == 1 && dump);
+            } else if (op.c2f >= 0 && c2f_of(e->c2fs[(size_t)op.c2f], &cp)) {
+                const C2fGroup& g = e->c2fs[(size_t)op.c2f];
+                if (g.leader == i) { L.kind = LK_C2F; L.c2f = cp; }
+                else covered(g.leader);
+                L.hbm = g.vis_of(i) == 0 || (g.vis_of(i) == 1 && dump);
             } else if (sppf && i == e->sppf_cv1) {
                 L.kind = LK_SPPF_FUSED;
                 L.hbm = dump;
@@ -925,11 +937,11 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
             } else if (merge && merged_at(i) >= 0) {
                 if (merged_at(i) == i) { L.kind = LK_MULTI; L.multi_ct = i == e->det_stem[2] ? 3 : 2; }
                 else covered(merged_at(i));
-            } else if (pair_of(op, &pp)) {
+            } else if (pair_of(i, &pp)) {
                 L.kind = LK_PAIR; L.pair = pp;
                 L.hbm = false;                                              // the intermediate map stays in LDS
-            } else if (op.pair == 2 && pair_of(e->ops[(size_t)i - 1], &pp)) {
-                covered(i - 1);
+            } else if (op.pair >= 0 && e->pairs[(size_t)op.pair].second == i && pair_of(e->pairs[(size_t)op.pair].first, &pp)) {
+                covered(e->pairs[(size_t)op.pair].first);
             } else if (op.wsk_w && !e->sw.no_wsk && bf16 && conv_wsk_ok(make_wsk_args(e, op, n), e->sw, &L.wsk)) {
                 L.kind = LK_CONV_WSK;
             } else {
@@ -953,13 +965,13 @@ static void op_reads(const zly_engine* e, const Op& op, std::vector<IoView>* out
         if (op.res.buf >= 0) { const Buffer& rb = e->bufs[(size_t)op.res.buf]; out->push_back({op.res.buf, op.res.co, op.res.C > 0 ? op.res.C : op.cout, (double)rb.H * rb.W, 1.0}); }
     } else if (op.kind == OP_SPPF) {
         const Buffer& b = e->bufs[(size_t)op.in.buf];
-        out->push_back({op.in.buf, op.in.co, op.c, (double)b.H * b.W, 1.0});
+        out->push_back({op.in.buf, op.in.co, op.in.C, (double)b.H * b.W, 1.0});
     } else if (op.kind == OP_HEAD) {                      // a tail op stands for its own level; one launch for all levels = a group of the three
-        const int l = op.level;
-        const Buffer& bb = e->bufs[(size_t)op.head_box[l]];
-        const Buffer& cb = e->bufs[(size_t)op.head_cls[l]];
-        out->push_back({op.head_box[l], 0, bb.C, (double)bb.H * bb.W, 1.0});
-        out->push_back({op.head_cls[l], 0, cb.C, (double)cb.H * cb.W, 1.0});
+        const int box = e->tail.box[op.level], cls = e->tail.cls[op.level];
+        const Buffer& bb = e->bufs[(size_t)box];
+        const Buffer& cb = e->bufs[(size_t)cls];
+        out->push_back({box, 0, bb.C, (double)bb.H * bb.W, 1.0});
+        out->push_back({cls, 0, cb.C, (double)cb.H * cb.W, 1.0});
     }
 }
 static void op_writes(const zly_engine* e, const Op& op, std::vector<IoView>* out)
@@ -969,7 +981,7 @@ static void op_writes(const zly_engine* e, const Op& op, std::vector<IoView>* ou
         out->push_back({op.out.buf, op.out.co, op.cout, (double)ob.H * ob.W, 1.0});
     } else if (op.kind == OP_SPPF) {
         const Buffer& b = e->bufs[(size_t)op.in.buf];
-        out->push_back({op.in.buf, op.in.co + op.c, 3 * op.c, (double)b.H * b.W, 1.0});
+        out->push_back({op.in.buf, op.in.co + op.in.C, 3 * op.in.C, (double)b.H * b.W, 1.0});
     } else if (op.kind == OP_PREPROCESS) {
         const Buffer& b = e->bufs[(size_t)e->in_buf];
         out->push_back({e->in_buf, 0, 8, (double)b.H * b.W, 3.0 / 8.0});
@@ -980,7 +992,6 @@ static void op_writes(const zly_engine* e, const Op& op, std::vector<IoView>* ou
 static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s)
 {
     const Op& op = e->ops[i];
-    const char* wb = (const char*)e->d_weights;
     switch (L.kind) {
     case LK_NONE:
         return hipSuccess;
@@ -1009,50 +1020,21 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
         return launch_conv_multi(m, L.multi_ct, s);
     }
     case LK_C2F: {
-        const C2fPlan* pl = &L.c2f;
-        const Buffer& cb = e->bufs[(size_t)op.c2f_cat];
-        const Buffer& xb = e->bufs[(size_t)op.c2f_x.buf];
-        const Buffer& ob2 = e->bufs[(size_t)op.c2f_out.buf];
-        C2fArgs ca{};
-        ca.x = xb.ptr; ca.x_cs = xb.C; ca.x_co = op.c2f_x.co;
-        if (op.c2f_x2.buf >= 0) {
-            const Buffer& x2 = e->bufs[(size_t)op.c2f_x2.buf];
-            ca.x2 = x2.ptr; ca.x2_cs = x2.C; ca.x2_co = op.c2f_x2.co; ca.split_c = op.c2f_x.C;
-        }
-        ca.w1 = wb + op.c2f_w1; ca.b1 = (const float*)(wb + op.c2f_b1); ca.nk1 = op.c2f_nk1;
-        ca.cat = cb.ptr; ca.cat_cs = cb.C; ca.pair_in_co = op.c2f_in_co; ca.pair_out_co = op.c2f_out_co;
-        ca.wA = wb + op.c2f_wA; ca.bA = (const float*)(wb + op.c2f_bA); ca.wB = wb + op.c2f_wB; ca.bB = (const float*)(wb + op.c2f_bB);
-        ca.res = op.c2f_res;
-        ca.w2 = wb + op.c2f_w2; ca.b2 = (const float*)(wb + op.c2f_b2); ca.nk2 = op.c2f_nk2; ca.Cout2 = op.c2f_cout2;
-        ca.out = ob2.ptr; ca.out_cs = ob2.C; ca.out_co = op.c2f_out.co;
-        ca.H = cb.H; ca.W = cb.W; ca.n = n;
-        ca.TH = pl->th; ca.TW = pl->tw; ca.tiles_x = pl->tiles_x; ca.tiles_y = pl->tiles_y; ca.total_tiles = pl->total_tiles;
-        ca.dump = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? 1 : 0;
-        if (op.c2f_c == 64 && op.c2f_mid.buf >= 0) { const Buffer& mb = e->bufs[(size_t)op.c2f_mid.buf]; ca.mid = mb.ptr; ca.mid_cs = mb.C; }
-        return launch_c2f(op.c2f_c, op.c2f_mode, ca, *pl, s);
+        const C2fGroup& g = e->c2fs[(size_t)op.c2f];
+        return launch_c2f(g.c, g.mode, make_c2f_args(e, g, L.c2f, n), L.c2f, s);
     }
     case LK_PAIR: {
-        const PairPlan* pl = &L.pair;
-        const Buffer& ib = e->bufs[(size_t)op.in.buf];
-        const Buffer& pb = e->bufs[(size_t)op.pair_out.buf];
-        PairArgs pa;
-        pa.in = ib.ptr; pa.in_cs = ib.C; pa.in_co = op.in.co;
-        pa.out = pb.ptr; pa.out_cs = pb.C; pa.out_co = op.pair_out.co;
-        pa.wA = wb + op.pair_wA; pa.bA = (const float*)(wb + op.pair_bA);
-        pa.wB = wb + op.pair_wB; pa.bB = (const float*)(wb + op.pair_bB);
-        pa.H = ib.H; pa.W = ib.W; pa.n = n;
-        pa.TH = pl->th; pa.TW = pl->tw; pa.tiles_x = pl->tiles_x; pa.tiles_y = pl->tiles_y; pa.total_tiles = pl->total_tiles;
-        pa.res = op.pair_res;
-        return launch_pair(op.pair_c, pa, *pl, s);
+        const PairGroup& g = e->pairs[(size_t)op.pair];
+        return launch_pair(g.c, make_pair_args(e, g, L.pair, n), L.pair, s);
     }
     case LK_SPPF_FUSED:
         return launch_sppf_fused(make_sppf_args(e, n), s);
     case LK_SPPF_POOL: {
         const Buffer& b = e->bufs[(size_t)op.in.buf];
-        return launch_sppf_pool(e->dtype, b.ptr, b.C, op.c, n, b.H, b.W, s, e->sw.pool_six_pass ? 1 : 0);
+        return launch_sppf_pool(e->dtype, b.ptr, b.C, op.in.C, n, b.H, b.W, s, e->sw.pool_six_pass ? 1 : 0);
     }
     case LK_HEAD: {
-        HeadArgs h = op.head;
+        HeadArgs h = e->tail.args;
         h.only_level = L.only_level;
         if (L.lb) { h.lb_tw = e->cfg.model_w; h.lb_th = e->cfg.model_h; }      // boxes are mapped out of the letterbox (the geometry comes from d_desc at run time: no graph key)
         h.head = (e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) ? nullptr : e->d_head; h.desc = e->d_desc; h.conf_thr = e->cfg.conf_thr; h.cand = e->cur_cand; h.cand_count = e->cur_count;
@@ -1096,7 +1078,7 @@ static hipError_t run_ops(zly_engine* e, const std::vector<Launch>& tab, size_t 
         if (op.kind == OP_NMS) { join_all(); if (r != hipSuccess) break; }       // the tail launches only append candidates: no join needed before them
         // the side streams are joined in front of the P5 branch rather than at the very end: they have long finished by then, and
         // the hand-over (~10 us on the main stream) then overlaps nothing less than at the step boundary (+0.7 %)
-        if (op.kind == OP_CONV && op.lane == 0 && op.name.rfind("model.22.cv2.2.0", 0) == 0) { join_all(); if (r != hipSuccess) break; }
+        if ((int)i == e->join_at) { join_all(); if (r != hipSuccess) break; }
         // ZLY_ABLATE_SKIP=<op name>[,<op name>...]: the named launches are left out (results are garbage): measures what a launch costs the
         // step when several engines' chains overlap, which its isolated duration does not tell (tools/ablate_launches.sh)
 #ifdef ZLY_DIAG         // diagnostic build only (libzly_diag.so): a shipped engine cannot be told to skip launches
@@ -1836,9 +1818,7 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
     std::string err;
     int rc = load_zlyw(e->weights_path.c_str(), &e->model, &err);        // host only: file parse
     if (rc != ZLY_OK) { delete e; return fail(rc, err); }
-    e->nc = e->model.nc;
-    PlanState plan_state;
-    rc = build_plan_host(e, &plan_state, &err);                          // host only: op list + weight repack, outside the gate
+    rc = build_plan(e->model, e->cfg, e->dtype, e->sw, e, &err);         // host only: op list + weight repack, outside the gate
     if (rc != ZLY_OK) { delete e; return fail(rc, err); }
 
     // Everything that allocates on / uploads to the device runs alone in the process (ExclusiveGate): a hot reload builds new engines beside
@@ -1871,9 +1851,8 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
                   hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming) == hipSuccess;
         }
         if (!sok) return fail(ZLY_ERR_SYSTEM, "hipStreamCreate failed");
-        int prc = build_plan_device(e, &plan_state, &err);
+        int prc = upload_plan(e, &err);
         if (prc != ZLY_OK) return fail(prc, err);
-        plan_state.blob = std::vector<uint8_t>();      // the host image of the weight blob is on the device now
 
         const size_t B = (size_t)cfg->max_batch, N = (size_t)e->N;
         bool ok = true;
@@ -2310,7 +2289,7 @@ int32_t zly_debug_tap(zly_engine* e, const char* name, int32_t idx, float* out, 
                 break;
             case LK_C2F:
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused C2f kernel at this batch size; create the engine with " +
-                                                          (op.c2f_vis == 1 ? "ZLY_FLAG_DUMP_LOGITS or " : "") + "ZLY_FLAG_NO_FUSION");
+                                                          (e->c2fs[(size_t)op.c2f].vis_of(it->second.first) == 1 ? "ZLY_FLAG_DUMP_LOGITS or " : "") + "ZLY_FLAG_NO_FUSION");
             case LK_SPPF_FUSED:
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused SPPF kernel; create the engine with ZLY_FLAG_DUMP_LOGITS or ZLY_FLAG_NO_FUSION");
             case LK_PAIR:
@@ -2382,11 +2361,13 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
     case LK_SPPF_POOL: k = L.pool16 ? "sppf_pool16_kernel<DPP row windows, one barrier>" : "sppf_pool_kernel"; break;
     case LK_SPPF_FUSED: k = "sppf_fused_kernel<cv1+3 pools+cv2,SPLIT=" + std::to_string(sppf_split(e->ops[(size_t)e->sppf_cv2].cout, n, e->sw)) + ">"; break;
     case LK_MULTI: k = L.multi_ct == 3 ? "conv_igemm_multi_kernel<CT=3> (the 3 Detect stems)" : "conv_igemm_multi_kernel<CT=2> (the 6 Detect branch convs)"; break;
-    case LK_C2F:
-        k = "c2f_kernel<C=" + std::to_string(op.c2f_c) + (op.c2f_c == 32 ? ",NW=" + std::to_string(L.c2f.nw) : std::string()) +
-            (op.c2f_mode == 3 ? ",cv1+bottleneck+cv2>" : op.c2f_mode == 1 ? ",cv1+bottleneck>" : ",bottleneck+cv2>");
+    case LK_C2F: {
+        const C2fGroup& g = e->c2fs[(size_t)op.c2f];
+        k = "c2f_kernel<C=" + std::to_string(g.c) + (g.c == 32 ? ",NW=" + std::to_string(L.c2f.nw) : std::string()) +
+            (g.mode == 3 ? ",cv1+bottleneck+cv2>" : g.mode == 1 ? ",cv1+bottleneck>" : ",bottleneck+cv2>");
         break;
-    case LK_PAIR: k = "bottleneck_pair_kernel<" + std::to_string(op.pair_c) + ">"; break;
+    }
+    case LK_PAIR: k = "bottleneck_pair_kernel<" + std::to_string(e->pairs[(size_t)op.pair].c) + ">"; break;
     case LK_CONV_WSK: k = "conv3x3_wsk_kernel<K=720 packed across taps,5 channel tiles>"; break;
     case LK_CONV: {
         const int cin = op.in.C + (op.in2.buf >= 0 ? op.in2.C : 0);
@@ -2441,7 +2422,7 @@ int32_t zly_launch_info_at(zly_engine* e, int32_t i, int32_t n, zly_launch_info*
         out->bytes_unfused_per_frame += op.bytes;
         wbytes += op.wbytes;
         if (op.kind == OP_PREPROCESS) ext_in += (double)e->cfg.model_w * e->cfg.model_h * 3;          // the u8 frame (model-sized requests)
-        if (op.kind == OP_HEAD && !(e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR)) ext_out += (double)op.head.lv[op.level].hw * (4 + e->nc) * 4.0;
+        if (op.kind == OP_HEAD && !(e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR)) ext_out += (double)e->tail.args.lv[op.level].hw * (4 + e->nc) * 4.0;
         io.clear(); op_reads(e, op, &io);
         for (const IoView& v : io) {
             int cext = 0;
