@@ -20,6 +20,8 @@
  *                                                                  onnx_engine.cpp:223-261, 315-398
  *   zly_detect_device          same path with frames already resident in HBM (no reference
  *                              counterpart; used by bench.py and the multi-GPU sharding)
+ *   zly_*_view                 the same entry points on a region of a larger, possibly pitched buffer (zly_frame_view below); the reference's
+ *                              client cuts its region of interest out on the CPU before it sends it   src/client/screen_capture.cpp:470-538
  *   zly_preprocess             OnnxInferenceEngine::preProcess     onnx_engine.cpp:649-700
  *   zly_forward / zly_head_tensor   Ort::Session::Run "images" -> "output0"
  *                                                                  onnx_engine.cpp:560-586
@@ -101,7 +103,8 @@ extern "C" {
  * stage keeps its model-sized input, and the postProcess stage keeps the stretch mapping (cx / img_w) on every engine. */
 #define ZLY_LETTERBOX_MAX_DIM 16384
 
-/* Pixel formats of a request frame (the *_fmt entry points; the others take ZLY_PIX_BGR).  Planes are tight: no row pitch, no padding.
+/* Pixel formats of a request frame (the *_fmt entry points; the others take ZLY_PIX_BGR).  Planes are tight: no row pitch, no padding
+ * (pitched surfaces and regions of a larger buffer go through a zly_frame_view and the *_view entry points, below).
  *   ZLY_PIX_BGR          packed B,G,R, 3 bytes per pixel: nbytes = w*h*3
  *   ZLY_PIX_NV12_*       Y plane [h][w], then ONE plane of interleaved U,V pairs [h/2][w/2][2]: nbytes = w*h*3/2
  *   ZLY_PIX_I420_*       Y plane [h][w], U plane [h/2][w/2], V plane [h/2][w/2]:            nbytes = w*h*3/2
@@ -123,6 +126,28 @@ extern "C" {
 #define ZLY_PIX_I420_BT601   2
 #define ZLY_PIX_NV12_BT709   3
 #define ZLY_PIX_I420_BT709   4
+
+/* A frame view: where a request's samples lie inside a larger buffer -- a decoder or capture surface with a row pitch, a region of interest of
+ * one, a tile.  Plane offsets and line sizes as usual, with offsets from the buffer's base instead of pointers, so that one view serves host and
+ * device memory alike.
+ *   Planes.  BGR uses plane 0; NV12 0 = Y, 1 = interleaved UV; I420 0 = Y, 1 = U, 2 = V.  Entries of planes a format does not have are ignored.
+ *   Rows of plane p, with cw = w/2, ch = h/2:    BGR: h rows of 3w bytes;  Y: h rows of w;  NV12 UV: ch rows of 2cw;  I420 U, V: ch rows of cw.
+ *   The extent of a plane is (rows-1)*pitch + row_bytes.
+ *   A view is valid when fmt is known; w, h >= 1 (YUV: even and >= 2); every used pitch[p] >= its row bytes; every used plane's extent is < 2^31.
+ *   There is no alignment requirement, no negative pitch and no overlap check.
+ * THE RULE: a view gives, bit for bit, what the tight frame made of its samples gives through the _fmt entry point of the same name -- same
+ * engine, same batch size and composition, stretch or letterbox.  w, h of the view are the REQUEST's size for the resize map, the letterbox geometry
+ * and the box normalisation: boxes come back as fractions of the region (INTEGRATION.md section 3 has the one-line map to surface coordinates).
+ * Bytes of the buffer outside the region never influence a result; the engine may read those that lie inside a plane's extent (row padding,
+ * neighbouring columns), and never reads a byte at or beyond off[p] + extent. */
+typedef struct zly_frame_view {
+    int32_t  fmt;        /* ZLY_PIX_* */
+    int32_t  w, h;       /* size of the viewed region in pixels = the REQUEST's size */
+    int32_t  pad_;
+    uint64_t off[3];     /* byte offset from the buffer base of the region's first sample in plane p */
+    int32_t  pitch[3];   /* bytes from one row of plane p to the next */
+    int32_t  pad2_;
+} zly_frame_view;
 
 typedef struct zly_engine zly_engine;
 
@@ -199,6 +224,18 @@ const char* zly_version(void);
  * dimensions (w or h < 1; for YUV: odd, or < 2).  Host only: needs no engine and no GPU. */
 size_t  zly_frame_bytes(int32_t fmt, int32_t w, int32_t h);
 
+/* Frame views, host only (no engine, no GPU).
+ * zly_view_bytes: the smallest buffer size that holds the view -- the maximum over its used planes of off[p] + extent; 0 for an invalid view.
+ * zly_view_tight: the view of a tight frame as defined above (its zly_view_bytes equals zly_frame_bytes); ZLY_ERR_INVALID_ARGUMENT for an unknown
+ *   format, invalid dimensions or a null output.
+ * zly_view_crop: the view of the sub-rectangle (x0, y0, w, h) of a view.  Pitches stay; the offset advances by y0*pitch0 + x0*bpp in plane 0
+ *   (bpp = 3 for BGR, 1 for Y), by (y0/2)*pitch + (x0/2)*2 in the NV12 UV plane and by (y0/2)*pitch + x0/2 in the I420 chroma planes.
+ *   ZLY_ERR_INVALID_ARGUMENT when the surface is invalid, the rectangle is not inside it, or -- YUV -- any of x0, y0, w, h is odd.  Crops compose
+ *   (out may be the surface itself). */
+size_t  zly_view_bytes(const zly_frame_view* v);
+int32_t zly_view_tight(int32_t fmt, int32_t w, int32_t h, zly_frame_view* out);
+int32_t zly_view_crop(const zly_frame_view* surface, int32_t x0, int32_t y0, int32_t w, int32_t h, zly_frame_view* out);
+
 /* The letterbox geometry of a w x h request in a model_w x model_h model (ZLY_FLAG_LETTERBOX, "Geometry" above): content size nw x nh and its
  * offset pad_x, pad_y inside the model tensor -- what an integrator needs to map anything else (a crosshair, a mask) between frame and model
  * space.  ZLY_OK, or ZLY_ERR_INVALID_ARGUMENT for a non-positive size or a null output.  Host only: needs no engine and no GPU. */
@@ -223,6 +260,14 @@ int32_t zly_detect_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t 
                        zly_det* out, int32_t cap, int32_t* n_out);
 int32_t zly_detect_batch_fmt(zly_engine* e, int32_t n, const int32_t* fmt, const uint8_t* const* frames, const size_t* nbytes,
                              const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out);
+
+/* The same on frame views: base / buf_bytes are the caller's whole buffer (one per frame for the batch call, with one view each).  An unknown
+ * format fails with ZLY_ERR_INVALID_ARGUMENT; an otherwise invalid view, or one with zly_view_bytes above buf_bytes, with ZLY_ERR_INVALID_INPUT.
+ * Letterbox engines apply ZLY_LETTERBOX_MAX_DIM to the view's w, h.  The one copy into pinned staging that the engine makes anyway takes the
+ * region's rows only: PCIe and staging are charged for the region, not the surface. */
+int32_t zly_detect_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, zly_det* out, int32_t cap, int32_t* n_out);
+int32_t zly_detect_batch_view(zly_engine* e, int32_t n, const uint8_t* const* base, const size_t* buf_bytes, const zly_frame_view* v,
+                              zly_det* out, int32_t cap, int32_t* n_out);
 
 /* --- asynchronous, pipelined host-to-host path ------------------------------------------------------
  * The throughput path of a server: many host threads hand over frames, the engine batches them and overlaps the PCIe
@@ -249,6 +294,9 @@ int32_t zly_submit_try(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t
  * formats.  A slot's capacity is in bytes (ZLY_STAGE_MB), so more YUV frames than BGR ones fit one. */
 int32_t zly_submit_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket);
 int32_t zly_submit_try_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket);
+/* On a frame view (errors as zly_detect_view: no ticket, nothing copied).  The region's rows are copied into a tight frame of the ring. */
+int32_t zly_submit_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, uint64_t* ticket);
+int32_t zly_submit_try_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, uint64_t* ticket);
 int32_t zly_poll(zly_engine* e, uint64_t ticket);
 int32_t zly_wait(zly_engine* e, uint64_t ticket, zly_det* out, int32_t cap, int32_t* n_out);
 
@@ -262,6 +310,10 @@ int32_t zly_detect_device(zly_engine* e, int32_t n, const void* d_frames, int32_
 /* The same for n frames of one format fmt (ZLY_PIX_*), contiguous in device memory zly_frame_bytes(fmt, w, h) apart (decoder output in HBM). */
 int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void* d_frames, int32_t w, int32_t h,
                               void* d_slabs, uint32_t frame_tag0, void* stream);
+/* n frame views (a HOST array of n) of ONE device buffer d_base of buf_bytes: each frame has its own size, format, pitches and offsets, and several
+ * views may lie in one surface -- tiling a large frame is one call and no copy.  The front kernel fetches through the views: nothing is staged. */
+int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v,
+                               void* d_slabs, uint32_t frame_tag0, void* stream);
 size_t  zly_slab_bytes(const zly_engine* e);
 int32_t zly_read_slabs(zly_engine* e, int32_t n, void* host_slabs);   /* syncs the engine stream */
 int32_t zly_sync(zly_engine* e);
@@ -274,6 +326,8 @@ int32_t zly_join(zly_engine* e, void* stream, int32_t lag);
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw);
 int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, float* out_nchw);
+/* preProcess of a frame view: the buffer's first zly_view_bytes bytes are uploaded as they are and the kernel fetches through the view. */
+int32_t zly_preprocess_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, float* out_nchw);
 /* Session::Run: images is host fp32 [n][3][model_h][model_w] (rounded to the engine dtype on
  * upload); head_out is host fp32 [n][4+nc][N]. */
 int32_t zly_forward(zly_engine* e, int32_t n, const float* images_nchw, float* head_out);

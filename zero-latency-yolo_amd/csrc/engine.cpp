@@ -185,6 +185,11 @@ struct zly_engine : Plan {
     bool desc_used[DESC_RING] = {};
     int desc_next = 0;
     std::vector<FrameDesc> desc_cache;
+    // a call on frame views (zly_*_view) uploads n ViewRec behind its n descriptors (zly_internal.h); a ring entry and d_desc hold both
+    static constexpr size_t DESC_SLOT = sizeof(FrameDesc) + sizeof(ViewRec);      // bytes per frame
+    std::vector<ViewRec> view_cache;
+    int last_desc_n = 0;              // frames of the upload d_desc holds
+    bool desc_cache_view = false;     // what d_desc holds came from a view call: a plain call and a view call never reuse each other's upload
     uint8_t* d_stage = nullptr;       // frame staging (host path)
     uint8_t* h_stage = nullptr;       // pinned
     size_t stage_bytes = 0;
@@ -196,6 +201,7 @@ struct zly_engine : Plan {
     Stem1Args stem1a{};
     bool ingest_active = false;       // set while the pipelined host path (zly_submit) enqueues: see run_path
     bool last_front = false;          // the most recent call launched the front kernel (zly_forward does not: model.0 is then in HBM)
+    bool front_view = false;          // the current call's frames are frame views: its front kernel is the VIEW instantiation (set by run_path)
     bool front_yuv = false;           // the current call's batch holds a YUV 4:2:0 frame: its front kernel is the YUV-capable instantiation (set by run_path)
     hipStream_t stream = nullptr;
     hipStream_t side[2] = {nullptr, nullptr};     // P3 / P4 Detect branches (forked from and joined to the main stream)
@@ -996,16 +1002,16 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
     case LK_NONE:
         return hipSuccess;
     case LK_PREPROCESS:
-        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front_yuv, L.lb);
+        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front_yuv, L.lb, e->front_view);
     case LK_STEM: {
         StemArgs st = e->stem;
         st.src = d_src; st.desc = e->d_desc;
-        return launch_stem_fused(st, n, s, e->front_yuv, L.lb);
+        return launch_stem_fused(st, n, s, e->front_yuv, L.lb, e->front_view);
     }
     case LK_STEM1: {
         Stem1Args st = e->stem1a;
         st.st.src = d_src; st.st.desc = e->d_desc;
-        return launch_stem_model1(st, n, s, e->front_yuv, L.lb);
+        return launch_stem_model1(st, n, s, e->front_yuv, L.lb, e->front_view);
     }
     case LK_CONV:
         return launch_conv(make_conv_args(e, op, n), L.conv, s);
@@ -1156,10 +1162,12 @@ static void harvest_timing(zly_engine* e)
 
 // nms_stream_out: the stream the call's NMS (its last kernel) was launched on -- `s`, or the engine's NMS stream when deferred
 // yuv: the batch holds at least one YUV 4:2:0 frame (d_desc says which): the front kernel runs its YUV-capable instantiation
+// view: the frames are frame views (d_desc holds their ViewRec too): the front kernel runs its VIEW instantiation
 static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s, bool with_pre, bool defer_nms = false,
-                    hipStream_t* nms_stream_out = nullptr, bool yuv = false)
+                    hipStream_t* nms_stream_out = nullptr, bool yuv = false, bool view = false)
 {
     e->front_yuv = with_pre && yuv;
+    e->front_view = with_pre && view;
     const size_t nops = e->ops.size();
     harvest_timing(e);
     const bool sample = with_pre && !e->t_pending && (e->sample_ctr++ % zly_engine::SAMPLE_EVERY) == 0;
@@ -1200,7 +1208,7 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
     // first call of any other batch size.  The pipelined host path (dispatcher threads, several per process) never captures: it replays
     // what exists -- a lone frame and a full batch, its two steady states -- and launches other partial batches eagerly with cached
     // kernel shapes: no capture storm over the 62 partial sizes, no capture while other engines run.
-    // No "YUV in batch" bit: the front kernel (preprocess / fused stem, the only kernel that reads pixels and hence the only one with a YUV
+    // No "YUV in batch" or "views" bit: the front kernel (preprocess / fused stem, the only kernel that reads pixels and hence the only one with a YUV
     // instantiation) is launched above, outside the captured range [first, nops - 1), so one graph serves BGR, YUV and mixed batches alike.
     const int key = (n * 2 + (fused ? 1 : 0)) * 2 + par;     // the captured Detect tail holds the candidate buffer's address
     auto git = e->graphs.find(key);
@@ -1256,11 +1264,18 @@ static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_ou
 }
 
 // fmt: per-frame ZLY_PIX_* (null = all BGR), packed into the top byte of src_off (zly_internal.h)
-static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, const size_t* offs, hipStream_t s, const int32_t* fmt = nullptr)
+// views: per-frame ViewRec of a call on frame views (null = tight frames), uploaded behind the n descriptors
+static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, const size_t* offs, hipStream_t s, const int32_t* fmt = nullptr,
+                    const ViewRec* views = nullptr)
 {
-    bool same = (int)e->desc_cache.size() >= n;
+    // what the device holds is reused only by a call of the same kind: a plain call's upload has no view records, and a view call's records
+    // belong to its own pitches and plane offsets even where src_off, w, h agree
+    bool same = (int)e->desc_cache.size() >= n && e->desc_cache_view == (views != nullptr);
     for (int i = 0; i < n && same; ++i)
         same = e->desc_cache[(size_t)i].w == w[i] && e->desc_cache[(size_t)i].h == h[i] && e->desc_cache[(size_t)i].src_off == desc_pack(offs[i], fmt ? fmt[i] : ZLY_PIX_BGR);
+    if (same && views) same = (int)e->view_cache.size() >= n && memcmp(e->view_cache.data(), views, sizeof(ViewRec) * (size_t)n) == 0;
+    // the view records lie at desc + n: a view call of another batch size finds them elsewhere
+    if (same && views) same = e->last_desc_n == n;
     if (same) return ZLY_OK;
     // frame sizes / offsets changed: next entry of the pinned ring, uploaded in stream order.  Calls on one engine are
     // stream-ordered by contract (they share every activation buffer), so the upload cannot overtake a kernel of the
@@ -1268,7 +1283,7 @@ static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, co
     const int r = e->desc_next;
     e->desc_next = (r + 1) % zly_engine::DESC_RING;
     if (e->desc_used[r]) HIP_TRY(hipEventSynchronize(e->ev_desc[r]), ZLY_ERR_INFERENCE);     // 8 uploads back: long complete
-    FrameDesc* hd = e->h_desc + (size_t)r * (size_t)e->cfg.max_batch;
+    FrameDesc* hd = reinterpret_cast<FrameDesc*>(reinterpret_cast<unsigned char*>(e->h_desc) + (size_t)r * (size_t)e->cfg.max_batch * zly_engine::DESC_SLOT);
     if ((int)e->desc_cache.size() < n) e->desc_cache.resize((size_t)n);
     for (int i = 0; i < n; ++i) {
         FrameDesc d; d.src_off = desc_pack(offs[i], fmt ? fmt[i] : ZLY_PIX_BGR); d.w = w[i]; d.h = h[i];
@@ -1276,7 +1291,15 @@ static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, co
         e->desc_cache[(size_t)i] = d;
     }
     for (size_t i = (size_t)n; i < e->desc_cache.size(); ++i) e->desc_cache[i].w = -1;
-    HIP_TRY(hipMemcpyAsync(e->d_desc, hd, sizeof(FrameDesc) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    size_t bytes = sizeof(FrameDesc) * (size_t)n;
+    if (views) {
+        memcpy(hd + n, views, sizeof(ViewRec) * (size_t)n);
+        e->view_cache.assign(views, views + n);
+        bytes += sizeof(ViewRec) * (size_t)n;
+    }
+    e->desc_cache_view = views != nullptr;
+    e->last_desc_n = n;
+    HIP_TRY(hipMemcpyAsync(e->d_desc, hd, bytes, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
     HIP_TRY(hipEventRecord(e->ev_desc[r], s), ZLY_ERR_INFERENCE);
     e->desc_used[r] = true;
     return ZLY_OK;
@@ -1337,6 +1360,73 @@ static int check_frame_mode(const zly_engine* e, int32_t w, int32_t h)
         return fail(ZLY_ERR_INVALID_INPUT, "letterbox mode takes frames of at most " + std::to_string(ZLY_LETTERBOX_MAX_DIM) + " pixels on a side, got " +
                                            std::to_string(w) + " x " + std::to_string(h));
     return ZLY_OK;
+}
+
+// ---- frame views (include/zly.h zly_frame_view) ----
+// planes of a w x h frame of format fmt: rows and bytes per row of each; 0 for an unknown format or invalid dimensions
+static int view_plane_shape(int32_t fmt, int32_t w, int32_t h, int64_t rows[3], int64_t row_bytes[3])
+{
+    if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
+    if (fmt == ZLY_PIX_BGR) { rows[0] = h; row_bytes[0] = 3 * (int64_t)w; return 1; }
+    if (w < 2 || h < 2 || ((w | h) & 1)) return 0;
+    rows[0] = h; row_bytes[0] = w;
+    if (fmt == ZLY_PIX_NV12_BT601 || fmt == ZLY_PIX_NV12_BT709) { rows[1] = h / 2; row_bytes[1] = w; return 2; }      // 2 * (w/2)
+    rows[1] = rows[2] = h / 2; row_bytes[1] = row_bytes[2] = w / 2;
+    return 3;
+}
+
+// include/zly.h's validity rule; *need = the smallest buffer that holds the view
+static bool view_valid(const zly_frame_view* v, size_t* need)
+{
+    int64_t rows[3], rb[3];
+    const int np = v ? view_plane_shape(v->fmt, v->w, v->h, rows, rb) : 0;
+    if (!np) return false;
+    uint64_t most = 0;
+    for (int p = 0; p < np; ++p) {
+        if ((int64_t)v->pitch[p] < rb[p]) return false;
+        const uint64_t ext = (uint64_t)(rows[p] - 1) * (uint64_t)v->pitch[p] + (uint64_t)rb[p];
+        if (ext >= (1ull << 31)) return false;
+        if (v->off[p] > UINT64_MAX - ext) return false;
+        most = std::max<uint64_t>(most, v->off[p] + ext);
+    }
+    if (most > (uint64_t)SIZE_MAX) return false;
+    *need = (size_t)most;
+    return true;
+}
+
+// the request checks of every entry point that takes a view: an unknown format is an argument error; an otherwise invalid view, or one that does
+// not fit the caller's buffer, is ZLY_ERR_INVALID_INPUT (as a wrong byte count is); letterbox engines bound the view's size
+static int check_view(const zly_engine* e, const void* base, size_t buf_bytes, const zly_frame_view* v)
+{
+    if (!v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null view");
+    if (!fmt_known(v->fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(v->fmt));
+    size_t need = 0;
+    if (!view_valid(v, &need)) return fail(ZLY_ERR_INVALID_INPUT, "invalid frame view (size " + std::to_string(v->w) + " x " + std::to_string(v->h) +
+                                                                  ": YUV 4:2:0 needs even width and height >= 2, every pitch at least its row's bytes, every plane below 2 GiB)");
+    if (!base || need > buf_bytes) return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: the view needs " + std::to_string(need) + " bytes, got " + std::to_string(buf_bytes));
+    return check_frame_mode(e, v->w, v->h);
+}
+
+// the region's rows, plane by plane, as the tight frame of zly_frame_bytes(fmt, w, h) at dst: the one host copy of a view request
+static void copy_view_tight(uint8_t* dst, const uint8_t* base, const zly_frame_view* v)
+{
+    int64_t rows[3], rb[3];
+    const int np = view_plane_shape(v->fmt, v->w, v->h, rows, rb);
+    for (int p = 0; p < np; ++p) {
+        const uint8_t* q = base + v->off[p];
+        if ((int64_t)v->pitch[p] == rb[p]) { memcpy(dst, q, (size_t)(rows[p] * rb[p])); dst += rows[p] * rb[p]; continue; }
+        for (int64_t r = 0; r < rows[p]; ++r, q += v->pitch[p], dst += rb[p]) memcpy(dst, q, (size_t)rb[p]);
+    }
+}
+
+static ViewRec view_rec(const zly_frame_view* v)
+{
+    int64_t rows[3], rb[3];
+    const int np = view_plane_shape(v->fmt, v->w, v->h, rows, rb);
+    ViewRec r{};
+    r.off1 = np > 1 ? v->off[1] : 0; r.off2 = np > 2 ? v->off[2] : 0;
+    r.pitch0 = v->pitch[0]; r.pitch1 = np > 1 ? v->pitch[1] : 0; r.pitch2 = np > 2 ? v->pitch[2] : 0;
+    return r;
 }
 
 // Returns the first HIP error met while draining / releasing (the engine is gone either way).
@@ -1624,11 +1714,19 @@ static void ingest_free(zly_engine* e, Ingest* g)
     delete g;                                          // the copy streams are shared by the process and stay
 }
 
+// view: the request is a frame view of the buffer bgr[0 .. nbytes) (zly_submit_view): the region's rows are copied into a tight frame of the ring, and
+// from there on the request is that frame
 static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket, bool nonblock = false,
-                         int32_t fmt = ZLY_PIX_BGR)
+                         int32_t fmt = ZLY_PIX_BGR, const zly_frame_view* view = nullptr)
 {
-    int rcv = check_frame(fmt, bgr, nbytes, w, h);
-    if (rcv == ZLY_OK) rcv = check_frame_mode(e, w, h);
+    int rcv;
+    if (view) {
+        rcv = check_view(e, bgr, nbytes, view);
+        if (rcv == ZLY_OK) { fmt = view->fmt; w = view->w; h = view->h; nbytes = zly_frame_bytes(fmt, w, h); }
+    } else {
+        rcv = check_frame(fmt, bgr, nbytes, w, h);
+        if (rcv == ZLY_OK) rcv = check_frame_mode(e, w, h);
+    }
     if (rcv != ZLY_OK) {
         with_stats(e, [](zly_stats& st) { st.inference_errors++; });
         return rcv;
@@ -1670,7 +1768,8 @@ static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32
             break;
         }
     }
-    memcpy(sl->h_stage + off, bgr, nbytes);               // the one host copy of the request, on the caller's thread
+    if (view) copy_view_tight(sl->h_stage + off, bgr, view);
+    else memcpy(sl->h_stage + off, bgr, nbytes);          // the one host copy of the request, on the caller's thread
     {
         std::lock_guard<std::mutex> lk(g->mu);
         sl->n_committed++;
@@ -1861,8 +1960,8 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
         ok = ok && hipMalloc((void**)&e->d_scratch, B * N * sizeof(Cand)) == hipSuccess;
         ok = ok && hipMalloc((void**)&e->d_count, B * sizeof(int)) == hipSuccess;
         ok = ok && hipMalloc((void**)&e->d_slabs, B * slab_bytes_of(e)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&e->d_desc, B * sizeof(FrameDesc)) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)&e->h_desc, zly_engine::DESC_RING * B * sizeof(FrameDesc), hipHostMallocDefault) == hipSuccess;
+        ok = ok && hipMalloc((void**)&e->d_desc, B * zly_engine::DESC_SLOT) == hipSuccess;
+        ok = ok && hipHostMalloc((void**)&e->h_desc, zly_engine::DESC_RING * B * zly_engine::DESC_SLOT, hipHostMallocDefault) == hipSuccess;
         for (int i = 0; i < zly_engine::DESC_RING && ok; ++i) ok = hipEventCreateWithFlags(&e->ev_desc[i], hipEventDisableTiming) == hipSuccess;
         for (int i = 0; i < 4 && ok; ++i) ok = hipEventCreate(&e->ev_t[i]) == hipSuccess;
         for (int i = 0; i < 2 && ok; ++i) ok = hipEventCreateWithFlags(&e->ev_call[i], hipEventDisableTiming) == hipSuccess;
@@ -1918,25 +2017,37 @@ int32_t zly_destroy(zly_engine* e)
 }
 
 // fmt: per-frame ZLY_PIX_* (null = all BGR)
+// views: per-frame views of the buffers bgr[i][0 .. nbytes[i]) (zly_detect[_batch]_view; w, h, fmt are then the views'): the staging copy takes the
+// regions' rows only, as tight frames, and everything behind it is the path of those frames
 static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bgr, const size_t* nbytes,
-                              const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out, const int32_t* fmt = nullptr)
+                              const int32_t* w, const int32_t* h, zly_det* out, int32_t cap, int32_t* n_out, const int32_t* fmt = nullptr,
+                              const zly_frame_view* views = nullptr)
 {
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     std::vector<size_t> offs((size_t)n);
+    std::vector<int32_t> vw, vh, vf;
+    if (views) { vw.resize((size_t)n); vh.resize((size_t)n); vf.resize((size_t)n); }
     size_t total = 0;
     bool yuv = false;
     for (int i = 0; i < n; ++i) {
-        const int32_t fi = fmt ? fmt[i] : ZLY_PIX_BGR;
-        int rcv = check_frame(fi, bgr[i], nbytes[i], w[i], h[i]);
-        if (rcv == ZLY_OK) rcv = check_frame_mode(e, w[i], h[i]);
+        int rcv;
+        if (views) {
+            rcv = check_view(e, bgr[i], nbytes[i], &views[i]);
+            vw[(size_t)i] = views[i].w; vh[(size_t)i] = views[i].h; vf[(size_t)i] = views[i].fmt;
+        } else {
+            rcv = check_frame(fmt ? fmt[i] : ZLY_PIX_BGR, bgr[i], nbytes[i], w[i], h[i]);
+            if (rcv == ZLY_OK) rcv = check_frame_mode(e, w[i], h[i]);
+        }
         if (rcv != ZLY_OK) {
             with_stats(e, [](zly_stats& st) { st.inference_errors++; });
             return rcv;
         }
+        const int32_t fi = views ? views[i].fmt : fmt ? fmt[i] : ZLY_PIX_BGR;
         yuv = yuv || fi != ZLY_PIX_BGR;
         offs[(size_t)i] = total;
-        total += (nbytes[i] + 15) / 16 * 16;
+        total += ((views ? zly_frame_bytes(fi, views[i].w, views[i].h) : nbytes[i]) + 15) / 16 * 16;
     }
+    if (views) { w = vw.data(); h = vh.data(); fmt = vf.data(); }
     int rc = ZLY_OK;
     if (total > e->stage_bytes) {                                        // growth beyond what zly_create staged (frames larger than the model input): an allocation, alone in the process
         ExclusiveGate x;
@@ -1945,7 +2056,10 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     }
     // waiting for the device and the host copy are not enqueue sections: no gate is held across them (other engines keep enqueuing)
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
-    for (int i = 0; i < n; ++i) memcpy(e->h_stage + offs[(size_t)i], bgr[i], nbytes[i]);
+    for (int i = 0; i < n; ++i) {
+        if (views) copy_view_tight(e->h_stage + offs[(size_t)i], bgr[i], &views[i]);
+        else memcpy(e->h_stage + offs[(size_t)i], bgr[i], nbytes[i]);
+    }
     SharedGate gl;
     HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, total, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
     rc = set_desc(e, n, w, h, offs.data(), e->stream, fmt);
@@ -1977,6 +2091,54 @@ size_t zly_frame_bytes(int32_t fmt, int32_t w, int32_t h)
     if (fmt == ZLY_PIX_BGR) return (size_t)w * (size_t)h * 3u;
     if (w < 2 || h < 2 || (w & 1) || (h & 1)) return 0;                // 4:2:0: one chroma sample per 2 x 2 block
     return (size_t)w * (size_t)h * 3u / 2u;
+}
+
+size_t zly_view_bytes(const zly_frame_view* v)
+{
+    size_t need = 0;
+    return view_valid(v, &need) ? need : 0;
+}
+
+int32_t zly_view_tight(int32_t fmt, int32_t w, int32_t h, zly_frame_view* out)
+{
+    int64_t rows[3], rb[3];
+    if (!out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    const int np = view_plane_shape(fmt, w, h, rows, rb);
+    if (!np) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_tight: unknown format or invalid size");
+    zly_frame_view v{};
+    v.fmt = fmt; v.w = w; v.h = h;
+    uint64_t off = 0;
+    for (int p = 0; p < np; ++p) {                       // the planes follow each other without padding, rows without pitch
+        v.off[p] = off; v.pitch[p] = (int32_t)rb[p];
+        off += (uint64_t)rows[p] * (uint64_t)rb[p];
+    }
+    *out = v;
+    return ZLY_OK;
+}
+
+int32_t zly_view_crop(const zly_frame_view* surface, int32_t x0, int32_t y0, int32_t w, int32_t h, zly_frame_view* out)
+{
+    if (!surface || !out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    size_t need = 0;
+    if (!view_valid(surface, &need)) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: invalid surface view");
+    if (x0 < 0 || y0 < 0 || w < 1 || h < 1 || (int64_t)x0 + w > surface->w || (int64_t)y0 + h > surface->h)
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: the rectangle is not inside the surface");
+    zly_frame_view v = *surface;                         // (out may be the surface itself: crops compose)
+    v.w = w; v.h = h;
+    if (v.fmt == ZLY_PIX_BGR) {
+        v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0 * 3u;
+    } else {
+        if ((x0 | y0 | w | h) & 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: a YUV 4:2:0 rectangle needs even x0, y0, w, h");
+        v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0;
+        if (v.fmt == ZLY_PIX_NV12_BT601 || v.fmt == ZLY_PIX_NV12_BT709) {
+            v.off[1] += (uint64_t)(y0 / 2) * (uint64_t)v.pitch[1] + (uint64_t)(x0 / 2) * 2u;
+        } else {
+            v.off[1] += (uint64_t)(y0 / 2) * (uint64_t)v.pitch[1] + (uint64_t)(x0 / 2);
+            v.off[2] += (uint64_t)(y0 / 2) * (uint64_t)v.pitch[2] + (uint64_t)(x0 / 2);
+        }
+    }
+    *out = v;
+    return ZLY_OK;
 }
 
 int32_t zly_letterbox_geometry(int32_t w, int32_t h, int32_t model_w, int32_t model_h, int32_t* nw, int32_t* nh, int32_t* pad_x, int32_t* pad_y)
@@ -2028,6 +2190,43 @@ int32_t zly_detect_batch_fmt(zly_engine* e, int32_t n, const int32_t* fmt, const
     if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
     std::lock_guard<std::mutex> lk(e->mu);
     return detect_host_locked(e, n, frames, nbytes, w, h, out, cap, n_out, fmt);
+}
+
+int32_t zly_detect_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, zly_det* out, int32_t cap, int32_t* n_out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!v || !out || !n_out || cap < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint8_t* ptrs[1] = {base};
+    int rc = detect_host_locked(e, 1, ptrs, &buf_bytes, nullptr, nullptr, out, cap, n_out, nullptr, v);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    with_stats(e, [&](zly_stats& st) { st.last_detect_ms = ms; });
+    return rc;
+}
+
+int32_t zly_detect_batch_view(zly_engine* e, int32_t n, const uint8_t* const* base, const size_t* buf_bytes, const zly_frame_view* v,
+                              zly_det* out, int32_t cap, int32_t* n_out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!base || !buf_bytes || !v || !out || !n_out || cap < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    return detect_host_locked(e, n, base, buf_bytes, nullptr, nullptr, out, cap, n_out, nullptr, v);
+}
+
+int32_t zly_submit_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, uint64_t* ticket)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!ticket || !v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    return ingest_submit(e, base, buf_bytes, 0, 0, ticket, false, ZLY_PIX_BGR, v);
+}
+
+int32_t zly_submit_try_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, uint64_t* ticket)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!ticket || !v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    return ingest_submit(e, base, buf_bytes, 0, 0, ticket, true, ZLY_PIX_BGR, v);
 }
 
 int32_t zly_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket)
@@ -2091,6 +2290,36 @@ int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void*
     if (rc != ZLY_OK) return rc;
     hipStream_t ns = s;
     rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, fmt != ZLY_PIX_BGR);
+    if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
+    HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
+    e->call_seq++;
+    with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
+    return ZLY_OK;
+}
+
+int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, void* d_slabs, uint32_t frame_tag0, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null views");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    std::vector<int32_t> ws((size_t)n), hs((size_t)n), fs((size_t)n);
+    std::vector<size_t> offs((size_t)n);
+    std::vector<ViewRec> recs((size_t)n);
+    bool yuv = false;
+    for (int i = 0; i < n; ++i) {
+        if (int rcv = check_view(e, d_base, buf_bytes, &v[i])) return rcv;
+        ws[(size_t)i] = v[i].w; hs[(size_t)i] = v[i].h; fs[(size_t)i] = v[i].fmt; offs[(size_t)i] = (size_t)v[i].off[0];
+        recs[(size_t)i] = view_rec(&v[i]);
+        yuv = yuv || v[i].fmt != ZLY_PIX_BGR;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data(), recs.data());
+    if (rc != ZLY_OK) return rc;
+    hipStream_t ns = s;
+    rc = run_path(e, n, (const uint8_t*)d_base, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, yuv, true);
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
     e->call_seq++;
@@ -2169,6 +2398,34 @@ int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_
     if (rc != ZLY_OK) return rc;
     HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, fmt != ZLY_PIX_BGR,
                               (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_preprocess_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, float* out_nchw)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!out_nchw) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    if (int rcv = check_view(e, base, buf_bytes, v)) return rcv;
+    const size_t nbytes = zly_view_bytes(v);             // the buffer's first bytes as they are: the kernel fetches through the view
+    std::lock_guard<std::mutex> lk(e->mu);
+    ExclusiveGate gl;                                    // parity / debug entry point: allocations and copies, alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    int rc = ensure_stage(e, nbytes);
+    if (rc != ZLY_OK) return rc;
+    const size_t elems = (size_t)3 * e->cfg.model_w * e->cfg.model_h;
+    rc = ensure_scratch_f32(e, elems);
+    if (rc != ZLY_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    memcpy(e->h_stage, base, nbytes);
+    HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, nbytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
+    const size_t off0 = (size_t)v->off[0];
+    const ViewRec rec = view_rec(v);
+    rc = set_desc(e, 1, &v->w, &v->h, &off0, e->stream, &v->fmt, &rec);
+    if (rc != ZLY_OK) return rc;
+    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, true,
+                              (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0, true), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
@@ -2461,7 +2718,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
     std::vector<size_t> offs((size_t)n);
     for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * (size_t)w * (size_t)h * 3u;
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream);
-    e->front_yuv = false;                                // BGR frames: the front kernels' BGR instantiations
+    e->front_yuv = false; e->front_view = false;         // tight BGR frames: the front kernels' BGR instantiations
     if (rc != ZLY_OK) return rc;
     const size_t nops = e->ops.size();
     const std::vector<Launch>& tab = resolve_launches(e, n);

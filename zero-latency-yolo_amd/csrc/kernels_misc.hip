@@ -25,7 +25,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // LB: the instantiation of a letterbox engine (ZLY_FLAG_LETTERBOX, letterbox_device.h): the fetch is the padding test + the bilinear blend of four
 // taps instead of the nearest-neighbour pick; the bytes it yields take the same path.  Compiled in kernels_lb.hip (ZLY_LB_TU), not here.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool YUV, bool LB = false>
+// VIEW: the instantiation for frame views (zly_frame_view: row pitches, plane offsets; planes_device.h); always YUV-capable.  Compiled in
+// kernels_view.hip (ZLY_VIEW_TU), not here.
+template <typename T, bool YUV, bool LB = false, bool VIEW = false>
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
                                                          T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
 {
@@ -38,22 +40,23 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     const float scale_h = (float)d.h / (float)th;
     int sy = (int)((float)y * scale_h); if (sy > d.h - 1) sy = d.h - 1;
     int sx = (int)((float)x * scale_w); if (sx > d.w - 1) sx = d.w - 1;
+    const Planes<VIEW> pl = frame_planes<VIEW>(src, src + (YUV ? desc_off(d.src_off) : d.src_off), desc, (int)gridDim.y, f, d, YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR);
     float b, g, r;
     if constexpr (LB) {
         const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
         const LbFrame lf = lb_frame(d.w, d.h, tw, th);
         LbTaps taps;
-        lb_issue<YUV>(src + (YUV ? desc_off(d.src_off) : d.src_off), fmt, lf, x, y, taps);
+        lb_issue<YUV>(pl, fmt, lf, x, y, taps);
         const unsigned int px = lb_blend<YUV>(taps, fmt);
         b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)((px >> 16) & 0xffu) / 255.0f;
     } else
     if (YUV && pix_is_yuv(desc_fmt(d.src_off))) {
         unsigned int yv, uv;
-        yuv_issue(src + desc_off(d.src_off), desc_fmt(d.src_off), d.w, d.h, sx, sy, yv, uv);
+        yuv_issue(pl, desc_fmt(d.src_off), sx, sy, yv, uv);
         const unsigned int px = yuv_bgr_word(yv, uv, desc_fmt(d.src_off));
         b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)(px >> 16) / 255.0f;
     } else {
-        const uint8_t* px = src + (YUV ? desc_off(d.src_off) : d.src_off) + ((size_t)sy * d.w + sx) * 3;
+        const uint8_t* px = pl.f + pl.bgr_off(sx, sy);
         b = (float)px[0] / 255.0f; g = (float)px[1] / 255.0f; r = (float)px[2] / 255.0f;
     }
     if (out8) {
@@ -69,18 +72,29 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
 
 typedef void (*preprocess_bf16_fn)(const uint8_t*, const FrameDesc*, bf16_t*, float*, int, int);
 typedef void (*preprocess_f32_fn)(const uint8_t*, const FrameDesc*, float*, float*, int, int);
-#ifdef ZLY_LB_TU
+#if defined(ZLY_VIEW_TU)
+// the frame-view instantiations, for the launcher in kernels_misc.hip
+preprocess_bf16_fn preprocess_view_bf16_kernel(bool lb) { return lb ? preprocess_kernel<bf16_t, true, true, true> : preprocess_kernel<bf16_t, true, false, true>; }
+preprocess_f32_fn  preprocess_view_f32_kernel(bool lb) { return lb ? preprocess_kernel<float, true, true, true> : preprocess_kernel<float, true, false, true>; }
+#elif defined(ZLY_LB_TU)
 // the letterbox instantiations, for the launcher in kernels_misc.hip
 preprocess_bf16_fn preprocess_lb_bf16_kernel(bool yuv) { return yuv ? preprocess_kernel<bf16_t, true, true> : preprocess_kernel<bf16_t, false, true>; }
 preprocess_f32_fn  preprocess_lb_f32_kernel(bool yuv) { return yuv ? preprocess_kernel<float, true, true> : preprocess_kernel<float, false, true>; }
 #else
 preprocess_bf16_fn preprocess_lb_bf16_kernel(bool yuv);      // kernels_lb.hip
 preprocess_f32_fn  preprocess_lb_f32_kernel(bool yuv);
+preprocess_bf16_fn preprocess_view_bf16_kernel(bool lb);     // kernels_view.hip
+preprocess_f32_fn  preprocess_view_f32_kernel(bool lb);
 
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv, bool lb)
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv, bool lb, bool view)
 {
     dim3 grid((tw * th + 255) / 256, n);
+    if (view) {
+        if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(preprocess_view_bf16_kernel(lb), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
+        else hipLaunchKernelGGL(preprocess_view_f32_kernel(lb), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
+        return hipGetLastError();
+    }
     if (lb) {
         if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(preprocess_lb_bf16_kernel(yuv), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
         else hipLaunchKernelGGL(preprocess_lb_f32_kernel(yuv), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
@@ -95,9 +109,9 @@ hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* des
     }
     return hipGetLastError();
 }
-#endif  // !ZLY_LB_TU
+#endif  // !ZLY_LB_TU && !ZLY_VIEW_TU
 
-#ifndef ZLY_LB_TU
+#if !defined(ZLY_LB_TU) && !defined(ZLY_VIEW_TU)
 // fp32 planar [n][3][th][tw] (the "images" tensor of onnx_engine.cpp:560-569) -> engine NHWC8
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const float* __restrict__ in, T* __restrict__ out8, int hw)
@@ -324,6 +338,6 @@ hipError_t launch_tap_to_nchw(int dtype, const void* in, int cs, int co, int C, 
     return hipGetLastError();
 }
 
-#endif  // !ZLY_LB_TU
+#endif  // !ZLY_LB_TU && !ZLY_VIEW_TU
 
 }  // namespace zly

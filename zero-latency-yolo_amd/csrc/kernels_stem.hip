@@ -18,12 +18,13 @@
 // The YUV = true instantiations of the front kernels (batches with YUV 4:2:0 frames) are compiled in a translation unit of their own,
 // kernels_stem_yuv.hip, which includes this file with ZLY_STEM_YUV_TU defined: instantiated here, next to the BGR ones, they changed the
 // register allocation of the BGR kernels (same resources, different code), and the BGR kernels are to stay exactly as they were.
-// The LB = true instantiations (letterbox engines, ZLY_FLAG_LETTERBOX) live in kernels_lb.hip for the same reason (ZLY_STEM_LB_TU).
+// The LB = true instantiations (letterbox engines, ZLY_FLAG_LETTERBOX) live in kernels_lb.hip for the same reason (ZLY_STEM_LB_TU), and the
+// VIEW = true ones (frame views: pitched surfaces and regions of interest, zly_frame_view) in kernels_view.hip (ZLY_STEM_VIEW_TU).
 #include "zly_internal.h"
 #include "conv_device.h"
 #include "yuv_device.h"
 #include "letterbox_device.h"
-#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_LB_TU)
+#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_VIEW_TU)
 #define ZLY_STEM_SIDE_TU 1                 // a translation unit of instantiations only: no launchers, no tables
 #endif
 #include <stdlib.h>
@@ -58,7 +59,9 @@ __device__ __forceinline__ FrameDesc load_desc(const FrameDesc* p)
 // the batch's BGR frames as well.  Batches of BGR frames only run YUV = false, the kernel as it was.
 // LB: the instantiation of a letterbox engine (letterbox_device.h): a frame that is not model-sized BGR is fetched as padding / a four-tap bilinear
 // blend instead of the nearest-neighbour pick.  Every other engine runs LB = false, the kernel as it was.
-template <int NT, bool YUV, bool LB = false>
+// VIEW: the instantiation for calls whose frames are frame views: every fetch takes its row pitch and plane bases from the frame's ViewRec
+// (planes_device.h) instead of deriving them from w, h.  Always with YUV = true; every other call runs VIEW = false, the kernel as it was.
+template <int NT, bool YUV, bool LB = false, bool VIEW = false>
 __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
 {
     __shared__ __attribute__((aligned(16))) bf16x4 patch[STEM_PH * STEM_PW];
@@ -84,7 +87,8 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
     const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
     const uint8_t* src = a.src + (YUV ? desc_off(d.src_off) : d.src_off);
     const bool same = (d.w == a.tw) & (d.h == a.th) & !pix_is_yuv(fmt);
-    const size_t frame_bytes = (size_t)d.w * d.h * 3;
+    const Planes<VIEW> pl = frame_planes<VIEW>(a.src, src, a.desc, (int)gridDim.y, f, d, fmt);
+    const auto frame_bytes = pl.bgr_end();                   // bound of the wide loads: the end of plane 0
     LbFrame lf;
     if constexpr (LB) lf = lb_frame(d.w, d.h, a.tw, a.th);
     for (int u = tid; u < STEM_PH * STEM_PW; u += 256) {
@@ -101,15 +105,15 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
             if (LB && !same) {         // (a model-sized BGR frame: the letterbox map is the identity too)
                 if constexpr (LB) {
                     LbTaps taps;
-                    lb_issue<YUV>(src, fmt, lf, ix, iy, taps);
+                    lb_issue<YUV>(pl, fmt, lf, ix, iy, taps);
                     px4 = lb_blend<YUV>(taps, fmt);
                 }
             } else if (YUV && pix_is_yuv(fmt)) {      // wave-uniform: one format per frame
                 unsigned int yv, uv;
-                yuv_issue(src, fmt, d.w, d.h, sx, sy, yv, uv);
+                yuv_issue(pl, fmt, sx, sy, yv, uv);
                 px4 = yuv_bgr_word(yv, uv, fmt);
             } else {
-            const size_t off = ((size_t)sy * d.w + sx) * 3;
+            const auto off = pl.bgr_off(sx, sy);
             const uint8_t* q = src + off;
             // one (unaligned) 4-byte load instead of three byte loads -- this kernel is bound by instruction issue; the very
             // last pixel of a frame would read one byte past it and keeps the byte loads
@@ -194,18 +198,29 @@ stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv)
     return nt == 2 ? stem_fused_kernel<2, false, true> : stem_fused_kernel<1, false, true>;
 }
 #endif
+#if defined(ZLY_STEM_VIEW_TU) || defined(ZLY_STEM_DIAG)
+// the frame-view instantiations (always YUV-capable: they serve BGR views too)
+stem_fused_fn stem_fused_view_kernel(int nt, bool lb)
+{
+    if (lb) return nt == 2 ? stem_fused_kernel<2, true, true, true> : stem_fused_kernel<1, true, true, true>;
+    return nt == 2 ? stem_fused_kernel<2, true, false, true> : stem_fused_kernel<1, true, false, true>;
+}
+#endif
 #ifndef ZLY_STEM_SIDE_TU
+stem_fused_fn stem_fused_view_kernel(int nt, bool lb);        // kernels_view.hip
+stem1_fn      stem1_view_kernel(int nw, int var, bool lb);
 stem_fused_fn stem_fused_yuv_kernel(int nt);         // kernels_stem_yuv.hip
 stem1_fn      stem1_yuv_kernel(int nw, int var);
 stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv);         // kernels_lb.hip
 stem1_fn      stem1_lb_kernel(int nw, int var, bool yuv);
 
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv, bool lb)
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv, bool lb, bool view)
 {
     if (a.Cout != 16 && a.Cout != 32) return hipErrorInvalidValue;         // one or two 16-channel MFMA tiles (YOLOv8n / YOLOv8-s); wider stems use the generic path
     if (a.Cout == 32 && (a.out_cs % 8 || a.out_co % 8)) return hipErrorInvalidValue;
     const int tiles_y = (a.Ho + STEM_TH - 1) / STEM_TH;
-    if (lb) hipLaunchKernelGGL(stem_fused_lb_kernel(a.Cout == 16 ? 1 : 2, yuv), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    if (view) hipLaunchKernelGGL(stem_fused_view_kernel(a.Cout == 16 ? 1 : 2, lb), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    else if (lb) hipLaunchKernelGGL(stem_fused_lb_kernel(a.Cout == 16 ? 1 : 2, yuv), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else if (yuv) hipLaunchKernelGGL(stem_fused_yuv_kernel(a.Cout == 16 ? 1 : 2), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else if (a.Cout == 16) hipLaunchKernelGGL((stem_fused_kernel<1, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((stem_fused_kernel<2, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
@@ -268,7 +283,9 @@ const int* stem1_tap_slot() { return STEM1_TAP_SLOT; }
 // BGR frames only run YUV = false, the kernel as it was.
 // LB: the instantiation of a letterbox engine.  Model-sized BGR frames keep the quad paths (the letterbox map is the identity for them); every other
 // frame takes the letterbox general path below.  Every other engine runs LB = false, the kernel as it was.
-template <int NW, int VAR, bool YUV, bool LB = false>
+// VIEW: the instantiation for frame views (planes_device.h).  A model-sized BGR view -- a model-sized window of a larger surface, the headline use --
+// keeps the quad paths: one 12-byte load per four pixels at row address iy * pitch0 + ix * 3.  A quad lies inside its row, hence inside the plane.
+template <int NW, int VAR, bool YUV, bool LB = false, bool VIEW = false>
 __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem_model1_kernel(const Stem1Args a)
 {
     constexpr bool NEWP = VAR >= 1, PERS = VAR >= 2;
@@ -357,12 +374,12 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
     // 1: the window IS the quad, 16 + (ix - clamped ix + 3): the quad hangs over the left / right frame border by 1-3 pixels -- the window is then shifted
     // by whole pixels at conversion time (zero bytes move in = the zero padding).  Round 4 up to here took such quads pixel by pixel with one byte-wise
     // global round trip each: every row of the half of all tiles that touch the left or right border had one.
-    auto issue_quad = [&](bool ok, int py, int px, int iy0, int ix0, const FrameDesc& d, const uint8_t* src, unsigned int& r0, unsigned int& r1, unsigned int& r2) -> int {
+    auto issue_quad = [&](bool ok, int py, int px, int iy0, int ix0, const Planes<VIEW>& pl, unsigned int& r0, unsigned int& r1, unsigned int& r2) -> int {
         if (!ok) return 0;
         const int iy = iy0 + py, ix = ix0 + px;
         if ((unsigned)iy >= (unsigned)a.st.th || ix >= a.st.tw || ix + 3 < 0) return 3;
         const int ixc = min(max(ix, 0), a.st.tw - 4);
-        const uint8_t* q = src + ((size_t)iy * d.w + ixc) * 3;
+        const uint8_t* q = pl.f + pl.bgr_off(ixc, iy);
         typedef unsigned int u32x3 __attribute__((ext_vector_type(3), aligned(1)));
         const u32x3 v = *reinterpret_cast<const u32x3*>(q);          // 12 bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3 (unaligned global access is enabled on amdhsa)
         r0 = v[0]; r1 = v[1]; r2 = v[2];
@@ -378,8 +395,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
         if (!((d.w == a.st.tw) & (d.h == a.st.th))) return;     // resized frame: the general path below does its own loads
         if (YUV && pix_is_yuv(desc_fmt(d.src_off))) return;     // YUV frame: so does it
         const uint8_t* src = a.st.src + (YUV ? desc_off(d.src_off) : d.src_off);
-        pma = issue_quad(qok[0], qpy[0], qpx[0], iy0, ix0, d, src, pa0, pa1, pa2);
-        pmb = issue_quad(qok[1], qpy[1], qpx[1], iy0, ix0, d, src, pb0, pb1, pb2);
+        const Planes<VIEW> pl = frame_planes<VIEW>(a.st.src, src, a.st.desc, a.n, f, d, ZLY_PIX_BGR);
+        pma = issue_quad(qok[0], qpy[0], qpx[0], iy0, ix0, pl, pa0, pa1, pa2);
+        pmb = issue_quad(qok[1], qpy[1], qpx[1], iy0, ix0, pl, pb0, pb1, pb2);
     };
 
     const f32x4 bias0 = *reinterpret_cast<const f32x4*>(a.st.bias + kq * 4);
@@ -412,7 +430,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
     const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
     const uint8_t* src = a.st.src + (YUV ? desc_off(d.src_off) : d.src_off);
     const bool same = (d.w == a.st.tw) & (d.h == a.st.th) & !pix_is_yuv(fmt);
-    const size_t frame_bytes = (size_t)d.w * d.h * 3;
+    const Planes<VIEW> pl = frame_planes<VIEW>(a.st.src, src, a.st.desc, a.n, f, d, fmt);
+    const auto frame_bytes = pl.bgr_end();                   // bound of the wide loads: the end of plane 0
     STEMSTAMP(0);
     if (same && NEWP) {
 #pragma unroll
@@ -466,10 +485,10 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                     pyq[k] = py; pxq[k] = q4;
                     const int iy = iy0 + py, ix = ix0 + q4;
                     const bool row_in = (unsigned)iy < (unsigned)a.st.th;
-                    const bool fast = row_in && ix >= 0 && ix + 3 < a.st.tw && q4 + 3 < PW && ((size_t)iy * d.w + ix) * 3 + 12 <= frame_bytes;
+                    const bool fast = row_in && ix >= 0 && ix + 3 < a.st.tw && q4 + 3 < PW && pl.bgr_off(ix, iy) + 12 <= frame_bytes;
                     mode[k] = fast ? 1 : 2;
                     if (fast) {
-                        const uint8_t* q = src + ((size_t)iy * d.w + ix) * 3;
+                        const uint8_t* q = src + pl.bgr_off(ix, iy);
                         typedef unsigned int u32x3 __attribute__((ext_vector_type(3), aligned(1)));
                         const u32x3 v = *reinterpret_cast<const u32x3*>(q);          // 12 bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3 (unaligned global access is enabled on amdhsa)
                         r0[k][0] = v[0]; r0[k][1] = v[1]; r0[k][2] = v[2];
@@ -500,7 +519,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                         const int iy = iy0 + pyq[k], ix = ix0 + pxx;
                         bf16x4 v = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
                         if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) {
-                            const uint8_t* q = src + ((size_t)iy * d.w + ix) * 3;
+                            const uint8_t* q = src + pl.bgr_off(ix, iy);
                             const float kk = 1.0f / 255.0f;
                             v[0] = (bf16_t)((float)q[2] * kk); v[1] = (bf16_t)((float)q[1] * kk); v[2] = (bf16_t)((float)q[0] * kk);
                         }
@@ -527,7 +546,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                 if (u < PH * PWV) {
                     const int py = div_small_s(u, invPW), px = u - py * PWV;
                     const int iy = iy0 + py, ix = ix0 + px;
-                    if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) lb_issue<YUV>(src, fmt, lf, ix, iy, tp[j]);
+                    if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) lb_issue<YUV>(pl, fmt, lf, ix, iy, tp[j]);
                 }
             }
     #pragma unroll
@@ -568,9 +587,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                         sx = (int)((float)ix * scale_w); if (sx > d.w - 1) sx = d.w - 1;
                     }
                     if (yuvf) {
-                        yuv_issue(src, fmt, d.w, d.h, sx, sy, raw[k], rawc[k]);
+                        yuv_issue(pl, fmt, sx, sy, raw[k], rawc[k]);
                     } else {
-                    const size_t off = ((size_t)sy * d.w + sx) * 3;
+                    const auto off = pl.bgr_off(sx, sy);
                     const uint8_t* q = src + off;
                     unsigned int px4;
                     if (off + 4 <= frame_bytes) __builtin_memcpy(&px4, q, 4);        // B | G<<8 | R<<16 | next B<<24 (unaligned global access is enabled on amdhsa)
@@ -773,6 +792,15 @@ template <bool YUV> static stem1_fn stem1_lb_pick(int nw, int var)
 }
 stem1_fn stem1_lb_kernel(int nw, int var, bool yuv) { return yuv ? stem1_lb_pick<true>(nw, var) : stem1_lb_pick<false>(nw, var); }
 #endif
+#if defined(ZLY_STEM_VIEW_TU) || defined(ZLY_STEM_DIAG)
+template <bool LB> static stem1_fn stem1_view_pick(int nw, int var)
+{
+    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, true, LB, true> : nw == 16 ? stem_model1_kernel<16, 2, true, LB, true> : stem_model1_kernel<STEM1_NW, 2, true, LB, true>;
+    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, true, LB, true> : nw == 16 ? stem_model1_kernel<16, 1, true, LB, true> : stem_model1_kernel<STEM1_NW, 1, true, LB, true>;
+    return nw == 12 ? stem_model1_kernel<12, 0, true, LB, true> : nw == 16 ? stem_model1_kernel<16, 0, true, LB, true> : stem_model1_kernel<STEM1_NW, 0, true, LB, true>;
+}
+stem1_fn stem1_view_kernel(int nw, int var, bool lb) { return lb ? stem1_view_pick<true>(nw, var) : stem1_view_pick<false>(nw, var); }
+#endif
 #ifndef ZLY_STEM_SIDE_TU
 static size_t stem1_lds_bytes(int th, int tw, int var)
 {
@@ -792,8 +820,9 @@ void stem1_plan(int H1, int W1, const Switches& sw, int* th, int* tw)
     (void)H1;
 }
 
-static stem1_fn pick_stem1(int nw, int var, bool yuv, bool lb = false)
+static stem1_fn pick_stem1(int nw, int var, bool yuv, bool lb = false, bool view = false)
 {
+    if (view) return stem1_view_kernel(nw, var, lb);
     if (lb) return stem1_lb_kernel(nw, var, yuv);
     if (yuv) return stem1_yuv_kernel(nw, var);
     if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, false> : nw == 16 ? stem_model1_kernel<16, 2, false> : stem_model1_kernel<STEM1_NW, 2, false>;
@@ -810,6 +839,9 @@ hipError_t stem1_init()
                 for (bool lb : {false, true}) {
                     hipError_t r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv, lb), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                     if (r != hipSuccess) return r;
+                    if (!yuv) continue;
+                    r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, true, lb, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                    if (r != hipSuccess) return r;
                 }
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_stem1_cus = cus;
@@ -819,7 +851,7 @@ hipError_t stem1_init()
 // a.nw: waves per workgroup (8; 12 / 16 = tuning aid ZLY_STEM1_NW); a.var: 2 = persistent workgroups with the next tile's input bytes in flight (default),
 // 1 = one tile per workgroup, 0 = round 3's staging / tap order as well (ZLY_STEM1_VAR, A/B on one box).  Both are read by the engine once per
 // zly_create, not here (a process-static switch cannot be toggled by a test)
-hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yuv, bool lb)
+hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yuv, bool lb, bool view)
 {
     Stem1Args a = a0;
     if (a.st.Cout != 16 || a.TH < 1 || a.TW < 1 || a.out1_cs % 8 || a.out1_co % 8) return hipErrorInvalidValue;
@@ -850,9 +882,9 @@ hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yu
         long long wgs = (long long)g_stem1_cus * (long long)((160 * 1024) / lds < 1 ? 1 : (160 * 1024) / lds);
         if (a.pgrid > 0) wgs = a.pgrid;                                                            // tuning aid ZLY_STEM1_GRID (read by the engine per zly_create)
         if (wgs > total) wgs = total;
-        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb), dim3((unsigned)wgs), dim3(nw * 64), lds, s, a);
+        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb, view), dim3((unsigned)wgs), dim3(nw * 64), lds, s, a);
     } else {
-        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb), dim3(a.tiles_x * a.tiles_y, n), dim3(nw * 64), lds, s, a);
+        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb, view), dim3(a.tiles_x * a.tiles_y, n), dim3(nw * 64), lds, s, a);
     }
     return hipGetLastError();
 }

@@ -72,8 +72,8 @@ __device__ __forceinline__ bool lb_is_pad(const LbFrame& f, int ix, int iy)
     return (unsigned)(ix - f.pad_x) >= (unsigned)f.nw || (unsigned)(iy - f.pad_y) >= (unsigned)f.nh;
 }
 
-template <bool YUV>
-__device__ __forceinline__ void lb_issue(const uint8_t* src, int fmt, const LbFrame& f, int ix, int iy, LbTaps& o)
+template <bool YUV, class PL>
+__device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f, int ix, int iy, LbTaps& o)
 {
     o.m = LB_PAD;
     o.t[0] = o.t[1] = o.t[2] = o.t[3] = 0u;
@@ -87,15 +87,17 @@ __device__ __forceinline__ void lb_issue(const uint8_t* src, int fmt, const LbFr
     o.m = ax | (ay << 16);
     if (YUV && pix_is_yuv(fmt)) {                       // uniform per frame; YUV frames are at least 2 x 2
         unsigned int y, uv;
-        yuv_issue(src, fmt, f.w, f.h, xl, y0, y, uv);     o.t[0] = y | (uv << 8);
-        yuv_issue(src, fmt, f.w, f.h, xl + 1, y0, y, uv); o.t[1] = y | (uv << 8);
-        yuv_issue(src, fmt, f.w, f.h, xl, y1, y, uv);     o.t[2] = y | (uv << 8);
-        yuv_issue(src, fmt, f.w, f.h, xl + 1, y1, y, uv); o.t[3] = y | (uv << 8);
+        yuv_issue(pl, fmt, xl, y0, y, uv);         o.t[0] = y | (uv << 8);
+        yuv_issue(pl, fmt, xl + 1, y0, y, uv); o.t[1] = y | (uv << 8);
+        yuv_issue(pl, fmt, xl, y1, y, uv);         o.t[2] = y | (uv << 8);
+        yuv_issue(pl, fmt, xl + 1, y1, y, uv); o.t[3] = y | (uv << 8);
         return;
     }
-    // 32-bit byte offsets from the frame's (uniform) base: a frame of this mode is at most ZLY_LETTERBOX_MAX_DIM on a side, 3 * 2^28 bytes
-    const unsigned int frame_bytes = (unsigned)f.w * (unsigned)f.h * 3u;
-    const unsigned int off0 = ((unsigned)y0 * (unsigned)f.w + (unsigned)xl) * 3u, off1 = ((unsigned)y1 * (unsigned)f.w + (unsigned)xl) * 3u;
+    // 32-bit byte offsets from the frame's (uniform) base: a frame of this mode is at most ZLY_LETTERBOX_MAX_DIM on a side, 3 * 2^28 bytes (a view's plane
+    // extends over less than 2^31); the bound of the 8-byte loads is the end of the plane (planes_device.h)
+    const uint8_t* src = pl.f;
+    const unsigned int frame_bytes = pl.bgr_end32();
+    const unsigned int off0 = pl.bgr_off32(xl, y0), off1 = pl.bgr_off32(xl, y1);
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2), aligned(1)));
     if (off1 + 8 <= frame_bytes) {                      // off0 <= off1
         const u32x2 r0 = *reinterpret_cast<const u32x2*>(src + off0);        // (amdhsa: unaligned global access is enabled)

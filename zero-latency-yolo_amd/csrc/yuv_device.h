@@ -7,23 +7,23 @@
 // Split into an issue half (the byte loads) and a convert half, so that a kernel can have all its loads in flight before it converts.
 #pragma once
 #include "zly_internal.h"
+#include "planes_device.h"
 
 namespace zly {
 
 __device__ __forceinline__ bool pix_is_yuv(int fmt) { return fmt != ZLY_PIX_BGR; }
 
-// loads of one pixel of the YUV frame at f: y = Y byte, uv = U | V << 8
-__device__ __forceinline__ void yuv_issue(const uint8_t* f, int fmt, int w, int h, int sx, int sy, unsigned int& y, unsigned int& uv)
+// loads of one pixel of the YUV frame whose planes pl lays out (planes_device.h: a tight frame or a frame view): y = Y byte, uv = U | V << 8
+template <class PL>
+__device__ __forceinline__ void yuv_issue(const PL& pl, int fmt, int sx, int sy, unsigned int& y, unsigned int& uv)
 {
-    y = f[(size_t)sy * w + sx];
-    const uint8_t* c = f + (size_t)w * h;                                          // chroma planes follow the Y plane
-    const size_t ci = (size_t)(sy >> 1) * (size_t)(w >> 1) + (size_t)(sx >> 1);     // one chroma sample per 2x2 block
+    y = *pl.luma(sx, sy);
     if (fmt == ZLY_PIX_NV12_BT601 || fmt == ZLY_PIX_NV12_BT709) {
         unsigned short p;
-        __builtin_memcpy(&p, c + 2 * ci, 2);                                        // interleaved U, V: one 2-byte load
+        __builtin_memcpy(&p, pl.nv12(sx, sy), 2);                                   // interleaved U, V: one 2-byte load (inside the row: it needs no guard)
         uv = p;
     } else {
-        uv = (unsigned int)c[ci] | ((unsigned int)c[(size_t)(w >> 1) * (size_t)(h >> 1) + ci] << 8);
+        uv = (unsigned int)*pl.cu(sx, sy) | ((unsigned int)*pl.cv(sx, sy) << 8);
     }
 }
 

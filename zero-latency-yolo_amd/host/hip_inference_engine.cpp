@@ -15,6 +15,12 @@
 // tests/cpp/test_plugin_stub.cpp) still links, and initialize() refuses a YUV ZLY_INPUT_FORMAT when they are missing.
 #pragma weak zly_submit_fmt
 #pragma weak zly_submit_try_fmt
+// ... and so are the frame-view calls behind ZLY_CROP: initialize() refuses ZLY_CROP when they are missing
+#pragma weak zly_view_tight
+#pragma weak zly_view_bytes
+#pragma weak zly_view_crop
+#pragma weak zly_submit_view
+#pragma weak zly_submit_try_view
 
 namespace zero_latency {
 
@@ -54,6 +60,30 @@ int parseResizeMode(const char* v)
     if (std::strcmp(v, "letterbox") == 0) return 1;
     return -1;
 }
+// ZLY_CROP=WxH (both >= 1) -> true; unset or empty: no crop (w = h = 0), true; anything else: false
+bool parseCrop(const char* v, int32_t* w, int32_t* h)
+{
+    *w = *h = 0;
+    if (!v || !*v) return true;
+    char* end = nullptr;
+    const long cw = std::strtol(v, &end, 10);
+    if (end == v || (*end != 'x' && *end != 'X')) return false;
+    const char* hs = end + 1;
+    const long ch = std::strtol(hs, &end, 10);
+    if (end == hs || *end || cw < 1 || ch < 1 || cw > (1 << 24) || ch > (1 << 24)) return false;
+    *w = (int32_t)cw; *h = (int32_t)ch;
+    return true;
+}
+// The box map of ZLY_CROP, single IEEE fp32 operations: a product is rounded to fp32 before it is added to or divided
+// (the volatile store keeps a compiler from contracting it into a fused multiply-add)
+inline float mulRounded(float a, float b) { volatile float p = a * b; return p; }
+void mapCropToFrame(Detection& d, int32_t x0, int32_t y0, int32_t cw, int32_t ch, int32_t fw, int32_t fh)
+{
+    d.box.x = (mulRounded(d.box.x, (float)cw) + (float)x0) / (float)fw;
+    d.box.y = (mulRounded(d.box.y, (float)ch) + (float)y0) / (float)fh;
+    d.box.width = mulRounded(d.box.width, (float)cw) / (float)fw;
+    d.box.height = mulRounded(d.box.height, (float)ch) / (float)fh;
+}
 int envInt(const char* name, int fallback)
 {
     const char* v = std::getenv(name);
@@ -90,6 +120,15 @@ Result<void> HipInferenceEngine::initialize()
                                                                  std::getenv("ZLY_INPUT_FORMAT") + "'");
     if (input_format_ != ZLY_PIX_BGR && (!zly_submit_fmt || !zly_submit_try_fmt))
         return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_INPUT_FORMAT: the engine library has no zly_submit_fmt");
+    // ZLY_CROP=WxH: every request is detected in the centred W x H window of its frame (x0 = (width - W) / 2, y0 = (height - H) / 2, both rounded down
+    // to even for a YUV ZLY_INPUT_FORMAT) -- a model-sized window around the crosshair is the engine's fast path -- and its boxes are mapped back to
+    // fractions of the whole frame before the callback.  A request smaller than the window on either axis is detected whole.
+    if (!parseCrop(std::getenv("ZLY_CROP"), &crop_w_, &crop_h_))
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_CROP must be WxH with W, H >= 1, got '") + std::getenv("ZLY_CROP") + "'");
+    if (crop_w_ > 0 && input_format_ != ZLY_PIX_BGR && ((crop_w_ | crop_h_) & 1))
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, "ZLY_CROP: a YUV 4:2:0 ZLY_INPUT_FORMAT needs an even window size");
+    if (crop_w_ > 0 && (!zly_view_tight || !zly_view_bytes || !zly_view_crop || !zly_submit_view || !zly_submit_try_view))
+        return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_CROP: the engine library has no zly_submit_view");
     // ZLY_RESIZE: how every engine of this plugin (a hot reload's new ones included) fits a request into the model's input: the reference's
     // stretch, or the aspect-preserving letterbox an Ultralytics-trained model expects (boxes then are normalised to the request frame itself)
     const int resize = parseResizeMode(std::getenv("ZLY_RESIZE"));
@@ -333,19 +372,41 @@ Result<void> HipInferenceEngine::submitInference(const InferenceRequest& request
             // A request with the wrong byte count fails alone (INVALID_INPUT, onnx_engine.cpp:659-665): counted, no callback.
             const size_t ne = snap->size(), first = (size_t)(seq % ne);
             int32_t rc = ZLY_PENDING;
+            // ZLY_CROP: the window of this request as a view of its (tight) frame; the engine copies the window's rows only
+            zly_frame_view win;
+            int32_t vrc = ZLY_OK;
+            if (crop_w_ > 0 && request.width >= crop_w_ && request.height >= crop_h_) {
+                zly_frame_view whole;
+                vrc = zly_view_tight(input_format_, request.width, request.height, &whole);
+                if (vrc == ZLY_OK && request.data.size() != zly_view_bytes(&whole)) vrc = ZLY_ERR_INVALID_INPUT;     // as a whole frame of the wrong size
+                if (vrc == ZLY_OK) {
+                    p.crop_x0 = (request.width - crop_w_) / 2; p.crop_y0 = (request.height - crop_h_) / 2;
+                    if (input_format_ != ZLY_PIX_BGR) { p.crop_x0 &= ~1; p.crop_y0 &= ~1; }
+                    p.frame_w = request.width; p.frame_h = request.height;
+                    vrc = zly_view_crop(&whole, p.crop_x0, p.crop_y0, crop_w_, crop_h_, &win);
+                    p.cropped = vrc == ZLY_OK;
+                }
+            }
+            auto offer = [&](zly_engine* e, bool blocking) -> int32_t {
+                if (p.cropped)
+                    return blocking ? zly_submit_view(e, request.data.data(), request.data.size(), &win, &p.ticket)
+                                    : zly_submit_try_view(e, request.data.data(), request.data.size(), &win, &p.ticket);
+                if (input_format_ == ZLY_PIX_BGR)
+                    return blocking ? zly_submit(e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket)
+                                    : zly_submit_try(e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
+                return blocking ? zly_submit_fmt(e, input_format_, request.data.data(), request.data.size(), request.width, request.height, &p.ticket)
+                                : zly_submit_try_fmt(e, input_format_, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
+            };
+            if (vrc != ZLY_OK) rc = vrc;
             for (size_t k = 0; k < ne && rc == ZLY_PENDING; ++k) {
                 p.slot = (first + k) % ne;
                 p.engine = (*snap)[p.slot];
-                rc = input_format_ == ZLY_PIX_BGR
-                         ? zly_submit_try(p.engine->e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket)
-                         : zly_submit_try_fmt(p.engine->e, input_format_, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
+                rc = offer(p.engine->e, false);
             }
             if (rc == ZLY_PENDING) {
                 p.slot = first;
                 p.engine = (*snap)[first];
-                rc = input_format_ == ZLY_PIX_BGR
-                         ? zly_submit(p.engine->e, request.data.data(), request.data.size(), request.width, request.height, &p.ticket)
-                         : zly_submit_fmt(p.engine->e, input_format_, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
+                rc = offer(p.engine->e, true);
             }
             if (rc != ZLY_OK) { p.failed = true; p.engine.reset(); }
         }
@@ -435,6 +496,8 @@ void HipInferenceEngine::completionLoop()
                 static_assert(sizeof(zly_det) == sizeof(Detection), "zly_det must be layout-identical to Detection");
                 d.state.detections.resize((size_t)cnt);
                 if (cnt) std::memcpy(d.state.detections.data(), dets.data(), (size_t)cnt * sizeof(Detection));
+                if (p.cropped)                                   // boxes came back as fractions of the window: make them fractions of the request frame
+                    for (Detection& det : d.state.detections) mapCropToFrame(det, p.crop_x0, p.crop_y0, crop_w_, crop_h_, p.frame_w, p.frame_h);
             } else {
                 inference_errors_++;
             }
@@ -536,6 +599,7 @@ std::unordered_map<std::string, std::string> HipInferenceEngine::getStatus() con
     s["dropped_frames"] = std::to_string(dropped_frames_.load());
     s["dynamic_batching"] = "enabled";
     s["resize_mode"] = letterbox_ ? "letterbox" : "stretch";
+    s["crop"] = crop_w_ > 0 ? std::to_string(crop_w_) + "x" + std::to_string(crop_h_) : "off";
     double avg = 0, p99 = 0;
     {
         std::lock_guard<std::mutex> lk(stats_mutex_);

@@ -71,6 +71,10 @@ private:
         uint32_t client_id = 0, frame_id = 0;
         uint64_t timestamp = 0, enqueue_ms = 0;
         size_t slot = 0;                                   // index of its queue in pending_
+        // ZLY_CROP: the request was detected in the window (crop_x0, crop_y0, crop_w_, crop_h_) of its frame_w x frame_h frame: its boxes are mapped
+        // back to fractions of the frame before the callback (cropped = false: detected whole)
+        bool cropped = false;
+        int32_t crop_x0 = 0, crop_y0 = 0, frame_w = 0, frame_h = 0;
     };
 
     void completionLoop();
@@ -94,6 +98,7 @@ private:
     int first_device_ = 0;
     int engines_per_gpu_ = 1;
     int32_t input_format_ = 0;                             // ZLY_INPUT_FORMAT (read by initialize()): ZLY_PIX_* of every request's data (0 = BGR)
+    int32_t crop_w_ = 0, crop_h_ = 0;                      // ZLY_CROP=WxH (read by initialize()): every request is detected in the centred W x H window of its frame (0 = whole frames)
     bool letterbox_ = false;                               // ZLY_RESIZE=letterbox (read by initialize()): every engine is created with ZLY_FLAG_LETTERBOX
     std::thread monitor_, completer_, reaper_;
     // Engines replaced by a hot reload are destroyed on the reaper thread: zly_destroy drains the engine's streams and takes the process-wide

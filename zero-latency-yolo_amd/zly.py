@@ -42,6 +42,8 @@ SYMBOLS = [
     "zly_detect", "zly_detect_batch", "zly_submit", "zly_submit_try", "zly_poll", "zly_wait", "zly_detect_device", "zly_slab_bytes", "zly_read_slabs", "zly_sync", "zly_join",
     "zly_frame_bytes", "zly_letterbox_geometry", "zly_detect_fmt", "zly_detect_batch_fmt", "zly_submit_fmt", "zly_submit_try_fmt", "zly_detect_device_fmt", "zly_preprocess_fmt",
     "zly_preprocess", "zly_forward", "zly_head_tensor", "zly_postprocess", "zly_debug_tap",
+    "zly_view_bytes", "zly_view_tight", "zly_view_crop", "zly_detect_view", "zly_detect_batch_view", "zly_submit_view", "zly_submit_try_view",
+    "zly_detect_device_view", "zly_preprocess_view",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -56,6 +58,12 @@ class Config(C.Structure):
                 ("conf_thr", C.c_float), ("iou_thr", C.c_float), ("max_batch", C.c_int32),
                 ("max_dets", C.c_int32), ("device", C.c_int32), ("dtype", C.c_int32),
                 ("warmup_runs", C.c_int32), ("use_graph", C.c_int32), ("flags", C.c_int32)]
+
+
+class FrameView(C.Structure):
+    """zly_frame_view: where a request's samples lie inside a larger buffer (offsets from the buffer base, row pitches)"""
+    _fields_ = [("fmt", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("pad_", C.c_int32),
+                ("off", C.c_uint64 * 3), ("pitch", C.c_int32 * 3), ("pad2_", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -122,6 +130,16 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_submit_try_fmt.argtypes = [vp, i32, vp, sz, i32, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_try_fmt.restype = i32
     lib.zly_detect_device_fmt.argtypes = [vp, i32, i32, vp, i32, i32, vp, u32, vp]; lib.zly_detect_device_fmt.restype = i32
     lib.zly_preprocess_fmt.argtypes = [vp, i32, vp, sz, i32, i32, vp]; lib.zly_preprocess_fmt.restype = i32
+    pv = C.POINTER(FrameView)
+    lib.zly_view_bytes.argtypes = [pv]; lib.zly_view_bytes.restype = sz
+    lib.zly_view_tight.argtypes = [i32, i32, i32, pv]; lib.zly_view_tight.restype = i32
+    lib.zly_view_crop.argtypes = [pv, i32, i32, i32, i32, pv]; lib.zly_view_crop.restype = i32
+    lib.zly_detect_view.argtypes = [vp, vp, sz, pv, vp, i32, pi32]; lib.zly_detect_view.restype = i32
+    lib.zly_detect_batch_view.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), pv, vp, i32, pi32]; lib.zly_detect_batch_view.restype = i32
+    lib.zly_submit_view.argtypes = [vp, vp, sz, pv, C.POINTER(C.c_uint64)]; lib.zly_submit_view.restype = i32
+    lib.zly_submit_try_view.argtypes = [vp, vp, sz, pv, C.POINTER(C.c_uint64)]; lib.zly_submit_try_view.restype = i32
+    lib.zly_detect_device_view.argtypes = [vp, i32, vp, sz, pv, vp, u32, vp]; lib.zly_detect_device_view.restype = i32
+    lib.zly_preprocess_view.argtypes = [vp, vp, sz, pv, vp]; lib.zly_preprocess_view.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -151,6 +169,27 @@ def letterbox_geometry(w: int, h: int, model_w: int, model_h: int) -> Tuple[int,
     o = [C.c_int32() for _ in range(4)]
     _check(lib, lib.zly_letterbox_geometry(w, h, model_w, model_h, *[C.byref(x) for x in o]))
     return tuple(int(x.value) for x in o)
+
+
+def view_tight(fmt: int, w: int, h: int) -> FrameView:
+    """the view of a tight w x h frame of format fmt (host only)"""
+    lib = load_library()
+    v = FrameView()
+    _check(lib, lib.zly_view_tight(fmt, w, h, C.byref(v)))
+    return v
+
+
+def view_crop(surface: FrameView, x0: int, y0: int, w: int, h: int) -> FrameView:
+    """the view of the rectangle (x0, y0, w, h) of a view; crops compose (host only)"""
+    lib = load_library()
+    v = FrameView()
+    _check(lib, lib.zly_view_crop(C.byref(surface), x0, y0, w, h, C.byref(v)))
+    return v
+
+
+def view_bytes(v: FrameView) -> int:
+    """the smallest buffer that holds the view; 0 for an invalid view (host only)"""
+    return int(load_library().zly_view_bytes(C.byref(v)))
 
 
 def _dims(frame: np.ndarray, fmt: int, w: Optional[int], h: Optional[int]) -> Tuple[int, int]:
@@ -250,7 +289,34 @@ class Engine:
             _check(self.lib, self.lib.zly_detect_batch_fmt(self.h, n, cfm, ptrs, nbytes, cws, chs, out.ctypes.data, cap, n_out))
         return [(out[i, :min(n_out[i], cap)], int(n_out[i])) for i in range(n)]
 
+    def detect_view(self, buf: np.ndarray, view: FrameView, cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+        """buf: the caller's whole u8 buffer (a surface); view: where the request lies in it"""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        cap = cap or self.max_dets
+        out = np.zeros(cap, dtype=DET_DTYPE)
+        n = C.c_int32(0)
+        _check(self.lib, self.lib.zly_detect_view(self.h, buf.ctypes.data, buf.nbytes, C.byref(view), out.ctypes.data, cap, C.byref(n)))
+        return out[:min(n.value, cap)], n.value
+
+    def detect_batch_view(self, bufs: Sequence[np.ndarray], views: Sequence[FrameView], cap: Optional[int] = None) -> List[Tuple[np.ndarray, int]]:
+        bufs = [np.ascontiguousarray(b, dtype=np.uint8) for b in bufs]
+        n = len(bufs)
+        cap = cap or self.max_dets
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        nbytes = (C.c_size_t * n)(*[b.nbytes for b in bufs])
+        cv = (FrameView * n)(*views)
+        out = np.zeros((n, cap), dtype=DET_DTYPE)
+        n_out = (C.c_int32 * n)()
+        _check(self.lib, self.lib.zly_detect_batch_view(self.h, n, ptrs, nbytes, cv, out.ctypes.data, cap, n_out))
+        return [(out[i, :min(n_out[i], cap)], int(n_out[i])) for i in range(n)]
+
     # -- asynchronous, pipelined host-to-host path ---------------------------------------------------
+    def submit_view(self, buf: np.ndarray, view: FrameView) -> int:
+        """copies the view's rows into the engine's pinned staging ring (on this thread) and returns a ticket"""
+        t = C.c_uint64(0)
+        _check(self.lib, self.lib.zly_submit_view(self.h, buf.ctypes.data, buf.nbytes, C.byref(view), C.byref(t)))
+        return t.value
+
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
         """copies the frame into the engine's pinned staging ring (on this thread) and returns a ticket"""
@@ -285,6 +351,12 @@ class Engine:
         else:
             _check(self.lib, self.lib.zly_detect_device_fmt(self.h, fmt, n, d_frames_ptr, w, h, d_slabs_ptr or None, tag0, stream or None))
 
+    def detect_device_view(self, d_base_ptr: int, buf_bytes: int, views: Sequence[FrameView], d_slabs_ptr: int = 0, tag0: int = 0, stream: int = 0):
+        """len(views) frame views of one device buffer of buf_bytes at d_base_ptr: sizes, formats, pitches and offsets per frame"""
+        n = len(views)
+        cv = (FrameView * n)(*views)
+        _check(self.lib, self.lib.zly_detect_device_view(self.h, n, d_base_ptr, buf_bytes, cv, d_slabs_ptr or None, tag0, stream or None))
+
     def sync(self):
         _check(self.lib, self.lib.zly_sync(self.h))
 
@@ -310,6 +382,12 @@ class Engine:
         else:
             ww, hh = _dims(frame, fmt, w, h)
             _check(self.lib, self.lib.zly_preprocess_fmt(self.h, fmt, frame.ctypes.data, nb, ww, hh, out.ctypes.data))
+        return out
+
+    def preprocess_view(self, buf: np.ndarray, view: FrameView) -> np.ndarray:
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.zeros((3, self.model_h, self.model_w), dtype=np.float32)
+        _check(self.lib, self.lib.zly_preprocess_view(self.h, buf.ctypes.data, buf.nbytes, C.byref(view), out.ctypes.data))
         return out
 
     def forward(self, images_nchw: np.ndarray) -> np.ndarray:
