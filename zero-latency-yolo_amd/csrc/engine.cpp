@@ -129,7 +129,7 @@ struct Plan {
 };
 
 // What one op launches at one batch size: a record of the launch table (resolve_launches)
-enum LaunchKind { LK_NONE, LK_PREPROCESS, LK_STEM, LK_STEM1, LK_CONV, LK_CONV_WSK, LK_MULTI, LK_C2F, LK_PAIR, LK_SPPF_FUSED, LK_SPPF_POOL, LK_HEAD, LK_NMS };
+enum LaunchKind { LK_NONE, LK_PREPROCESS, LK_STEM, LK_STEM1, LK_CONV, LK_CONV_WSK, LK_MULTI, LK_C2F, LK_PAIR, LK_WS_PAIR, LK_SPPF_FUSED, LK_SPPF_POOL, LK_HEAD, LK_NMS };
 struct Launch {
     int kind = LK_NONE;                // LK_NONE: the op's work is done inside the launch of op `covered_by`
     int covered_by = -1;               // index of the op whose launch does this op's work (the op itself when it launches)
@@ -138,6 +138,7 @@ struct Launch {
     WskPlan wsk{};                     // LK_CONV_WSK
     C2fPlan c2f{};                     // LK_C2F
     PairPlan pair{};                   // LK_PAIR
+    WsPairPlan ws_pair{};              // LK_WS_PAIR
     int multi_ct = 0;                  // LK_MULTI: 3 = the three Detect stems, 2 = the six Detect branch convs
     int only_level = -1;               // LK_HEAD: -1 = all three levels, else that level only
     bool pool16 = false;               // LK_SPPF_POOL: sppf_pool16_kernel (else sppf_pool_kernel)
@@ -296,6 +297,9 @@ static void read_switches(Switches* sw)
     num("ZLY_WS_TPW1_MAXCT", &sw->ws_tpw1_maxct);
     num("ZLY_WS_MIN_TILES", &sw->ws_min_tiles);
     num("ZLY_WS_MAX_BYTES", &sw->ws_max_bytes);
+    num("ZLY_WS_PAIR", &sw->ws_pair);
+    num("ZLY_WS_PAIR_GRID", &sw->ws_pair_grid);
+    num("ZLY_WS_PAIR_MAX_TILES", &sw->ws_pair_max_tiles);
     sw->no_wres = on("ZLY_NO_WRES");
     num("ZLY_WRES_MAXCHUNKS", &sw->wres_maxchunks);
     sw->lds_s2_pt1 = on("ZLY_LDS_S2_PT1");
@@ -872,6 +876,19 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
         const Buffer& b = e->bufs[(size_t)A.in.buf];
         return pair_plan(g.c, n, b.H, b.W, e->sw, pl) && pl->total_tiles >= e->sw.pair_min_tiles;
     };
+    // a 64-channel bottleneck's pair as one weight-stationary launch at its first conv, op a (conv3x3_ws_pair_kernel): where the old LDS-weight pair
+    // kernel is not asked for (width 64 in ZLY_PAIR_WIDTHS keeps that meaning) and both convs would on their own be the weight-stationary kernel
+    auto ws_pair_of = [&](int a, WsPairPlan* pl) {
+        const Op& A = e->ops[(size_t)a];
+        if (A.pair < 0 || !fusion) return false;
+        const PairGroup& g = e->pairs[(size_t)A.pair];
+        if (g.first != a || g.c != 64 || (e->sw.pair_widths & 64)) return false;
+        const ConvArgs ca = make_conv_args(e, A, n), cb = make_conv_args(e, e->ops[(size_t)g.second], n);
+        ConvPlan pa{}, pb{};
+        conv_plan(e->dtype, 3, ca, e->sw, &pa);
+        conv_plan(e->dtype, 3, cb, e->sw, &pb);
+        return conv_ws_pair_plan(ca, cb, pa, pb, e->sw, pl);
+    };
     // SPPF as one launch at model.9.cv1 (opt-in, ZLY_SPPF_FUSED=1); the pool and cv2 then launch nothing
     bool sppf = fusion && e->sw.sppf_fused && e->sppf_cv1 >= 0;
     if (sppf) {
@@ -925,6 +942,7 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
             conv_plan(e->dtype, op.ks, make_conv_args(e, op, n), e->sw, &L.conv);
             C2fPlan cp{};
             PairPlan pp{};
+            WsPairPlan wp{};
             if (i == 1 && e->stem_fused) {
                 L.kind = e->stem1 ? LK_STEM1 : LK_STEM;
                 L.hbm = !e->stem1 || dump;                                  // stem_model1_kernel keeps the stem map in LDS
@@ -947,6 +965,11 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
                 L.kind = LK_PAIR; L.pair = pp;
                 L.hbm = false;                                              // the intermediate map stays in LDS
             } else if (op.pair >= 0 && e->pairs[(size_t)op.pair].second == i && pair_of(e->pairs[(size_t)op.pair].first, &pp)) {
+                covered(e->pairs[(size_t)op.pair].first);
+            } else if (ws_pair_of(i, &wp)) {
+                L.kind = LK_WS_PAIR; L.ws_pair = wp;
+                L.hbm = dump;                                               // the intermediate map stays in LDS; with the dump flag the kernel writes it out as well
+            } else if (op.pair >= 0 && e->pairs[(size_t)op.pair].second == i && ws_pair_of(e->pairs[(size_t)op.pair].first, &wp)) {
                 covered(e->pairs[(size_t)op.pair].first);
             } else if (op.wsk_w && !e->sw.no_wsk && bf16 && conv_wsk_ok(make_wsk_args(e, op, n), e->sw, &L.wsk)) {
                 L.kind = LK_CONV_WSK;
@@ -1032,6 +1055,10 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
     case LK_PAIR: {
         const PairGroup& g = e->pairs[(size_t)op.pair];
         return launch_pair(g.c, make_pair_args(e, g, L.pair, n), L.pair, s);
+    }
+    case LK_WS_PAIR: {
+        const PairGroup& g = e->pairs[(size_t)op.pair];
+        return launch_conv_ws_pair(make_conv_args(e, op, n), make_conv_args(e, e->ops[(size_t)g.second], n), L.ws_pair, (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) != 0, s);
     }
     case LK_SPPF_FUSED:
         return launch_sppf_fused(make_sppf_args(e, n), s);
@@ -2551,6 +2578,8 @@ int32_t zly_debug_tap(zly_engine* e, const char* name, int32_t idx, float* out, 
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused SPPF kernel; create the engine with ZLY_FLAG_DUMP_LOGITS or ZLY_FLAG_NO_FUSION");
             case LK_PAIR:
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused bottleneck kernel at this batch size; create the engine with ZLY_FLAG_NO_FUSION");
+            case LK_WS_PAIR:
+                return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused bottleneck kernel at this batch size; create the engine with ZLY_FLAG_DUMP_LOGITS or ZLY_FLAG_NO_FUSION");
             }
             buf = op.out.buf; co = op.out.co + op.tap_co[(size_t)it->second.second]; C = op.tap_c[(size_t)it->second.second];
             f32 = op.out_f32 != 0;
@@ -2605,7 +2634,7 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
     case LK_NONE:
         switch (t[(size_t)L.covered_by].kind) {
         case LK_STEM: case LK_STEM1: k = op.kind == OP_PREPROCESS ? "(fused into stem_fused_kernel)" : "(fused into the previous launch)"; break;
-        case LK_PAIR: k = "(fused into the previous launch)"; break;
+        case LK_PAIR: case LK_WS_PAIR: k = "(fused into the previous launch)"; break;
         case LK_C2F: k = "(fused into the C2f kernel at " + e->ops[(size_t)L.covered_by].name + ")"; break;
         case LK_SPPF_FUSED: k = "(fused into the SPPF kernel at model.9.cv1)"; break;
         case LK_MULTI: k = "(in a merged Detect launch)"; break;
@@ -2625,6 +2654,7 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
         break;
     }
     case LK_PAIR: k = "bottleneck_pair_kernel<" + std::to_string(e->pairs[(size_t)op.pair].c) + ">"; break;
+    case LK_WS_PAIR: k = std::string("conv3x3_ws_pair_kernel<") + (e->pairs[(size_t)op.pair].res ? "RES," : "") + "64->64->64," + std::to_string(L.ws_pair.g.TH) + "x" + std::to_string(L.ws_pair.g.TW) + " tiles>"; break;
     case LK_CONV_WSK: k = "conv3x3_wsk_kernel<K=720 packed across taps,5 channel tiles>"; break;
     case LK_CONV: {
         const int cin = op.in.C + (op.in2.buf >= 0 ? op.in2.C : 0);

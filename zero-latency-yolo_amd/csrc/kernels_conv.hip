@@ -1138,6 +1138,274 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ws_kernel(const ConvArgs a, co
 }
 
 // ------------------------------------------------------------------------------------------------
+// A 64-channel bottleneck's TWO 3x3 convs (64 -> 64 -> 64, SiLU on both, optional shortcut) as one weight-stationary launch: conv3x3_ws_kernel<TPW = 1>
+// twice, with the intermediate map in LDS instead of a round trip through memory and one launch boundary, one weight prologue and one patch wait
+// instead of two (the 26 x 26 maps at batch 64: 512 tiles on 512 resident workgroups, every workgroup lives for one tile and most of its 11.6 k cycles
+// are those three, profiles/r03_ws_kernel_phase_stamps_v4.txt).
+//   * four waves, one 16-channel output tile each (tile_channel as in the TPW = 1 form); a wave keeps the 18 k-step fragments of BOTH convs for its
+//     tile in registers (2 x 72 VGPRs, the count the TPW = 2 form holds).  Conv B's fragments are requested right behind conv A's and are not waited
+//     for before conv A's MFMAs: the wait in front of the first tile leaves exactly those 18 loads (and that tile's conv B bias) outstanding.  What it takes
+//     to keep the compiler from waiting earlier (checked in the ISA; each was an s_waitcnt vmcnt(0) in front of or inside conv A): conv A's bias is loaded
+//     in FRONT of the weights, conv B's bias per tile INSIDE the loop, and the waits for conv B's operands are placed behind conv A by naming the
+//     registers there.  One wait remains in the instantiation without shortcut: the compiler puts vmcnt(3) in front of conv A's first store to the LDS
+//     map (it cannot rule out the previous tile's LDS-DMA there), so on a workgroup's first tile conv B's weights must have landed when the first pair of
+//     region rows has been through its 36 MFMAs;
+//   * persistent over TH x TW pixel tiles (ws_pair_plan: TW <= 14).  The input patch is (TH + 4) x (TW + 4) by LDS-DMA, the buffer range check is
+//     the zero padding; the next tile's patch is requested as soon as conv A has read this one, and lands while conv B runs.  Patch and map are TWO LDS
+//     objects: with one buffer the compiler made conv B's map reads wait for the DMA issued before them.  With the shortcut, conv B's first shortcut
+//     load (issued behind the DMA, returned in order) waits for the patch too: the DMA then overlaps conv B's first pair of column tiles only;
+//   * conv A runs over the (TH + 2) x (TW + 2) region, one region ROW per 16-pixel MFMA tile (lane p = region column p: 16 consecutive patch pixels
+//     per fragment read, conflict-free at the 160-byte pixel pitch whatever the row pitch; lanes beyond the region compute on pixels of the next patch
+//     row and their columns of the map are never read), bias + SiLU, rounded to bf16, into an LDS map.  Region pixels OUTSIDE THE FRAME are written
+//     as zero: conv B pads the intermediate map with zeros, not with conv A of padded input (kernels_pair.hip's header);
+//   * conv B reads the map over TH x TW in linearised 16-pixel column tiles; the map's rows are TW + 8 pixels apart, so a tile that wraps into the
+//     next row hits the banks 16 consecutive pixels would (row pitch - TW = 8: the rule of conv3x3_ws_kernel).  Bias + SiLU (+ the bottleneck's input,
+//     loaded as the TPW = 1 epilogue loads it), 8-byte NHWC stores;
+//   * both convs accumulate in conv3x3_ws_kernel's k-step order (s = tap * 2 + chunk) with the same MFMA, silu<bf16_t> and rounding points: the
+//     result is bit-identical to the two launches it replaces (tests/test_gpu_ws_pair.py);
+//   * with a.mid set (ZLY_FLAG_DUMP_LOGITS) conv A also writes the TH x TW interior of its map to the first conv's output buffer (debug taps).
+// Two barriers per tile: patch landed / previous conv B done with the map, and map complete / patch free.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ws_pair_mma(const bf16x8 (&w)[18], const unsigned char* const (&px)[2], const int (&toff)[18], f32x4 (&acc)[2])
+{
+    // pixel fragments are read WS_DEPTH k-steps ahead of the MFMAs that consume them (statically indexed rings), as in conv3x3_ws_kernel
+    constexpr int WS_DEPTH = 3;
+    acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bf16x8 xf[2][WS_DEPTH + 1];
+#pragma unroll
+    for (int s = 0; s < WS_DEPTH; ++s) { xf[0][s] = *reinterpret_cast<const bf16x8*>(px[0] + toff[s]); xf[1][s] = *reinterpret_cast<const bf16x8*>(px[1] + toff[s]); }
+#pragma unroll
+    for (int s = 0; s < 18; ++s) {
+        if (s + WS_DEPTH < 18) {
+            xf[0][(s + WS_DEPTH) % (WS_DEPTH + 1)] = *reinterpret_cast<const bf16x8*>(px[0] + toff[s + WS_DEPTH]);
+            xf[1][(s + WS_DEPTH) % (WS_DEPTH + 1)] = *reinterpret_cast<const bf16x8*>(px[1] + toff[s + WS_DEPTH]);
+        }
+        acc[0] = mma_step(w[s], xf[0][s % (WS_DEPTH + 1)], acc[0]);
+        acc[1] = mma_step(w[s], xf[1][s % (WS_DEPTH + 1)], acc[1]);
+    }
+}
+
+constexpr int WS_PAIR_PATCH_MAX = 32 * 1024, WS_PAIR_MID_MAX = 32 * 1024;        // together WS_LDS_MAX: two workgroups per CU
+
+template <bool RES>
+__global__ __launch_bounds__(256, 2) void conv3x3_ws_pair_kernel(const WsPairArgs a, const WsPairGeom g)
+{
+    // TWO LDS objects, not two halves of one: the compiler makes every LDS read wait for the LDS-DMAs issued before it unless it can tell the objects apart,
+    // and with one buffer conv B's reads of the map waited for the next tile's patch to land (s_waitcnt vmcnt(0) behind the DMA issue, in every tile)
+    __shared__ __attribute__((aligned(16))) unsigned char lpatch[WS_PAIR_PATCH_MAX];
+    __shared__ __attribute__((aligned(16))) unsigned char lmid[WS_PAIR_MID_MAX];
+    constexpr int NKS = 18, PITCH = 160, UPITCH = PITCH / 16, UPP = 8;     // k-steps per conv; pixel pitch in bytes / in 16-byte units; units that hold channels
+    typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+    const int PWA = g.TW + 4, PHA = g.TH + 4;                    // input patch
+    const int MW = g.TW + 8, NRT = g.TH + 2;                     // row pitch of the intermediate map in pixels; its rows = conv A's row tiles
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int p = lane & 15, kq = lane >> 4;
+    const int ch0 = tile_channel(wave, kq, 4);                   // this lane's first output channel, of both convs
+    const int NPB = g.TH * g.TW, nct = (NPB + 15) >> 4;          // conv B: pixels / 16-pixel column tiles of a tile
+    const int tiles_per_img = g.tiles_x * g.tiles_y;
+    const float invPWA = 1.0f / (float)PWA, invTW = 1.0f / (float)g.TW, inv_upitch = 1.0f / (float)UPITCH;
+    const bf16_t* __restrict__ in = static_cast<const bf16_t*>(a.in) + a.in_co;
+    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(in), 0, (unsigned)(((size_t)a.n * a.H * a.W * a.in_cs - a.in_co) * 2), 0x00020000);
+    const unsigned npx = (unsigned)((size_t)a.n * a.H * a.W);
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, npx * (unsigned)a.out_cs * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.res ? a.res : a.out), 0, npx * (unsigned)(a.res ? a.res_cs : a.out_cs) * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rmid = __builtin_amdgcn_make_buffer_rsrc(a.mid ? a.mid : a.out, 0, npx * (unsigned)(a.mid ? a.mid_cs : a.out_cs) * 2, 0x00020000);
+    const bool dump = a.mid != nullptr;
+
+    // patch staging by LDS-DMA, as conv3x3_ws_kernel's: the patch's origin is two pixels up and left of the tile
+    const int NLU = PHA * PWA * UPITCH, ndma = (NLU + 63) >> 6;
+    auto dma_patch = [&](int tl) {
+        const int b = tl / tiles_per_img;
+        const int r = tl - b * tiles_per_img;
+        const int ty = r / g.tiles_x;
+        const int y0 = ty * g.TH, x0 = (r - ty * g.tiles_x) * g.TW;
+        for (int k = wave; k < ndma; k += 4) {
+            const int u = k * 64 + lane;
+            const int px = (int)(((float)u + 0.5f) * inv_upitch), part = u - px * UPITCH;
+            const int py = (int)(((float)px + 0.5f) * invPWA), pxx = px - py * PWA;
+            const int gy = y0 - 2 + py, gx = x0 - 2 + pxx;
+            const bool ok = part < UPP && py < PHA && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
+            const unsigned off = ok ? (unsigned)((((b * a.H + gy) * a.W + gx) * a.in_cs) * 2 + part * 16) : 0x80000000u;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (__attribute__((address_space(3))) void*)(lpatch + k * 1024), 16, off, 0, 0, 0);
+        }
+    };
+    if ((int)blockIdx.x < g.total_tiles) dma_patch(blockIdx.x);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- this wave's weights of both convs, resident in registers for the workgroup's lifetime: conv A's (and the biases) first, conv B's LAST -- the
+    //      wait in front of the first tile counts on conv B's 18 loads being the youngest ----
+    const f32x4 biasA = *reinterpret_cast<const f32x4*>(a.bA + ch0);        // in FRONT of the weights: whoever waits for it (the row-pair loop's entry) then waits for nothing younger
+    bf16x8 wA[NKS], wB[NKS];
+    {
+        const bf16_t* __restrict__ wb = static_cast<const bf16_t*>(a.wA) + (size_t)wave * NKS * 512 + lane * 8;
+#pragma unroll
+        for (int s = 0; s < NKS; ++s) wA[s] = *reinterpret_cast<const bf16x8*>(wb + s * 512);
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    {
+        const bf16_t* __restrict__ wb = static_cast<const bf16_t*>(a.wB) + (size_t)wave * NKS * 512 + lane * 8;
+#pragma unroll
+        for (int s = 0; s < NKS; ++s) wB[s] = *reinterpret_cast<const bf16x8*>(wb + s * 512);
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+
+    // tap offsets of the k-steps (wave-uniform), k-step s = tap * 2 + chunk: inside the patch (conv A) and inside the map (conv B)
+    int toffA[NKS], toffB[NKS];
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+        const int tap = s >> 1, chunk = s & 1;
+        const int ky = tap / 3, kx = tap - ky * 3;
+        toffA[s] = (ky * PWA + kx) * PITCH + chunk * 64;
+        toffB[s] = (ky * MW + kx) * PITCH + chunk * 64;
+    }
+
+#ifdef ZLY_WS_DIAG
+    unsigned long long dsum[4] = {0, 0, 0, 0}, dT0 = 0, dT1 = 0;     // tools/ws_pair_bench.hip: patch + conv A's weights + barrier | conv A | barrier + next-patch DMA issue | conv B
+    const unsigned long long dstart = __builtin_amdgcn_s_memtime();
+    WSSTAMP(dT0);
+#endif
+    bool first = true;
+    for (int tl = blockIdx.x; tl < g.total_tiles; tl += gridDim.x) {
+        const int b = tl / tiles_per_img;
+        const int r = tl - b * tiles_per_img;
+        const int ty = r / g.tiles_x;
+        const int y0 = ty * g.TH, x0 = (r - ty * g.tiles_x) * g.TW;
+        // conv B's bias is fetched per tile (16 bytes per lane, consumed behind conv A): with every load in front of the loop and none in it whose result
+        // the loop uses, the compiler waits for ALL of them before it enters the loop -- conv B's weights too
+        f32x4 biasB = *reinterpret_cast<const f32x4*>(a.bB + ch0);
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        // this wave's pieces of the patch have landed: in front of the first tile everything but conv B's weights (the 18 youngest loads), later
+        // everything (the previous tile's stores too)
+        if (first) asm volatile("s_waitcnt vmcnt(19)" ::: "memory");       // conv B's 18 weight loads and this tile's bias
+        else       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        first = false;
+        __syncthreads();                                        // everybody's have, and everybody is done reading the previous tile's map
+        WSPHASE(0);
+
+        // ---- conv A: region rows two at a time, the epilogue of a pair beside the MFMAs of the next (conv3x3_ws_kernel's pipeline) ----
+        {
+            auto setup = [&](int t0, const unsigned char* (&px)[2], int (&lo)[2], unsigned (&msk)[2], int (&db)[2]) {
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    const int rr = min(t0 + h2, NRT - 1);       // a missing second row: the last one once more, written twice with the same values
+                    px[h2] = lpatch + (rr * PWA + p) * PITCH + kq * 16;
+                    lo[h2] = (rr * MW + p) * PITCH + ch0 * 2;
+                    const int gy = y0 - 1 + rr, gx = x0 - 1 + p;
+                    const bool inside = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
+                    msk[h2] = inside ? 0xffffffffu : 0u;
+                    const bool interior = inside && rr >= 1 && rr <= g.TH && p >= 1 && p <= g.TW;
+                    db[h2] = interior ? (((b * a.H + gy) * a.W + gx) * a.mid_cs + a.mid_co + ch0) * 2 : (int)0x80000000;
+                }
+            };
+            auto store = [&](const f32x4 (&acc)[2], const int (&lo)[2], const unsigned (&msk)[2], const int (&db)[2]) {
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    f32x4 o = acc[h2] + biasA;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = silu<bf16_t>(o[k]);
+                    u32x2 bits = __builtin_bit_cast(u32x2, to_bf16x4(o));
+                    bits[0] &= msk[h2]; bits[1] &= msk[h2];     // outside the frame: conv B's zero padding
+                    *reinterpret_cast<u32x2*>(lmid + lo[h2]) = bits;
+                    if (dump) __builtin_amdgcn_raw_buffer_store_b64(bits, rmid, db[h2], 0, 0);      // wave-uniform
+                }
+            };
+            const unsigned char* pxa[2];
+            int loa[2], dba[2];
+            unsigned mka[2];
+            f32x4 acca[2];
+            setup(0, pxa, loa, mka, dba);
+            ws_pair_mma(wA, pxa, toffA, acca);
+            for (int t0 = 2; t0 < NRT; t0 += 2) {
+                const unsigned char* pxb[2];
+                int lob[2], dbb[2];
+                unsigned mkb[2];
+                f32x4 accb[2];
+                setup(t0, pxb, lob, mkb, dbb);
+                store(acca, loa, mka, dba);
+                ws_pair_mma(wA, pxb, toffA, accb);
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) { loa[h2] = lob[h2]; mka[h2] = mkb[h2]; dba[h2] = dbb[h2]; acca[h2] = accb[h2]; }
+            }
+            store(acca, loa, mka, dba);
+        }
+        WSPHASE(1);
+        __syncthreads();                                        // the map is complete, and everybody is done reading the patch
+        // conv B's weights and bias are waited for HERE, in front of the next patch's DMA: an empty statement that names the registers makes the compiler
+        // place its wait for their loads at this point (first tile: behind conv A, as intended; later tiles: only the bias is outstanding).  Left to conv
+        // B's first use, the wait would stand behind the DMA issue and cover the DMA as well.
+#pragma unroll
+        for (int s = 0; s < NKS; ++s) asm volatile("" : "+v"(wB[s]));
+        asm volatile("" : "+v"(biasB));
+        if (tl + (int)gridDim.x < g.total_tiles) dma_patch(tl + gridDim.x);        // the next tile's: lands while conv B runs (RES: until the first shortcut load, issued behind it, is needed)
+        WSPHASE(2);
+
+        // ---- conv B: the tile's column tiles two at a time, same pipeline; the epilogue of conv3x3_ws_kernel<TPW = 1> ----
+        {
+            auto setup = [&](int t0, const unsigned char* (&px)[2], int (&ob)[2], int (&rb)[2]) {
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    const int t = min(t0 + h2, nct - 1);
+                    const int q = t * 16 + p;
+                    const int qc = min(q, NPB - 1);
+                    const int oy = (int)(((float)qc + 0.5f) * invTW), ox = qc - oy * g.TW;
+                    px[h2] = lmid + (oy * MW + ox) * PITCH + kq * 16;
+                    const int gy = y0 + oy, gx = x0 + ox;
+                    const bool ok = (t0 + h2 < nct) && q < NPB && gy < a.H && gx < a.W;     // a missing second tile: computed on a copy of the last, never stored
+                    const int m = (b * a.H + gy) * a.W + gx;
+                    ob[h2] = ok ? (m * a.out_cs + a.out_co + ch0) * 2 : (int)0x80000000;
+                    rb[h2] = ok ? (m * a.res_cs + a.res_co + ch0) * 2 : (int)0x80000000;
+                }
+            };
+            auto store = [&](const f32x4 (&acc)[2], const int (&ob)[2], const int (&rb)[2]) {
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    f32x4 o = acc[h2] + biasB;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = silu<bf16_t>(o[k]);
+                    f32x4 x = o;
+                    if (RES) {
+                        const bf16x4 rv = __builtin_bit_cast(bf16x4, __builtin_amdgcn_raw_buffer_load_b64(rres, rb[h2], 0, 0));
+                        x += f32x4{(float)rv[0], (float)rv[1], (float)rv[2], (float)rv[3]};
+                    }
+                    const bf16x4 wv = to_bf16x4(x);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, wv), rout, ob[h2], 0, 0);
+                }
+            };
+            const unsigned char* pxa[2];
+            int oba[2], rba[2];
+            f32x4 acca[2];
+            setup(0, pxa, oba, rba);
+            ws_pair_mma(wB, pxa, toffB, acca);
+            for (int t0 = 2; t0 < nct; t0 += 2) {
+                const unsigned char* pxb[2];
+                int obb[2], rbb[2];
+                f32x4 accb[2];
+                setup(t0, pxb, obb, rbb);
+                store(acca, oba, rba);
+                ws_pair_mma(wB, pxb, toffB, accb);
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) { oba[h2] = obb[h2]; rba[h2] = rbb[h2]; acca[h2] = accb[h2]; }
+            }
+            store(acca, oba, rba);
+        }
+        WSPHASE(3);
+    }
+#ifdef ZLY_WS_DIAG
+    if (lane == 0 && g_ws_diag) {
+        unsigned long long* o = g_ws_diag + ((size_t)blockIdx.x * 4 + wave) * 8;
+        for (int k = 0; k < 4; ++k) o[k] = dsum[k];
+        o[4] = __builtin_amdgcn_s_memtime() - dstart;
+    }
+#endif
+}
+
+// ------------------------------------------------------------------------------------------------
 // The 80 -> 80 class-branch convs of Detect (model.22.cv3.L.1; nc = 80), weight-stationary with K PACKED ACROSS TAPS.
 //
 // Round 3 ran them on conv3x3_lds_kernel with the input stored as 96 channels and a sixth, all-zero output tile (27 k-steps x 6 tiles): 31 % of its
@@ -1378,6 +1646,70 @@ static bool ws_plan(int H, int W, int cin, int n, int ncu, WsGeom* g, int stride
     if (best < 0) return false;
     g->pitch = pitch; g->nchunks = cin / 32;
     return true;
+}
+
+// The fused pair's tile: TW <= 14 (a region row of TW + 2 pixels is one MFMA tile), patch (rounded to whole 1 KiB DMA pieces) + map within WS_LDS_MAX so that
+// two workgroups stay resident per CU; among those the least work on the busiest workgroup, as ws_plan -- per tile TH + 2 row tiles of conv A, the column
+// tiles of conv B and a fixed cost.  26 x 26 at batch 64: 7 x 13, 512 tiles of 10 + 6 MFMA tiles (nine region rows in pairs).
+static bool ws_pair_tiles(int H, int W, int n, int ncu, WsPairGeom* g, unsigned* lds)
+{
+    long best = -1;
+    for (int th = 4; th <= 32; ++th)
+        for (int tw = 8; tw <= 14; ++tw) {
+            const long patch = ((long)(th + 4) * (tw + 4) * 160 + 1023) / 1024 * 1024, mid = (long)(th + 2) * (tw + 8) * 160;
+            if (patch + 1024 > WS_PAIR_PATCH_MAX || mid > WS_PAIR_MID_MAX) continue;      // + 1024: conv A's lanes beyond the region read up to six pixels past the patch
+            const int tx = (W + tw - 1) / tw, ty = (H + th - 1) / th;
+            const long tiles = (long)tx * ty * n;
+            const long rounds = (tiles + 2 * ncu - 1) / (2 * ncu);
+            const long key = rounds * ((th + 2) * 16 + (th * tw + 15) / 16 * 16 + 64) * 65536 + patch + mid;
+            if (best < 0 || key < best) { best = key; g->TH = th; g->TW = tw; g->tiles_x = tx; g->tiles_y = ty; *lds = (unsigned)(WS_PAIR_PATCH_MAX + WS_PAIR_MID_MAX); }
+        }
+    return best >= 0;
+}
+
+typedef void (*conv_ws_pair_fn)(const WsPairArgs, const WsPairGeom);
+
+// Taken only where BOTH convs would on their own be the weight-stationary kernel: the pair so inherits plan_ws's pixel-count gate (ws_min_tiles), its
+// tile-utilisation test and its 2 GiB / ws_max_bytes fall-back (32-bit byte offsets here too), and is never planned where it would refuse at launch.
+bool conv_ws_pair_plan(const ConvArgs& a, const ConvArgs& b, const ConvPlan& pa, const ConvPlan& pb, const Switches& sw, WsPairPlan* plan)
+{
+    if (!sw.ws_pair || pa.kind != CONV_WS || pb.kind != CONV_WS) return false;
+    if (pa.rowt || pb.rowt) return false;                        // ZLY_WS_ROWT asks for conv3x3_ws_kernel's row-tile form: the pair replaces its default forms only
+    if (a.Cin != 64 || a.Cout != 64 || a.cout_pad != 64 || a.nk != 18 || b.Cin != 64 || b.Cout != 64 || b.cout_pad != 64 || b.nk != 18) return false;
+    if (a.stride != 1 || b.stride != 1 || a.pad != 1 || b.pad != 1 || !a.act || !b.act || a.res || a.in2 || b.in2 || a.out_f32 || b.out_f32) return false;
+    if (a.H != a.Ho || a.W != a.Wo || b.H != a.H || b.W != a.W || b.Ho != a.H || b.Wo != a.W || a.M != b.M) return false;
+    if (b.in != a.out || b.in_cs != a.out_cs || b.in_co != a.out_co) return false;      // conv B reads what conv A writes
+    if (a.out_cs % 4 || a.out_co % 4 || b.out_cs % 4 || b.out_co % 4 || (b.res && (b.res_cs % 4 || b.res_co % 4))) return false;     // 8-byte stores / loads
+    const int n = a.M / (a.Ho * a.Wo);
+    WsPairPlan p{};
+    if (!ws_pair_tiles(a.H, a.W, n, sw.num_cus, &p.g, &p.lds)) return false;
+    p.g.total_tiles = p.g.tiles_x * p.g.tiles_y * n;
+    // At most two tiles per resident workgroup (ZLY_WS_PAIR_MAX_TILES).  What the pair saves is fixed per launch (a boundary, a weight prologue, a patch wait); what
+    // it costs grows with the map: conv A's halo rows are a third more MFMA work than the two launches do (7 x 13 tiles: 10 + 6 MFMA tiles against 2 x 6).  Chains
+    // of 20 bottlenecks back to back (tools/ws_pair_bench.hip, profiles/r05_ws_pair_kernel_phase_stamps.txt), two launches -> pair: 26 x 26 x 64 frames (1 tile per
+    // workgroup) 18.20 -> 15.34 us, 26 x 26 x 16 11.54 -> 9.63, 40 x 40 x 32 (1.9 tiles) 20.00 -> 18.33, 40 x 40 x 48 (2.0) 25.36 -> 23.24, but 40 x 40 x 64
+    // (3 tiles) 29.97 -> 31.96 and 80 x 80 x 32 (5 tiles) 50.19 -> 54.52 us.
+    if (p.g.total_tiles > (long)sw.ws_pair_max_tiles * 2 * sw.num_cus) return false;
+    int gx = p.g.total_tiles < 2 * sw.num_cus ? p.g.total_tiles : 2 * sw.num_cus;       // persistent: two resident workgroups per CU
+    if (sw.ws_pair_grid > 0 && gx > sw.ws_pair_grid) gx = sw.ws_pair_grid;
+    p.gx = (unsigned)gx;
+    p.fn = b.res ? (const void*)conv3x3_ws_pair_kernel<true> : (const void*)conv3x3_ws_pair_kernel<false>;
+    *plan = p;
+    return true;
+}
+
+hipError_t launch_conv_ws_pair(const ConvArgs& a, const ConvArgs& b, const WsPairPlan& plan, bool dump, hipStream_t s)
+{
+    if (!plan.fn || plan.gx < 1) return hipErrorInvalidValue;
+    WsPairArgs pa{};
+    pa.in = a.in; pa.in_cs = a.in_cs; pa.in_co = a.in_co;
+    pa.wA = a.wgt; pa.bA = a.bias; pa.wB = b.wgt; pa.bB = b.bias;
+    pa.H = a.H; pa.W = a.W; pa.n = a.M / (a.Ho * a.Wo);
+    pa.out = b.out; pa.out_cs = b.out_cs; pa.out_co = b.out_co;
+    pa.res = b.res; pa.res_cs = b.res_cs; pa.res_co = b.res_co;
+    if (dump) { pa.mid = a.out; pa.mid_cs = a.out_cs; pa.mid_co = a.out_co; }
+    hipLaunchKernelGGL(reinterpret_cast<conv_ws_pair_fn>(const_cast<void*>(plan.fn)), dim3(plan.gx), dim3(256), 0, s, pa, plan.g);      // static LDS (plan.lds)
+    return hipGetLastError();
 }
 
 hipError_t ws_init()

@@ -117,6 +117,9 @@ struct Switches {
     int  ws_tpw1_maxct = 6;         // ZLY_WS_TPW1_MAXCT: 64 -> 64 as 4 waves x one tile on pixel tiles of up to this many column tiles (0 = never)
     long ws_min_tiles = 64;         // ZLY_WS_MIN_TILES: fewest 13 x 13 tiles' worth of pixels it (and the K-packed kernel) takes
     size_t ws_max_bytes = (size_t)1 << 31;  // ZLY_WS_MAX_BYTES: tensors of this size or more take the LDS-tiled / direct kernel (32-bit offsets; tests lower it)
+    int  ws_pair = 1;               // ZLY_WS_PAIR: a 64-channel bottleneck whose two 3x3 convs both plan as the weight-stationary kernel runs as one launch of conv3x3_ws_pair_kernel (0 = the two launches)
+    int  ws_pair_max_tiles = 2;     // ZLY_WS_PAIR_MAX_TILES: most tiles per resident workgroup (two per CU) for which it is planned; larger launches keep the two kernels
+    int  ws_pair_grid = 0;          // ZLY_WS_PAIR_GRID: most workgroups of its persistent grid (tests: every workgroup walks several tiles; 0 = two per CU)
     bool no_wres = false;           // ZLY_NO_WRES: LDS-tiled kernel without resident weights
     int  wres_maxchunks = 1;        // ZLY_WRES_MAXCHUNKS: most 32-channel chunks whose weights stay resident
     bool lds_s2_pt1 = false;        // ZLY_LDS_S2_PT1: 4-row tiles at stride 2
@@ -159,6 +162,21 @@ struct WskPlan { WsGeom g; unsigned gx, lds; };
 bool       conv_wsk_ok(const ConvArgs& a, const Switches& sw, WskPlan* plan);     // does launch_conv_wsk take this launch?  (fills the plan if so)
 hipError_t launch_conv_wsk(const ConvArgs& a, const WskPlan& plan, hipStream_t s);
 int        conv_kstep(int dtype);
+// a 64-channel bottleneck's two 3x3 convs as one weight-stationary launch (kernels_conv.hip: conv3x3_ws_pair_kernel); the intermediate map stays in LDS
+struct WsPairArgs {
+    const void* in;  int in_cs, in_co;        // x (NHWC view)
+    const void* wA;  const float* bA;         // first conv: weights as the generic convs tile them ([4 tiles][18 k-steps][lane][8], pair-permuted rows)
+    const void* wB;  const float* bB;         // second conv
+    int H, W, n;
+    void* out;       int out_cs, out_co;
+    const void* res; int res_cs, res_co;      // the RES instantiation: added to the output after the activation (the bottleneck's shortcut)
+    void* mid;       int mid_cs, mid_co;      // debug taps: the first conv's output view, written as well when set (null: the map stays in LDS)
+};
+struct WsPairGeom { int TH, TW, tiles_x, tiles_y, total_tiles; };
+struct WsPairPlan { WsPairGeom g; unsigned gx, lds; const void* fn; };
+// do convs a, b (their own launches planned as pa, pb) run as one pair launch?  Only where both would be the weight-stationary kernel; fills the plan if so
+bool       conv_ws_pair_plan(const ConvArgs& a, const ConvArgs& b, const ConvPlan& pa, const ConvPlan& pb, const Switches& sw, WsPairPlan* plan);
+hipError_t launch_conv_ws_pair(const ConvArgs& a, const ConvArgs& b, const WsPairPlan& plan, bool dump, hipStream_t s);
 
 // kernels_pair.hip -- a C2f bottleneck (two 3x3 convs, c -> c -> c, optional shortcut) as one kernel; bf16, c = 16 / 32
 struct PairArgs {
