@@ -102,6 +102,7 @@ struct DetectTail {
     HeadArgs args{};                   // the launch template: the weight / activation pointers are set once the blob and the buffers are on the device
     int op[3] = {-1, -1, -1};          // the tail op of each level
     int box[3] = {-1, -1, -1}, cls[3] = {-1, -1, -1}, logits[3] = {-1, -1, -1};     // buffers the tail reads / (ZLY_FLAG_DUMP_LOGITS) writes per level
+    int stem[3] = {-1, -1, -1};        // the level's Detect stem buffer: what the tail reads instead of box[] where it computes cv2.L.1 itself (Launch::box_mode)
     size_t wb[3] = {}, bb[3] = {}, wc[3] = {}, bc[3] = {};                          // final 1x1 weights / biases in the weight blob
 };
 
@@ -141,6 +142,7 @@ struct Launch {
     WsPairPlan ws_pair{};              // LK_WS_PAIR
     int multi_ct = 0;                  // LK_MULTI: 3 = the three Detect stems, 2 = the six Detect branch convs
     int only_level = -1;               // LK_HEAD: -1 = all three levels, else that level only
+    int box_mode[3] = {0, 0, 0};       // LK_HEAD: per level, HeadLevel::box_mode -- the tail computes the box branch's second conv itself, at surviving anchors (tail_box_mode)
     bool pool16 = false;               // LK_SPPF_POOL: sppf_pool16_kernel (else sppf_pool_kernel)
     bool lb = false;                   // front kernels and LK_HEAD of a letterbox engine (ZLY_FLAG_LETTERBOX): the LB instantiation (kernels_lb.hip)
 };
@@ -256,6 +258,8 @@ static void read_switches(Switches* sw)
     sw->no_c2f = on("ZLY_NO_C2F");
     sw->no_det_merge = on("ZLY_NO_DET_MERGE");
     sw->no_tail_split = on("ZLY_NO_TAIL_SPLIT");
+    num("ZLY_TAIL_BOX", &sw->tail_box);
+    if (const char* v = getenv("ZLY_TAIL_BOX_MIN_CONF")) sw->tail_box_min_conf = (float)atof(v);
     sw->sppf_fused = on("ZLY_SPPF_FUSED");
     sw->pool_six_pass = on("ZLY_SPPF_POOL_LDS");
     sw->no_wsk = on("ZLY_NO_WSK");
@@ -517,6 +521,7 @@ struct PlanBuilder {
         // Cin % 32 == 0 and takes the LDS-tiled kernel; the padded k-steps carry zero weights
         const int c3s = (bf16() && c3 % 32 != 0 && c2 % 32 == 0 && !sw.no_cin_pad) ? (c3 + 31) / 32 * 32 : c3;
         const int hd1 = add_buffer("detect." + L + ".stem", hl.H, hl.W, c2 + c3s);
+        t.stem[l] = hd1;
         t.box[l] = add_buffer("detect." + L + ".box2", hl.H, hl.W, c2);
         t.cls[l] = add_buffer("detect." + L + ".cls2", hl.H, hl.W, c3);
         t.logits[l] = add_buffer("detect." + L + ".logits", hl.H, hl.W, hl.logits_cs, true);
@@ -733,6 +738,11 @@ static int upload_plan(zly_engine* e, std::string* err)
         hl.wb = wb + t.wb[l]; hl.bb = (const float*)(wb + t.bb[l]);
         hl.wc = wb + t.wc[l]; hl.bc = (const float*)(wb + t.bc[l]);
         hl.logits = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? (float*)e->bufs[(size_t)t.logits[l]].ptr : nullptr;
+        // cv2.L.1's operands for the launches in which the tail computes it (Launch::box_mode): the dense op's own tiles
+        const Op& a1 = e->ops[(size_t)e->det_a[l]];
+        hl.box_mode = 0;
+        hl.w1 = wb + a1.w_off; hl.b1 = (const float*)(wb + a1.b_off);
+        hl.box2 = (e->cfg.flags & ZLY_FLAG_DUMP_LOGITS) ? e->bufs[(size_t)t.box[l]].ptr : nullptr;
     }
     return ZLY_OK;
 }
@@ -911,6 +921,28 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
     // all levels at the last tail op
     const bool tail_split = lanes_active(e, n) && !e->sw.no_tail_split;
     const int tail = e->tail.op[2];
+    // The box branch's second conv (cv2.L.1, 64 -> 64) inside the tail, at surviving anchors only (kernels_head.hip: tail_box_conv): per level, where the
+    // tail can reproduce the bits of the dense launch -- i.e. where that launch would be one of the two kernels whose k-step order it carries.
+    // conv3x3_ws_kernel (TPW = 1 and 2 alike) walks the k-steps in storage order, conv3x3_lds_kernel chunk by chunk; the row-tile form (ZLY_WS_ROWT) has a
+    // third order, the direct kernel and the merged latency-path launch stay dense.  Automatic mode: only where the tail's early-out is live, and from
+    // the confidence threshold up at which it measured no slower than the dense launch.
+    auto tail_box_mode = [&](int l) {
+        const int ai = e->det_a[l];
+        if (!bf16 || !fusion || e->sw.tail_box == 0 || ai < 0 || merge) return 0;
+        if (e->sw.tail_box != 2 && (dump || !(e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) || e->cfg.conf_thr < e->sw.tail_box_min_conf)) return 0;
+        const Op& op = e->ops[(size_t)ai];
+        const Buffer& sb = e->bufs[(size_t)e->tail.stem[l]];
+        if (op.ks != 3 || op.stride != 1 || !op.act || op.in.C != 64 || op.cout != 64 || op.cout_pad != 64 || op.nk != 18 || op.res.buf >= 0 || op.in.co != 0 || op.pair >= 0 || op.c2f >= 0) return 0;
+        if ((size_t)n * sb.H * sb.W * sb.C * 2 >= ((size_t)1 << 31)) return 0;          // the tail's pixel fragments are buffer loads with 32-bit offsets
+        ConvPlan cp{};
+        conv_plan(e->dtype, op.ks, make_conv_args(e, op, n), e->sw, &cp);
+        if (cp.ksplit > 1) return 0;
+        if (cp.kind == CONV_WS && !cp.rowt) return 1;
+        if (cp.kind == CONV_LDS) return 2;
+        return 0;
+    };
+    const int box_mode[3] = {tail_box_mode(0), tail_box_mode(1), tail_box_mode(2)};
+    auto box_level = [&](int i) { for (int l = 0; l < 3; ++l) if (i == e->det_a[l] && box_mode[l]) return l; return -1; };
 
     const bool lb = (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0;
     std::vector<Launch> t((size_t)nops);
@@ -932,7 +964,7 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
             break;
         }
         case OP_HEAD:
-            if (tail_split || op.level == 2) { L.kind = LK_HEAD; L.only_level = tail_split ? op.level : -1; }
+            if (tail_split || op.level == 2) { L.kind = LK_HEAD; L.only_level = tail_split ? op.level : -1; for (int l = 0; l < 3; ++l) L.box_mode[l] = box_mode[l]; }
             else covered(tail);
             break;
         case OP_NMS:
@@ -958,6 +990,9 @@ static const std::vector<Launch>& resolve_launches(zly_engine* e, int n)
                 L.hbm = dump;
             } else if (sppf && i == e->sppf_cv2) {
                 covered(e->sppf_cv1);
+            } else if (box_level(i) >= 0) {
+                covered(tail_split ? e->tail.op[box_level(i)] : tail);
+                L.hbm = dump;                                               // computed where a wave survives the tail's early-out; with the dump flag at every anchor, and written out
             } else if (merge && merged_at(i) >= 0) {
                 if (merged_at(i) == i) { L.kind = LK_MULTI; L.multi_ct = i == e->det_stem[2] ? 3 : 2; }
                 else covered(merged_at(i));
@@ -1069,6 +1104,11 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
     case LK_HEAD: {
         HeadArgs h = e->tail.args;
         h.only_level = L.only_level;
+        for (int l = 0; l < 3; ++l) {
+            if (!L.box_mode[l]) continue;
+            const Buffer& sb = e->bufs[(size_t)e->tail.stem[l]];
+            h.lv[l].box_mode = L.box_mode[l]; h.lv[l].box_in = sb.ptr; h.lv[l].box_cs = sb.C;     // cv2.L.1's input: the stem buffer's box half (channels [0, 64))
+        }
         if (L.lb) { h.lb_tw = e->cfg.model_w; h.lb_th = e->cfg.model_h; }      // boxes are mapped out of the letterbox (the geometry comes from d_desc at run time: no graph key)
         h.head = (e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) ? nullptr : e->d_head; h.desc = e->d_desc; h.conf_thr = e->cfg.conf_thr; h.cand = e->cur_cand; h.cand_count = e->cur_count;
         return launch_head_fused(e->dtype, h, n, s);
@@ -2580,6 +2620,8 @@ int32_t zly_debug_tap(zly_engine* e, const char* name, int32_t idx, float* out, 
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused bottleneck kernel at this batch size; create the engine with ZLY_FLAG_NO_FUSION");
             case LK_WS_PAIR:
                 return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " stays in LDS inside the fused bottleneck kernel at this batch size; create the engine with ZLY_FLAG_DUMP_LOGITS or ZLY_FLAG_NO_FUSION");
+            case LK_HEAD:
+                return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("tap ") + name + " is computed inside the fused Detect kernel, at surviving anchors only, at this batch size; create the engine with ZLY_FLAG_DUMP_LOGITS or ZLY_FLAG_NO_FUSION");
             }
             buf = op.out.buf; co = op.out.co + op.tap_co[(size_t)it->second.second]; C = op.tap_c[(size_t)it->second.second];
             f32 = op.out_f32 != 0;
@@ -2638,7 +2680,7 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
         case LK_C2F: k = "(fused into the C2f kernel at " + e->ops[(size_t)L.covered_by].name + ")"; break;
         case LK_SPPF_FUSED: k = "(fused into the SPPF kernel at model.9.cv1)"; break;
         case LK_MULTI: k = "(in a merged Detect launch)"; break;
-        case LK_HEAD: k = "(covered by the last tail launch)"; break;
+        case LK_HEAD: k = op.kind == OP_CONV ? "(computed in the Detect tail at surviving anchors)" : "(covered by the last tail launch)"; break;
         }
         break;
     case LK_PREPROCESS: k = L.lb ? "preprocess_kernel<LB> (letterbox)" : "preprocess_kernel"; break;
@@ -2669,7 +2711,14 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
         }
         break;
     }
-    case LK_HEAD: k = L.lb ? "head_fused_kernel<LB> (letterbox box mapping)" : "head_fused_kernel"; break;
+    case LK_HEAD: {
+        k = L.lb ? "head_fused_kernel<LB> (letterbox box mapping)" : "head_fused_kernel";
+        std::string lv;
+        for (int l = 0; l < 3; ++l)
+            if (L.box_mode[l] && (L.only_level < 0 || L.only_level == l)) lv += std::string(lv.empty() ? "" : ",") + "P" + std::to_string(3 + l) + (L.box_mode[l] == 1 ? ":ws" : ":lds");
+        if (!lv.empty()) k += " (+ box conv in k-step order " + lv + ")";
+        break;
+    }
     case LK_NMS: k = "nms_kernel"; break;
     }
     snprintf(out, cap, "%s", k.c_str());
@@ -2705,9 +2754,15 @@ int32_t zly_launch_info_at(zly_engine* e, int32_t i, int32_t n, zly_launch_info*
         if (!in_group[(size_t)j]) continue;
         const Op& op = e->ops[(size_t)j];
         out->n_ops++;
-        out->flops_per_frame += op.flops;
-        out->bytes_unfused_per_frame += op.bytes;
-        wbytes += op.wbytes;
+        // a conv the Detect tail computes at surviving anchors only: its dense flops, bytes and weights are work that is not done, and are not booked on the
+        // tail.  Its input view is: the stem buffer's box half is what the tail reads in place of the conv's output (which counts as written inside the
+        // group), booked whole -- the bound with every wave surviving; the tail reads the share that survives, plus those tiles' halo
+        const bool in_tail = op.kind == OP_CONV && j != i && t[(size_t)i].kind == LK_HEAD;
+        if (!in_tail) {
+            out->flops_per_frame += op.flops;
+            out->bytes_unfused_per_frame += op.bytes;
+            wbytes += op.wbytes;
+        }
         if (op.kind == OP_PREPROCESS) ext_in += (double)e->cfg.model_w * e->cfg.model_h * 3;          // the u8 frame (model-sized requests)
         if (op.kind == OP_HEAD && !(e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR)) ext_out += (double)e->tail.args.lv[op.level].hw * (4 + e->nc) * 4.0;
         io.clear(); op_reads(e, op, &io);
@@ -2720,6 +2775,7 @@ int32_t zly_launch_info_at(zly_engine* e, int32_t i, int32_t n, zly_launch_info*
             }
             ext_in += v.px * cext * (double)e->esz * v.scale;
         }
+        if (in_tail) continue;                                   // its output exists only under the dump flag, and nothing outside the group reads it
         io.clear(); op_writes(e, op, &io);
         for (const IoView& v : io) {
             int cext = 0;

@@ -9,6 +9,7 @@
 // round trip through HBM.  decode here and decode_kernel (kernels_post.hip, used by zly_postprocess)
 // apply the same comparisons to the same fp32 values, so both give the same candidates.
 #include "zly_internal.h"
+#include "conv_device.h"
 #include "letterbox_device.h"
 #include <algorithm>
 #include <math.h>
@@ -16,9 +17,6 @@
 #pragma clang fp contract(off)
 
 namespace zly {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 template <typename T> struct HFrag;
 template <> struct HFrag<bf16_t> { typedef bf16x8 type; static constexpr int EPL = 8; static constexpr int KSTEP = 32; };
@@ -45,6 +43,72 @@ template <typename T> __device__ __forceinline__ float h_div(float a, float b);
 template <> __device__ __forceinline__ float h_div<float>(float a, float b) { return a / b; }
 template <> __device__ __forceinline__ float h_div<bf16_t>(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
+// The box branch's second 3x3 conv (model.22.cv2.L.1, 64 -> 64, SiLU) for the 16 anchors of ONE surviving wave (HeadLevel::box_mode): the dense
+// launch computes it at every anchor and the tail then reads the few percent of it that pass the early-out.  `rstem` is the level's Detect stem
+// buffer, whose first 64 channels are the conv's input (pixel pitch box_cs elements); `ok` masks this lane's anchor.
+//   * 9 taps x 2 chunks of 32 channels = 18 k-steps x 4 channel tiles = 72 MFMAs.  A lane's pixel fragment of tap (ky, kx) is one 16-byte buffer
+//     load at (y + ky - 1, x + kx - 1); a neighbour outside the map (and every tap of a masked lane) takes the out-of-range offset and reads
+//     zeros -- the conv's zero padding, with no branch around a load.  A tile may span several map rows: every lane has its own (y, x).
+//   * the weights are the dense op's own tiles (tile c, k-step s = tap * 2 + chunk: 1 KiB in MFMA lane order), read straight from L2.
+//   * fp32 accumulation ORDER is that of the dense kernel the planner would have launched, so the result has its bits: box_mode 1 =
+//     conv3x3_ws_kernel (k-steps in storage order: tap outer, chunk inner), 2 = conv3x3_lds_kernel (chunk outer, tap inner).  The order is
+//     wave-uniform: step i's tap / chunk / weight tile are scalar selects between two compile-time constants, the registers statically indexed.
+//   * bias + silu<bf16_t> + round to bf16 exactly as epilogue_px_buf / conv3x3_ws_kernel's pair_store.  With the dense op's pair-permuted rows
+//     lane (p, kq) holds channels g * 32 + kq * 8 + {0..3} in tile 2g and + {4..7} in tile 2g + 1: tiles (2g, 2g + 1) ARE the B fragment of
+//     k-step g of the box GEMM, no transpose.
+// Fragments are requested BOXC_DEPTH k-steps ahead of the MFMAs that consume them (statically indexed ring): loads return in order, so each
+// step waits with a vmcnt that leaves the younger requests in flight.
+#define BOXC_DEPTH 2
+#ifdef ZLY_HEAD_DIAG
+__device__ unsigned long long* g_head_diag = nullptr;            // diagnostic build only (tools/head_bench.hip): cycles in tail_box_conv, one slot per wave of the grid
+#define HSTAMP(t) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#endif
+__device__ __forceinline__ void tail_box_conv(const HeadLevel& L, const __amdgpu_buffer_rsrc_t rstem, int pixoff, int an, bool ok, int lane, int kq, bf16x8 (&xb)[2])
+{
+    const int y = an / L.W, x = an - y * L.W;
+    const bool ws = L.box_mode == 1;
+    unsigned toff[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int ky = t / 3 - 1, kx = t % 3 - 1;
+        const bool in = ok && (unsigned)(y + ky) < (unsigned)L.H && (unsigned)(x + kx) < (unsigned)L.W;
+        toff[t] = in ? (unsigned)(pixoff + ((ky * L.W + kx) * L.box_cs + kq * 8) * 2) : 0x80000000u;
+    }
+    const bf16_t* w = static_cast<const bf16_t*>(L.w1) + lane * 8;
+    bf16x8 xp[BOXC_DEPTH], wf[BOXC_DEPTH][4];
+    auto request = [&](int i, bf16x8& px, bf16x8 (&wt)[4]) {
+        const unsigned off = ws ? toff[i / 2] + (unsigned)(i % 2) * 64u : toff[i % 9] + (unsigned)(i / 9) * 64u;      // an out-of-range offset stays out of range
+        const int s = ws ? i : (i % 9) * 2 + i / 9;
+        px = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rstem, (int)off, 0, 0));
+#pragma unroll
+        for (int c = 0; c < 4; ++c) wt[c] = *reinterpret_cast<const bf16x8*>(w + (size_t)(c * 18 + s) * 512);
+    };
+    f32x4 acc[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < BOXC_DEPTH; ++i) request(i, xp[i], wf[i]);
+    f32x4 bias[4];
+#pragma unroll
+    for (int i = 0; i < 18; ++i) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = mma_step(wf[i % BOXC_DEPTH][c], xp[i % BOXC_DEPTH], acc[c]);
+        if (i + BOXC_DEPTH < 18) request(i + BOXC_DEPTH, xp[i % BOXC_DEPTH], wf[i % BOXC_DEPTH]);
+        if (i + BOXC_DEPTH == 18) {                        // the ring starts to drain: the bias takes the registers it frees (requested earlier it cost the kernel a resident workgroup)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) bias[c] = *reinterpret_cast<const f32x4*>(L.b1 + tile_channel(c, kq, 4));
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        acc[c] = acc[c] + bias[c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[c][r] = silu<bf16_t>(acc[c][r]);
+    }
+    xb[0] = to_bf16x8(acc[0], acc[1]);
+    xb[1] = to_bf16x8(acc[2], acc[3]);
+}
+
 // A workgroup (HEAD_WAVES = 8 waves) owns HEAD_GROUP = 128 consecutive anchors of one level of one frame, one wave per 16 anchors (MFMA
 // columns): lane (p = lane & 15, kq = lane >> 4) ends up holding, for every 16-channel tile c, channels c*16 + kq*4 + {0..3} of anchor p.
 // What the ablation showed (tools/head_bench.hip, profiles/r03_head_kernel_ablation.txt; 36.6 us for the batch-64 tail): 11.5 us are the
@@ -59,7 +123,7 @@ template <> __device__ __forceinline__ float h_div<bf16_t>(float a, float b) { r
 // LB: the instantiation of a letterbox engine (include/zly.h ZLY_FLAG_LETTERBOX): a surviving anchor's box is mapped out of the letterbox -- its
 // geometry recomputed from the frame descriptor, for survivors only -- instead of divided by the request size.  Compiled in kernels_lb.hip.
 template <typename T, int CTC, bool LB = false>
-__global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(const HeadArgs a)
+__global__ __launch_bounds__(HEAD_WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void head_fused_kernel(const HeadArgs a)
 {
     typedef typename HFrag<T>::type F;
     constexpr int EPL = HFrag<T>::EPL, KSTEP = HFrag<T>::KSTEP, WTILE = 16 * KSTEP;
@@ -162,6 +226,7 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(const HeadA
             }
         }
     }
+    bool sel = true;                                       // production mode: this lane's anchor can reach the threshold (a box is read only where it does)
     if (a.head == nullptr && L.logits == nullptr) {
         float zmax = -3.0e38f;
 #pragma unroll
@@ -174,6 +239,7 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(const HeadA
         zmax = fmaxf(zmax, __shfl_xor(zmax, 16));
         zmax = fmaxf(zmax, __shfl_xor(zmax, 32));
         if (__ballot(valid && zmax >= a.skip_logit) == 0ull) return;
+        sel = zmax >= a.skip_logit;
     }
     // ---- box branch: [64 x cin] . [cin x 16] ----------------------------------------------------
     f32x4 accb[4];
@@ -182,7 +248,36 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void head_fused_kernel(const HeadA
     {
         F xb[KMAX];
         const T* pb = static_cast<const T*>(L.box_in) + pix * L.box_cs;
-        if (a.buf32) {
+        bool conv_here = false;
+        if constexpr (sizeof(T) == 2) conv_here = L.box_mode != 0;              // wave-uniform; launch_head_fused refuses the mode without a.buf32
+        if (conv_here) {
+            if constexpr (sizeof(T) == 2) {
+                // box_in is cv2.L.1's INPUT (the Detect stem's box half): the surviving wave computes the conv for its own 16 anchors
+                bf16x8 xc2[2];
+#ifdef ZLY_HEAD_DIAG
+                unsigned long long dT0 = 0, dT1 = 0;
+                HSTAMP(dT0);
+#endif
+                tail_box_conv(L, rbox, (int)(pix * L.box_cs * 2), an, valid && sel, lane, kq, xc2);
+#ifdef ZLY_HEAD_DIAG
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                HSTAMP(dT1);
+                if (lane == 0 && g_head_diag) g_head_diag[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * HEAD_WAVES + wave] = dT1 - dT0;      // a slot per wave: zero = did not run the conv
+#endif
+#pragma unroll
+                for (int s = 0; s < KMAX; ++s) xb[s] = s < 2 ? xc2[s < 2 ? s : 0] : zero;
+                // the class biases are fetched again rather than kept across the conv: 20 registers at the kernel's widest point, i.e. 2 -> 1 resident workgroups per CU
+                const float* bc2 = L.bc;
+                asm volatile("" : "+s"(bc2));
+#pragma unroll
+                for (int c = 0; c < CTC; ++c) bcls[c] = *reinterpret_cast<const f32x4*>(bc2 + c * 16 + kq * 4);
+                if (L.box2 && valid) {                                          // debug taps (ZLY_FLAG_DUMP_LOGITS): the conv's output as the dense launch writes it
+                    bf16_t* o = static_cast<bf16_t*>(L.box2) + pix * 64 + kq * 8;
+                    *reinterpret_cast<bf16x8*>(o) = xc2[0];
+                    *reinterpret_cast<bf16x8*>(o + 32) = xc2[1];
+                }
+            }
+        } else if (a.buf32) {
 #pragma unroll
             for (int s = 0; s < KMAX; ++s) {
                 const int ci = s * KSTEP + kq * EPL;
@@ -350,6 +445,8 @@ hipError_t launch_head_fused(int dtype, const HeadArgs& a0, int n, hipStream_t s
         const size_t el = dtype == ZLY_DTYPE_BF16 ? 2 : 4;
         if ((size_t)n * a.lv[l].hw * (size_t)std::max(a.lv[l].box_cs, a.lv[l].cls_cs) * el >= ((size_t)1 << 31)) a.buf32 = 0;      // 32-bit offsets would not reach: pointer loads
     }
+    for (int l = 0; l < 3; ++l)
+        if (a.lv[l].box_mode && (dtype != ZLY_DTYPE_BF16 || !a.buf32 || a.lv[l].box_mode > 2 || a.lv[l].box_cin != 64 || a.lv[l].nkb != 2)) return hipErrorInvalidValue;      // the tail's own box conv: bf16, 64 channels, 32-bit offsets (the planner's gate)
     const int blocks = a.only_level >= 0 ? (a.lv[a.only_level].hw + HEAD_GROUP - 1) / HEAD_GROUP : a.total_blocks;
     hipLaunchKernelGGL(fn, dim3(blocks, n), dim3(HEAD_WAVES * 64), lds, s, a);
     return hipGetLastError();

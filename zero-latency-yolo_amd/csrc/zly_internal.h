@@ -80,6 +80,11 @@ struct Switches {
     bool no_c2f = false;            // ZLY_NO_C2F: no fused C2f kernel
     bool no_det_merge = false;      // ZLY_NO_DET_MERGE: the Detect convs as launches of their own at batch <= 4 too
     bool no_tail_split = false;     // ZLY_NO_TAIL_SPLIT: one Detect tail launch for all levels also with side streams
+    int  tail_box = 1;              // ZLY_TAIL_BOX: the box branch's second conv (cv2.L.1) inside the Detect tail, at surviving anchors only: 0 = never, 1 = where the tail's early-out is
+                                    // live (no head tensor, no logit dump) and conf_thr >= tail_box_min_conf, 2 = wherever the dense launch's k-step order can be reproduced (tests)
+    float tail_box_min_conf = 0.05f;    // ZLY_TAIL_BOX_MIN_CONF: lowest confidence threshold at which the automatic mode takes it (the tail's cost per surviving tile is a multiple of the dense kernel's).
+                                    // 0.05 is the lowest threshold tried, NOT a measured break-even: from 0.25 down nearly every wave survives and the step is 2-4 ms of NMS, in which
+                                    // the tail's growth could not be told from noise (profiles/r06_ab_tail_box.txt; the tail alone per surviving fraction: r06_head_bench_tail_box.txt)
     bool sppf_fused = false;        // ZLY_SPPF_FUSED: the fused SPPF kernel (opt-in: 36 -> ~24 us in isolation at batch 64, but the step gets 0.5 % slower)
     bool pool_six_pass = false;     // ZLY_SPPF_POOL_LDS: SPPF's pools on the six-pass LDS kernel also on small maps
     bool no_wsk = false;            // ZLY_NO_WSK: the class-branch convs on the LDS-tiled kernel (96-channel padding)
@@ -284,6 +289,12 @@ struct HeadLevel {
     int nkb, nkc;                             // k-steps of the two GEMMs
     int H, W, hw, stride_px, anchor_off, block0;
     float* logits; int logits_cs;             // optional fp32 [n][H*W][logits_cs] dump (debug taps), or null
+    // box_mode != 0 (bf16; set per launch by the planner, engine.cpp: tail_box_mode): box_in is not cv2.L.1's output but its INPUT, the box half of the level's
+    // Detect stem buffer (box_cs = that buffer's pixel pitch), and a wave that survives the early-out computes the 64 -> 64 3x3 conv for its own 16 anchors
+    // (kernels_head.hip: tail_box_conv) in the k-step order of the dense kernel it stands in for: 1 = conv3x3_ws_kernel's, 2 = conv3x3_lds_kernel's
+    int box_mode;
+    const void* w1; const float* b1;          // cv2.L.1's weights as the dense op tiles them ([4 tiles][18 k-steps][lane][8], pair-permuted rows) and its bias
+    void* box2;                               // debug taps: the conv's output [n][H*W][64] is written as well when set
 };
 #define HEAD_KMAX 8                           // most k-steps of one Detect branch the fused tail holds in registers (bf16: 256 channels, fp32: 128)
 #define HEAD_WAVES 8                          // waves per workgroup of the fused Detect tail, one 16-anchor tile each
