@@ -18,6 +18,7 @@ import torch
 import yolov8_ref
 import zly
 import zly_model as zm
+from closed_loop_ref import check_closed_loop, check_head_decode, lds_resident_from_kernels
 from oracle_lib import det_fields_equal
 from parity_sets import compare_detection_sets
 from test_gpu_parity import (BF16_FLIP_BAND, FP32_BOX_TOL, FP32_SCORE_TOL, MIN_COMPARED_FRACTION, _assert_bf16_close,
@@ -66,6 +67,12 @@ def _family_parity(oracle, spec, path, w, h, n, lds_resident):
     _assert_bf16_close(got, want32)
     checked = _check_taps(e, ref16, range(n), skip_ok=tuple(lds_resident), names=names)
     assert len(checked) == len(names) - len(lds_resident), sorted(set(names) - set(checked))
+    # every conv against float64 on the engine's own tapped inputs, per element, first and last frame (tests/closed_loop_ref.py); what is
+    # checked through the ambiguity allowance is what the caller says stays in LDS, and that is what the kernel table says
+    assert lds_resident_from_kernels(e, n) == set(lds_resident)
+    assert len(check_closed_loop(e, path, (0, n - 1), lds_resident=lds_resident)) == len(names)
+    for i in (0, n - 1):
+        check_head_decode(e, got[i], i)
     compared = skipped = 0
     for i, f in enumerate(frames):
         dets, k = e.detect(f, cap=512)
@@ -83,6 +90,9 @@ def _family_parity(oracle, spec, path, w, h, n, lds_resident):
     e = zly.Engine(path, model_w=w, model_h=h, max_batch=n, warmup_runs=0, flags=zly.FLAG_NO_FUSION | zly.FLAG_DUMP_LOGITS)
     got = e.forward(x)
     assert len(_check_taps(e, ref16, range(n), names=names)) == len(names)
+    assert len(check_closed_loop(e, path, (0, n - 1))) == len(names)
+    for i in (0, n - 1):
+        check_head_decode(e, got[i], i)
     _assert_bf16_close(got, want16)
     _assert_bf16_close(got, want32)
     e.close()
@@ -168,6 +178,10 @@ def test_yolov8n_class_counts(tmp_path, oracle, nc, dtype):
             for i in range(3):
                 g, t = e.tap(name, i), ref32.taps[name][i].numpy()
                 assert g.shape == t.shape and np.abs(g - t).max() <= 2e-4 * max(1.0, np.abs(t).max()), (name, i)
+    # every conv (the masked rows of a partial class tile among them) against float64 on the engine's own inputs, per element
+    assert len(check_closed_loop(e, p, (0, 2), lds_resident=lds_resident_from_kernels(e, 3) if bf16 else ())) == len(spec.convs)
+    for i in (0, 2):
+        check_head_decode(e, got[i], i)
     total = 0
     for f in frames:
         dets, k = e.detect(f, cap=1024)

@@ -8,6 +8,8 @@ Tolerances (stated here, used below):
   * bf16 engine head tensor, against the fp32 oracle AND the bf16-rounding oracle: box rows <= 1.5 px, score rows <= 2e-2
     (max over every anchor of every frame), plus rms bounds a few times the measured noise floor of bf16 itself;
     every conv output of the PRODUCTION kernels within 2^-5 of the tensor's range of the bf16-rounding oracle;
+    every conv output PER ELEMENT within 2^-8 |y| + C_ACC 2^-24 B of a float64 conv of the engine's own tapped inputs, and the head tensor within
+    2^-9 px / 2^-19 of the float64 decode of the engine's own logits (tests/closed_loop_ref.py: bound, derivation, measured constants);
     detection SETS equal to the fp32 oracle's outside the threshold-flip band (tests/parity_sets.py).
   The synthetic weights are calibrated so that these bounds mean something (tools/zly_model.py: noise-stable
   activations, peaked Gaussian DFL): the noise floor of bf16 itself on this model -- bf16-rounding oracle vs fp32
@@ -20,6 +22,7 @@ import torch
 
 import zly
 import zly_model as zm
+from closed_loop_ref import check_closed_loop, check_head_decode, lds_resident_from_kernels
 from oracle_lib import det_fields_equal
 from parity_sets import compare_detection_sets
 
@@ -425,6 +428,10 @@ def test_throughput_kernels_on_ragged_maps(weights_path, oracle, monkeypatch, w,
     checked = _check_taps(e, ref, range(n), skip_ok=(".m.0.cv1", ".m.1.cv1"))
     assert len(checked) >= 59, checked
     _assert_bf16_close(got, want)
+    # ... and every conv against float64 on the engine's own tapped inputs, per element (tests/closed_loop_ref.py), first and last frame
+    assert len(check_closed_loop(e, weights_path, (0, n - 1), lds_resident=lds_resident_from_kernels(e, n))) == 63
+    for i in (0, n - 1):
+        check_head_decode(e, got[i], i)
     # the detect path's front (stem_model1_kernel: ragged tiles of the model.1 map, stem halo beyond the map edges)
     res = e.detect_batch(list(frames), cap=64)
     for i in range(n):
@@ -759,6 +766,9 @@ def test_yolov8s_widths(tmp_path, oracle):
     _assert_bf16_close(got, want16)
     _assert_bf16_close(got, want)
     assert len(_check_taps(e, ref16, (0, 1), skip_ok=(".m.0.cv1", ".m.1.cv1"), names=[c.name for c in spec.convs])) >= 55
+    assert len(check_closed_loop(e, p, (0, 1), lds_resident=lds_resident_from_kernels(e, 2))) == len(spec.convs)
+    for i in (0, 1):
+        check_head_decode(e, got[i], i)
     e.close()
 
 
@@ -795,6 +805,16 @@ def test_yolov8s_640_fp8_weights(tmp_path, oracle, monkeypatch, env):
         # the head tensor it leads to must be the forward pass of the preprocessed frame within the bf16 tolerance
         _assert_bf16_close(e.head_tensor(0)[None], want32[i][None])
         _assert_layer_close(e.tap("model.0", 0), ref16.taps["model.0"][i].numpy(), f"model.0 of frame {i} (fused stem, 32 channels)")
+    e.close()
+    # every conv against float64 on the engine's own inputs with the weights as the loader dequantises them, on a 96 x 64 engine beside the 640 one
+    # (P5 is a 3 x 2 map; keeps the float64 work small)
+    small = _pre(oracle, zm.synth_frames(2, 96, 64, seed=11, rects=False), 96, 64)
+    e = zly.Engine(p, model_w=96, model_h=64, max_batch=2, warmup_runs=0, flags=zly.FLAG_DUMP_LOGITS)
+    assert e.weights_fp8
+    got = e.forward(small)
+    assert len(check_closed_loop(e, p, (0, 1), lds_resident=lds_resident_from_kernels(e, 2))) == len(spec.convs)
+    for i in (0, 1):
+        check_head_decode(e, got[i], i)
     e.close()
     e = zly.Engine(zly.DEFAULT_WEIGHTS, warmup_runs=0)
     assert not e.weights_fp8
@@ -984,6 +1004,20 @@ def test_streaming_1x1_kernel(weights_path, oracle, monkeypatch):
 PAIR_TAPS = ("model.2.m.0.cv2", "model.4.m.0.cv2", "model.4.m.1.cv2", "model.15.m.0.cv2")
 
 
+def _closed_loop_with_dumps(weights_path, w, h, n, x, must_be_resident):
+    """an engine under the switches now in the environment, with the debug dumps (the final logits are tappable): every conv of the first and the
+    last frame against float64 on the engine's own inputs.  The bottlenecks in `must_be_resident` must really keep their first conv in LDS, so
+    that they are checked through their second conv with the ambiguity allowance (tests/closed_loop_ref.py)."""
+    e = zly.Engine(weights_path, model_w=w, model_h=h, max_batch=n, warmup_runs=0, flags=zly.FLAG_DUMP_LOGITS)
+    lds = lds_resident_from_kernels(e, n)
+    assert set(must_be_resident) <= lds, (must_be_resident, lds, e.op_kernels(n))
+    head = e.forward(x)
+    assert len(check_closed_loop(e, weights_path, (0, n - 1), lds_resident=lds)) == 63
+    for i in (0, n - 1):
+        check_head_decode(e, head[i], i)
+    e.close()
+
+
 @pytest.mark.parametrize("w,h,n", [(416, 416, 16), (320, 256, 2), (352, 288, 5)])
 def test_fused_bottleneck_pairs(weights_path, oracle, monkeypatch, w, h, n):
     """kernels_pair.hip (3x3 -> 3x3 [+ shortcut] with the intermediate map in LDS) against the one-kernel-per-conv path
@@ -1021,6 +1055,7 @@ def test_fused_bottleneck_pairs(weights_path, oracle, monkeypatch, w, h, n):
     else:
         _assert_bf16_close(h32, hp)
     e.close()
+    _closed_loop_with_dumps(weights_path, w, h, n, x, ("model.4.m.0.cv1",))
 
     monkeypatch.setenv("ZLY_PAIR_WIDTHS", "16")
     e = zly.Engine(weights_path, model_w=w, model_h=h, max_batch=n, warmup_runs=0)
@@ -1035,6 +1070,7 @@ def test_fused_bottleneck_pairs(weights_path, oracle, monkeypatch, w, h, n):
         assert np.abs(g - t).max() <= 2.0 ** -5 * rng
     _assert_bf16_close(h16, hp)
     e.close()
+    _closed_loop_with_dumps(weights_path, w, h, n, x, ("model.2.m.0.cv1",))
 
     # 64-channel pairs (26x26 stage): one shared weight buffer, k order (tap, half) instead of the LDS kernel's (half, tap):
     # same products, other fp32 summation order.  The first such pair sees identical inputs in both engines.
@@ -1053,6 +1089,7 @@ def test_fused_bottleneck_pairs(weights_path, oracle, monkeypatch, w, h, n):
         assert g.shape == t.shape and np.isfinite(g).all() and _rms(g - t) <= 0.05 * max(_rms(t), 1e-6), name
     _assert_bf16_close(h64, hp)
     e.close(); pl.close()
+    _closed_loop_with_dumps(weights_path, w, h, n, x, ("model.6.m.0.cv1",))
 
 
 C2F_TAPS = ("model.2.cv1", "model.2.m.0.cv2", "model.2.cv2", "model.4.cv1", "model.4.m.0.cv2", "model.4.m.1.cv2", "model.4.cv2",
@@ -1081,6 +1118,12 @@ def test_fused_c2f_blocks(weights_path, oracle, w, h, n):
     hf = e.forward(x)
     with pytest.raises(zly.ZlyError):
         e.tap("model.2.m.0.cv1", 0)                               # stays in LDS even with the dumps
+    # ... so the four fused bottlenecks are checked through their second conv, with the ambiguity allowance; every other conv directly
+    lds = lds_resident_from_kernels(e, n)
+    assert lds == {"model.2.m.0.cv1", "model.4.m.0.cv1", "model.4.m.1.cv1", "model.15.m.0.cv1"}, lds
+    assert len(check_closed_loop(e, weights_path, (0, n - 1), lds_resident=lds)) == 63
+    for i in (0, n - 1):
+        check_head_decode(e, hf[i], i)
     ref = yolov8_ref.load(weights_path, "bf16")
     ref.forward(torch.from_numpy(x))
     tf = {name: [e.tap(name, i) for i in range(n)] for name in C2F_TAPS}           # the fused engine's taps, dumps on

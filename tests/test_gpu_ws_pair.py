@@ -17,6 +17,7 @@ import pytest
 
 import zly
 import zly_model as zm
+from closed_loop_ref import check_closed_loop, lds_resident_from_kernels
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +59,12 @@ def _on_off(monkeypatch, path, w, h, n, pairs, env, expect_pair=True):
         if not expect_pair:
             assert not any("ws_pair" in k for k in kern.values()), kern
         got_head, got = _run(on, x, taps)
+        if flags:
+            # against float64 on the engine's own inputs, per element (tests/closed_loop_ref.py): with the dump flag the pair kernel writes its
+            # intermediate map out, so both convs of every pair are checked directly -- none of them through the ambiguity allowance
+            lds = lds_resident_from_kernels(on, n)
+            assert not lds & {p + ".cv1" for p in pairs}, lds
+            assert len(check_closed_loop(on, path or zly.DEFAULT_WEIGHTS, (0, n - 1), lds_resident=lds)) == len(zm.read_zlyw(path or zly.DEFAULT_WEIGHTS)[0]["convs"])
         if expect_pair and not flags:                            # without the dump flag the intermediate map stays in LDS: its tap fails
             with pytest.raises(zly.ZlyError):
                 on.tap(pairs[0] + ".cv1", 0)
