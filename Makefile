@@ -12,9 +12,9 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wal
 CXX      ?= g++
 PY       ?= python3
 
-KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip
+KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_pix.hip $(CSRC)/kernels_pix_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
-OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/engine.o $(OUT)/weights.o
+OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/engine.o $(OUT)/weights.o
 
 all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench oracle weights host
 
@@ -27,6 +27,8 @@ $(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/zly_internal.h $(CSRC)/conv_device.h $(CSRC)/y
 $(OUT)/kernels_stem_yuv.o: $(CSRC)/kernels_stem.hip
 $(OUT)/kernels_lb.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_head.hip
 $(OUT)/kernels_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
+$(OUT)/kernels_pix.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
+$(OUT)/kernels_pix_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
 
 $(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
@@ -62,7 +64,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -72,6 +74,9 @@ $(OUT)/test_hip_engine: tests/cpp/test_hip_engine.cpp $(OUT)/libzly_plugin.so
 
 $(OUT)/test_hip_engine_yuv: tests/cpp/test_hip_engine_yuv.cpp $(OUT)/libzly_plugin.so
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_hip_engine_yuv.cpp -Wl,--no-as-needed -L$(OUT) -lzly_plugin -lzly -pthread -Wl,-rpath,'$$ORIGIN'
+
+$(OUT)/test_hip_engine_pix: tests/cpp/test_hip_engine_pix.cpp $(OUT)/libzly_plugin.so
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_hip_engine_pix.cpp -Wl,--no-as-needed -L$(OUT) -lzly_plugin -lzly -pthread -Wl,-rpath,'$$ORIGIN'
 
 $(OUT)/zly_h2h_bench: $(PKG)/tools/bench_h2h.cpp $(OUT)/libzly_plugin.so
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ $(PKG)/tools/bench_h2h.cpp -Wl,--no-as-needed -L$(OUT) -lzly_plugin -lzly -pthread -Wl,-rpath,'$$ORIGIN'

@@ -108,6 +108,11 @@ extern "C" {
  *   ZLY_PIX_BGR          packed B,G,R, 3 bytes per pixel: nbytes = w*h*3
  *   ZLY_PIX_NV12_*       Y plane [h][w], then ONE plane of interleaved U,V pairs [h/2][w/2][2]: nbytes = w*h*3/2
  *   ZLY_PIX_I420_*       Y plane [h][w], U plane [h/2][w/2], V plane [h/2][w/2]:            nbytes = w*h*3/2
+ *   ZLY_PIX_RGB          packed R,G,B, 3 bytes per pixel: nbytes = w*h*3
+ *   ZLY_PIX_BGRA         packed B,G,R,X, 4 bytes per pixel: nbytes = w*h*4   (GDI 32-bit DIB, DXGI B8G8R8A8, DRM XRGB8888 / ARGB8888)
+ *   ZLY_PIX_RGBA         packed R,G,B,X, 4 bytes per pixel: nbytes = w*h*4   (DXGI R8G8B8A8, DRM XBGR8888 / ABGR8888, GL_RGBA)
+ * The known formats are a set, not a range: the values between the YUV formats and ZLY_PIX_RGB (5..15) are unknown, reserved for further YUV
+ * layouts.
  * YUV frames (8-bit 4:2:0, limited range) need even w and h (>= 2).  Colour conversion happens in the front kernel: for the source pixel
  * (sx, sy) that the stretch-nearest resize picks (the BGR map, unchanged),
  *   Y = Yplane[sy*w + sx];  ci = (sy>>1)*(w/2) + (sx>>1);  NV12: U = UV[2ci], V = UV[2ci+1];  I420: U = Uplane[ci], V = Vplane[ci]
@@ -120,20 +125,30 @@ extern "C" {
  *   BT.601   1220542  1673527  -852492  -409993  2116026   (1.164, 1.596, 0.813, 0.391, 2.018 x 2^20)
  *   BT.709   1220945  1879825  -558796  -223607  2215014   (round(c x 2^20) from Kr = 0.2126, Kb = 0.0722, luma x 255/219, chroma x 255/224)
  * Those B,G,R bytes then take the BGR path exactly (resize map, /255, BGR->RGB): a YUV frame gives, bit for bit, what its converted BGR frame
- * gives.  Boxes stay normalised by the request's w, h.  (A letterbox engine converts each of its four taps this way, then interpolates.) */
+ * gives.  Boxes stay normalised by the request's w, h.  (A letterbox engine converts each of its four taps this way, then interpolates.)
+ * Packed RGB / BGRA / RGBA frames follow THE SAME RULE: a frame of one of these formats gives, bit for bit, what the BGR frame made of its
+ * B, G, R bytes gives through the same entry point -- same engine, same batch size and composition, stretch or letterbox.  The front kernel
+ * fetches a pixel as the BGR fetch's word (B | G<<8 | R<<16) and everything behind the fetch is the BGR path.  Consequences: the fourth byte X
+ * is never interpreted -- no alpha blending, no un-premultiplying, its value never influences a result; w, h >= 1 is the only size constraint;
+ * boxes are normalised as for BGR.  The 4-byte formats are staged as they are (4/3 of a BGR frame's bytes): nothing is repacked on the host. */
 #define ZLY_PIX_BGR          0
 #define ZLY_PIX_NV12_BT601   1
 #define ZLY_PIX_I420_BT601   2
 #define ZLY_PIX_NV12_BT709   3
 #define ZLY_PIX_I420_BT709   4
+#define ZLY_PIX_RGB          16
+#define ZLY_PIX_BGRA         17
+#define ZLY_PIX_RGBA         18
 
 /* A frame view: where a request's samples lie inside a larger buffer -- a decoder or capture surface with a row pitch, a region of interest of
  * one, a tile.  Plane offsets and line sizes as usual, with offsets from the buffer's base instead of pointers, so that one view serves host and
  * device memory alike.
- *   Planes.  BGR uses plane 0; NV12 0 = Y, 1 = interleaved UV; I420 0 = Y, 1 = U, 2 = V.  Entries of planes a format does not have are ignored.
- *   Rows of plane p, with cw = w/2, ch = h/2:    BGR: h rows of 3w bytes;  Y: h rows of w;  NV12 UV: ch rows of 2cw;  I420 U, V: ch rows of cw.
+ *   Planes.  The packed formats (BGR, RGB, BGRA, RGBA) use plane 0 only; NV12 0 = Y, 1 = interleaved UV; I420 0 = Y, 1 = U, 2 = V.  Entries of
+ *   planes a format does not have are ignored.
+ *   Rows of plane p, with cw = w/2, ch = h/2:    packed: h rows of bpp*w bytes (bpp = 3 for BGR / RGB, 4 for BGRA / RGBA);  Y: h rows of w;
+ *   NV12 UV: ch rows of 2cw;  I420 U, V: ch rows of cw.
  *   The extent of a plane is (rows-1)*pitch + row_bytes.
- *   A view is valid when fmt is known; w, h >= 1 (YUV: even and >= 2); every used pitch[p] >= its row bytes; every used plane's extent is < 2^31.
+ *   A view is valid when fmt is known; w, h >= 1 (YUV: even and >= 2; the packed formats have no evenness rule); every used pitch[p] >= its row bytes; every used plane's extent is < 2^31.
  *   There is no alignment requirement, no negative pitch and no overlap check.
  * THE RULE: a view gives, bit for bit, what the tight frame made of its samples gives through the _fmt entry point of the same name -- same
  * engine, same batch size and composition, stretch or letterbox.  w, h of the view are the REQUEST's size for the resize map, the letterbox geometry
@@ -220,7 +235,7 @@ int32_t zly_destroy(zly_engine* e);
 const char* zly_last_error(void);          /* thread-local message of the last failing call */
 const char* zly_version(void);
 
-/* Bytes of one frame of format fmt (ZLY_PIX_*) and size w x h: w*h*3 for BGR, w*h*3/2 for YUV 4:2:0; 0 for an unknown format or invalid
+/* Bytes of one frame of format fmt (ZLY_PIX_*) and size w x h: w*h*3 for BGR / RGB, w*h*4 for BGRA / RGBA, w*h*3/2 for YUV 4:2:0; 0 for an unknown format or invalid
  * dimensions (w or h < 1; for YUV: odd, or < 2).  Host only: needs no engine and no GPU. */
 size_t  zly_frame_bytes(int32_t fmt, int32_t w, int32_t h);
 
@@ -229,7 +244,7 @@ size_t  zly_frame_bytes(int32_t fmt, int32_t w, int32_t h);
  * zly_view_tight: the view of a tight frame as defined above (its zly_view_bytes equals zly_frame_bytes); ZLY_ERR_INVALID_ARGUMENT for an unknown
  *   format, invalid dimensions or a null output.
  * zly_view_crop: the view of the sub-rectangle (x0, y0, w, h) of a view.  Pitches stay; the offset advances by y0*pitch0 + x0*bpp in plane 0
- *   (bpp = 3 for BGR, 1 for Y), by (y0/2)*pitch + (x0/2)*2 in the NV12 UV plane and by (y0/2)*pitch + x0/2 in the I420 chroma planes.
+ *   (bpp = 3 for BGR / RGB, 4 for BGRA / RGBA, 1 for Y), by (y0/2)*pitch + (x0/2)*2 in the NV12 UV plane and by (y0/2)*pitch + x0/2 in the I420 chroma planes.
  *   ZLY_ERR_INVALID_ARGUMENT when the surface is invalid, the rectangle is not inside it, or -- YUV -- any of x0, y0, w, h is odd.  Crops compose
  *   (out may be the surface itself). */
 size_t  zly_view_bytes(const zly_frame_view* v);

@@ -205,7 +205,7 @@ struct zly_engine : Plan {
     bool ingest_active = false;       // set while the pipelined host path (zly_submit) enqueues: see run_path
     bool last_front = false;          // the most recent call launched the front kernel (zly_forward does not: model.0 is then in HBM)
     bool front_view = false;          // the current call's frames are frame views: its front kernel is the VIEW instantiation (set by run_path)
-    bool front_yuv = false;           // the current call's batch holds a YUV 4:2:0 frame: its front kernel is the YUV-capable instantiation (set by run_path)
+    int front_yuv = ZLY_FRONT_BGR;    // the format level of the current call's batch (ZLY_FRONT_*: BGR only / a YUV 4:2:0 frame / a packed RGB, BGRA, RGBA frame): which instantiation of the front kernel runs (set by run_path)
     hipStream_t stream = nullptr;
     hipStream_t side[2] = {nullptr, nullptr};     // P3 / P4 Detect branches (forked from and joined to the main stream)
     hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
@@ -1228,12 +1228,12 @@ static void harvest_timing(zly_engine* e)
 }
 
 // nms_stream_out: the stream the call's NMS (its last kernel) was launched on -- `s`, or the engine's NMS stream when deferred
-// yuv: the batch holds at least one YUV 4:2:0 frame (d_desc says which): the front kernel runs its YUV-capable instantiation
+// yuv: the format level of the batch (ZLY_FRONT_*, zly_internal.h; d_desc says which format each frame has): the front kernel runs the instantiation of that level
 // view: the frames are frame views (d_desc holds their ViewRec too): the front kernel runs its VIEW instantiation
 static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s, bool with_pre, bool defer_nms = false,
-                    hipStream_t* nms_stream_out = nullptr, bool yuv = false, bool view = false)
+                    hipStream_t* nms_stream_out = nullptr, int yuv = ZLY_FRONT_BGR, bool view = false)
 {
-    e->front_yuv = with_pre && yuv;
+    e->front_yuv = with_pre ? yuv : ZLY_FRONT_BGR;
     e->front_view = with_pre && view;
     const size_t nops = e->ops.size();
     harvest_timing(e);
@@ -1404,7 +1404,11 @@ static uint64_t now_ms()
 
 static void ingest_destroy(zly_engine* e);
 
-static bool fmt_known(int32_t fmt) { return fmt >= ZLY_PIX_BGR && fmt <= ZLY_PIX_I420_BT709; }
+// the known formats are a set, not a range (include/zly.h): 5..15 lie between the YUV layouts and the packed RGB family and are unknown
+static bool fmt_yuv(int32_t fmt) { return fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709; }
+static bool fmt_known(int32_t fmt) { return fmt == ZLY_PIX_BGR || fmt_yuv(fmt) || fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA; }
+// bytes per pixel of a packed format (BGR, RGB: 3; BGRA, RGBA: 4)
+static uint32_t fmt_bpp(int32_t fmt) { return fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : 3u; }
 
 // the request checks of every entry point that takes host frames (onnx_engine.cpp:659-665): an unknown format is an argument error; a byte count
 // that is not zly_frame_bytes(fmt, w, h) -- odd or too small YUV sizes included -- is ZLY_ERR_INVALID_INPUT
@@ -1413,9 +1417,9 @@ static int check_frame(int32_t fmt, const uint8_t* p, size_t nbytes, int32_t w, 
     if (!fmt_known(fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(fmt));
     const size_t want = zly_frame_bytes(fmt, w, h);
     if (!p || want == 0 || nbytes != want) {
-        const size_t shown = want ? want : (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * (fmt == ZLY_PIX_BGR ? 6u : 3u) / 2u;
+        const size_t shown = want ? want : (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * (fmt_yuv(fmt) ? 3u : 2u * fmt_bpp(fmt)) / 2u;
         return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: expected " + std::to_string(shown) + ", got " + std::to_string(nbytes) +
-                                           (fmt != ZLY_PIX_BGR && (w < 2 || h < 2 || (w | h) & 1) ? " (YUV 4:2:0 needs even width and height >= 2)" : ""));
+                                           (fmt_yuv(fmt) && (w < 2 || h < 2 || (w | h) & 1) ? " (YUV 4:2:0 needs even width and height >= 2)" : ""));
     }
     return ZLY_OK;
 }
@@ -1434,7 +1438,7 @@ static int check_frame_mode(const zly_engine* e, int32_t w, int32_t h)
 static int view_plane_shape(int32_t fmt, int32_t w, int32_t h, int64_t rows[3], int64_t row_bytes[3])
 {
     if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
-    if (fmt == ZLY_PIX_BGR) { rows[0] = h; row_bytes[0] = 3 * (int64_t)w; return 1; }
+    if (!fmt_yuv(fmt)) { rows[0] = h; row_bytes[0] = (int64_t)fmt_bpp(fmt) * (int64_t)w; return 1; }
     if (w < 2 || h < 2 || ((w | h) & 1)) return 0;
     rows[0] = h; row_bytes[0] = w;
     if (fmt == ZLY_PIX_NV12_BT601 || fmt == ZLY_PIX_NV12_BT709) { rows[1] = h / 2; row_bytes[1] = w; return 2; }      // 2 * (w/2)
@@ -1559,7 +1563,7 @@ struct IngestSlot {
     size_t bytes_used = 0;
     std::vector<int32_t> w, h, fmt;
     std::vector<size_t> off;
-    int n_yuv = 0;                       // frames of a YUV format in the batch
+    int n_yuv = 0;                       // the batch's format level (ZLY_FRONT_*): the highest of its frames', i.e. which front kernel serves it
     std::vector<uint8_t> consumed;
     int rc = ZLY_OK;
     std::string err;
@@ -1626,7 +1630,7 @@ static void ingest_enqueue(zly_engine* e, Ingest* g, IngestSlot& sl)
         if (rc != ZLY_OK) return rc;
         hipStream_t ns = e->stream;
         e->ingest_active = true;
-        rc = run_path(e, n, sl.d_stage, sl.d_slabs, (uint32_t)(sl.batch << 16), e->stream, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, sl.n_yuv > 0);
+        rc = run_path(e, n, sl.d_stage, sl.d_slabs, (uint32_t)(sl.batch << 16), e->stream, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, sl.n_yuv);
         e->ingest_active = false;
         if (rc != ZLY_OK) return rc;
         // the slabs (n x 2.6 KB) go back on the stream the NMS ran on, right behind it: a download stream of its own would be the fifth
@@ -1829,7 +1833,7 @@ static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32
             off = o.bytes_used;
             o.bytes_used += padded;
             o.w[(size_t)idx] = w; o.h[(size_t)idx] = h; o.fmt[(size_t)idx] = fmt; o.off[(size_t)idx] = off;
-            if (fmt != ZLY_PIX_BGR) o.n_yuv++;
+            o.n_yuv = std::max(o.n_yuv, front_level(fmt));
             *ticket = (o.batch << 16) | (uint64_t)idx;
             if (o.n_reserved == e->cfg.max_batch) ingest_close_open(g);
             break;
@@ -2095,7 +2099,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     std::vector<int32_t> vw, vh, vf;
     if (views) { vw.resize((size_t)n); vh.resize((size_t)n); vf.resize((size_t)n); }
     size_t total = 0;
-    bool yuv = false;
+    int yuv = ZLY_FRONT_BGR;
     for (int i = 0; i < n; ++i) {
         int rcv;
         if (views) {
@@ -2110,7 +2114,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
             return rcv;
         }
         const int32_t fi = views ? views[i].fmt : fmt ? fmt[i] : ZLY_PIX_BGR;
-        yuv = yuv || fi != ZLY_PIX_BGR;
+        yuv = std::max(yuv, front_level(fi));
         offs[(size_t)i] = total;
         total += ((views ? zly_frame_bytes(fi, views[i].w, views[i].h) : nbytes[i]) + 15) / 16 * 16;
     }
@@ -2155,7 +2159,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
 size_t zly_frame_bytes(int32_t fmt, int32_t w, int32_t h)
 {
     if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
-    if (fmt == ZLY_PIX_BGR) return (size_t)w * (size_t)h * 3u;
+    if (!fmt_yuv(fmt)) return (size_t)w * (size_t)h * fmt_bpp(fmt);
     if (w < 2 || h < 2 || (w & 1) || (h & 1)) return 0;                // 4:2:0: one chroma sample per 2 x 2 block
     return (size_t)w * (size_t)h * 3u / 2u;
 }
@@ -2192,8 +2196,8 @@ int32_t zly_view_crop(const zly_frame_view* surface, int32_t x0, int32_t y0, int
         return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: the rectangle is not inside the surface");
     zly_frame_view v = *surface;                         // (out may be the surface itself: crops compose)
     v.w = w; v.h = h;
-    if (v.fmt == ZLY_PIX_BGR) {
-        v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0 * 3u;
+    if (!fmt_yuv(v.fmt)) {
+        v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0 * fmt_bpp(v.fmt);
     } else {
         if ((x0 | y0 | w | h) & 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: a YUV 4:2:0 rectangle needs even x0, y0, w, h");
         v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0;
@@ -2356,7 +2360,7 @@ int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void*
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data());
     if (rc != ZLY_OK) return rc;
     hipStream_t ns = s;
-    rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, fmt != ZLY_PIX_BGR);
+    rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_level(fmt));
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
     e->call_seq++;
@@ -2372,12 +2376,12 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     std::vector<int32_t> ws((size_t)n), hs((size_t)n), fs((size_t)n);
     std::vector<size_t> offs((size_t)n);
     std::vector<ViewRec> recs((size_t)n);
-    bool yuv = false;
+    int yuv = ZLY_FRONT_BGR;
     for (int i = 0; i < n; ++i) {
         if (int rcv = check_view(e, d_base, buf_bytes, &v[i])) return rcv;
         ws[(size_t)i] = v[i].w; hs[(size_t)i] = v[i].h; fs[(size_t)i] = v[i].fmt; offs[(size_t)i] = (size_t)v[i].off[0];
         recs[(size_t)i] = view_rec(&v[i]);
-        yuv = yuv || v[i].fmt != ZLY_PIX_BGR;
+        yuv = std::max(yuv, front_level(v[i].fmt));
     }
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
@@ -2463,7 +2467,7 @@ int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_
     size_t off0 = 0;
     rc = set_desc(e, 1, &w, &h, &off0, e->stream, &fmt);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, fmt != ZLY_PIX_BGR,
+    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, front_level(fmt),
                               (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
@@ -2491,7 +2495,7 @@ int32_t zly_preprocess_view(zly_engine* e, const uint8_t* base, size_t buf_bytes
     const ViewRec rec = view_rec(v);
     rc = set_desc(e, 1, &v->w, &v->h, &off0, e->stream, &v->fmt, &rec);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, true,
+    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, std::max(ZLY_FRONT_YUV, front_level(v->fmt)),
                               (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0, true), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
@@ -2804,7 +2808,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
     std::vector<size_t> offs((size_t)n);
     for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * (size_t)w * (size_t)h * 3u;
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream);
-    e->front_yuv = false; e->front_view = false;         // tight BGR frames: the front kernels' BGR instantiations
+    e->front_yuv = ZLY_FRONT_BGR; e->front_view = false;         // tight BGR frames: the front kernels' BGR instantiations
     if (rc != ZLY_OK) return rc;
     const size_t nops = e->ops.size();
     const std::vector<Launch>& tab = resolve_launches(e, n);

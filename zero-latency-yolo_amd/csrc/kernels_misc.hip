@@ -21,13 +21,14 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // Two outputs: the engine's NHWC tensor padded to 8 channels (one 16-byte store per pixel in bf16),
 // and optionally the reference's planar fp32 [3][th][tw] layout for the parity entry point.
 // YUV: the instantiation for batches with YUV 4:2:0 frames -- a YUV frame's pixel is converted to the B, G, R bytes of its integer BGR
-// equivalent (yuv_device.h) and then takes exactly the BGR path; the BGR-only instantiation is unchanged.
+// equivalent (yuv_device.h) and then takes exactly the BGR path; the BGR-only instantiation is unchanged.  The same instantiation serves the
+// packed RGB / BGRA / RGBA frames when PK is set as well (kernels_pix.hip, kernels_pix_view.hip; yuv_device.h has the three format levels).
 // LB: the instantiation of a letterbox engine (ZLY_FLAG_LETTERBOX, letterbox_device.h): the fetch is the padding test + the bilinear blend of four
 // taps instead of the nearest-neighbour pick; the bytes it yields take the same path.  Compiled in kernels_lb.hip (ZLY_LB_TU), not here.
 // ------------------------------------------------------------------------------------------------
 // VIEW: the instantiation for frame views (zly_frame_view: row pitches, plane offsets; planes_device.h); always YUV-capable.  Compiled in
 // kernels_view.hip (ZLY_VIEW_TU), not here.
-template <typename T, bool YUV, bool LB = false, bool VIEW = false>
+template <typename T, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
                                                          T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
 {
@@ -40,21 +41,32 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     const float scale_h = (float)d.h / (float)th;
     int sy = (int)((float)y * scale_h); if (sy > d.h - 1) sy = d.h - 1;
     int sx = (int)((float)x * scale_w); if (sx > d.w - 1) sx = d.w - 1;
-    const Planes<VIEW> pl = frame_planes<VIEW>(src, src + (YUV ? desc_off(d.src_off) : d.src_off), desc, (int)gridDim.y, f, d, YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR);
+    const Planes<VIEW> pl = frame_planes<VIEW, PK>(src, src + (YUV ? desc_off(d.src_off) : d.src_off), desc, (int)gridDim.y, f, d, YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR);
     float b, g, r;
     if constexpr (LB) {
         const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
         const LbFrame lf = lb_frame(d.w, d.h, tw, th);
         LbTaps taps;
-        lb_issue<YUV>(pl, fmt, lf, x, y, taps);
-        const unsigned int px = lb_blend<YUV>(taps, fmt);
+        lb_issue<YUV, PK>(pl, fmt, lf, x, y, taps);
+        const unsigned int px = lb_blend<YUV, PK>(taps, fmt);
         b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)((px >> 16) & 0xffu) / 255.0f;
     } else
-    if (YUV && pix_is_yuv(desc_fmt(d.src_off))) {
+    if (YUV && pix_yuv_frame<PK>(desc_fmt(d.src_off))) {
         unsigned int yv, uv;
         yuv_issue(pl, desc_fmt(d.src_off), sx, sy, yv, uv);
         const unsigned int px = yuv_bgr_word(yv, uv, desc_fmt(d.src_off));
         b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)(px >> 16) / 255.0f;
+    } else if (PK && pix_not_bgr(desc_fmt(d.src_off))) {
+        // packed RGB / BGRA / RGBA: the pixel as the word B | G<<8 | R<<16.  Four bytes per pixel: one dword load that ends inside the plane; RGB: the
+        // same load, except for the frame's very last pixel, which keeps byte loads
+        const int fmt = desc_fmt(d.src_off);
+        const auto off = pl.bgr_off(sx, sy, pix_bpp(fmt));
+        const uint8_t* q = pl.f + off;
+        unsigned int px;
+        if (off + 4 <= pl.bgr_end(pix_bpp(fmt))) __builtin_memcpy(&px, q, 4);          // (it always is for a four-byte pixel)
+        else px = (unsigned int)q[0] | ((unsigned int)q[1] << 8) | ((unsigned int)q[2] << 16);
+        if (pix_is_rgb_order(fmt)) px = pix_swap_rb(px);
+        b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)((px >> 16) & 0xffu) / 255.0f;
     } else {
         const uint8_t* px = pl.f + pl.bgr_off(sx, sy);
         b = (float)px[0] / 255.0f; g = (float)px[1] / 255.0f; r = (float)px[2] / 255.0f;
@@ -72,7 +84,16 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
 
 typedef void (*preprocess_bf16_fn)(const uint8_t*, const FrameDesc*, bf16_t*, float*, int, int);
 typedef void (*preprocess_f32_fn)(const uint8_t*, const FrameDesc*, float*, float*, int, int);
-#if defined(ZLY_VIEW_TU)
+#if defined(ZLY_PIX_TU) || defined(ZLY_PIX_VIEW_TU)
+// the instantiations that serve every format (PK), for the launcher in kernels_misc.hip: tight frames in kernels_pix.hip, views in kernels_pix_view.hip
+#if defined(ZLY_PIX_VIEW_TU)
+preprocess_bf16_fn preprocess_pix_view_bf16_kernel(bool lb) { return lb ? preprocess_kernel<bf16_t, true, true, true, true> : preprocess_kernel<bf16_t, true, false, true, true>; }
+preprocess_f32_fn  preprocess_pix_view_f32_kernel(bool lb) { return lb ? preprocess_kernel<float, true, true, true, true> : preprocess_kernel<float, true, false, true, true>; }
+#else
+preprocess_bf16_fn preprocess_pix_bf16_kernel(bool lb) { return lb ? preprocess_kernel<bf16_t, true, true, false, true> : preprocess_kernel<bf16_t, true, false, false, true>; }
+preprocess_f32_fn  preprocess_pix_f32_kernel(bool lb) { return lb ? preprocess_kernel<float, true, true, false, true> : preprocess_kernel<float, true, false, false, true>; }
+#endif
+#elif defined(ZLY_VIEW_TU)
 // the frame-view instantiations, for the launcher in kernels_misc.hip
 preprocess_bf16_fn preprocess_view_bf16_kernel(bool lb) { return lb ? preprocess_kernel<bf16_t, true, true, true> : preprocess_kernel<bf16_t, true, false, true>; }
 preprocess_f32_fn  preprocess_view_f32_kernel(bool lb) { return lb ? preprocess_kernel<float, true, true, true> : preprocess_kernel<float, true, false, true>; }
@@ -85,11 +106,20 @@ preprocess_bf16_fn preprocess_lb_bf16_kernel(bool yuv);      // kernels_lb.hip
 preprocess_f32_fn  preprocess_lb_f32_kernel(bool yuv);
 preprocess_bf16_fn preprocess_view_bf16_kernel(bool lb);     // kernels_view.hip
 preprocess_f32_fn  preprocess_view_f32_kernel(bool lb);
+preprocess_bf16_fn preprocess_pix_bf16_kernel(bool lb);      // kernels_pix.hip
+preprocess_f32_fn  preprocess_pix_f32_kernel(bool lb);
+preprocess_bf16_fn preprocess_pix_view_bf16_kernel(bool lb); // kernels_pix_view.hip
+preprocess_f32_fn  preprocess_pix_view_f32_kernel(bool lb);
 
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, bool yuv, bool lb, bool view)
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, int yuv, bool lb, bool view)
 {
     dim3 grid((tw * th + 255) / 256, n);
+    if (yuv >= ZLY_FRONT_PACKED) {
+        if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(view ? preprocess_pix_view_bf16_kernel(lb) : preprocess_pix_bf16_kernel(lb), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
+        else hipLaunchKernelGGL(view ? preprocess_pix_view_f32_kernel(lb) : preprocess_pix_f32_kernel(lb), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
+        return hipGetLastError();
+    }
     if (view) {
         if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(preprocess_view_bf16_kernel(lb), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
         else hipLaunchKernelGGL(preprocess_view_f32_kernel(lb), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
@@ -111,7 +141,7 @@ hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* des
 }
 #endif  // !ZLY_LB_TU && !ZLY_VIEW_TU
 
-#if !defined(ZLY_LB_TU) && !defined(ZLY_VIEW_TU)
+#if !defined(ZLY_LB_TU) && !defined(ZLY_VIEW_TU) && !defined(ZLY_PIX_TU) && !defined(ZLY_PIX_VIEW_TU)
 // fp32 planar [n][3][th][tw] (the "images" tensor of onnx_engine.cpp:560-569) -> engine NHWC8
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const float* __restrict__ in, T* __restrict__ out8, int hw)

@@ -20,11 +20,13 @@
 // register allocation of the BGR kernels (same resources, different code), and the BGR kernels are to stay exactly as they were.
 // The LB = true instantiations (letterbox engines, ZLY_FLAG_LETTERBOX) live in kernels_lb.hip for the same reason (ZLY_STEM_LB_TU), and the
 // VIEW = true ones (frame views: pitched surfaces and regions of interest, zly_frame_view) in kernels_view.hip (ZLY_STEM_VIEW_TU).
+// The PK = true ones (batches with a packed RGB / BGRA / RGBA frame) are new code next to all of those and live in kernels_pix.hip (tight frames,
+// ZLY_STEM_PIX_TU) and kernels_pix_view.hip (views, ZLY_STEM_PIX_VIEW_TU): every instantiation that existed before them compiles to the code it compiled to.
 #include "zly_internal.h"
 #include "conv_device.h"
 #include "yuv_device.h"
 #include "letterbox_device.h"
-#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_VIEW_TU)
+#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_VIEW_TU) || defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_PIX_VIEW_TU)
 #define ZLY_STEM_SIDE_TU 1                 // a translation unit of instantiations only: no launchers, no tables
 #endif
 #include <stdlib.h>
@@ -56,12 +58,13 @@ __device__ __forceinline__ FrameDesc load_desc(const FrameDesc* p)
 // NT = output channel tiles of 16: 1 (YOLOv8n, 16-channel stem: rows in channel order) or 2 (YOLOv8-s, 32 channels: pair-permuted rows, a lane
 // ends with 8 consecutive channels = one 16-byte store); the pixel fragments are read once for both tiles.
 // YUV: the instantiation for batches with YUV 4:2:0 frames (yuv_device.h: a YUV frame's pixel becomes its BGR bytes, then the BGR path); it serves
-// the batch's BGR frames as well.  Batches of BGR frames only run YUV = false, the kernel as it was.
+// the batch's BGR frames as well.  Batches of BGR frames only run YUV = false, the kernel as it was.  The same instantiation serves the packed
+// RGB / BGRA / RGBA frames when PK is set as well (the BGR fetch with the frame's pixel size, bytes 0 and 2 exchanged for the R-first layouts).
 // LB: the instantiation of a letterbox engine (letterbox_device.h): a frame that is not model-sized BGR is fetched as padding / a four-tap bilinear
 // blend instead of the nearest-neighbour pick.  Every other engine runs LB = false, the kernel as it was.
 // VIEW: the instantiation for calls whose frames are frame views: every fetch takes its row pitch and plane bases from the frame's ViewRec
 // (planes_device.h) instead of deriving them from w, h.  Always with YUV = true; every other call runs VIEW = false, the kernel as it was.
-template <int NT, bool YUV, bool LB = false, bool VIEW = false>
+template <int NT, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
 {
     __shared__ __attribute__((aligned(16))) bf16x4 patch[STEM_PH * STEM_PW];
@@ -86,9 +89,9 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
     const float scale_h = (float)d.h / (float)a.th;
     const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
     const uint8_t* src = a.src + (YUV ? desc_off(d.src_off) : d.src_off);
-    const bool same = (d.w == a.tw) & (d.h == a.th) & !pix_is_yuv(fmt);
-    const Planes<VIEW> pl = frame_planes<VIEW>(a.src, src, a.desc, (int)gridDim.y, f, d, fmt);
-    const auto frame_bytes = pl.bgr_end();                   // bound of the wide loads: the end of plane 0
+    const bool same = (d.w == a.tw) & (d.h == a.th) & !pix_not_bgr(fmt);
+    const Planes<VIEW> pl = frame_planes<VIEW, PK>(a.src, src, a.desc, (int)gridDim.y, f, d, fmt);
+    const auto frame_bytes = pix_end<PK>(pl, fmt);          // bound of the wide loads: the end of plane 0
     LbFrame lf;
     if constexpr (LB) lf = lb_frame(d.w, d.h, a.tw, a.th);
     for (int u = tid; u < STEM_PH * STEM_PW; u += 256) {
@@ -105,20 +108,22 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
             if (LB && !same) {         // (a model-sized BGR frame: the letterbox map is the identity too)
                 if constexpr (LB) {
                     LbTaps taps;
-                    lb_issue<YUV>(pl, fmt, lf, ix, iy, taps);
-                    px4 = lb_blend<YUV>(taps, fmt);
+                    lb_issue<YUV, PK>(pl, fmt, lf, ix, iy, taps);
+                    px4 = lb_blend<YUV, PK>(taps, fmt);
                 }
-            } else if (YUV && pix_is_yuv(fmt)) {      // wave-uniform: one format per frame
+            } else if (YUV && pix_yuv_frame<PK>(fmt)) {      // wave-uniform: one format per frame
                 unsigned int yv, uv;
                 yuv_issue(pl, fmt, sx, sy, yv, uv);
                 px4 = yuv_bgr_word(yv, uv, fmt);
             } else {
-            const auto off = pl.bgr_off(sx, sy);
+            const auto off = pix_off<PK>(pl, fmt, sx, sy);
             const uint8_t* q = src + off;
             // one (unaligned) 4-byte load instead of three byte loads -- this kernel is bound by instruction issue; the very
             // last pixel of a frame would read one byte past it and keeps the byte loads
-            if (off + 4 <= frame_bytes) __builtin_memcpy(&px4, q, 4);                        // B | G<<8 | R<<16 | next B<<24 (amdhsa: unaligned global access is enabled)
+            // (a BGRA / RGBA pixel is a dword of its own that ends inside the plane: the guard holds for every one of them, the tail is never taken)
+            if (off + 4 <= frame_bytes) __builtin_memcpy(&px4, q, 4);      // B | G<<8 | R<<16 | next B<<24 (amdhsa: unaligned global access is enabled)
             else px4 = (unsigned int)q[0] | ((unsigned int)q[1] << 8) | ((unsigned int)q[2] << 16);
+            if (PK && pix_is_rgb_order(fmt)) px4 = pix_swap_rb(px4);       // RGB / RGBA: wave-uniform
             }
             // BGR -> RGB; bf16(u8 * (1/255.f)) == bf16(u8 / 255.f) for all 256 values (tests/test_model_spec.py), so the
             // reference's divide (:693) + the bf16 rounding is one v_cvt_f32_ubyte + v_mul + convert, no table
@@ -190,6 +195,22 @@ typedef void (*stem1_fn)(const Stem1Args);
 // the YUV instantiations, for the launchers in kernels_stem.hip
 stem_fused_fn stem_fused_yuv_kernel(int nt) { return nt == 2 ? stem_fused_kernel<2, true> : stem_fused_kernel<1, true>; }
 #endif
+#if defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_DIAG)
+// the instantiations that serve every format (tight frames)
+stem_fused_fn stem_fused_pix_kernel(int nt, bool lb)
+{
+    if (lb) return nt == 2 ? stem_fused_kernel<2, true, true, false, true> : stem_fused_kernel<1, true, true, false, true>;
+    return nt == 2 ? stem_fused_kernel<2, true, false, false, true> : stem_fused_kernel<1, true, false, false, true>;
+}
+#endif
+#if defined(ZLY_STEM_PIX_VIEW_TU) || defined(ZLY_STEM_DIAG)
+// ... and frame views
+stem_fused_fn stem_fused_pix_view_kernel(int nt, bool lb)
+{
+    if (lb) return nt == 2 ? stem_fused_kernel<2, true, true, true, true> : stem_fused_kernel<1, true, true, true, true>;
+    return nt == 2 ? stem_fused_kernel<2, true, false, true, true> : stem_fused_kernel<1, true, false, true, true>;
+}
+#endif
 #if defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_DIAG)
 // the letterbox instantiations
 stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv)
@@ -213,13 +234,18 @@ stem_fused_fn stem_fused_yuv_kernel(int nt);         // kernels_stem_yuv.hip
 stem1_fn      stem1_yuv_kernel(int nw, int var);
 stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv);         // kernels_lb.hip
 stem1_fn      stem1_lb_kernel(int nw, int var, bool yuv);
+stem_fused_fn stem_fused_pix_kernel(int nt, bool lb);         // kernels_pix.hip
+stem1_fn      stem1_pix_kernel(int nw, int var, bool lb);
+stem_fused_fn stem_fused_pix_view_kernel(int nt, bool lb);    // kernels_pix_view.hip
+stem1_fn      stem1_pix_view_kernel(int nw, int var, bool lb);
 
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, bool yuv, bool lb, bool view)
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, int yuv, bool lb, bool view)
 {
     if (a.Cout != 16 && a.Cout != 32) return hipErrorInvalidValue;         // one or two 16-channel MFMA tiles (YOLOv8n / YOLOv8-s); wider stems use the generic path
     if (a.Cout == 32 && (a.out_cs % 8 || a.out_co % 8)) return hipErrorInvalidValue;
     const int tiles_y = (a.Ho + STEM_TH - 1) / STEM_TH;
-    if (view) hipLaunchKernelGGL(stem_fused_view_kernel(a.Cout == 16 ? 1 : 2, lb), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    if (yuv >= ZLY_FRONT_PACKED) hipLaunchKernelGGL(view ? stem_fused_pix_view_kernel(a.Cout == 16 ? 1 : 2, lb) : stem_fused_pix_kernel(a.Cout == 16 ? 1 : 2, lb), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    else if (view) hipLaunchKernelGGL(stem_fused_view_kernel(a.Cout == 16 ? 1 : 2, lb), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else if (lb) hipLaunchKernelGGL(stem_fused_lb_kernel(a.Cout == 16 ? 1 : 2, yuv), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else if (yuv) hipLaunchKernelGGL(stem_fused_yuv_kernel(a.Cout == 16 ? 1 : 2), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     else if (a.Cout == 16) hipLaunchKernelGGL((stem_fused_kernel<1, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
@@ -278,14 +304,14 @@ static const int STEM1_TAP_SLOT[9] = {0, 2, 5, 4, 6, 8, 1, 3, 12};
 const int* stem1_tap_slot() { return STEM1_TAP_SLOT; }
 #endif
 
-// YUV: the instantiation for batches with YUV 4:2:0 frames.  A YUV frame never counts as `same` (request size == model size), so it never reaches the
-// BGR quad paths; the per-pixel general path fetches it through yuv_device.h (all byte loads of a thread first, then the conversions).  Batches of
+// YUV: the instantiation for batches with frames that are not plain BGR (YUV 4:2:0, packed RGB / BGRA / RGBA).  Such a frame never counts as `same`
+// (request size == model size), so it never reaches the BGR quad paths, which are for 3-byte B-first pixels only; the per-pixel general path fetches it through yuv_device.h (all byte loads of a thread first, then the conversions).  Batches of
 // BGR frames only run YUV = false, the kernel as it was.
 // LB: the instantiation of a letterbox engine.  Model-sized BGR frames keep the quad paths (the letterbox map is the identity for them); every other
 // frame takes the letterbox general path below.  Every other engine runs LB = false, the kernel as it was.
 // VIEW: the instantiation for frame views (planes_device.h).  A model-sized BGR view -- a model-sized window of a larger surface, the headline use --
 // keeps the quad paths: one 12-byte load per four pixels at row address iy * pitch0 + ix * 3.  A quad lies inside its row, hence inside the plane.
-template <int NW, int VAR, bool YUV, bool LB = false, bool VIEW = false>
+template <int NW, int VAR, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem_model1_kernel(const Stem1Args a)
 {
     constexpr bool NEWP = VAR >= 1, PERS = VAR >= 2;
@@ -393,7 +419,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
         const int iy0 = 4 * oy1 - 3, ix0 = 4 * ox1 - 3;
         const FrameDesc d = load_desc(&a.st.desc[f]);
         if (!((d.w == a.st.tw) & (d.h == a.st.th))) return;     // resized frame: the general path below does its own loads
-        if (YUV && pix_is_yuv(desc_fmt(d.src_off))) return;     // YUV frame: so does it
+        if (YUV && pix_not_bgr(desc_fmt(d.src_off))) return;    // YUV or packed RGB / BGRA / RGBA frame: so does it
         const uint8_t* src = a.st.src + (YUV ? desc_off(d.src_off) : d.src_off);
         const Planes<VIEW> pl = frame_planes<VIEW>(a.st.src, src, a.st.desc, a.n, f, d, ZLY_PIX_BGR);
         pma = issue_quad(qok[0], qpy[0], qpx[0], iy0, ix0, pl, pa0, pa1, pa2);
@@ -429,9 +455,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
     const FrameDesc d = load_desc(&a.st.desc[f]);
     const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
     const uint8_t* src = a.st.src + (YUV ? desc_off(d.src_off) : d.src_off);
-    const bool same = (d.w == a.st.tw) & (d.h == a.st.th) & !pix_is_yuv(fmt);
-    const Planes<VIEW> pl = frame_planes<VIEW>(a.st.src, src, a.st.desc, a.n, f, d, fmt);
-    const auto frame_bytes = pl.bgr_end();                   // bound of the wide loads: the end of plane 0
+    const bool same = (d.w == a.st.tw) & (d.h == a.st.th) & !pix_not_bgr(fmt);
+    const Planes<VIEW> pl = frame_planes<VIEW, PK>(a.st.src, src, a.st.desc, a.n, f, d, fmt);
+    const auto frame_bytes = pix_end<PK>(pl, fmt);          // bound of the wide loads: the end of plane 0
     STEMSTAMP(0);
     if (same && NEWP) {
 #pragma unroll
@@ -546,7 +572,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                 if (u < PH * PWV) {
                     const int py = div_small_s(u, invPW), px = u - py * PWV;
                     const int iy = iy0 + py, ix = ix0 + px;
-                    if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) lb_issue<YUV>(pl, fmt, lf, ix, iy, tp[j]);
+                    if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) lb_issue<YUV, PK>(pl, fmt, lf, ix, iy, tp[j]);
                 }
             }
     #pragma unroll
@@ -556,7 +582,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                     bf16x4 v = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
                     if (tp[j].m != LB_OUT) {
                         const float kk = 1.0f / 255.0f;
-                        const unsigned int px = lb_blend<YUV>(tp[j], fmt);
+                        const unsigned int px = lb_blend<YUV, PK>(tp[j], fmt);
                         v[0] = (bf16_t)((float)((px >> 16) & 0xffu) * kk); v[1] = (bf16_t)((float)((px >> 8) & 0xffu) * kk); v[2] = (bf16_t)((float)(px & 0xffu) * kk);
                     }
                     const int py = div_small_s(u, invPW);
@@ -571,7 +597,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
         const float scale_h = (float)d.h / (float)a.st.th;
         unsigned int raw[STEM1_MAXIT];
         unsigned int rawc[YUV ? STEM1_MAXIT : 1];                   // YUV frames: raw = the Y byte, rawc = U | V << 8
-        const bool yuvf = YUV && pix_is_yuv(fmt);                   // workgroup-uniform
+        const bool yuvf = YUV && pix_yuv_frame<PK>(fmt);            // workgroup-uniform
+        const unsigned int rb_sel = PK && pix_is_rgb_order(fmt) ? ZLY_PERM_SWAP_RB : ZLY_PERM_KEEP_BGR;
         const int tidg = PERS ? pin_here(tid) : tid;
     #pragma unroll
         for (int k = 0; k < STEM1_MAXIT; ++k) {
@@ -589,12 +616,15 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                     if (yuvf) {
                         yuv_issue(pl, fmt, sx, sy, raw[k], rawc[k]);
                     } else {
-                    const auto off = pl.bgr_off(sx, sy);
+                    const auto off = pix_off<PK>(pl, fmt, sx, sy);
                     const uint8_t* q = src + off;
                     unsigned int px4;
+                    // (a BGRA / RGBA pixel is a dword of its own that ends inside the plane: the guard holds for every one of them, the tail is never taken)
                     if (off + 4 <= frame_bytes) __builtin_memcpy(&px4, q, 4);        // B | G<<8 | R<<16 | next B<<24 (unaligned global access is enabled on amdhsa)
                     else px4 = (unsigned int)q[0] | ((unsigned int)q[1] << 8) | ((unsigned int)q[2] << 16);
-                    raw[k] = px4 & 0x00ffffffu;
+                    // byte 3 cleared; RGB / RGBA: bytes 0 and 2 exchanged on the way -- one v_perm_b32 with a workgroup-uniform selector in place of the mask
+                    if constexpr (PK) raw[k] = __builtin_amdgcn_perm(0u, px4, rb_sel);
+                    else raw[k] = px4 & 0x00ffffffu;
                     }
                 }
             }
@@ -783,6 +813,20 @@ stem1_fn stem1_yuv_kernel(int nw, int var)
     return nw == 12 ? stem_model1_kernel<12, 0, true> : nw == 16 ? stem_model1_kernel<16, 0, true> : stem_model1_kernel<STEM1_NW, 0, true>;
 }
 #endif
+#if defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_PIX_VIEW_TU) || defined(ZLY_STEM_DIAG)
+template <bool LB, bool VIEW> static stem1_fn stem1_pix_pick(int nw, int var)
+{
+    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, true, LB, VIEW, true> : nw == 16 ? stem_model1_kernel<16, 2, true, LB, VIEW, true> : stem_model1_kernel<STEM1_NW, 2, true, LB, VIEW, true>;
+    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, true, LB, VIEW, true> : nw == 16 ? stem_model1_kernel<16, 1, true, LB, VIEW, true> : stem_model1_kernel<STEM1_NW, 1, true, LB, VIEW, true>;
+    return nw == 12 ? stem_model1_kernel<12, 0, true, LB, VIEW, true> : nw == 16 ? stem_model1_kernel<16, 0, true, LB, VIEW, true> : stem_model1_kernel<STEM1_NW, 0, true, LB, VIEW, true>;
+}
+#endif
+#if defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_DIAG)
+stem1_fn stem1_pix_kernel(int nw, int var, bool lb) { return lb ? stem1_pix_pick<true, false>(nw, var) : stem1_pix_pick<false, false>(nw, var); }
+#endif
+#if defined(ZLY_STEM_PIX_VIEW_TU) || defined(ZLY_STEM_DIAG)
+stem1_fn stem1_pix_view_kernel(int nw, int var, bool lb) { return lb ? stem1_pix_pick<true, true>(nw, var) : stem1_pix_pick<false, true>(nw, var); }
+#endif
 #if defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_DIAG)
 template <bool YUV> static stem1_fn stem1_lb_pick(int nw, int var)
 {
@@ -820,8 +864,9 @@ void stem1_plan(int H1, int W1, const Switches& sw, int* th, int* tw)
     (void)H1;
 }
 
-static stem1_fn pick_stem1(int nw, int var, bool yuv, bool lb = false, bool view = false)
+static stem1_fn pick_stem1(int nw, int var, int yuv, bool lb = false, bool view = false)
 {
+    if (yuv >= ZLY_FRONT_PACKED) return view ? stem1_pix_view_kernel(nw, var, lb) : stem1_pix_kernel(nw, var, lb);
     if (view) return stem1_view_kernel(nw, var, lb);
     if (lb) return stem1_lb_kernel(nw, var, yuv);
     if (yuv) return stem1_yuv_kernel(nw, var);
@@ -835,12 +880,12 @@ hipError_t stem1_init()
 {
     for (int var = 0; var <= 2; ++var)
         for (int nw : {STEM1_NW, 12, 16})
-            for (bool yuv : {false, true})
+            for (int yuv : {ZLY_FRONT_BGR, ZLY_FRONT_YUV, ZLY_FRONT_PACKED})
                 for (bool lb : {false, true}) {
                     hipError_t r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv, lb), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                     if (r != hipSuccess) return r;
                     if (!yuv) continue;
-                    r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, true, lb, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                    r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv, lb, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                     if (r != hipSuccess) return r;
                 }
     int dev = 0, cus = 0;
@@ -851,7 +896,7 @@ hipError_t stem1_init()
 // a.nw: waves per workgroup (8; 12 / 16 = tuning aid ZLY_STEM1_NW); a.var: 2 = persistent workgroups with the next tile's input bytes in flight (default),
 // 1 = one tile per workgroup, 0 = round 3's staging / tap order as well (ZLY_STEM1_VAR, A/B on one box).  Both are read by the engine once per
 // zly_create, not here (a process-static switch cannot be toggled by a test)
-hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, bool yuv, bool lb, bool view)
+hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, int yuv, bool lb, bool view)
 {
     Stem1Args a = a0;
     if (a.st.Cout != 16 || a.TH < 1 || a.TW < 1 || a.out1_cs % 8 || a.out1_co % 8) return hipErrorInvalidValue;

@@ -59,11 +59,12 @@ __device__ __forceinline__ void lb_coord(int d, int step, int S, int& i0, int& a
 }
 
 // The loads of one model pixel.  m = LB_PAD: padding, nothing was loaded; else m = ax | ay << 16 and t[] holds the taps:
-//   BGR: t[0], t[1] = 8 bytes from (xl, y0): B G R B' | G' R' . .   t[2], t[3] = the same from (xl, y1)
+//   BGR, RGB: t[0], t[1] = 8 bytes from (xl, y0): B G R B' | G' R' . .   t[2], t[3] = the same from (xl, y1)
+//   BGRA, RGBA: t[0], t[1] = 8 bytes from (xl, y0): B G R X | B' G' R' X' -- the two dwords ARE the two taps --   t[2], t[3] = the same from (xl, y1)
 //   YUV: t[0..3] = the four taps p00, p01, p10, p11 as Y | U << 8 | V << 16
 // The second column is always xl + 1: where the reference's x1 = min(x0 + 1, w - 1) is x0 itself (the last column), its weight ax is 0, so the fetch
 // steps one column back (xl = w - 2) and gives the SECOND tap the whole weight (ax = 256) -- the same products.  One (unaligned) 8-byte load per row
-// then covers both taps of a BGR frame.
+// then covers both taps of a packed frame.  The R-first formats (RGB, RGBA) are loaded like their B-first twins; lb_blend exchanges the lanes.
 #define LB_PAD (-1)
 struct LbTaps { unsigned int t[4]; int m; };
 
@@ -72,7 +73,7 @@ __device__ __forceinline__ bool lb_is_pad(const LbFrame& f, int ix, int iy)
     return (unsigned)(ix - f.pad_x) >= (unsigned)f.nw || (unsigned)(iy - f.pad_y) >= (unsigned)f.nh;
 }
 
-template <bool YUV, class PL>
+template <bool YUV, bool PK = false, class PL>
 __device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f, int ix, int iy, LbTaps& o)
 {
     o.m = LB_PAD;
@@ -85,7 +86,7 @@ __device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f
     const int xl = min(x0, max(f.w - 2, 0));
     if (x0 > xl) ax = 256;
     o.m = ax | (ay << 16);
-    if (YUV && pix_is_yuv(fmt)) {                       // uniform per frame; YUV frames are at least 2 x 2
+    if (YUV && pix_yuv_frame<PK>(fmt)) {                // uniform per frame; YUV frames are at least 2 x 2
         unsigned int y, uv;
         yuv_issue(pl, fmt, xl, y0, y, uv);         o.t[0] = y | (uv << 8);
         yuv_issue(pl, fmt, xl + 1, y0, y, uv); o.t[1] = y | (uv << 8);
@@ -93,16 +94,27 @@ __device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f
         yuv_issue(pl, fmt, xl + 1, y1, y, uv); o.t[3] = y | (uv << 8);
         return;
     }
-    // 32-bit byte offsets from the frame's (uniform) base: a frame of this mode is at most ZLY_LETTERBOX_MAX_DIM on a side, 3 * 2^28 bytes (a view's plane
-    // extends over less than 2^31); the bound of the 8-byte loads is the end of the plane (planes_device.h)
+    // 32-bit byte offsets from the frame's (uniform) base: a frame of this mode is at most ZLY_LETTERBOX_MAX_DIM on a side, 3 * 2^28 bytes -- 4 * 2^28 = 2^30
+    // with four bytes per pixel, still below 2^31 (a view's plane extends over less than 2^31); the bound of the 8-byte loads is the end of the plane
+    // (planes_device.h)
     const uint8_t* src = pl.f;
-    const unsigned int frame_bytes = pl.bgr_end32();
-    const unsigned int off0 = pl.bgr_off32(xl, y0), off1 = pl.bgr_off32(xl, y1);
+    unsigned int frame_bytes, off0, off1;
+    if constexpr (PK) {
+        const unsigned int bpp = pix_bpp(fmt);
+        frame_bytes = pl.bgr_end32(bpp); off0 = pl.bgr_off32(xl, y0, bpp); off1 = pl.bgr_off32(xl, y1, bpp);
+    } else {
+        frame_bytes = pl.bgr_end32(); off0 = pl.bgr_off32(xl, y0); off1 = pl.bgr_off32(xl, y1);
+    }
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2), aligned(1)));
     if (off1 + 8 <= frame_bytes) {                      // off0 <= off1
         const u32x2 r0 = *reinterpret_cast<const u32x2*>(src + off0);        // (amdhsa: unaligned global access is enabled)
         const u32x2 r1 = *reinterpret_cast<const u32x2*>(src + off1);
         o.t[0] = r0[0]; o.t[1] = r0[1]; o.t[2] = r1[0]; o.t[3] = r1[1];
+    } else if (PK && pix_bpp(fmt) == 4u) {
+        // the last pixel of a one-column BGRA / RGBA frame: two dword loads, the second column clamped into the row (w == 1: its weight is 0)
+        const unsigned int dx = f.w > 1 ? 4u : 0u;
+        __builtin_memcpy(&o.t[0], src + off0, 4); __builtin_memcpy(&o.t[1], src + off0 + dx, 4);
+        __builtin_memcpy(&o.t[2], src + off1, 4); __builtin_memcpy(&o.t[3], src + off1 + dx, 4);
     } else {
         // the last pixels of a frame: an 8-byte load would read past it.  Byte loads, the second column clamped into the row (w == 1: its weight is 0)
         const int dx = f.w > 1 ? 3 : 0;
@@ -116,16 +128,18 @@ __device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f
 }
 
 // taps -> B | G << 8 | R << 16 (include/zly.h "Sampling": the four products per channel, + 32768, >> 16)
-template <bool YUV>
+template <bool YUV, bool PK = false>
 __device__ __forceinline__ unsigned int lb_blend(const LbTaps& o, int fmt)
 {
     if (o.m == LB_PAD) return ZLY_LB_PAD_WORD;
     const int ax = o.m & 0xffff, ay = o.m >> 16;
     const int w00 = __mul24(256 - ax, 256 - ay), w01 = __mul24(ax, 256 - ay), w10 = __mul24(256 - ax, ay), w11 = __mul24(ax, ay);
     unsigned int p00, p01, p10, p11;                     // B | G << 8 | R << 16 (| junk << 24)
-    if (YUV && pix_is_yuv(fmt)) {
+    if (YUV && pix_yuv_frame<PK>(fmt)) {
         p00 = yuv_bgr_word(o.t[0] & 0xffu, o.t[0] >> 8, fmt); p01 = yuv_bgr_word(o.t[1] & 0xffu, o.t[1] >> 8, fmt);
         p10 = yuv_bgr_word(o.t[2] & 0xffu, o.t[2] >> 8, fmt); p11 = yuv_bgr_word(o.t[3] & 0xffu, o.t[3] >> 8, fmt);
+    } else if (PK && pix_bpp(fmt) == 4u) {              // BGRA / RGBA: a dword per tap
+        p00 = o.t[0]; p01 = o.t[1]; p10 = o.t[2]; p11 = o.t[3];
     } else {
         p00 = o.t[0]; p01 = __builtin_amdgcn_alignbyte(o.t[1], o.t[0], 3);
         p10 = o.t[2]; p11 = __builtin_amdgcn_alignbyte(o.t[3], o.t[2], 3);
@@ -138,6 +152,9 @@ __device__ __forceinline__ unsigned int lb_blend(const LbTaps& o, int fmt)
                        __mul24((int)((p10 >> sh) & 0xffu), w10) + __mul24((int)((p11 >> sh) & 0xffu), w11) + 32768) >> 16;
         px |= (unsigned int)v << sh;
     }
+    // the blend is the same arithmetic on each byte lane, so an R-first frame is blended as it lies and lanes 0 and 2 of the RESULT are exchanged: one
+    // permute per pixel instead of one per tap (the pad word is grey on all three lanes and needs none)
+    if (PK && pix_is_rgb_order(fmt)) px = pix_swap_rb(px);
     return px;
 }
 

@@ -6,8 +6,11 @@
 //   Planes<true>   a frame view (zly_frame_view): plane bases and row pitches come from the frame's ViewRec (zly_internal.h), which lies behind the call's
 //                  descriptors and is read with two scalar loads per workgroup.  A valid view's planes extend over less than 2^31 bytes, so a sample's
 //                  offset from its (uniform, 64-bit) plane base is a 32-bit value: no 64-bit multiply per pixel.
-// Wide loads (the 4-byte stretch fetch, the 8-byte letterbox taps, the 12-byte quads) are guarded by bgr_end(), the END OF PLANE 0: (h-1)*pitch + 3w for a
-// view, w*h*3 for a tight frame.  Inside it they may read row padding or a neighbouring column of the surface -- bytes of the caller's validated buffer --
+// A packed frame's pixel size (3 bytes for BGR / RGB, 4 for BGRA / RGBA) is an ARGUMENT of the bgr_* members, defaulted to the literal 3: the front kernels'
+// instantiations that never meet a 4-byte pixel do not name it and compile to the `* 3` they always were; those that serve the packed family (PK) pass
+// pix_bpp(fmt) (yuv_device.h).
+// Wide loads (the 4-byte stretch fetch, the 8-byte letterbox taps, the 12-byte quads) are guarded by bgr_end(), the END OF PLANE 0: (h-1)*pitch + bpp*w for a
+// view, w*h*bpp for a tight frame.  Inside it they may read row padding or a neighbouring column of the surface -- bytes of the caller's validated buffer --
 // which the fetches mask or shift out as they always did with the next pixel's bytes.  The 2-byte NV12 pair and all byte loads lie inside a row.
 #pragma once
 #include "zly_internal.h"
@@ -20,9 +23,13 @@ template <> struct Planes<false> {
     const uint8_t* f; int w, h;
     __device__ __forceinline__ size_t bgr_off(int x, int y) const { return ((size_t)y * w + x) * 3; }
     __device__ __forceinline__ size_t bgr_end() const { return (size_t)w * h * 3; }
-    // the letterbox taps' 32-bit forms (requests of that mode are at most ZLY_LETTERBOX_MAX_DIM on a side: 3 * 2^28 bytes)
+    __device__ __forceinline__ size_t bgr_off(int x, int y, unsigned int bpp) const { return ((size_t)y * w + x) * bpp; }
+    __device__ __forceinline__ size_t bgr_end(unsigned int bpp) const { return (size_t)w * h * bpp; }
+    // the letterbox taps' 32-bit forms (requests of that mode are at most ZLY_LETTERBOX_MAX_DIM on a side: at most 4 * 2^28 = 2^30 bytes)
     __device__ __forceinline__ unsigned int bgr_off32(int x, int y) const { return ((unsigned)y * (unsigned)w + (unsigned)x) * 3u; }
     __device__ __forceinline__ unsigned int bgr_end32() const { return (unsigned)w * (unsigned)h * 3u; }
+    __device__ __forceinline__ unsigned int bgr_off32(int x, int y, unsigned int bpp) const { return ((unsigned)y * (unsigned)w + (unsigned)x) * bpp; }
+    __device__ __forceinline__ unsigned int bgr_end32(unsigned int bpp) const { return (unsigned)w * (unsigned)h * bpp; }
     __device__ __forceinline__ const uint8_t* luma(int x, int y) const { return f + ((size_t)y * w + x); }
     __device__ __forceinline__ size_t ci(int x, int y) const { return (size_t)(y >> 1) * (size_t)(w >> 1) + (size_t)(x >> 1); }     // one chroma sample per 2x2 block
     __device__ __forceinline__ const uint8_t* nv12(int x, int y) const { return f + (size_t)w * h + 2 * ci(x, y); }                 // interleaved U, V
@@ -33,10 +40,10 @@ template <> struct Planes<false> {
 template <> struct Planes<true> {
     const uint8_t* f; const uint8_t* p1; const uint8_t* p2;     // first sample of the region in plane 0 / 1 / 2
     unsigned int pitch0, pitch1, pitch2, end0;                  // end0: extent of plane 0 in bytes
-    __device__ __forceinline__ unsigned int bgr_off(int x, int y) const { return (unsigned)y * pitch0 + (unsigned)x * 3u; }
-    __device__ __forceinline__ unsigned int bgr_end() const { return end0; }
-    __device__ __forceinline__ unsigned int bgr_off32(int x, int y) const { return bgr_off(x, y); }
-    __device__ __forceinline__ unsigned int bgr_end32() const { return end0; }
+    __device__ __forceinline__ unsigned int bgr_off(int x, int y, unsigned int bpp = 3u) const { return (unsigned)y * pitch0 + (unsigned)x * bpp; }
+    __device__ __forceinline__ unsigned int bgr_end(unsigned int = 3u) const { return end0; }
+    __device__ __forceinline__ unsigned int bgr_off32(int x, int y, unsigned int bpp = 3u) const { return bgr_off(x, y, bpp); }
+    __device__ __forceinline__ unsigned int bgr_end32(unsigned int = 3u) const { return end0; }
     __device__ __forceinline__ const uint8_t* luma(int x, int y) const { return f + ((unsigned)y * pitch0 + (unsigned)x); }
     __device__ __forceinline__ const uint8_t* nv12(int x, int y) const { return p1 + ((unsigned)(y >> 1) * pitch1 + ((unsigned)x & ~1u)); }
     __device__ __forceinline__ const uint8_t* cu(int x, int y) const { return p1 + ((unsigned)(y >> 1) * pitch1 + (unsigned)(x >> 1)); }
@@ -44,7 +51,8 @@ template <> struct Planes<true> {
 };
 
 // The layout of frame fi of a call of n frames.  src: the frame's first sample in the source buffer (base + its descriptor's offset).
-template <bool VIEW>
+// fmt: the frame's format.  PK: the instantiation serves the packed RGB / BGRA / RGBA family (otherwise "not BGR" means YUV: one byte per pixel in plane 0).
+template <bool VIEW, bool PK = false>
 __device__ __forceinline__ Planes<VIEW> frame_planes(const uint8_t* base, const uint8_t* src, const FrameDesc* desc, int n, int fi, const FrameDesc& d, int fmt)
 {
     Planes<VIEW> pl;
@@ -56,7 +64,8 @@ __device__ __forceinline__ Planes<VIEW> frame_planes(const uint8_t* base, const 
         pl.p1 = base + ((unsigned long long)a[0] | ((unsigned long long)a[1] << 32));
         pl.p2 = base + ((unsigned long long)a[2] | ((unsigned long long)a[3] << 32));
         pl.pitch0 = b[0]; pl.pitch1 = b[1]; pl.pitch2 = b[2];
-        pl.end0 = (unsigned)(d.h - 1) * pl.pitch0 + (unsigned)d.w * (fmt == ZLY_PIX_BGR ? 3u : 1u);
+        pl.end0 = (unsigned)(d.h - 1) * pl.pitch0 + (unsigned)d.w * (!PK ? (fmt == ZLY_PIX_BGR ? 3u : 1u) :
+                                                                             fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709 ? 1u : fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : 3u);
     } else {
         pl.f = src; pl.w = d.w; pl.h = d.h;
     }

@@ -11,7 +11,31 @@
 
 namespace zly {
 
-__device__ __forceinline__ bool pix_is_yuv(int fmt) { return fmt != ZLY_PIX_BGR; }
+// The formats a format-aware front kernel meets (include/zly.h): BGR, the four YUV 4:2:0 layouts, and the packed family RGB / BGRA / RGBA, whose
+// fetch is the BGR fetch with the frame's own pixel size and, for the two R-first layouts, bytes 0 and 2 of the fetched word exchanged.  All of
+// them are uniform per frame, hence per wave.
+// The front kernels come in three format levels: BGR only (YUV = false), BGR + YUV (YUV = true: the kernels as they were before the packed family
+// existed -- a batch without a packed frame runs them, and they compile to the same code as ever), and every format (YUV = true, PK = true:
+// kernels_pix.hip, kernels_pix_view.hip).  Only a PK instantiation ever meets a packed frame, so only there "is YUV" differs from "is not BGR".
+__device__ __forceinline__ bool pix_is_yuv(int fmt) { return fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709; }
+__device__ __forceinline__ bool pix_not_bgr(int fmt) { return fmt != ZLY_PIX_BGR; }          // the frame needs a format-aware fetch (the host's flag says the same of the batch)
+template <bool PK> __device__ __forceinline__ bool pix_yuv_frame(int fmt) { if constexpr (PK) return pix_is_yuv(fmt); else return pix_not_bgr(fmt); }
+__device__ __forceinline__ unsigned int pix_bpp(int fmt) { return fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : 3u; }        // bytes per pixel of a packed format
+__device__ __forceinline__ bool pix_is_rgb_order(int fmt) { return fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_RGBA; }
+// R | G<<8 | B<<16 | X<<24  ->  B | G<<8 | R<<16 | 0: one v_perm_b32 (selector bytes, low to high: source byte 2, 1, 0, constant 0)
+#define ZLY_PERM_SWAP_RB 0x0c000102u
+#define ZLY_PERM_KEEP_BGR 0x0c020100u        // the same word with byte 3 cleared: the B-first formats' selector where one permute serves every packed format
+__device__ __forceinline__ unsigned int pix_swap_rb(unsigned int v) { return __builtin_amdgcn_perm(0u, v, ZLY_PERM_SWAP_RB); }
+// a packed pixel's offset in plane 0 and that plane's end (planes_device.h): with the frame's own pixel size in an instantiation that serves the packed
+// family (PK), with the literal 3 in every other
+template <bool PK, class PL> __device__ __forceinline__ auto pix_off(const PL& pl, int fmt, int x, int y)
+{
+    if constexpr (PK) return pl.bgr_off(x, y, pix_bpp(fmt)); else return pl.bgr_off(x, y);
+}
+template <bool PK, class PL> __device__ __forceinline__ auto pix_end(const PL& pl, int fmt)
+{
+    if constexpr (PK) return pl.bgr_end(pix_bpp(fmt)); else return pl.bgr_end();
+}
 
 // loads of one pixel of the YUV frame whose planes pl lays out (planes_device.h: a tight frame or a frame view): y = Y byte, uv = U | V << 8
 template <class PL>

@@ -43,7 +43,7 @@ ErrorCode toErrorCode(int32_t rc)
         default: return ErrorCode::INFERENCE_ERROR;
     }
 }
-// ZLY_INPUT_FORMAT: bgr (default), nv12, i420 (BT.601), nv12_709, i420_709 -> ZLY_PIX_*, -1 = unknown
+// ZLY_INPUT_FORMAT: bgr (default), nv12, i420 (BT.601), nv12_709, i420_709, rgb, bgra, rgba -> ZLY_PIX_*, -1 = unknown
 int32_t parseInputFormat(const char* v)
 {
     if (!v || !*v || std::strcmp(v, "bgr") == 0) return ZLY_PIX_BGR;
@@ -51,7 +51,25 @@ int32_t parseInputFormat(const char* v)
     if (std::strcmp(v, "i420") == 0) return ZLY_PIX_I420_BT601;
     if (std::strcmp(v, "nv12_709") == 0) return ZLY_PIX_NV12_BT709;
     if (std::strcmp(v, "i420_709") == 0) return ZLY_PIX_I420_BT709;
+    if (std::strcmp(v, "rgb") == 0) return ZLY_PIX_RGB;
+    if (std::strcmp(v, "bgra") == 0) return ZLY_PIX_BGRA;
+    if (std::strcmp(v, "rgba") == 0) return ZLY_PIX_RGBA;
     return -1;
+}
+// YUV 4:2:0 formats: even sizes and even crop origins; the packed formats (BGR, RGB, BGRA, RGBA) have no such rule
+bool isYuvFormat(int32_t fmt) { return fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709; }
+const char* inputFormatName(int32_t fmt)
+{
+    switch (fmt) {
+    case ZLY_PIX_NV12_BT601: return "nv12";
+    case ZLY_PIX_I420_BT601: return "i420";
+    case ZLY_PIX_NV12_BT709: return "nv12_709";
+    case ZLY_PIX_I420_BT709: return "i420_709";
+    case ZLY_PIX_RGB: return "rgb";
+    case ZLY_PIX_BGRA: return "bgra";
+    case ZLY_PIX_RGBA: return "rgba";
+    default: return "bgr";
+    }
 }
 // ZLY_RESIZE: stretch (default: the reference's nearest-neighbour stretch), letterbox (ZLY_FLAG_LETTERBOX) -> 0 / 1, -1 = unknown
 int parseResizeMode(const char* v)
@@ -112,11 +130,11 @@ Result<void> HipInferenceEngine::initialize()
 {
     if (running_) return Result<void>::ok();
     simulate_ = envInt("ZLY_SIMULATE", 0) != 0;               // explicit opt-in only: a missing or bad model file is an ERROR below, never a silent fake
-    // ZLY_INPUT_FORMAT: requests carry YUV 4:2:0 frames (decoder output) instead of packed BGR; request.data must then hold
+    // ZLY_INPUT_FORMAT: requests carry YUV 4:2:0 frames (decoder output) or packed RGB / BGRA / RGBA frames (capture surfaces) instead of packed BGR; request.data must then hold
     // zly_frame_bytes(format, width, height) bytes, a request of any other size fails alone with INVALID_INPUT
     input_format_ = parseInputFormat(std::getenv("ZLY_INPUT_FORMAT"));
     if (input_format_ < 0)
-        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_INPUT_FORMAT must be bgr, nv12, i420, nv12_709 or i420_709, got '") +
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_INPUT_FORMAT must be bgr, nv12, i420, nv12_709, i420_709, rgb, bgra or rgba, got '") +
                                                                  std::getenv("ZLY_INPUT_FORMAT") + "'");
     if (input_format_ != ZLY_PIX_BGR && (!zly_submit_fmt || !zly_submit_try_fmt))
         return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_INPUT_FORMAT: the engine library has no zly_submit_fmt");
@@ -125,7 +143,7 @@ Result<void> HipInferenceEngine::initialize()
     // fractions of the whole frame before the callback.  A request smaller than the window on either axis is detected whole.
     if (!parseCrop(std::getenv("ZLY_CROP"), &crop_w_, &crop_h_))
         return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_CROP must be WxH with W, H >= 1, got '") + std::getenv("ZLY_CROP") + "'");
-    if (crop_w_ > 0 && input_format_ != ZLY_PIX_BGR && ((crop_w_ | crop_h_) & 1))
+    if (crop_w_ > 0 && isYuvFormat(input_format_) && ((crop_w_ | crop_h_) & 1))
         return Result<void>::error(ErrorCode::INVALID_ARGUMENT, "ZLY_CROP: a YUV 4:2:0 ZLY_INPUT_FORMAT needs an even window size");
     if (crop_w_ > 0 && (!zly_view_tight || !zly_view_bytes || !zly_view_crop || !zly_submit_view || !zly_submit_try_view))
         return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_CROP: the engine library has no zly_submit_view");
@@ -381,7 +399,7 @@ Result<void> HipInferenceEngine::submitInference(const InferenceRequest& request
                 if (vrc == ZLY_OK && request.data.size() != zly_view_bytes(&whole)) vrc = ZLY_ERR_INVALID_INPUT;     // as a whole frame of the wrong size
                 if (vrc == ZLY_OK) {
                     p.crop_x0 = (request.width - crop_w_) / 2; p.crop_y0 = (request.height - crop_h_) / 2;
-                    if (input_format_ != ZLY_PIX_BGR) { p.crop_x0 &= ~1; p.crop_y0 &= ~1; }
+                    if (isYuvFormat(input_format_)) { p.crop_x0 &= ~1; p.crop_y0 &= ~1; }
                     p.frame_w = request.width; p.frame_h = request.height;
                     vrc = zly_view_crop(&whole, p.crop_x0, p.crop_y0, crop_w_, crop_h_, &win);
                     p.cropped = vrc == ZLY_OK;
@@ -599,6 +617,7 @@ std::unordered_map<std::string, std::string> HipInferenceEngine::getStatus() con
     s["dropped_frames"] = std::to_string(dropped_frames_.load());
     s["dynamic_batching"] = "enabled";
     s["resize_mode"] = letterbox_ ? "letterbox" : "stretch";
+    s["input_format"] = inputFormatName(input_format_);
     s["crop"] = crop_w_ > 0 ? std::to_string(crop_w_) + "x" + std::to_string(crop_h_) : "off";
     double avg = 0, p99 = 0;
     {

@@ -6,6 +6,8 @@
 //
 // format (bgr, the default, nv12, i420, nv12_709, i420_709): the requests carry YUV 4:2:0 frames (include/zly.h ZLY_PIX_*), the same
 // synthetic frames put through a float BGR -> YUV transform; cabi submits with zly_submit_fmt, plugin / lone set ZLY_INPUT_FORMAT.
+// format rgb, bgra, rgba: packed frames made by permuting the synthetic BGR frames' bytes and, for the 4-byte formats, padding every pixel with a
+// fourth byte (a 4-byte frame is 4/3 of the BGR frame's PCIe and staging bytes: the GB/s column counts them).
 // Without it the output is unchanged (bench.py --full parses it); with it the JSON line is the same and the format is named on stderr.
 //
 // engines > 1: that many engine instances on the GPU (ZLY_FLAG_SINGLE_CHAIN), submitting thread t feeds engine t % engines; their
@@ -74,6 +76,21 @@ static std::vector<uint8_t> toYuv420(const std::vector<uint8_t>& bgr, int W, int
     return out;
 }
 
+// BGR -> packed RGB / BGRA / RGBA: the same pixels, permuted and padded (the fourth byte is never interpreted: any value)
+static std::vector<uint8_t> toPacked(const std::vector<uint8_t>& bgr, int W, int H, int32_t fmt)
+{
+    const size_t bpp = fmt == ZLY_PIX_RGB ? 3 : 4;
+    const bool rfirst = fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_RGBA;
+    std::vector<uint8_t> out(zly_frame_bytes(fmt, W, H));
+    for (size_t i = 0; i < (size_t)W * (size_t)H; ++i) {
+        const uint8_t* s = &bgr[i * 3];
+        uint8_t* d = &out[i * bpp];
+        d[0] = rfirst ? s[2] : s[0]; d[1] = s[1]; d[2] = rfirst ? s[0] : s[2];
+        if (bpp == 4) d[3] = (uint8_t)(i * 131u);
+    }
+    return out;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 6) { std::fprintf(stderr, "usage: %s weights cabi|plugin|lone threads seconds max_batch [engines [w h [format]]]\n", argv[0]); return 2; }
@@ -85,7 +102,9 @@ int main(int argc, char** argv)
     const int W = argc > 8 ? atoi(argv[7]) : 416, H = argc > 8 ? atoi(argv[8]) : 416;
     const std::string fmt_name = argc > 9 ? argv[9] : "bgr";
     const int32_t fmt = fmt_name == "bgr" ? ZLY_PIX_BGR : fmt_name == "nv12" ? ZLY_PIX_NV12_BT601 : fmt_name == "i420" ? ZLY_PIX_I420_BT601
-                      : fmt_name == "nv12_709" ? ZLY_PIX_NV12_BT709 : fmt_name == "i420_709" ? ZLY_PIX_I420_BT709 : -1;
+                      : fmt_name == "nv12_709" ? ZLY_PIX_NV12_BT709 : fmt_name == "i420_709" ? ZLY_PIX_I420_BT709
+                      : fmt_name == "rgb" ? ZLY_PIX_RGB : fmt_name == "bgra" ? ZLY_PIX_BGRA : fmt_name == "rgba" ? ZLY_PIX_RGBA : -1;
+    const bool packed = fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA;
     if (fmt < 0 || zly_frame_bytes(fmt, W, H) == 0) { std::fprintf(stderr, "bad format '%s' for %dx%d\n", fmt_name.c_str(), W, H); return 2; }
     if (fmt != ZLY_PIX_BGR) {
         setenv("ZLY_INPUT_FORMAT", fmt_name.c_str(), 1);        // plugin / lone: read by initialize()
@@ -101,7 +120,8 @@ int main(int argc, char** argv)
             f.resize(fb);
             uint32_t* p = reinterpret_cast<uint32_t*>(f.data());
             for (size_t i = 0; i < fb / 4; ++i) p[i] = rng();
-            if (fmt != ZLY_PIX_BGR) f = toYuv420(f, W, H, fmt);
+            if (packed) f = toPacked(f, W, H, fmt);
+            else if (fmt != ZLY_PIX_BGR) f = toYuv420(f, W, H, fmt);
         }
     }
 

@@ -33,8 +33,11 @@ FLAG_ASYNC_NMS = 8
 FLAG_SINGLE_CHAIN = 16
 FLAG_LETTERBOX = 32          # per-engine resize mode: aspect-preserving bilinear letterbox (include/zly.h), boxes normalised to the request frame
 LETTERBOX_MAX_DIM = 16384    # largest request side (and model side) of a letterbox engine
-# pixel formats of a request frame (include/zly.h ZLY_PIX_*): packed BGR, or 8-bit YUV 4:2:0 (limited range) converted in the front kernel
+# pixel formats of a request frame (include/zly.h ZLY_PIX_*): packed BGR, 8-bit YUV 4:2:0 (limited range) converted in the front kernel, or
+# packed RGB / BGRA / RGBA (the fourth byte is never interpreted) fetched in the front kernel as the BGR frame of their B, G, R bytes
 PIX_BGR, PIX_NV12_BT601, PIX_I420_BT601, PIX_NV12_BT709, PIX_I420_BT709 = 0, 1, 2, 3, 4
+PIX_RGB, PIX_BGRA, PIX_RGBA = 16, 17, 18
+_PACKED_BPP = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
 
 # every symbol include/zly.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
@@ -159,7 +162,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 
 
 def frame_bytes(fmt: int, w: int, h: int) -> int:
-    """bytes of one w x h frame of format fmt (PIX_*): 3wh for BGR, 3wh/2 for YUV 4:2:0; 0 for an unknown format or invalid sizes (host only)"""
+    """bytes of one w x h frame of format fmt (PIX_*): 3wh for BGR / RGB, 4wh for BGRA / RGBA, 3wh/2 for YUV 4:2:0; 0 for an unknown format or invalid sizes (host only)"""
     return int(load_library().zly_frame_bytes(fmt, w, h))
 
 
@@ -193,8 +196,11 @@ def view_bytes(v: FrameView) -> int:
 
 
 def _dims(frame: np.ndarray, fmt: int, w: Optional[int], h: Optional[int]) -> Tuple[int, int]:
-    """(w, h) of a request: BGR frames carry them in their shape ([h][w][3]); a YUV frame is a flat u8 buffer with explicit w, h"""
-    if fmt == PIX_BGR and frame.ndim == 3:
+    """(w, h) of a request: packed frames carry them in their shape ([h][w][3] for BGR / RGB, [h][w][4] for BGRA / RGBA); a YUV frame, or a
+    packed one given as a flat u8 buffer, needs explicit w, h"""
+    if fmt in _PACKED_BPP and frame.ndim == 3:
+        if frame.shape[2] != _PACKED_BPP[fmt]:
+            raise ValueError(f"a frame of format {fmt} is [h][w][{_PACKED_BPP[fmt]}], got shape {frame.shape}")
         return (w if w is not None else frame.shape[1]), (h if h is not None else frame.shape[0])
     if w is None or h is None:
         raise ValueError("a YUV frame (1-D u8 buffer) needs explicit w and h")
