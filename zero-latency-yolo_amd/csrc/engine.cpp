@@ -2696,7 +2696,7 @@ int32_t zly_op_kernel_name(zly_engine* e, int32_t i, int32_t n, char* out, size_
     case LK_C2F: {
         const C2fGroup& g = e->c2fs[(size_t)op.c2f];
         k = "c2f_kernel<C=" + std::to_string(g.c) + (g.c == 32 ? ",NW=" + std::to_string(L.c2f.nw) : std::string()) +
-            (g.mode == 3 ? ",cv1+bottleneck+cv2>" : g.mode == 1 ? ",cv1+bottleneck>" : ",bottleneck+cv2>");
+            (g.mode == 3 ? ",cv1+bottleneck+cv2," : g.mode == 1 ? ",cv1+bottleneck," : ",bottleneck+cv2,") + std::to_string(L.c2f.th) + "x" + std::to_string(L.c2f.tw) + " tiles>";
         break;
     }
     case LK_PAIR: k = "bottleneck_pair_kernel<" + std::to_string(e->pairs[(size_t)op.pair].c) + ">"; break;

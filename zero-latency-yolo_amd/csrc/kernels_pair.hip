@@ -23,6 +23,7 @@
 #include "conv_device.h"
 #include <stdlib.h>
 #include <stdio.h>
+#include <type_traits>
 
 namespace zly {
 
@@ -264,13 +265,19 @@ __global__ __launch_bounds__(NW * 64) void bottleneck_pair_kernel(const PairArgs
 //                                                     the concat buffer in HBM for MODE 2
 //   MODE 2  bottleneck -> cv2 (1x1)                   back half: y0 | y1 come from the concat buffer, y2 is the staged patch,
 //                                                     y3 stays in LDS
-// cv1 is pointwise, so it is simply evaluated on every pixel of the bottleneck's (TH+4) x (TW+4) input patch straight from
-// global memory (fragments = 16-byte NHWC loads, optionally dual-source: the fused Upsample+Concat of the neck), its second
-// half y1 lands in the patch buffer the 3x3 convs read, its first half y0 (tile interior only) in an LDS map for cv2.  cv2
-// takes its k-steps from the LDS maps in concat order.  Every intermediate is rounded to bf16 exactly where the unfused
-// path rounds it (bias + SiLU in fp32, then bf16), so the results match the one-kernel-per-conv path up to fp32 summation
-// order.  Halo pixels of cv1 are recomputed by neighbouring tiles (1.3-1.7x the cv1 work; these layers are bound by bytes
-// and SiLU issue, not by MFMAs).  With a.dump (debug taps) the intermediates are also written to the concat buffer.
+// cv1 is pointwise, so it is evaluated on the pixels of the bottleneck's (TH+4) x (TW+4) input patch straight from global
+// memory (fragments = 16-byte NHWC loads, optionally dual-source: the fused Upsample+Concat of the neck).  Its second half
+// y1 lands in the patch buffer the 3x3 convs read (halo pixels are recomputed by neighbouring tiles), its first half y0,
+// needed on the tile interior only, in an LDS map for cv2.  The 32-channel whole-block kernel (c2f_ring) therefore walks
+// the patch as ring tiles (the 2-pixel halo, 4*PW + 4*TH pixels: y1 channel tiles only) followed by interior tiles (all
+// channel tiles), one wave-strided list; the other kernels walk the whole patch with all channel tiles.
+// cv2 takes its k-steps in concat order: y0 | y1 from the LDS maps (MODE 2: from HBM), then the bottleneck's output.  The
+// 16-channel kernel reads that from an LDS map behind a barrier.  In the 32-channel kernels (c2f_y2reg) it never leaves
+// the registers: conv B and cv2 hand the same pixel to the same lane, and with the pair-permuted rows a lane's rounded
+// conv B epilogue values ARE its B fragment of cv2's last k-step; cv2's other fragments are requested before conv B.
+// Every intermediate is rounded to bf16 exactly where the unfused path rounds it (bias + SiLU in fp32, then bf16), so the
+// results match the one-kernel-per-conv path up to fp32 summation order.  With a.dump (debug taps) the intermediates are
+// also written to the concat buffer.
 // ------------------------------------------------------------------------------------------------
 #ifdef ZLY_C2F_DIAG
 __device__ unsigned long long* g_c2f_diag = nullptr;             // diagnostic build only (tools/c2f_bench.hip): per-wave cycle sums of the phases
@@ -279,12 +286,27 @@ __device__ unsigned long long* g_c2f_diag = nullptr;             // diagnostic b
 #define C2FSTAMP(k) do { } while (0)
 #endif
 static constexpr int C2F_BIAS_BYTES = 1024;
+// Which builds take which form -- decided by measurement (profiles/r08_c2f_unused_work.txt), per instantiation:
+//  * ring tiles in cv1 (y0 on the interior only): the 32-channel whole-block kernel.  The 16-channel kernel has ONE y0 channel tile to save per ring tile, less
+//    than the second enumeration costs it, and the 8-wave front half has the same number of tile rounds on its busiest wave either way: both were slower
+static constexpr bool c2f_ring(int c, int mode) { return c == 32 && mode == 3; }
+//  * the bottleneck's output handed to cv2 in registers, cv2's other fragments requested early: the 32-channel kernels.  The 16-channel kernel is bound by
+//    VALU issue, not by the LDS round trip and its barrier; the selects and copies of the hand-over cost it 1-1.5 us, so it keeps the y map
+static constexpr bool c2f_y2reg(int c, int mode) { return c == 32 && (mode & 2) != 0; }
+//  * builds at the 128-VGPR cap: per-lane address parts are recomputed per phase instead of living in registers through the kernel
+static constexpr bool c2f_tight(int c, int nw) { return c == 32 && nw == 16; }
+// 16-pixel tiles per wave whose conv B result a wave carries in registers to cv2 (4 VGPRs each); c2f_plan and launch_c2f keep to it.  What the LDS budget
+// and the staging registers let a plan reach today is less: two per wave at 16 waves (back half), three at 8 waves (back half; whole block with one or two
+// cv1 k-steps).  The bound stays at four: the register allocation of the 16-wave back half is at the 128-VGPR cap, and with three (or two) carried
+// fragments the compiler arranges the rest so that 12-20 bytes go to scratch (tests/test_c2f_resources.py watches this)
+static constexpr int C2F_MAXY = 4;
 template <int C, int MODE, int NW, int NLD, int NK1>
 __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
 {
     typedef PairGeom<C> G;
     typedef typename G::frag F;
     constexpr bool FRONT = (MODE & 1) != 0, BACK = (MODE & 2) != 0;
+    constexpr bool RING = c2f_ring(C, MODE), Y2REG = c2f_y2reg(C, MODE), TIGHT = c2f_tight(C, NW);
     constexpr int NT = NW * 64;
     constexpr int UPP = C / 8;
     constexpr int WBYTES = 9 * G::CT * G::WTILE;          // one 3x3 conv's weights
@@ -308,8 +330,8 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
     unsigned char* lw2 = lw1 + w1_bytes;
     unsigned char* lin = lw2 + w2_bytes;
     unsigned char* lmid = lin + (PH * PW * G::PITCH + 15) / 16 * 16;
-    unsigned char* ly2 = lmid + (MH * MW * G::PITCH + 15) / 16 * 16;                       // BACK: the bottleneck's output map
-    unsigned char* ly0 = ly2 + (BACK ? (a.TH * a.TW * G::PITCH + 15) / 16 * 16 : 0);      // MODE 3: first half of cv1's output
+    unsigned char* ly2 = lmid + (MH * MW * G::PITCH + 15) / 16 * 16;                       // BACK, not Y2REG: the bottleneck's output map
+    unsigned char* ly0 = ly2 + (BACK && !Y2REG ? (a.TH * a.TW * G::PITCH + 15) / 16 * 16 : 0);      // MODE 3: first half of cv1's output
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -360,7 +382,10 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
     const float invPW = 1.0f / (float)PW, invMW = 1.0f / (float)MW, invTW = 1.0f / (float)a.TW;
     const int tiles_per_img = a.tiles_x * a.tiles_y;
     const int NP0 = PH * PW, NPA = MH * MW, NPB = a.TH * a.TW;
-    const int nt0 = (NP0 + 15) >> 4, ntA = (NPA + 15) >> 4, ntB = (NPB + 15) >> 4;
+    const int ntA = (NPA + 15) >> 4, ntB = (NPB + 15) >> 4;
+    const int NPR = RING ? 4 * PW + 4 * a.TH : 0;        // cv1: the halo ring of the patch (two rows above, two below, 2 + 2 side columns) ...
+    const int NPI = RING ? NPB : NP0;                    // ... in front of the interior (no ring tiles: the whole patch, row by row)
+    const int ntR = (NPR + 15) >> 4, nt0 = ntR + ((NPI + 15) >> 4);
     const int NPU = NP0 * UPP;
 
     auto tile_origin = [&](int tl, int& b, int& y0, int& x0) {
@@ -434,22 +459,45 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
             if (tnext < a.total_tiles) stage_load(tnext);
         } else {
             // ---- cv1 on every pixel of the patch: x (global) -> y0 | y1 ----------------------------------------------
+            const int pF = TIGHT ? opaque_offset(p) : p, kqF = TIGHT ? opaque_offset(kq) : kq, laneF = TIGHT ? opaque_offset(lane) : lane;       // as pB, kqB, laneB below
             const bf16_t* __restrict__ xa = static_cast<const bf16_t*>(a.x) + a.x_co;
             const bf16_t* __restrict__ xb = static_cast<const bf16_t*>(a.x2) + a.x2_co;
             const bool dual = a.x2 != nullptr;
-            const unsigned char* w1l = lw1 + lane * 16;
+            const unsigned char* w1l = lw1 + laneF * 16;
             // the NK1 input fragments of a 16-pixel tile are loaded together, one tile ahead of the MFMAs that consume them: with one
             // load per k-step every k-step exposed an L2 round trip (model.15.cv1: 6 per tile, most of the kernel's time)
+            // patch pixel of this lane in cv1 tile t (wave-uniform kind: t < ntR = ring tile); false for the lanes past the ring / the interior
+            auto cv1_pixel = [&](int t, int& py, int& px) -> bool {
+                if (RING && t < ntR) {
+                    const int q = t * 16 + pF, r = min(q, NPR - 1);
+                    if (r < 4 * PW) {                  // rows 0, 1, PH-2, PH-1 over the whole patch width
+                        const int row = div_small(r, invPW);
+                        px = r - row * PW; py = row < 2 ? row : row + a.TH;
+                    } else {                           // rows 2 .. TH+1: columns 0, 1, TW+2, TW+3
+                        const int s = r - 4 * PW, col = s & 3;
+                        py = 2 + (s >> 2); px = col < 2 ? col : col + a.TW;
+                    }
+                    return q < NPR;
+                }
+                const int q = (t - ntR) * 16 + pF, j = min(q, NPI - 1);
+                if (RING) {                            // interior: j = iy * TW + ix, the index of ly0
+                    const int iy = div_small(j, invTW);
+                    py = iy + 2; px = j - iy * a.TW + 2;
+                } else {
+                    py = div_small(j, invPW); px = j - py * PW;
+                }
+                return q < NPI;
+            };
             auto load_x = [&](int t, bf16x8 (&xf)[NK1]) {
-                const int qc = min(t * 16 + p, NP0 - 1);
-                const int py = div_small(qc, invPW), px = qc - py * PW;
+                int py, px;
+                cv1_pixel(t, py, px);
                 const int gy = y0 - 2 + py, gx = x0 - 2 + px;
                 const bool inimg = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
                 const size_t pa = dual ? ((size_t)(b * (a.H >> 1) + (gy >> 1)) * (a.W >> 1) + (gx >> 1)) * a.x_cs : ((size_t)(b * a.H + gy) * a.W + gx) * a.x_cs;
                 const size_t pb2 = ((size_t)(b * a.H + gy) * a.W + gx) * a.x2_cs;
 #pragma unroll
                 for (int s = 0; s < NK1; ++s) {
-                    const int ci = s * 32 + kq * 8;
+                    const int ci = s * 32 + kqF * 8;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) xf[s][j] = (bf16_t)0.0f;
                     if (inimg) xf[s] = (dual && ci >= a.split_c) ? *reinterpret_cast<const bf16x8*>(xb + pb2 + (ci - a.split_c)) : *reinterpret_cast<const bf16x8*>(xa + pa + ci);
@@ -459,39 +507,37 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
             if (wave < nt0) load_x(wave, xcur);        // issued BEFORE the tile barrier: the loads touch no LDS, and the wait at the barrier (2-2.4 k cycles, c2f_bench) covers their latency
             __syncthreads();                           // weights visible / previous tile's readers of lin, ly0 done
             C2FSTAMP(1);
-            for (int t = wave; t < nt0; t += NW) {
-                if (t + NW < nt0) load_x(t + NW, xnext);
-                const int q = t * 16 + p;
-                const int qc = min(q, NP0 - 1);
-                const int py = div_small(qc, invPW), px = qc - py * PW;
-                const int gy = y0 - 2 + py, gx = x0 - 2 + px;
-                const bool inimg = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
+            // one 16-pixel tile: output channel tiles C0 .. T1-1 (ring tiles: y1 only, C0 = CT)
+            auto cv1_tile = [&](auto c0, int t) {
+                constexpr int C0 = decltype(c0)::value;
                 f32x4 acc[T1];
 #pragma unroll
-                for (int c = 0; c < T1; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int c = C0; c < T1; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int s = 0; s < NK1; ++s)
 #pragma unroll
-                    for (int c = 0; c < T1; ++c) {
+                    for (int c = C0; c < T1; ++c) {
                         const bf16x8 wf = *reinterpret_cast<const bf16x8*>(w1l + (c * NK1 + s) * 1024);
                         acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xcur[s], acc[c], 0, 0, 0);
                     }
 #pragma unroll
                 for (int s = 0; s < NK1; ++s) xcur[s] = xnext[s];
+                int py, px;
+                const bool valid = cv1_pixel(t, py, px);
+                const int gy = y0 - 2 + py, gx = x0 - 2 + px;
+                const bool inimg = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
                 f32x4 o[T1];
 #pragma unroll
-                for (int c = 0; c < T1; ++c) {
+                for (int c = C0; c < T1; ++c) {
                     f32x4 v = acc[c] + bias_of(2, c);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = inimg ? silu<bf16_t>(v[r]) : 0.0f;      // outside the frame: the 3x3 convs' zero padding
                     o[c] = v;
                 }
-                if (q < NP0) {
-                    put_map(lin + (size_t)qc * G::PITCH, o + G::CT);                          // y1: the bottleneck's input
-                    const int iy = py - 2, ix = px - 2;
-                    const bool interior = (unsigned)iy < (unsigned)a.TH && (unsigned)ix < (unsigned)a.TW && inimg;
-                    if (interior) {
-                        if (MODE == 3) put_map(ly0 + (size_t)(iy * a.TW + ix) * G::PITCH, o);
+                if (valid) {
+                    put_map(lin + (size_t)(py * PW + px) * G::PITCH, o + G::CT);              // y1: the bottleneck's input
+                    if (C0 == 0 && inimg && (RING || ((unsigned)(py - 2) < (unsigned)a.TH && (unsigned)(px - 2) < (unsigned)a.TW))) {      // y0: interior only
+                        if (MODE == 3) put_map(ly0 + (size_t)((py - 2) * a.TW + px - 2) * G::PITCH, o);
                         if (MODE == 1 || a.dump) {
                             const int dst = ((b * a.H + gy) * a.W + gx) * a.cat_cs;
                             put_global(dst, o);
@@ -499,6 +545,11 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
                         }
                     }
                 }
+            };
+            for (int t = wave; t < nt0; t += NW) {
+                if (t + NW < nt0) load_x(t + NW, xnext);
+                if (RING && t < ntR) cv1_tile(std::integral_constant<int, G::CT>(), t);
+                else cv1_tile(std::integral_constant<int, 0>(), t);
             }
             C2FSTAMP(2);                               // cv1 loop
             __syncthreads();                           // y1 patch complete
@@ -506,12 +557,13 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
         }
 
         // ---- conv A: patch -> intermediate map in LDS ----------------------------------------------------------------
+        const int pA = TIGHT ? opaque_offset(p) : p, kqA = TIGHT ? opaque_offset(kq) : kq, laneA = TIGHT ? opaque_offset(lane) : lane;                 // as pB, kqB, laneB below
         for (int t = wave; t < ntA; t += NW) {
-            const int q = t * 16 + p;
+            const int q = t * 16 + pA;
             const int qc = min(q, NPA - 1);
             const int my = div_small(qc, invMW), mx = qc - my * MW;
             f32x4 acc[G::CT];
-            pair_taps<C>(lin, lwA, (my * PW + mx) * G::PITCH + kq * G::FRAGB, PW * G::PITCH, lane, acc);
+            pair_taps<C>(lin, lwA, (my * PW + mx) * G::PITCH + kqA * G::FRAGB, PW * G::PITCH, laneA, acc);
             const int gy = y0 - 1 + my, gx = x0 - 1 + mx;
             const bool inimg = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
             f32x4 o[G::CT];
@@ -529,12 +581,47 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
         C2FSTAMP(5);
 
         // ---- conv B: intermediate -> y (+ shortcut from the patch) ----------------------------------------------------
-        for (int t = wave; t < ntB; t += NW) {
-            const int q = t * 16 + p;
+        // Y2REG: a wave's y fragments stay in registers for cv2 (same lane, same pixel in both loops): at most C2F_MAXY pixel tiles per wave,
+        // picked by the wave-uniform loop count (scalar compares, no indexed register file access); cv2's other fragments (concat order:
+        // [HBM: y0 | y1, or the y0 map] | patch interior) do not depend on conv B and are requested ahead of it / one tile ahead
+        constexpr int NS = MODE == 2 ? 4 : 3;
+        // TIGHT: the lane's indices again, as values the compiler cannot trace to the kernel's start: what this section derives from them per lane (map and
+        // weight fragment addresses) is then computed here, per tile, and not kept in VGPRs through cv1, whose 16-wave builds have none to spare
+        const int pB = TIGHT ? opaque_offset(p) : p, kqB = TIGHT ? opaque_offset(kq) : kq, laneB = TIGHT ? opaque_offset(lane) : lane;
+        constexpr int NY = Y2REG ? C2F_MAXY : 1;
+        F y2f[NY], xs2[NS - 1], xs2n[NS - 1];
+#pragma unroll
+        for (int i = 0; i < NY; ++i) y2f[i] = F{};
+#pragma unroll
+        for (int s = 0; s < NS - 1; ++s) xs2n[s] = F{};
+        auto y2_put = [&](int i, F v) {
+            static_assert(C2F_MAXY == 4, "one branch per carried tile");
+            if (i == 0) y2f[0] = v; else if (i == 1) y2f[1 % NY] = v; else if (i == 2) y2f[2 % NY] = v; else y2f[3 % NY] = v;
+        };
+        auto y2_get = [&](int i) -> F { return i == 0 ? y2f[0] : i == 1 ? y2f[1 % NY] : i == 2 ? y2f[2 % NY] : y2f[3 % NY]; };
+        auto load_cv2 = [&](int t, F (&x)[NS - 1]) {
+            const int qc = min(t * 16 + pB, NPB - 1);
+            const int oy = div_small(qc, invTW), ox = qc - oy * a.TW;
+            if (MODE == 2) {
+                const int gy = min(y0 + oy, a.H - 1), gx = min(x0 + ox, a.W - 1);
+                const bf16_t* gp = cat + ((size_t)(b * a.H + gy) * a.W + gx) * a.cat_cs + kqB * (G::FRAGB / 2);
+                x[0] = *reinterpret_cast<const F*>(gp);
+                x[1] = *reinterpret_cast<const F*>(gp + C);
+            } else {
+                x[0] = *reinterpret_cast<const F*>(ly0 + (size_t)qc * G::PITCH + kqB * G::FRAGB);
+            }
+            x[NS - 2] = *reinterpret_cast<const F*>(lin + (size_t)((oy + 2) * PW + ox + 2) * G::PITCH + kqB * G::FRAGB);
+        };
+        if (Y2REG) load_cv2(wave, xs2);
+        auto conv_b_tile = [&](int t, int i) {
+            // 16 waves, C = 32: conv B's 18 weight fragments stay in LDS, as they did while the loop still stored the y map (an LDS store in the loop kept the
+            // compiler from hoisting the reads): hoisted they are 72 of the 128 VGPRs, and with the carried fragments the build spills 150-350 bytes
+            if (BACK && TIGHT) asm volatile("" ::: "memory");
+            const int q = t * 16 + pB;
             const int qc = min(q, NPB - 1);
             const int oy = div_small(qc, invTW), ox = qc - oy * a.TW;
             f32x4 acc[G::CT];
-            pair_taps<C>(lmid, lwB, (oy * MW + ox) * G::PITCH + kq * G::FRAGB, MW * G::PITCH, lane, acc);
+            pair_taps<C>(lmid, lwB, (oy * MW + ox) * G::PITCH + kqB * G::FRAGB, MW * G::PITCH, laneB, acc);
             f32x4 o[G::CT];
 #pragma unroll
             for (int c = 0; c < G::CT; ++c) {
@@ -544,42 +631,35 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
                 o[c] = v;
             }
             const int gy = y0 + oy, gx = x0 + ox;
-            if (q < NPB) {
-                if (a.res) {
-                    const unsigned char* xs = lin + ((oy + 2) * PW + ox + 2) * G::PITCH;
-                    if (C == 16) o[0] += load4(reinterpret_cast<const bf16_t*>(xs) + kq * 4);
-                    else { f32x4 ra, rb; load8(reinterpret_cast<const bf16_t*>(xs) + kq * 8, ra, rb); o[0] += ra; o[1 % G::CT] += rb; }
-                }
-                if (BACK) put_map(ly2 + (size_t)qc * G::PITCH, o);
-                if ((!BACK || a.dump) && gy < a.H && gx < a.W)
-                    put_global(((b * a.H + gy) * a.W + gx) * a.cat_cs + a.pair_out_co, o);
+            if (a.res) {
+                const unsigned char* xs = lin + ((oy + 2) * PW + ox + 2) * G::PITCH;
+                if (C == 16) o[0] += load4(reinterpret_cast<const bf16_t*>(xs) + kqB * 4);
+                else { f32x4 ra, rb; load8(reinterpret_cast<const bf16_t*>(xs) + kqB * 8, ra, rb); o[0] += ra; o[1 % G::CT] += rb; }
             }
-        }
+            // the lane's pixel of the y map, rounded to bf16 as a map store would: channels kq*4..+3 (C = 16) / kq*8..+7 (C = 32) = its B fragment of cv2's last k-step
+            if constexpr (Y2REG) {
+                if constexpr (C == 16) y2_put(i, __builtin_bit_cast(F, to_bf16x4(o[0])));
+                else y2_put(i, __builtin_bit_cast(F, to_bf16x8(o[0], o[1 % G::CT])));
+            } else if (BACK && q < NPB) put_map(ly2 + (size_t)qc * G::PITCH, o);
+            if ((!BACK || a.dump) && q < NPB && gy < a.H && gx < a.W)
+                put_global(((b * a.H + gy) * a.W + gx) * a.cat_cs + a.pair_out_co, o);
+        };
+        for (int t = wave, i = 0; t < ntB; t += NW, ++i) conv_b_tile(t, i);
 
         C2FSTAMP(6);                                   // conv B loop
         if (BACK) {
-            __syncthreads();                           // y map complete
+            if (!Y2REG) __syncthreads();               // y map complete
             C2FSTAMP(7);
-            // ---- cv2 over the concat [from HBM: channels below the bottleneck's input | patch interior | y] -> out -----------
-            // k-step size = C (one source map per k-step); MODE 3: y0 comes from its LDS map instead of HBM
-            const unsigned char* w2l = lw2 + lane * G::FRAGB;
-            for (int t = wave; t < ntB; t += NW) {
-                const int q = t * 16 + p;
+            // ---- cv2 over the concat -> out: k-step size = C (one source per k-step), the last one from y2f / the y map ----------------------------
+            const unsigned char* w2l = lw2 + laneB * G::FRAGB;
+            for (int t = wave, i = 0; t < ntB; t += NW, ++i) {
+                if (!Y2REG) load_cv2(t, xs2);
+                else if (t + NW < ntB) load_cv2(t + NW, xs2n);
+                const int q = t * 16 + pB;
                 const int qc = min(q, NPB - 1);
+                const F yf = Y2REG ? y2_get(i) : *reinterpret_cast<const F*>(ly2 + (size_t)qc * G::PITCH + kqB * G::FRAGB);
                 const int oy = div_small(qc, invTW), ox = qc - oy * a.TW;
                 const int gy = min(y0 + oy, a.H - 1), gx = min(x0 + ox, a.W - 1);
-                const bf16_t* gp = cat + ((size_t)(b * a.H + gy) * a.W + gx) * a.cat_cs + kq * (G::FRAGB / 2);
-                // the k-steps' fragments, in concat order, are all fetched before the MFMAs (MODE 2: the first two from HBM)
-                constexpr int NS = MODE == 2 ? 4 : 3;
-                F xs[NS];
-                if (MODE == 2) {
-                    xs[0] = *reinterpret_cast<const F*>(gp);
-                    xs[1] = *reinterpret_cast<const F*>(gp + C);
-                } else {
-                    xs[0] = *reinterpret_cast<const F*>(ly0 + (size_t)qc * G::PITCH + kq * G::FRAGB);
-                }
-                xs[NS - 2] = *reinterpret_cast<const F*>(lin + (size_t)((oy + 2) * PW + ox + 2) * G::PITCH + kq * G::FRAGB);
-                xs[NS - 1] = *reinterpret_cast<const F*>(ly2 + (size_t)qc * G::PITCH + kq * G::FRAGB);
                 f32x4 acc[T2MAX];
 #pragma unroll
                 for (int c = 0; c < T2MAX; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -587,7 +667,11 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
                 for (int s = 0; s < NS; ++s)
 #pragma unroll
                     for (int c = 0; c < T2MAX; ++c)
-                        if (c < T2) acc[c] = G::mma(*reinterpret_cast<const F*>(w2l + (c * NS + s) * G::WTILE), xs[s], acc[c]);
+                        if (c < T2) acc[c] = G::mma(*reinterpret_cast<const F*>(w2l + (c * NS + s) * G::WTILE), s < NS - 1 ? xs2[s < NS - 1 ? s : 0] : yf, acc[c]);
+                if (Y2REG) {
+#pragma unroll
+                    for (int s = 0; s < NS - 1; ++s) xs2[s] = xs2n[s];
+                }
                 if (q < NPB && y0 + oy < a.H && x0 + ox < a.W) {
                     bf16_t* dst = static_cast<bf16_t*>(a.out) + ((size_t)(b * a.H + gy) * a.W + gx) * a.out_cs + a.out_co;
 #pragma unroll
@@ -596,7 +680,7 @@ __global__ __launch_bounds__(NW * 64) void c2f_kernel(const C2fArgs a)
                         f32x4 lo = acc[2 * g2] + bias_of(3, 2 * g2), hi = acc[2 * g2 + 1] + bias_of(3, 2 * g2 + 1);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { lo[r] = silu<bf16_t>(lo[r]); hi[r] = silu<bf16_t>(hi[r]); }
-                        store8(dst + g2 * 32 + kq * 8, lo, hi);
+                        store8(dst + g2 * 32 + kqB * 8, lo, hi);
                     }
                 }
             }
@@ -686,7 +770,7 @@ static size_t c2f_lds_bytes(int c, int mode, int nk1, int nk2, int cout2, int th
     if (mode & 1) b += (size_t)(2 * c / 16) * nk1 * 1024;
     if (mode & 2) b += (size_t)(cout2 / 16) * nk2 * wtile;
     b += ((size_t)(th + 4) * (tw + 4) * pitch + 15) / 16 * 16 + ((size_t)(th + 2) * (tw + 2) * pitch + 15) / 16 * 16;
-    if (mode & 2) b += ((size_t)th * tw * pitch + 15) / 16 * 16;
+    if ((mode & 2) && !c2f_y2reg(c, mode)) b += ((size_t)th * tw * pitch + 15) / 16 * 16;
     if (mode == 3) b += ((size_t)th * tw * pitch + 15) / 16 * 16;
     return b;
 }
@@ -708,17 +792,26 @@ bool c2f_plan(int c, int mode, int nk1, int nk2, int cout2, int n, int H, int W,
             if (c2f_lds_bytes(c, mode, nk1, nk2, cout2, th, tw) > lds_cap) continue;
             if (sw.c2f_tile_th && (sw.c2f_tile_th != th || sw.c2f_tile_tw != tw)) continue;      // tuning aid: only this shape
             if (!(mode & 1) && (th + 4) * (tw + 4) * (c / 8) > nw * 64 * C2F_NLD) continue;
+            if (c2f_y2reg(c, mode) && (th * tw + 15) / 16 > nw * C2F_MAXY) continue;                     // conv B's results wait in registers for cv2
             const int tx = (W + tw - 1) / tw, ty = (H + th - 1) / th;
             const long tiles = (long)n * tx * ty;
             const long rounds = (tiles + ncu - 1) / ncu;
-            const int nt0 = ((th + 4) * (tw + 4) + 15) / 16, ntA = ((th + 2) * (tw + 2) + 15) / 16, ntB = (th * tw + 15) / 16;
+            const bool ring = c2f_ring(c, mode);
+            const int ntR = ring ? (4 * (tw + 4) + 4 * th + 15) / 16 : 0, nt1 = ((ring ? th * tw : (th + 4) * (tw + 4)) + 15) / 16, ntA = ((th + 2) * (tw + 2) + 15) / 16, ntB = (th * tw + 15) / 16;
             const int ct = c / 16;
             // phase weights in units of one 3x3 conv tile round (9 x CT MFMAs + CT epilogue tiles)
             const double w_cv1 = (double)(2 * ct * nk1 + 2.0 * 2 * ct) / (9.0 * ct + 2.0 * ct);
             const double w_cv2 = (double)((cout2 / 16) * nk2 + 2.0 * (cout2 / 16)) / (9.0 * ct + 2.0 * ct);
             double per_tile = (double)((ntA + nw - 1) / nw + (ntB + nw - 1) / nw) + 1.5 * 16 / nw;
-            if (mode & 1) per_tile += w_cv1 * ((nt0 + nw - 1) / nw);
+            // cv1: ntR ring tiles (the y1 half of the channel tiles) then nt1 full tiles, wave-strided; wave 0 has the most of both
+            if (mode & 1) {
+                const int ring0 = (ntR + nw - 1) / nw, all0 = (ntR + nt1 + nw - 1) / nw;
+                per_tile += w_cv1 * (0.5 * ring0 + (all0 - ring0));
+            }
             if (mode & 2) per_tile += w_cv2 * ((ntB + nw - 1) / nw);
+            // the kernels without the y map have room for shapes the search never weighed: among those of equal cost over several rounds, the smaller
+            // patch (fewer halo pixels staged and recomputed).  Every other launch keeps the first shape of the search, as before
+            if (c2f_y2reg(c, mode) && tiles > ncu) per_tile += 1e-5 * (th + 4) * (tw + 4);
             const double cost = (double)rounds * per_tile;
             if (cost < best) { best = cost; plan->th = th; plan->tw = tw; plan->tiles_x = tx; plan->tiles_y = ty; plan->total_tiles = (int)tiles; }
         }
@@ -765,6 +858,7 @@ hipError_t launch_c2f(int c, int mode, const C2fArgs& a, const C2fPlan& plan, hi
     if ((mode & 2) && (a.Cout2 % 32 || a.Cout2 > 64)) return hipErrorInvalidValue;
     const int nw = c == 16 ? C2F_NW16 : plan.nw;
     if (c == 32 && nw != 8 && nw != 16) return hipErrorInvalidValue;
+    if (c2f_y2reg(c, mode) && (a.TH * a.TW + 15) / 16 > nw * C2F_MAXY) return hipErrorInvalidValue;         // more pixel tiles per wave than it can carry to cv2
     c2f_fn fn = pick_c2f(c, mode, a.nk1, nw);
     if (!fn || (mode == 2 && a.pair_in_co != 2 * c)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fn, dim3((unsigned)plan.grid), dim3(nw * 64), (size_t)plan.lds_bytes, s, a);

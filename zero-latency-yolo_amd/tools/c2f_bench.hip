@@ -2,7 +2,10 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Izero-latency-yolo_amd/csrc -DZLY_C2F_DIAG=1 zero-latency-yolo_amd/tools/c2f_bench.hip \
 //         -o zero-latency-yolo_amd/_build/c2f_bench && ./zero-latency-yolo_amd/_build/c2f_bench
 // Blocks of YOLOv8n at 416 x 416, batch 64: model.2 (C = 16, whole block), model.4 front / back (C = 32), model.15 (C = 32, whole, dual source).
-// Per launch: time, and per wave and tile the cycle sums of: prologue | tile barrier | cv1 loop | barrier | conv A loop | barrier | conv B loop | barrier | cv2 loop.
+// Per launch: time, and per wave and tile the cycle sums of: prologue | tile barrier | cv1 loop (32-channel whole block: ring tiles, then interior tiles) |
+// barrier | conv A loop | barrier | conv B loop (32 channels: cv2's first fragments are requested in front of it) | barrier (16 channels only: the y map; the
+// 32-channel kernels hand y to cv2 in registers and have none) | cv2 loop.
+// Optional arguments: a tile shape "th,tw" per block in the order below ("-" = the planned one), e.g. c2f_bench 26,26 - - 13,13.
 #include "../csrc/kernels_pair.hip"
 #include <stdio.h>
 #include <string.h>
@@ -22,11 +25,13 @@ static void* dalloc_rand(size_t elems, unsigned seed, unsigned short base, unsig
     return d;
 }
 
-static void run(const char* name, int c, int mode, int n, int H, int W, int cin, bool dual, int nmaps, int cout2)
+static void run(const char* name, const char* tile, int c, int mode, int n, int H, int W, int cin, bool dual, int nmaps, int cout2)
 {
     const int nk1 = cin / 32, nk2 = nmaps;
     C2fPlan pl{};
-    if (!c2f_plan(c, mode, nk1, nk2, cout2, n, H, W, Switches(), &pl)) { printf("%s: no plan\n", name); return; }
+    Switches sw;
+    if (tile && sscanf(tile, "%d,%d", &sw.c2f_tile_th, &sw.c2f_tile_tw) != 2) sw.c2f_tile_th = sw.c2f_tile_tw = 0;      // "-": the planned shape
+    if (!c2f_plan(c, mode, nk1, nk2, cout2, n, H, W, sw, &pl)) { printf("%s: no plan\n", name); return; }
     C2fArgs a; memset(&a, 0, sizeof a);
     const size_t px = (size_t)n * H * W;
     if (dual) { a.x = dalloc_rand(px / 4 * 128, 1, 0x3c00, 0x1ff); a.x_cs = 128; a.x2 = dalloc_rand(px * 64, 2, 0x3c00, 0x1ff); a.x2_cs = 64; a.split_c = 128; }
@@ -63,11 +68,12 @@ static void run(const char* name, int c, int mode, int n, int H, int W, int cin,
            s[0] / nwaves, s[1] / nwaves / tpw, s[2] / nwaves / tpw, s[3] / nwaves / tpw, s[4] / nwaves / tpw, s[5] / nwaves / tpw, s[6] / nwaves / tpw, s[7] / nwaves / tpw, s[8] / nwaves / tpw, s[9] / nwaves, tpw);
 }
 
-int main()
+int main(int argc, char** argv)
 {
-    run("model.2 (C=16, 32->32) x64", 16, 3, 64, 104, 104, 32, false, 3, 32);
-    run("model.4 front (C=32) x64", 32, 1, 64, 52, 52, 64, false, 4, 64);
-    run("model.4 back (C=32) x64", 32, 2, 64, 52, 52, 64, false, 4, 64);
-    run("model.15 (C=32, 192->64 dual) x64", 32, 3, 64, 52, 52, 192, true, 3, 64);
+    const char* t[4] = {argc > 1 ? argv[1] : nullptr, argc > 2 ? argv[2] : nullptr, argc > 3 ? argv[3] : nullptr, argc > 4 ? argv[4] : nullptr};
+    run("model.2 (C=16, 32->32) x64", t[0], 16, 3, 64, 104, 104, 32, false, 3, 32);
+    run("model.4 front (C=32) x64", t[1], 32, 1, 64, 52, 52, 64, false, 4, 64);
+    run("model.4 back (C=32) x64", t[2], 32, 2, 64, 52, 52, 64, false, 4, 64);
+    run("model.15 (C=32, 192->64 dual) x64", t[3], 32, 3, 64, 52, 52, 192, true, 3, 64);
     return 0;
 }
