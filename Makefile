@@ -21,16 +21,16 @@ all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_shar
 $(OUT):
 	mkdir -p $(OUT)
 
-$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/zly_internal.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h $(CSRC)/letterbox_device.h $(CSRC)/planes_device.h include/zly.h | $(OUT)
+KHDRS    := $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h $(CSRC)/letterbox_device.h $(CSRC)/planes_device.h include/zly.h
+$(OUT)/%.o: $(CSRC)/%.hip $(KHDRS) | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# the side units of the front kernels (front_variants.h) compile the main units' text
 $(OUT)/kernels_stem_yuv.o: $(CSRC)/kernels_stem.hip
 $(OUT)/kernels_lb.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_head.hip
-$(OUT)/kernels_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
-$(OUT)/kernels_pix.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
-$(OUT)/kernels_pix_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
+$(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
 
-$(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/weights.h include/zly.h | $(OUT)
+$(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(OUT)/weights.o: $(CSRC)/weights.cpp $(CSRC)/weights.h include/zly.h | $(OUT)
@@ -42,7 +42,7 @@ $(OUT)/libzly.so: $(OBJS)
 # ---- diagnostic build of the engine (never shipped, never loaded by tests / bench.py / the plugin): the same kernels, engine.cpp with -DZLY_DIAG, which
 #      compiles in the result-changing ZLY_ABLATE_SKIP switch of tools/ablate_launches.sh (ZLY_LIB=.../libzly_diag.so python3 bench.py ...)
 diaglib: $(OUT)/libzly_diag.so
-$(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/weights.h include/zly.h | $(OUT)
+$(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -DZLY_DIAG=1 -x hip -c $< -o $@
 $(OUT)/libzly_diag.so: $(filter-out $(OUT)/engine.o,$(OBJS)) $(OUT)/engine_diag.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
@@ -114,7 +114,7 @@ $(OUT)/yolov8n_synth.zlyw: $(PKG)/tools/zly_model.py | $(OUT)
 # ---- diagnostic build of the LDS conv kernel with s_memtime stamps per phase (never linked into libzly.so) --------
 diag: $(OUT)/diag_lds
 
-$(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_internal.h | $(OUT)
+$(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_internal.h $(CSRC)/front_variants.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -DZLY_DIAG=1 $< -o $@
 
 clean:

@@ -144,7 +144,8 @@ struct Launch {
     int only_level = -1;               // LK_HEAD: -1 = all three levels, else that level only
     int box_mode[3] = {0, 0, 0};       // LK_HEAD: per level, HeadLevel::box_mode -- the tail computes the box branch's second conv itself, at surviving anchors (tail_box_mode)
     bool pool16 = false;               // LK_SPPF_POOL: sppf_pool16_kernel (else sppf_pool_kernel)
-    bool lb = false;                   // front kernels and LK_HEAD of a letterbox engine (ZLY_FLAG_LETTERBOX): the LB instantiation (kernels_lb.hip)
+    bool lb = false;                   // LK_HEAD of a letterbox engine (ZLY_FLAG_LETTERBOX): the Detect tail's LB instantiation (kernels_lb.hip).  Set on the front launches too, where it
+                                       // only names the kernel for zly_profile_ops: which front kernel runs is zly_engine::front
 };
 
 struct Ingest;        // pipelined host-to-host path (zly_submit / zly_wait), below
@@ -204,8 +205,7 @@ struct zly_engine : Plan {
     Stem1Args stem1a{};
     bool ingest_active = false;       // set while the pipelined host path (zly_submit) enqueues: see run_path
     bool last_front = false;          // the most recent call launched the front kernel (zly_forward does not: model.0 is then in HBM)
-    bool front_view = false;          // the current call's frames are frame views: its front kernel is the VIEW instantiation (set by run_path)
-    int front_yuv = ZLY_FRONT_BGR;    // the format level of the current call's batch (ZLY_FRONT_*: BGR only / a YUV 4:2:0 frame / a packed RGB, BGRA, RGBA frame): which instantiation of the front kernel runs (set by run_path)
+    FrontVariant front;               // which instantiation of the front kernel the current call launches (front_variants.h; set by run_path)
     hipStream_t stream = nullptr;
     hipStream_t side[2] = {nullptr, nullptr};     // P3 / P4 Detect branches (forked from and joined to the main stream)
     hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
@@ -1060,16 +1060,16 @@ static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const 
     case LK_NONE:
         return hipSuccess;
     case LK_PREPROCESS:
-        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front_yuv, L.lb, e->front_view);
+        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front);
     case LK_STEM: {
         StemArgs st = e->stem;
         st.src = d_src; st.desc = e->d_desc;
-        return launch_stem_fused(st, n, s, e->front_yuv, L.lb, e->front_view);
+        return launch_stem_fused(st, n, s, e->front);
     }
     case LK_STEM1: {
         Stem1Args st = e->stem1a;
         st.st.src = d_src; st.st.desc = e->d_desc;
-        return launch_stem_model1(st, n, s, e->front_yuv, L.lb, e->front_view);
+        return launch_stem_model1(st, n, s, e->front);
     }
     case LK_CONV:
         return launch_conv(make_conv_args(e, op, n), L.conv, s);
@@ -1227,14 +1227,15 @@ static void harvest_timing(zly_engine* e)
     e->t_pending = false;
 }
 
+// the front-kernel variant of a call on this engine: the batch's format level (the highest front_level of its frames), tight frames or frame views
+static FrontVariant front_of(const zly_engine* e, int level, bool view = false) { return FrontVariant(level, (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0, view); }
+
 // nms_stream_out: the stream the call's NMS (its last kernel) was launched on -- `s`, or the engine's NMS stream when deferred
-// yuv: the format level of the batch (ZLY_FRONT_*, zly_internal.h; d_desc says which format each frame has): the front kernel runs the instantiation of that level
-// view: the frames are frame views (d_desc holds their ViewRec too): the front kernel runs its VIEW instantiation
-static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s, bool with_pre, bool defer_nms = false,
-                    hipStream_t* nms_stream_out = nullptr, int yuv = ZLY_FRONT_BGR, bool view = false)
+// variant: the call's front-kernel variant (front_of: the batch's format level -- d_desc says which format each frame has --, and whether the frames are views, d_desc then holding their ViewRec too)
+static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s, bool with_pre, bool defer_nms,
+                    hipStream_t* nms_stream_out, FrontVariant variant)
 {
-    e->front_yuv = with_pre ? yuv : ZLY_FRONT_BGR;
-    e->front_view = with_pre && view;
+    e->front = variant;
     const size_t nops = e->ops.size();
     harvest_timing(e);
     const bool sample = with_pre && !e->t_pending && (e->sample_ctr++ % zly_engine::SAMPLE_EVERY) == 0;
@@ -1563,7 +1564,7 @@ struct IngestSlot {
     size_t bytes_used = 0;
     std::vector<int32_t> w, h, fmt;
     std::vector<size_t> off;
-    int n_yuv = 0;                       // the batch's format level (ZLY_FRONT_*): the highest of its frames', i.e. which front kernel serves it
+    int level = 0;                       // the batch's format level (ZLY_FRONT_*): the highest of its frames', i.e. which front kernel serves it
     std::vector<uint8_t> consumed;
     int rc = ZLY_OK;
     std::string err;
@@ -1599,7 +1600,7 @@ static bool ingest_try_open(zly_engine* e, Ingest* g)
     IngestSlot& sl = g->slots[(size_t)(g->next_batch % g->slots.size())];
     if (sl.state != SLOT_FREE) return false;
     sl.state = SLOT_OPEN; sl.batch = g->next_batch++;
-    sl.n_reserved = sl.n_committed = sl.n_consumed = 0; sl.bytes_used = 0; sl.n_yuv = 0; sl.rc = ZLY_OK; sl.err.clear();
+    sl.n_reserved = sl.n_committed = sl.n_consumed = 0; sl.bytes_used = 0; sl.level = 0; sl.rc = ZLY_OK; sl.err.clear();
     std::fill(sl.consumed.begin(), sl.consumed.end(), (uint8_t)0);
     g->open = (int)(sl.batch % g->slots.size());
     (void)e;
@@ -1630,7 +1631,7 @@ static void ingest_enqueue(zly_engine* e, Ingest* g, IngestSlot& sl)
         if (rc != ZLY_OK) return rc;
         hipStream_t ns = e->stream;
         e->ingest_active = true;
-        rc = run_path(e, n, sl.d_stage, sl.d_slabs, (uint32_t)(sl.batch << 16), e->stream, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, sl.n_yuv);
+        rc = run_path(e, n, sl.d_stage, sl.d_slabs, (uint32_t)(sl.batch << 16), e->stream, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, sl.level));
         e->ingest_active = false;
         if (rc != ZLY_OK) return rc;
         // the slabs (n x 2.6 KB) go back on the stream the NMS ran on, right behind it: a download stream of its own would be the fifth
@@ -1833,7 +1834,7 @@ static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32
             off = o.bytes_used;
             o.bytes_used += padded;
             o.w[(size_t)idx] = w; o.h[(size_t)idx] = h; o.fmt[(size_t)idx] = fmt; o.off[(size_t)idx] = off;
-            o.n_yuv = std::max(o.n_yuv, front_level(fmt));
+            o.level = std::max(o.level, front_level(fmt));
             *ticket = (o.batch << 16) | (uint64_t)idx;
             if (o.n_reserved == e->cfg.max_batch) ingest_close_open(g);
             break;
@@ -1952,7 +1953,7 @@ static int warm_batch(zly_engine* e, int n)
     if (rc != ZLY_OK) return rc;
     const bool defer = (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0;
     for (int k = 0; k < (defer ? 4 : 2); ++k) {
-        rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, defer);
+        rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, defer, nullptr, front_of(e, ZLY_FRONT_BGR));
         if (rc != ZLY_OK) return rc;
     }
     gl.release();
@@ -2099,7 +2100,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     std::vector<int32_t> vw, vh, vf;
     if (views) { vw.resize((size_t)n); vh.resize((size_t)n); vf.resize((size_t)n); }
     size_t total = 0;
-    int yuv = ZLY_FRONT_BGR;
+    int level = ZLY_FRONT_BGR;
     for (int i = 0; i < n; ++i) {
         int rcv;
         if (views) {
@@ -2114,7 +2115,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
             return rcv;
         }
         const int32_t fi = views ? views[i].fmt : fmt ? fmt[i] : ZLY_PIX_BGR;
-        yuv = std::max(yuv, front_level(fi));
+        level = std::max(level, front_level(fi));
         offs[(size_t)i] = total;
         total += ((views ? zly_frame_bytes(fi, views[i].w, views[i].h) : nbytes[i]) + 15) / 16 * 16;
     }
@@ -2135,7 +2136,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, total, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
     rc = set_desc(e, n, w, h, offs.data(), e->stream, fmt);
     if (rc != ZLY_OK) return rc;
-    rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, false, nullptr, yuv);
+    rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, false, nullptr, front_of(e, level));
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     const size_t sb = slab_bytes_of(e);
     HIP_TRY(hipMemcpyAsync(e->h_slabs, e->d_slabs, sb * (size_t)n, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
@@ -2360,7 +2361,7 @@ int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void*
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data());
     if (rc != ZLY_OK) return rc;
     hipStream_t ns = s;
-    rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_level(fmt));
+    rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, front_level(fmt)));
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
     e->call_seq++;
@@ -2376,12 +2377,12 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     std::vector<int32_t> ws((size_t)n), hs((size_t)n), fs((size_t)n);
     std::vector<size_t> offs((size_t)n);
     std::vector<ViewRec> recs((size_t)n);
-    int yuv = ZLY_FRONT_BGR;
+    int level = ZLY_FRONT_BGR;
     for (int i = 0; i < n; ++i) {
         if (int rcv = check_view(e, d_base, buf_bytes, &v[i])) return rcv;
         ws[(size_t)i] = v[i].w; hs[(size_t)i] = v[i].h; fs[(size_t)i] = v[i].fmt; offs[(size_t)i] = (size_t)v[i].off[0];
         recs[(size_t)i] = view_rec(&v[i]);
-        yuv = std::max(yuv, front_level(v[i].fmt));
+        level = std::max(level, front_level(v[i].fmt));
     }
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
@@ -2390,7 +2391,7 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data(), recs.data());
     if (rc != ZLY_OK) return rc;
     hipStream_t ns = s;
-    rc = run_path(e, n, (const uint8_t*)d_base, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, yuv, true);
+    rc = run_path(e, n, (const uint8_t*)d_base, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, level, true));
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
     e->call_seq++;
@@ -2467,8 +2468,7 @@ int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_
     size_t off0 = 0;
     rc = set_desc(e, 1, &w, &h, &off0, e->stream, &fmt);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, front_level(fmt),
-                              (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, front_of(e, front_level(fmt))), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
@@ -2495,8 +2495,7 @@ int32_t zly_preprocess_view(zly_engine* e, const uint8_t* base, size_t buf_bytes
     const ViewRec rec = view_rec(v);
     rc = set_desc(e, 1, &v->w, &v->h, &off0, e->stream, &v->fmt, &rec);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, std::max(ZLY_FRONT_YUV, front_level(v->fmt)),
-                              (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0, true), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, front_of(e, front_level(v->fmt), true)), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
@@ -2525,7 +2524,7 @@ int32_t zly_forward(zly_engine* e, int32_t n, const float* images_nchw, float* h
     rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream);
     if (rc != ZLY_OK) return rc;
     if (e->cfg.flags & ZLY_FLAG_NO_HEAD_TENSOR) return fail(ZLY_ERR_INVALID_ARGUMENT, "engine was created with ZLY_FLAG_NO_HEAD_TENSOR: the head tensor is not materialised");
-    rc = run_path(e, n, nullptr, nullptr, 0, e->stream, false);
+    rc = run_path(e, n, nullptr, nullptr, 0, e->stream, false, false, nullptr, FrontVariant());     // no front kernel: model.0 is computed from the caller's images
     if (rc != ZLY_OK) return rc;
     HIP_TRY(hipMemcpyAsync(head_out, e->d_head, (size_t)n * (4 + (size_t)e->nc) * e->N * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
@@ -2808,7 +2807,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
     std::vector<size_t> offs((size_t)n);
     for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * (size_t)w * (size_t)h * 3u;
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream);
-    e->front_yuv = ZLY_FRONT_BGR; e->front_view = false;         // tight BGR frames: the front kernels' BGR instantiations
+    e->front = front_of(e, ZLY_FRONT_BGR);         // tight BGR frames
     if (rc != ZLY_OK) return rc;
     const size_t nops = e->ops.size();
     const std::vector<Launch>& tab = resolve_launches(e, n);

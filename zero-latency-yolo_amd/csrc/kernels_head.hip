@@ -417,12 +417,12 @@ template <typename T, bool LB> static head_fn pick_head(int ctc) {
     }
     return nullptr;
 }
-#if defined(ZLY_LB_TU) || defined(ZLY_HEAD_DIAG)              // (diagnostic builds, tools/head_bench.hip: one translation unit)
-// the letterbox instantiations, for the launcher in kernels_head.hip
+#if ZLY_FRONT_OWNS(ZLY_TU_LB)
+// the letterbox instantiations, for the launcher below: compiled in kernels_lb.hip (front_variants.h)
 head_fn head_fused_lb_kernel(int dtype, int ctc) { return dtype == ZLY_DTYPE_BF16 ? pick_head<bf16_t, true>(ctc) : pick_head<float, true>(ctc); }
 #endif
-#ifndef ZLY_LB_TU
-head_fn head_fused_lb_kernel(int dtype, int ctc);          // kernels_lb.hip
+#if ZLY_FRONT_LAUNCHERS
+head_fn head_fused_lb_kernel(int dtype, int ctc);
 
 hipError_t launch_head_fused(int dtype, const HeadArgs& a0, int n, hipStream_t s)
 {
@@ -451,6 +451,6 @@ hipError_t launch_head_fused(int dtype, const HeadArgs& a0, int n, hipStream_t s
     hipLaunchKernelGGL(fn, dim3(blocks, n), dim3(HEAD_WAVES * 64), lds, s, a);
     return hipGetLastError();
 }
-#endif  // !ZLY_LB_TU
+#endif  // ZLY_FRONT_LAUNCHERS
 
 }  // namespace zly

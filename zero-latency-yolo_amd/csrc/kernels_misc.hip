@@ -20,14 +20,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // Every operation is a single IEEE fp32 op, so the result is bit-identical to the CPU oracle.
 // Two outputs: the engine's NHWC tensor padded to 8 channels (one 16-byte store per pixel in bf16),
 // and optionally the reference's planar fp32 [3][th][tw] layout for the parity entry point.
-// YUV: the instantiation for batches with YUV 4:2:0 frames -- a YUV frame's pixel is converted to the B, G, R bytes of its integer BGR
-// equivalent (yuv_device.h) and then takes exactly the BGR path; the BGR-only instantiation is unchanged.  The same instantiation serves the
-// packed RGB / BGRA / RGBA frames when PK is set as well (kernels_pix.hip, kernels_pix_view.hip; yuv_device.h has the three format levels).
-// LB: the instantiation of a letterbox engine (ZLY_FLAG_LETTERBOX, letterbox_device.h): the fetch is the padding test + the bilinear blend of four
-// taps instead of the nearest-neighbour pick; the bytes it yields take the same path.  Compiled in kernels_lb.hip (ZLY_LB_TU), not here.
+// YUV, LB, VIEW, PK: the input variants (front_variants.h has what each flag selects and which object its instantiations are compiled in).  Whatever
+// the fetch, the B, G, R bytes it yields take the same path.
 // ------------------------------------------------------------------------------------------------
-// VIEW: the instantiation for frame views (zly_frame_view: row pitches, plane offsets; planes_device.h); always YUV-capable.  Compiled in
-// kernels_view.hip (ZLY_VIEW_TU), not here.
 template <typename T, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
                                                          T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
@@ -82,66 +77,39 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     }
 }
 
-typedef void (*preprocess_bf16_fn)(const uint8_t*, const FrameDesc*, bf16_t*, float*, int, int);
-typedef void (*preprocess_f32_fn)(const uint8_t*, const FrameDesc*, float*, float*, int, int);
-#if defined(ZLY_PIX_TU) || defined(ZLY_PIX_VIEW_TU)
-// the instantiations that serve every format (PK), for the launcher in kernels_misc.hip: tight frames in kernels_pix.hip, views in kernels_pix_view.hip
-#if defined(ZLY_PIX_VIEW_TU)
-preprocess_bf16_fn preprocess_pix_view_bf16_kernel(bool lb) { return lb ? preprocess_kernel<bf16_t, true, true, true, true> : preprocess_kernel<bf16_t, true, false, true, true>; }
-preprocess_f32_fn  preprocess_pix_view_f32_kernel(bool lb) { return lb ? preprocess_kernel<float, true, true, true, true> : preprocess_kernel<float, true, false, true, true>; }
-#else
-preprocess_bf16_fn preprocess_pix_bf16_kernel(bool lb) { return lb ? preprocess_kernel<bf16_t, true, true, false, true> : preprocess_kernel<bf16_t, true, false, false, true>; }
-preprocess_f32_fn  preprocess_pix_f32_kernel(bool lb) { return lb ? preprocess_kernel<float, true, true, false, true> : preprocess_kernel<float, true, false, false, true>; }
-#endif
-#elif defined(ZLY_VIEW_TU)
-// the frame-view instantiations, for the launcher in kernels_misc.hip
-preprocess_bf16_fn preprocess_view_bf16_kernel(bool lb) { return lb ? preprocess_kernel<bf16_t, true, true, true> : preprocess_kernel<bf16_t, true, false, true>; }
-preprocess_f32_fn  preprocess_view_f32_kernel(bool lb) { return lb ? preprocess_kernel<float, true, true, true> : preprocess_kernel<float, true, false, true>; }
-#elif defined(ZLY_LB_TU)
-// the letterbox instantiations, for the launcher in kernels_misc.hip
-preprocess_bf16_fn preprocess_lb_bf16_kernel(bool yuv) { return yuv ? preprocess_kernel<bf16_t, true, true> : preprocess_kernel<bf16_t, false, true>; }
-preprocess_f32_fn  preprocess_lb_f32_kernel(bool yuv) { return yuv ? preprocess_kernel<float, true, true> : preprocess_kernel<float, false, true>; }
-#else
-preprocess_bf16_fn preprocess_lb_bf16_kernel(bool yuv);      // kernels_lb.hip
-preprocess_f32_fn  preprocess_lb_f32_kernel(bool yuv);
-preprocess_bf16_fn preprocess_view_bf16_kernel(bool lb);     // kernels_view.hip
-preprocess_f32_fn  preprocess_view_f32_kernel(bool lb);
-preprocess_bf16_fn preprocess_pix_bf16_kernel(bool lb);      // kernels_pix.hip
-preprocess_f32_fn  preprocess_pix_f32_kernel(bool lb);
-preprocess_bf16_fn preprocess_pix_view_bf16_kernel(bool lb); // kernels_pix_view.hip
-preprocess_f32_fn  preprocess_pix_view_f32_kernel(bool lb);
+// The instantiations this unit owns (front_variants.h), as the kernel's host address: dtype bf16, or fp32 for every other
+template <int TU> static const void* preprocess_own(FrontVariant v, int dtype)
+{
+#define ZLY_ROW(level, lb, view, pre_tu, stem_tu) \
+    if constexpr (TU == front_owner(pre_tu)) \
+        if (v == FrontVariant(level, lb, view)) \
+            return dtype == ZLY_DTYPE_BF16 ? (const void*)preprocess_kernel<bf16_t, ZLY_FRONT_FLAGS(level, lb, view)> : (const void*)preprocess_kernel<float, ZLY_FRONT_FLAGS(level, lb, view)>;
+    ZLY_FRONT_VARIANTS(ZLY_ROW)
+#undef ZLY_ROW
+    return nullptr;
+}
+template <int TU> const void* preprocess_kernel_in(FrontVariant v, int dtype);      // unit TU's getter, defined where TU is compiled
+template <> const void* preprocess_kernel_in<ZLY_FRONT_TU>(FrontVariant v, int dtype) { return preprocess_own<ZLY_FRONT_TU>(v, dtype); }
+
+#if ZLY_FRONT_LAUNCHERS
+static const void* preprocess_kernel_of(FrontVariant v, int dtype)
+{
+#define ZLY_ROW(level, lb, view, pre_tu, stem_tu) if (v == FrontVariant(level, lb, view)) return preprocess_kernel_in<front_owner(pre_tu)>(v, dtype);
+    ZLY_FRONT_VARIANTS(ZLY_ROW)
+#undef ZLY_ROW
+    return nullptr;
+}
 
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, int yuv, bool lb, bool view)
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, FrontVariant v)
 {
-    dim3 grid((tw * th + 255) / 256, n);
-    if (yuv >= ZLY_FRONT_PACKED) {
-        if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(view ? preprocess_pix_view_bf16_kernel(lb) : preprocess_pix_bf16_kernel(lb), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
-        else hipLaunchKernelGGL(view ? preprocess_pix_view_f32_kernel(lb) : preprocess_pix_f32_kernel(lb), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
-        return hipGetLastError();
-    }
-    if (view) {
-        if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(preprocess_view_bf16_kernel(lb), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
-        else hipLaunchKernelGGL(preprocess_view_f32_kernel(lb), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
-        return hipGetLastError();
-    }
-    if (lb) {
-        if (dtype == ZLY_DTYPE_BF16) hipLaunchKernelGGL(preprocess_lb_bf16_kernel(yuv), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
-        else hipLaunchKernelGGL(preprocess_lb_f32_kernel(yuv), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
-        return hipGetLastError();
-    }
-    if (dtype == ZLY_DTYPE_BF16) {
-        if (yuv) hipLaunchKernelGGL((preprocess_kernel<bf16_t, true>), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
-        else hipLaunchKernelGGL((preprocess_kernel<bf16_t, false>), grid, dim3(256), 0, s, src, desc, (bf16_t*)out_nhwc8, out_nchw_f32, tw, th);
-    } else {
-        if (yuv) hipLaunchKernelGGL((preprocess_kernel<float, true>), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
-        else hipLaunchKernelGGL((preprocess_kernel<float, false>), grid, dim3(256), 0, s, src, desc, (float*)out_nhwc8, out_nchw_f32, tw, th);
-    }
+    const void* fn = preprocess_kernel_of(v, dtype);
+    if (!fn) return hipErrorInvalidValue;
+    void* args[] = {&src, &desc, &out_nhwc8, &out_nchw_f32, &tw, &th};      // (the bf16 and fp32 kernels differ in the pointee of out_nhwc8 only)
+    (void)hipLaunchKernel(fn, dim3((tw * th + 255) / 256, n), dim3(256), args, 0, s);
     return hipGetLastError();
 }
-#endif  // !ZLY_LB_TU && !ZLY_VIEW_TU
 
-#if !defined(ZLY_LB_TU) && !defined(ZLY_VIEW_TU) && !defined(ZLY_PIX_TU) && !defined(ZLY_PIX_VIEW_TU)
 // fp32 planar [n][3][th][tw] (the "images" tensor of onnx_engine.cpp:560-569) -> engine NHWC8
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const float* __restrict__ in, T* __restrict__ out8, int hw)
@@ -368,6 +336,6 @@ hipError_t launch_tap_to_nchw(int dtype, const void* in, int cs, int co, int C, 
     return hipGetLastError();
 }
 
-#endif  // !ZLY_LB_TU && !ZLY_VIEW_TU
+#endif  // ZLY_FRONT_LAUNCHERS
 
 }  // namespace zly

@@ -1,7 +1,5 @@
-// kernels_pix_view.hip -- the PK = true, VIEW = true instantiations of the front kernels: frame views (zly_frame_view) of every pixel format, packed
-// RGB / BGRA / RGBA included -- a region of a BGRA capture surface detected in place.  The counterpart of kernels_pix.hip for calls on views, split off
-// so that the two compile side by side.
-#define ZLY_PIX_VIEW_TU 1
-#define ZLY_STEM_PIX_VIEW_TU 1
+// kernels_pix_view.hip -- the PIX_VIEW unit of front_variants.h: kernels_pix.hip's counterpart for calls on frame views -- a region of a BGRA capture
+// surface detected in place --, split off so that the two compile side by side.
+#define ZLY_FRONT_TU ZLY_TU_PIX_VIEW
 #include "kernels_misc.hip"
 #include "kernels_stem.hip"

@@ -15,20 +15,12 @@
 //      fragment (two taps x 4 channels);
 //   4. bias + SiLU, 8-byte NHWC stores: the 4 lanes of a pixel write its 32 bytes contiguously.
 //
-// The YUV = true instantiations of the front kernels (batches with YUV 4:2:0 frames) are compiled in a translation unit of their own,
-// kernels_stem_yuv.hip, which includes this file with ZLY_STEM_YUV_TU defined: instantiated here, next to the BGR ones, they changed the
-// register allocation of the BGR kernels (same resources, different code), and the BGR kernels are to stay exactly as they were.
-// The LB = true instantiations (letterbox engines, ZLY_FLAG_LETTERBOX) live in kernels_lb.hip for the same reason (ZLY_STEM_LB_TU), and the
-// VIEW = true ones (frame views: pitched surfaces and regions of interest, zly_frame_view) in kernels_view.hip (ZLY_STEM_VIEW_TU).
-// The PK = true ones (batches with a packed RGB / BGRA / RGBA frame) are new code next to all of those and live in kernels_pix.hip (tight frames,
-// ZLY_STEM_PIX_TU) and kernels_pix_view.hip (views, ZLY_STEM_PIX_VIEW_TU): every instantiation that existed before them compiles to the code it compiled to.
+// This text is compiled in several translation units, each with some of the input variants <YUV, LB, VIEW, PK> of the two kernels: front_variants.h
+// lists them, says what each flag selects and why the objects are split.
 #include "zly_internal.h"
 #include "conv_device.h"
 #include "yuv_device.h"
 #include "letterbox_device.h"
-#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_VIEW_TU) || defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_PIX_VIEW_TU)
-#define ZLY_STEM_SIDE_TU 1                 // a translation unit of instantiations only: no launchers, no tables
-#endif
 #include <stdlib.h>
 #include <type_traits>
 
@@ -57,13 +49,8 @@ __device__ __forceinline__ FrameDesc load_desc(const FrameDesc* p)
 
 // NT = output channel tiles of 16: 1 (YOLOv8n, 16-channel stem: rows in channel order) or 2 (YOLOv8-s, 32 channels: pair-permuted rows, a lane
 // ends with 8 consecutive channels = one 16-byte store); the pixel fragments are read once for both tiles.
-// YUV: the instantiation for batches with YUV 4:2:0 frames (yuv_device.h: a YUV frame's pixel becomes its BGR bytes, then the BGR path); it serves
-// the batch's BGR frames as well.  Batches of BGR frames only run YUV = false, the kernel as it was.  The same instantiation serves the packed
-// RGB / BGRA / RGBA frames when PK is set as well (the BGR fetch with the frame's pixel size, bytes 0 and 2 exchanged for the R-first layouts).
-// LB: the instantiation of a letterbox engine (letterbox_device.h): a frame that is not model-sized BGR is fetched as padding / a four-tap bilinear
-// blend instead of the nearest-neighbour pick.  Every other engine runs LB = false, the kernel as it was.
-// VIEW: the instantiation for calls whose frames are frame views: every fetch takes its row pitch and plane bases from the frame's ViewRec
-// (planes_device.h) instead of deriving them from w, h.  Always with YUV = true; every other call runs VIEW = false, the kernel as it was.
+// YUV, LB, VIEW, PK: the input variant (front_variants.h).  A frame that is not model-sized BGR is fetched as YUV -> BGR bytes, as a packed pixel or as
+// the letterbox's padding / bilinear blend; the bytes then take the same path.
 template <int NT, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
 {
@@ -191,65 +178,36 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
 
 typedef void (*stem_fused_fn)(const StemArgs);
 typedef void (*stem1_fn)(const Stem1Args);
-#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_DIAG)        // (diagnostic builds, tools/stem_bench.hip: one translation unit)
-// the YUV instantiations, for the launchers in kernels_stem.hip
-stem_fused_fn stem_fused_yuv_kernel(int nt) { return nt == 2 ? stem_fused_kernel<2, true> : stem_fused_kernel<1, true>; }
-#endif
-#if defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_DIAG)
-// the instantiations that serve every format (tight frames)
-stem_fused_fn stem_fused_pix_kernel(int nt, bool lb)
+// The instantiations this unit owns (front_variants.h)
+template <int TU> static stem_fused_fn stem_fused_own(FrontVariant v, int nt)
 {
-    if (lb) return nt == 2 ? stem_fused_kernel<2, true, true, false, true> : stem_fused_kernel<1, true, true, false, true>;
-    return nt == 2 ? stem_fused_kernel<2, true, false, false, true> : stem_fused_kernel<1, true, false, false, true>;
+#define ZLY_ROW(level, lb, view, pre_tu, stem_tu) \
+    if constexpr (TU == front_owner(stem_tu)) \
+        if (v == FrontVariant(level, lb, view)) return nt == 2 ? stem_fused_kernel<2, ZLY_FRONT_FLAGS(level, lb, view)> : stem_fused_kernel<1, ZLY_FRONT_FLAGS(level, lb, view)>;
+    ZLY_FRONT_VARIANTS(ZLY_ROW)
+#undef ZLY_ROW
+    return nullptr;
 }
-#endif
-#if defined(ZLY_STEM_PIX_VIEW_TU) || defined(ZLY_STEM_DIAG)
-// ... and frame views
-stem_fused_fn stem_fused_pix_view_kernel(int nt, bool lb)
-{
-    if (lb) return nt == 2 ? stem_fused_kernel<2, true, true, true, true> : stem_fused_kernel<1, true, true, true, true>;
-    return nt == 2 ? stem_fused_kernel<2, true, false, true, true> : stem_fused_kernel<1, true, false, true, true>;
-}
-#endif
-#if defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_DIAG)
-// the letterbox instantiations
-stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv)
-{
-    if (yuv) return nt == 2 ? stem_fused_kernel<2, true, true> : stem_fused_kernel<1, true, true>;
-    return nt == 2 ? stem_fused_kernel<2, false, true> : stem_fused_kernel<1, false, true>;
-}
-#endif
-#if defined(ZLY_STEM_VIEW_TU) || defined(ZLY_STEM_DIAG)
-// the frame-view instantiations (always YUV-capable: they serve BGR views too)
-stem_fused_fn stem_fused_view_kernel(int nt, bool lb)
-{
-    if (lb) return nt == 2 ? stem_fused_kernel<2, true, true, true> : stem_fused_kernel<1, true, true, true>;
-    return nt == 2 ? stem_fused_kernel<2, true, false, true> : stem_fused_kernel<1, true, false, true>;
-}
-#endif
-#ifndef ZLY_STEM_SIDE_TU
-stem_fused_fn stem_fused_view_kernel(int nt, bool lb);        // kernels_view.hip
-stem1_fn      stem1_view_kernel(int nw, int var, bool lb);
-stem_fused_fn stem_fused_yuv_kernel(int nt);         // kernels_stem_yuv.hip
-stem1_fn      stem1_yuv_kernel(int nw, int var);
-stem_fused_fn stem_fused_lb_kernel(int nt, bool yuv);         // kernels_lb.hip
-stem1_fn      stem1_lb_kernel(int nw, int var, bool yuv);
-stem_fused_fn stem_fused_pix_kernel(int nt, bool lb);         // kernels_pix.hip
-stem1_fn      stem1_pix_kernel(int nw, int var, bool lb);
-stem_fused_fn stem_fused_pix_view_kernel(int nt, bool lb);    // kernels_pix_view.hip
-stem1_fn      stem1_pix_view_kernel(int nw, int var, bool lb);
+template <int TU> stem_fused_fn stem_fused_kernel_in(FrontVariant v, int nt);      // unit TU's getter, defined where TU is compiled
+template <> stem_fused_fn stem_fused_kernel_in<ZLY_FRONT_TU>(FrontVariant v, int nt) { return stem_fused_own<ZLY_FRONT_TU>(v, nt); }
 
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, int yuv, bool lb, bool view)
+#if ZLY_FRONT_LAUNCHERS
+static stem_fused_fn stem_fused_kernel_of(FrontVariant v, int nt)
+{
+#define ZLY_ROW(level, lb, view, pre_tu, stem_tu) if (v == FrontVariant(level, lb, view)) return stem_fused_kernel_in<front_owner(stem_tu)>(v, nt);
+    ZLY_FRONT_VARIANTS(ZLY_ROW)
+#undef ZLY_ROW
+    return nullptr;
+}
+
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, FrontVariant v)
 {
     if (a.Cout != 16 && a.Cout != 32) return hipErrorInvalidValue;         // one or two 16-channel MFMA tiles (YOLOv8n / YOLOv8-s); wider stems use the generic path
     if (a.Cout == 32 && (a.out_cs % 8 || a.out_co % 8)) return hipErrorInvalidValue;
+    const stem_fused_fn fn = stem_fused_kernel_of(v, a.Cout == 16 ? 1 : 2);
+    if (!fn) return hipErrorInvalidValue;
     const int tiles_y = (a.Ho + STEM_TH - 1) / STEM_TH;
-    if (yuv >= ZLY_FRONT_PACKED) hipLaunchKernelGGL(view ? stem_fused_pix_view_kernel(a.Cout == 16 ? 1 : 2, lb) : stem_fused_pix_kernel(a.Cout == 16 ? 1 : 2, lb), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
-    else if (view) hipLaunchKernelGGL(stem_fused_view_kernel(a.Cout == 16 ? 1 : 2, lb), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
-    else if (lb) hipLaunchKernelGGL(stem_fused_lb_kernel(a.Cout == 16 ? 1 : 2, yuv), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
-    else if (yuv) hipLaunchKernelGGL(stem_fused_yuv_kernel(a.Cout == 16 ? 1 : 2), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
-    else if (a.Cout == 16) hipLaunchKernelGGL((stem_fused_kernel<1, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((stem_fused_kernel<2, false>), dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(fn, dim3(a.tiles_x * tiles_y, n), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -299,18 +257,16 @@ __device__ unsigned long long* g_stem_diag = nullptr;            // diagnostic b
 //   read 2 (k-step 1, first half):  kq0 (1,2)  kq1 zero   kq2 (2,2)  kq3 zero            (k-step 1, second half: all zero weights, not read)
 // Round 3's order (tap = s * 8 + kq * 2 + j) put two taps of equal pixel parity into half of the lane groups' pairs: 2-way conflicts on 4 of 8 half-wave
 // reads, and a fourth read for slots whose weights are all zero.
-#ifndef ZLY_STEM_SIDE_TU
+#if ZLY_FRONT_LAUNCHERS
 static const int STEM1_TAP_SLOT[9] = {0, 2, 5, 4, 6, 8, 1, 3, 12};
 const int* stem1_tap_slot() { return STEM1_TAP_SLOT; }
 #endif
 
-// YUV: the instantiation for batches with frames that are not plain BGR (YUV 4:2:0, packed RGB / BGRA / RGBA).  Such a frame never counts as `same`
-// (request size == model size), so it never reaches the BGR quad paths, which are for 3-byte B-first pixels only; the per-pixel general path fetches it through yuv_device.h (all byte loads of a thread first, then the conversions).  Batches of
-// BGR frames only run YUV = false, the kernel as it was.
-// LB: the instantiation of a letterbox engine.  Model-sized BGR frames keep the quad paths (the letterbox map is the identity for them); every other
-// frame takes the letterbox general path below.  Every other engine runs LB = false, the kernel as it was.
-// VIEW: the instantiation for frame views (planes_device.h).  A model-sized BGR view -- a model-sized window of a larger surface, the headline use --
-// keeps the quad paths: one 12-byte load per four pixels at row address iy * pitch0 + ix * 3.  A quad lies inside its row, hence inside the plane.
+// YUV, LB, VIEW, PK: the input variant (front_variants.h).  The quad paths are for 3-byte B-first pixels only: model-sized BGR frames -- tight, in a
+// letterbox engine (the letterbox map is the identity for them) or as a view (a model-sized window of a larger surface, the headline use: one 12-byte load
+// per four pixels at row address iy * pitch0 + ix * 3; a quad lies inside its row, hence inside the plane).  A YUV or packed RGB / BGRA / RGBA frame never
+// counts as `same`; the per-pixel general path fetches it through yuv_device.h (all byte loads of a thread first, then the conversions), a letterbox engine's
+// other frames take the letterbox general path.
 template <int NW, int VAR, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem_model1_kernel(const Stem1Args a)
 {
@@ -805,47 +761,27 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
 }
 
 static constexpr int STEM1_NW = 8;
-#if defined(ZLY_STEM_YUV_TU) || defined(ZLY_STEM_DIAG)
-stem1_fn stem1_yuv_kernel(int nw, int var)
+// waves per workgroup x kernel variant of one input variant
+template <bool YUV, bool LB, bool VIEW, bool PK> static stem1_fn stem1_nw_var(int nw, int var)
 {
-    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, true> : nw == 16 ? stem_model1_kernel<16, 2, true> : stem_model1_kernel<STEM1_NW, 2, true>;
-    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, true> : nw == 16 ? stem_model1_kernel<16, 1, true> : stem_model1_kernel<STEM1_NW, 1, true>;
-    return nw == 12 ? stem_model1_kernel<12, 0, true> : nw == 16 ? stem_model1_kernel<16, 0, true> : stem_model1_kernel<STEM1_NW, 0, true>;
+    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 2, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 2, YUV, LB, VIEW, PK>;
+    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 1, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 1, YUV, LB, VIEW, PK>;
+    return nw == 12 ? stem_model1_kernel<12, 0, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 0, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 0, YUV, LB, VIEW, PK>;
 }
-#endif
-#if defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_PIX_VIEW_TU) || defined(ZLY_STEM_DIAG)
-template <bool LB, bool VIEW> static stem1_fn stem1_pix_pick(int nw, int var)
+// The instantiations this unit owns (front_variants.h)
+template <int TU> static stem1_fn stem1_own(FrontVariant v, int nw, int var)
 {
-    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, true, LB, VIEW, true> : nw == 16 ? stem_model1_kernel<16, 2, true, LB, VIEW, true> : stem_model1_kernel<STEM1_NW, 2, true, LB, VIEW, true>;
-    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, true, LB, VIEW, true> : nw == 16 ? stem_model1_kernel<16, 1, true, LB, VIEW, true> : stem_model1_kernel<STEM1_NW, 1, true, LB, VIEW, true>;
-    return nw == 12 ? stem_model1_kernel<12, 0, true, LB, VIEW, true> : nw == 16 ? stem_model1_kernel<16, 0, true, LB, VIEW, true> : stem_model1_kernel<STEM1_NW, 0, true, LB, VIEW, true>;
+#define ZLY_ROW(level, lb, view, pre_tu, stem_tu) \
+    if constexpr (TU == front_owner(stem_tu)) \
+        if (v == FrontVariant(level, lb, view)) return stem1_nw_var<ZLY_FRONT_FLAGS(level, lb, view)>(nw, var);
+    ZLY_FRONT_VARIANTS(ZLY_ROW)
+#undef ZLY_ROW
+    return nullptr;
 }
-#endif
-#if defined(ZLY_STEM_PIX_TU) || defined(ZLY_STEM_DIAG)
-stem1_fn stem1_pix_kernel(int nw, int var, bool lb) { return lb ? stem1_pix_pick<true, false>(nw, var) : stem1_pix_pick<false, false>(nw, var); }
-#endif
-#if defined(ZLY_STEM_PIX_VIEW_TU) || defined(ZLY_STEM_DIAG)
-stem1_fn stem1_pix_view_kernel(int nw, int var, bool lb) { return lb ? stem1_pix_pick<true, true>(nw, var) : stem1_pix_pick<false, true>(nw, var); }
-#endif
-#if defined(ZLY_STEM_LB_TU) || defined(ZLY_STEM_DIAG)
-template <bool YUV> static stem1_fn stem1_lb_pick(int nw, int var)
-{
-    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, YUV, true> : nw == 16 ? stem_model1_kernel<16, 2, YUV, true> : stem_model1_kernel<STEM1_NW, 2, YUV, true>;
-    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, YUV, true> : nw == 16 ? stem_model1_kernel<16, 1, YUV, true> : stem_model1_kernel<STEM1_NW, 1, YUV, true>;
-    return nw == 12 ? stem_model1_kernel<12, 0, YUV, true> : nw == 16 ? stem_model1_kernel<16, 0, YUV, true> : stem_model1_kernel<STEM1_NW, 0, YUV, true>;
-}
-stem1_fn stem1_lb_kernel(int nw, int var, bool yuv) { return yuv ? stem1_lb_pick<true>(nw, var) : stem1_lb_pick<false>(nw, var); }
-#endif
-#if defined(ZLY_STEM_VIEW_TU) || defined(ZLY_STEM_DIAG)
-template <bool LB> static stem1_fn stem1_view_pick(int nw, int var)
-{
-    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, true, LB, true> : nw == 16 ? stem_model1_kernel<16, 2, true, LB, true> : stem_model1_kernel<STEM1_NW, 2, true, LB, true>;
-    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, true, LB, true> : nw == 16 ? stem_model1_kernel<16, 1, true, LB, true> : stem_model1_kernel<STEM1_NW, 1, true, LB, true>;
-    return nw == 12 ? stem_model1_kernel<12, 0, true, LB, true> : nw == 16 ? stem_model1_kernel<16, 0, true, LB, true> : stem_model1_kernel<STEM1_NW, 0, true, LB, true>;
-}
-stem1_fn stem1_view_kernel(int nw, int var, bool lb) { return lb ? stem1_view_pick<true>(nw, var) : stem1_view_pick<false>(nw, var); }
-#endif
-#ifndef ZLY_STEM_SIDE_TU
+template <int TU> stem1_fn stem1_kernel_in(FrontVariant v, int nw, int var);      // unit TU's getter, defined where TU is compiled
+template <> stem1_fn stem1_kernel_in<ZLY_FRONT_TU>(FrontVariant v, int nw, int var) { return stem1_own<ZLY_FRONT_TU>(v, nw, var); }
+
+#if ZLY_FRONT_LAUNCHERS
 static size_t stem1_lds_bytes(int th, int tw, int var)
 {
     const size_t RH = 2 * th + 1, RW = 2 * tw + 1, PH = 2 * RH + 1, PW = 2 * RW + 1 + (var >= 1 ? 3 : 0);
@@ -864,30 +800,25 @@ void stem1_plan(int H1, int W1, const Switches& sw, int* th, int* tw)
     (void)H1;
 }
 
-static stem1_fn pick_stem1(int nw, int var, int yuv, bool lb = false, bool view = false)
+static stem1_fn stem1_kernel_of(FrontVariant v, int nw, int var)
 {
-    if (yuv >= ZLY_FRONT_PACKED) return view ? stem1_pix_view_kernel(nw, var, lb) : stem1_pix_kernel(nw, var, lb);
-    if (view) return stem1_view_kernel(nw, var, lb);
-    if (lb) return stem1_lb_kernel(nw, var, yuv);
-    if (yuv) return stem1_yuv_kernel(nw, var);
-    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, false> : nw == 16 ? stem_model1_kernel<16, 2, false> : stem_model1_kernel<STEM1_NW, 2, false>;
-    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, false> : nw == 16 ? stem_model1_kernel<16, 1, false> : stem_model1_kernel<STEM1_NW, 1, false>;
-    return nw == 12 ? stem_model1_kernel<12, 0, false> : nw == 16 ? stem_model1_kernel<16, 0, false> : stem_model1_kernel<STEM1_NW, 0, false>;
+#define ZLY_ROW(level, lb, view, pre_tu, stem_tu) if (v == FrontVariant(level, lb, view)) return stem1_kernel_in<front_owner(stem_tu)>(v, nw, var);
+    ZLY_FRONT_VARIANTS(ZLY_ROW)
+#undef ZLY_ROW
+    return nullptr;
 }
 
 static int g_stem1_cus = 256;
 hipError_t stem1_init()
 {
-    for (int var = 0; var <= 2; ++var)
-        for (int nw : {STEM1_NW, 12, 16})
-            for (int yuv : {ZLY_FRONT_BGR, ZLY_FRONT_YUV, ZLY_FRONT_PACKED})
-                for (bool lb : {false, true}) {
-                    hipError_t r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv, lb), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (r != hipSuccess) return r;
-                    if (!yuv) continue;
-                    r = hipFuncSetAttribute((const void*)pick_stem1(nw, var, yuv, lb, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (r != hipSuccess) return r;
-                }
+    for (const FrontVariant& v : FRONT_VARIANTS)
+        for (int var = 0; var <= 2; ++var)
+            for (int nw : {STEM1_NW, 12, 16}) {
+                const stem1_fn fn = stem1_kernel_of(v, nw, var);
+                if (!fn) return hipErrorInvalidValue;           // a row of the table that no unit instantiates
+                const hipError_t r = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (r != hipSuccess) return r;
+            }
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_stem1_cus = cus;
     return hipSuccess;
@@ -896,7 +827,7 @@ hipError_t stem1_init()
 // a.nw: waves per workgroup (8; 12 / 16 = tuning aid ZLY_STEM1_NW); a.var: 2 = persistent workgroups with the next tile's input bytes in flight (default),
 // 1 = one tile per workgroup, 0 = round 3's staging / tap order as well (ZLY_STEM1_VAR, A/B on one box).  Both are read by the engine once per
 // zly_create, not here (a process-static switch cannot be toggled by a test)
-hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, int yuv, bool lb, bool view)
+hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, FrontVariant v)
 {
     Stem1Args a = a0;
     if (a.st.Cout != 16 || a.TH < 1 || a.TW < 1 || a.out1_cs % 8 || a.out1_co % 8) return hipErrorInvalidValue;
@@ -922,18 +853,20 @@ hipError_t launch_stem_model1(const Stem1Args& a0, int n, hipStream_t s, int yuv
     a.n = n;
     const long long total = (long long)a.tiles_x * a.tiles_y * n;
     if (total > 0x7fffffff) return hipErrorInvalidValue;
+    const stem1_fn fn = stem1_kernel_of(v, nw, var);
+    if (!fn) return hipErrorInvalidValue;
+    dim3 grid(a.tiles_x * a.tiles_y, n);
     if (var >= 2) {
         // as many workgroups as stay resident (LDS: 160 KB per CU); with fewer tiles than that, one tile each
         long long wgs = (long long)g_stem1_cus * (long long)((160 * 1024) / lds < 1 ? 1 : (160 * 1024) / lds);
         if (a.pgrid > 0) wgs = a.pgrid;                                                            // tuning aid ZLY_STEM1_GRID (read by the engine per zly_create)
         if (wgs > total) wgs = total;
-        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb, view), dim3((unsigned)wgs), dim3(nw * 64), lds, s, a);
-    } else {
-        hipLaunchKernelGGL(pick_stem1(nw, var, yuv, lb, view), dim3(a.tiles_x * a.tiles_y, n), dim3(nw * 64), lds, s, a);
+        grid = dim3((unsigned)wgs);
     }
+    hipLaunchKernelGGL(fn, grid, dim3(nw * 64), lds, s, a);
     return hipGetLastError();
 }
 
-#endif  // !ZLY_STEM_SIDE_TU
+#endif  // ZLY_FRONT_LAUNCHERS
 
 }  // namespace zly

@@ -1,8 +1,5 @@
-// kernels_view.hip -- the VIEW = true instantiations of the front kernels (preprocess_kernel, stem_fused_kernel, stem_model1_kernel; stretch and
-// letterbox forms) for calls whose frames are frame views (include/zly.h zly_frame_view: pitched surfaces and regions of interest), in a translation
-// unit of their own so that the instantiations every other call launches compile exactly as before (see kernels_stem.hip).  They are YUV-capable and
-// serve BGR views too; the Detect tail does not change (FrameDesc::w, h hold the view's size).
-#define ZLY_VIEW_TU 1
-#define ZLY_STEM_VIEW_TU 1
+// kernels_view.hip -- the VIEW unit of front_variants.h: the front kernels' instantiations for calls on frame views (include/zly.h zly_frame_view)
+// of BGR and YUV 4:2:0 frames, stretch and letterbox.  The Detect tail does not change (FrameDesc::w, h hold the view's size).
+#define ZLY_FRONT_TU ZLY_TU_VIEW
 #include "kernels_misc.hip"
 #include "kernels_stem.hip"

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <string>
 #include "zly.h"
+#include "front_variants.h"
 
 namespace zly {
 
@@ -22,10 +23,7 @@ __host__ __device__ __forceinline__ unsigned long long desc_pack(unsigned long l
 __host__ __device__ __forceinline__ unsigned long long desc_off(unsigned long long v) { return v & ((1ull << ZLY_DESC_FMT_SHIFT) - 1); }
 __host__ __device__ __forceinline__ int desc_fmt(unsigned long long v) { return (int)(v >> ZLY_DESC_FMT_SHIFT); }
 
-// The format level of a batch: which instantiation of the front kernel its frames need (yuv_device.h).  A level serves the levels below it as well.
-#define ZLY_FRONT_BGR    0      // plain BGR frames only: the headline kernels
-#define ZLY_FRONT_YUV    1      // at least one YUV 4:2:0 frame, no packed RGB / BGRA / RGBA frame
-#define ZLY_FRONT_PACKED 2      // at least one packed RGB / BGRA / RGBA frame
+// The format level a frame of this format asks of the front kernels (front_variants.h: ZLY_FRONT_*)
 __host__ __device__ __forceinline__ int front_level(int fmt)
 {
     return fmt == ZLY_PIX_BGR ? ZLY_FRONT_BGR : fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709 ? ZLY_FRONT_YUV : ZLY_FRONT_PACKED;
@@ -232,13 +230,9 @@ hipError_t c2f64_init();
 hipError_t launch_c2f64(int mode, const C2fArgs& a, const C2fPlan& plan, hipStream_t s);
 
 // kernels_misc.hip
-// yuv: the format level of the batch (ZLY_FRONT_*) -> the instantiation of the front kernel that serves it: BGR only; BGR + YUV 4:2:0 (at least one YUV
-// frame, no packed one); every format (at least one packed RGB / BGRA / RGBA frame).  A level serves the batches of the levels below it too.
-// lb: a letterbox engine (ZLY_FLAG_LETTERBOX) -> the letterbox instantiations of the front kernels and of the Detect tail (kernels_lb.hip)
-// view: the call's frames are frame views (n ViewRec behind the n descriptors) -> the VIEW instantiations of the front kernels (kernels_view.hip), which
-//       are YUV-capable and serve BGR frames too
+// v (here and in the two stem launchers): which instantiation of the front kernel runs (front_variants.h); with view set, n ViewRec lie behind the n descriptors
 hipError_t launch_preprocess(int dtype, const uint8_t* src, const FrameDesc* desc, int n,
-                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, int yuv = 0, bool lb = false, bool view = false);
+                             void* out_nhwc8, float* out_nchw_f32, int tw, int th, hipStream_t s, FrontVariant v);
 hipError_t launch_nchw_to_nhwc8(int dtype, const float* in_nchw, void* out_nhwc8, int n, int tw, int th, hipStream_t s);
 hipError_t launch_sppf_pool(int dtype, void* buf, int cs, int c, int n, int H, int W, hipStream_t s, int six_pass = 0);      // six_pass: sppf_pool_kernel also on maps of <= 16 x 16 pixels (tests / A-B)
 bool       sppf_pool16_ok(int dtype, int cs, int c, int n, int H, int W, int six_pass);                        // does launch_sppf_pool take sppf_pool16_kernel?
@@ -251,7 +245,7 @@ struct StemArgs {
     void* out; int out_cs, out_co;
     int tw, th, Ho, Wo, Cout, tiles_x;
 };
-hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, int yuv = 0, bool lb = false, bool view = false);
+hipError_t launch_stem_fused(const StemArgs& a, int n, hipStream_t s, FrontVariant v);
 int stem_tiles_x(int Wo);
 // preprocess + model.0 + model.1 in one kernel (the stem map stays in LDS); st.out is only written with dump = 1 (debug taps)
 struct Stem1Args {
@@ -271,7 +265,7 @@ struct Stem1Args {
 };
 void       stem1_plan(int H1, int W1, const Switches& sw, int* th, int* tw);
 hipError_t stem1_init();
-hipError_t launch_stem_model1(const Stem1Args& a, int n, hipStream_t s, int yuv = 0, bool lb = false, bool view = false);
+hipError_t launch_stem_model1(const Stem1Args& a, int n, hipStream_t s, FrontVariant v);
 const int* stem1_tap_slot();              // [9]: k slot of tap ky * 3 + kx in Stem1Args::wgt0p (weights.h: repack_conv's tap_slot)
 
 // kernels_sppf.hip -- SPPF (cv1 -> three 5x5 max pools -> cv2 over the concat) as one kernel; bf16, hidden width 128, maps of up to 176 pixels

@@ -46,7 +46,7 @@ static void run(int n, int var, int nw, int th, int tw, int pgrid = 0, int fw = 
     float ms = 0, best = 1e9f;
     for (int rep = 0; rep < 30; ++rep) {
         (void)hipEventRecord(e0, 0);
-        if (launch_stem_model1(a, n, 0, false, lb) != hipSuccess) { printf("launch failed (var %d nw %d tile %dx%d)\n", var, nw, th, tw); return; }
+        if (launch_stem_model1(a, n, 0, FrontVariant(ZLY_FRONT_BGR, lb)) != hipSuccess) { printf("launch failed (var %d nw %d tile %dx%d)\n", var, nw, th, tw); return; }
         (void)hipEventRecord(e1, 0); (void)hipEventSynchronize(e1);
         (void)hipEventElapsedTime(&ms, e0, e1);
         if (rep >= 10 && ms < best) best = ms;
