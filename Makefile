@@ -16,7 +16,7 @@ KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_mi
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
 OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/engine.o $(OUT)/weights.o
 
-all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench oracle weights host
+all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so oracle weights host
 
 $(OUT):
 	mkdir -p $(OUT)
@@ -46,6 +46,14 @@ $(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_va
 	$(HIPCC) $(HIPFLAGS) -DZLY_DIAG=1 -x hip -c $< -o $@
 $(OUT)/libzly_diag.so: $(filter-out $(OUT)/engine.o,$(OBJS)) $(OUT)/engine_diag.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
+
+# ---- test infrastructure: one batched launch of the shipped nms_kernel on caller-made candidate buffers (tests/test_gpu_nms_batched.py).  It links the
+#      kernels_post.o of libzly.so itself -- the object under test, not a recompilation; -Bsymbolic: its calls bind to its own copy beside libzly.so
+nms_probe: $(OUT)/libnms_probe.so
+$(OUT)/nms_probe_main.o: tests/cpp/nms_probe.hip $(CSRC)/zly_internal.h include/zly.h | $(OUT)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OUT)/libnms_probe.so: $(OUT)/nms_probe_main.o $(OUT)/kernels_post.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-Bsymbolic -o $@ $^
 
 # ---- in-process RCCL gather of result slabs (include/zly_gather.h): a library of its own -- it links RCCL, and a process that already carries
 #      PyTorch's bundled RCCL (bench.py, the tests) must never load a second one
@@ -120,4 +128,4 @@ $(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_
 clean:
 	rm -rf $(OUT) oracle/_build
 
-.PHONY: all host oracle weights diag diaglib clean
+.PHONY: all host oracle weights diag diaglib nms_probe clean
