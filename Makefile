@@ -21,7 +21,7 @@ all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_shar
 $(OUT):
 	mkdir -p $(OUT)
 
-KHDRS    := $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h $(CSRC)/letterbox_device.h $(CSRC)/planes_device.h include/zly.h
+KHDRS    := $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h $(CSRC)/letterbox_device.h $(CSRC)/planes_device.h $(CSRC)/head_skip.h include/zly.h
 $(OUT)/%.o: $(CSRC)/%.hip $(KHDRS) | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -72,7 +72,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -105,6 +105,10 @@ $(OUT)/test_wire: tests/cpp/test_wire.cpp $(HOST)/zly_wire.hpp $(HOST)/zly_sha25
 
 $(OUT)/test_game_step: tests/cpp/test_game_step.cpp $(HOST)/zly_game_step.hpp $(HOST)/zly_compat.hpp | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -I$(HOST) -o $@ tests/cpp/test_game_step.cpp
+
+# the Detect tail's early-out bound (csrc/head_skip.h) as the launcher computes it, printed for tests/test_head_skip.py (test infrastructure: no GPU)
+$(OUT)/test_head_skip: tests/cpp/test_head_skip.cpp $(CSRC)/head_skip.h | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ tests/cpp/test_head_skip.cpp
 
 # ---- CPU oracle (test infrastructure only) --------------------------------------------------------
 oracle: oracle/_build/libzly_oracle.so

@@ -11,6 +11,7 @@
 #include "zly_internal.h"
 #include "conv_device.h"
 #include "letterbox_device.h"
+#include "head_skip.h"
 #include <algorithm>
 #include <math.h>
 
@@ -117,8 +118,9 @@ __device__ __forceinline__ void tail_box_conv(const HeadLevel& L, const __amdgpu
 // per 16) and the fragments come from there; the class-branch activations are requested BEFORE the weight staging and its barrier, so
 // they are in flight meanwhile; and the epilogue is skipped where it cannot matter:
 // Early out (production: no head tensor, no logit dump): when NO anchor of the tile has a class logit above skip_logit =
-// logit(conf_thr) - 1e-2, none can reach the confidence threshold (the margin is four orders of magnitude above the error of
-// v_exp / v_rcp), and the box loads, the box GEMM, the DFL and the 80 sigmoids per anchor are skipped -- ~4 of 5 tiles on a detector that
+// -log((1 - conf_thr) / conf_thr + 4 * 2^-24) - 1e-2 (head_skip.h), none can reach the confidence threshold: the 1e-2 is four orders of
+// magnitude above the relative error of v_exp / v_rcp, and the 4 * 2^-24 is the absolute rounding of 1 + e and of the quotient, which is
+// what decides once 1 - conf_thr is itself a few units of 2^-24 (tests/test_head_skip.py scans every fp32 logit below the bound), and the box loads, the box GEMM, the DFL and the 80 sigmoids per anchor are skipped -- ~4 of 5 tiles on a detector that
 // passes ~1.5 % of its anchors.  Tiles that are not skipped run the full arithmetic, so the candidates are exactly the same.
 // LB: the instantiation of a letterbox engine (include/zly.h ZLY_FLAG_LETTERBOX): a surviving anchor's box is mapped out of the letterbox -- its
 // geometry recomputed from the frame descriptor, for survivors only -- instead of divided by the request size.  Compiled in kernels_lb.hip.
@@ -427,10 +429,8 @@ head_fn head_fused_lb_kernel(int dtype, int ctc);
 hipError_t launch_head_fused(int dtype, const HeadArgs& a0, int n, hipStream_t s)
 {
     HeadArgs a = a0;
-    // the class logit below which no score can reach conf_thr (see the kernel): logit(thr) minus a margin; thr <= 0 keeps everything,
-    // thr >= 1 needs sigmoid(z) to round to 1.0f, i.e. z > 17
-    const double thr = (double)a.conf_thr;
-    a.skip_logit = thr <= 0.0 ? -3.0e38f : (thr >= 1.0 ? 15.0f : (float)(log(thr / (1.0 - thr)) - 1e-2));
+    // the class logit below which no score can reach conf_thr (see the kernel), derived in head_skip.h; thr <= 0 keeps everything
+    a.skip_logit = head_skip_logit(a.conf_thr);
     const int ctc = (a.nc + 15) / 16;
     head_fn fn = a.lb_tw > 0 ? head_fused_lb_kernel(dtype, ctc) : dtype == ZLY_DTYPE_BF16 ? pick_head<bf16_t, false>(ctc) : pick_head<float, false>(ctc);
     if (!fn) return hipErrorInvalidValue;                  // nc > 80 is not supported by this kernel

@@ -1,6 +1,6 @@
 """How many of the Detect tail's 16-anchor waves survive its early-out -- i.e. run the box half, and with ZLY_TAIL_BOX the box branch's second conv --
 on the benchmark's frames: the class logits of a ZLY_FLAG_DUMP_LOGITS engine (the kernel's own fp32 values), cut into the kernel's tiles (16 consecutive
-anchors of one level of one frame) and compared with its skip_logit = logit(conf_thr) - 1e-2.
+anchors of one level of one frame) and compared with its skip_logit (csrc/head_skip.h: logit(conf_thr) - 1e-2 but for a term that matters next to conf_thr = 1).
 usage: surviving_waves.py [thresholds=0.5,0.25,0.1,0.05] [frames=64] [size=416] [scale=n]"""
 import math, os, sys
 import numpy as np
@@ -30,7 +30,7 @@ for f0 in range(0, n, B):
             zt = np.concatenate([z, np.full(pad, -np.inf, np.float32)]).reshape(-1, 16).max(axis=1)
             total[l] += len(zt)
             for t in thrs:
-                skip = math.log(t / (1.0 - t)) - 1e-2
+                skip = -math.log((1.0 - t) / t + 4.0 * 2.0 ** -24) - 1e-2             # csrc/head_skip.h
                 tiles[t][l] += int((zt >= skip).sum())
                 passing[t] += int((z >= skip).sum())
 e.close()
