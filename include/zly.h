@@ -337,6 +337,75 @@ int32_t zly_sync(zly_engine* e);
  * completion events of its last two calls only, any other lag fails with ZLY_ERR_INVALID_ARGUMENT. */
 int32_t zly_join(zly_engine* e, void* stream, int32_t lag);
 
+/* --- tracking ----------------------------------------------------------------------------------------------------------------------
+ * Fills zly_det::track_id on the GPU, behind NMS.  Opt-in per engine (zly_track_enable) and per frame (its stream index): without it nothing
+ * changes -- no extra launch, identical bytes, track_id = 0.  The reference's game step gives every detection with id 0 a fresh id on every frame
+ * (cs16_game_adapter.cpp:243-262) and its client keys its Kalman filters by track_id (src/client/prediction_engine.cpp:19-72), so only a
+ * tracked frame lets a client filter see a second measurement.  The association is the reference's own IoU matching (src/game/kalman_tracker.h,
+ * threshold 0.3) without its motion model: no prediction, no min_hits, no re-identification -- the client filters what it gets.
+ *
+ * A frame may name a STREAM, an index in [0, max_streams): an ordered sequence of frames, for example one client.  The engine keeps one track
+ * table per stream in HBM.
+ * THE RULE: the track_ids of a stream's frames are a function of that stream's own sequence of detection lists and of nothing else -- not of
+ * which other frames or streams share a call or a batch, the batch size, the entry point, whether the stream's frames arrive one per call or
+ * many in one call (they are then taken in index order), or what other streams did before.  Every byte of a slab other than the track_id fields
+ * equals the untracked result.
+ *
+ * The step for one frame of a stream.  State: frame_no (u32, starts at 0), next_id (u32, starts at 1), T = max_tracks slots
+ * {live, x, y, w, h, class_id, id, last_seen}.  Input: the frame's stored detections D[0..K) in slab order, K = clamp(n_kept, 0, cap).
+ *   1. frame_no += 1.
+ *   2. Candidate pairs (d, t): slot t is live, D[d].class_id == slot[t].class_id and iou(D[d], slot[t]) > match_iou (strict, as in NMS); iou is
+ *      calculateIoU (onnx_engine.cpp:881-909) in the same single fp32 operations, in the same order, without contraction, as NMS computes it.
+ *   3. Greedy match: go through the pairs in the total order (iou descending as fp32 value, d ascending, t ascending) and accept a pair when
+ *      neither its detection nor its slot has been accepted yet.  (Not the optimal assignment.)
+ *   4. An accepted pair: the slot takes the detection's box, last_seen = frame_no, D[d].track_id = slot.id.
+ *   5. Expiry: a live slot that was not matched in this frame and has frame_no - last_seen > max_lost (u32 arithmetic) becomes free.
+ *   6. Births, for each unmatched detection in ascending d: the lowest free slot -- or, if none is free, the live slot that was neither
+ *      matched nor born in this frame with the smallest last_seen, the lowest index breaking ties (one exists because T >= cap; counted as an
+ *      eviction) -- becomes {live, box, class, id = next_id, last_seen = frame_no}; D[d].track_id = next_id; next_id becomes next_id + 1, or 1
+ *      if that is 0.
+ * So every stored detection of a tracked frame leaves with a non-zero id, and ids are per stream.
+ * Not tracked: frames that go through the synchronous host calls or the _fmt submits, and engines behind host/zly_sharded*.hpp (consecutive
+ * frames of a stream land on different GPUs).  A new engine (the plugin's hot reload) starts with fresh tables. */
+typedef struct zly_track_config {
+    int32_t max_streams;   /* >= 1 */
+    int32_t max_tracks;    /* T: max_dets <= T <= 64 (an engine with max_dets > 64 cannot track) */
+    float   match_iou;     /* in [0, 1); default 0.3, kalman_tracker.h:173 */
+    int32_t max_lost;      /* >= 0; default 6 = the adapter's 100 ms at the reference's 60 FPS target */
+} zly_track_config;
+
+typedef struct zly_track_state {
+    uint32_t frame_no, next_id;
+    int32_t  n_live;       /* live slots */
+    uint32_t evictions;    /* births that found no free slot, since the stream's last reset */
+} zly_track_state;
+
+void    zly_default_track_config(zly_track_config* cfg);
+/* Once per engine, before the first tracked call: allocates the tables (alone in the process, like the allocations of zly_create).  Errors --
+ * ZLY_ERR_INVALID_ARGUMENT for a null or out-of-range config (see the fields) and for a second call, ZLY_ERR_SYSTEM for a failed allocation.
+ * Every other tracking call on an engine without tables, a stream index below -1 or >= max_streams and a batch size outside 1..max_batch
+ * fail with ZLY_ERR_INVALID_ARGUMENT and enqueue nothing. */
+int32_t zly_track_enable(zly_engine* e, const zly_track_config* cfg);
+/* All slots of the stream become free, frame_no and the eviction count 0; stream = -1: every stream.  first_id = 0 keeps next_id, any other value
+ * sets it.  Waits for the tracking enqueued so far and takes effect before it returns; frames still waiting in the submit ring are tracked after it. */
+int32_t zly_track_reset(zly_engine* e, int32_t stream, uint32_t first_id);
+/* Synchronises with the tracking enqueued so far, then reads (tests, status pages). */
+int32_t zly_track_state_at(zly_engine* e, int32_t stream, zly_track_state* out);
+
+/* The device path: tracks, in place, the n slabs that the most recent zly_detect_device* call on this engine wrote.  d_slabs = NULL: the engine's
+ * own slab buffer.  streams is a HOST array of n; streams[i] = -1 leaves slab i untouched, and a call with nothing but -1 launches nothing.
+ * Enqueued, not synchronised: it is ordered behind that call's NMS on whichever stream the NMS ran -- with ZLY_FLAG_ASYNC_NMS the engine's NMS
+ * stream, otherwise `stream` (NULL = the engine's own), which should be the stream the call was given -- and zly_join, zly_sync and
+ * zly_read_slabs afterwards cover the tracking too.  A later call's kernels never overwrite slabs that the tracker still reads.
+ * Slabs made elsewhere (tests) are tracked the same way on an engine that has made no call yet. */
+int32_t zly_track_slabs(zly_engine* e, int32_t n, const int32_t* streams, void* d_slabs, void* stream);
+
+/* The pipelined path: zly_submit_view / zly_submit_try_view plus the frame's stream (-1 = untracked), which rides with the frame through the ring;
+ * zly_view_tight gives the view of a tight frame.  The tracker runs behind the batch's NMS, before its slabs go back to the host.  Frames of a stream
+ * are tracked in ticket order; a batch may mix tracked and untracked frames.  A refused submit produces no ticket and copies nothing. */
+int32_t zly_submit_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket);
+int32_t zly_submit_try_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket);
+
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw);

@@ -150,6 +150,22 @@ struct Launch {
 
 struct Ingest;        // pipelined host-to-host path (zly_submit / zly_wait), below
 
+// Tracking (zly_track_enable; include/zly.h "Tracking"): the streams' track tables in HBM, and the ring through which a call's grouping of its
+// frames by stream reaches track_kernel.  A ring entry is a pinned host record plus a device record of its own; it follows h_desc's reuse
+// discipline -- rewritten only after the work that read it has completed (its event, recorded behind the kernel) -- so no call waits for the device.
+struct Track {
+    zly_track_config cfg{};
+    TrackStream* d_state = nullptr;   // [max_streams]
+    static constexpr int RING = 8;
+    size_t grp_ints = 0;              // int32 per ring entry: 2 + 3 * max_batch (zly_internal.h: launch_track)
+    int* h_grp = nullptr;             // pinned [RING][grp_ints]
+    int* d_grp = nullptr;             // device [RING][grp_ints]
+    hipEvent_t ev[RING] = {};         // behind the kernel that read entry r
+    bool used[RING] = {};
+    int next = 0;
+    std::vector<int> seg_of;          // [max_streams] scratch of the grouping: a stream's segment in the current call, -1 = none yet
+};
+
 }  // namespace zly
 
 using namespace zly;
@@ -229,6 +245,9 @@ struct zly_engine : Plan {
     int cu_part_n = 1;                // ZLY_CU_PART: number of CU partitions (1 = whole chip)
     uint32_t cu_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::atomic<Ingest*> ingest{nullptr};   // created by the first zly_submit (under mu), read lock-free afterwards
+    std::atomic<Track*> track{nullptr};     // created by zly_track_enable (under mu), read lock-free afterwards
+    hipStream_t last_ns = nullptr;          // the stream the most recent zly_detect_device* call's NMS ran on, and whether that was the engine's NMS stream
+    bool last_deferred = false;
 
     Switches sw;                      // tuning / test switches of the environment, read ONCE at zly_create (read_switches; the list: zly_internal.h)
 
@@ -1373,6 +1392,59 @@ static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, co
     return ZLY_OK;
 }
 
+// Track, in place, the frames of `slabs` (n slabs of this engine's size) whose entry of streams[] is not -1: group them by stream, upload the
+// grouping, launch track_kernel on `s` -- the stream the slabs' NMS ran on, or one already ordered behind it.  Under e->mu, enqueue gate held;
+// streams[] is validated by the caller.  A call without a tracked frame launches nothing (*launched = false).
+static int track_enqueue(zly_engine* e, Track* tk, int n, const int32_t* streams, void* slabs, hipStream_t s, bool* launched)
+{
+    *launched = false;
+    int n_tracked = 0, n_seg = 0;
+    for (int i = 0; i < n; ++i) if (streams[i] >= 0) ++n_tracked;
+    if (n_tracked == 0) return ZLY_OK;
+    const int r = tk->next;
+    tk->next = (r + 1) % Track::RING;
+    if (tk->used[r]) HIP_TRY(hipEventSynchronize(tk->ev[r]), ZLY_ERR_INFERENCE);      // 8 tracked calls back: long complete
+    int* g = tk->h_grp + (size_t)r * tk->grp_ints;
+    // segments in the order of their stream's first occurrence; frames of a segment in index order
+    std::vector<int>& seg_of = tk->seg_of;
+    int* count = g + 1;                                                              // first: frames per segment, at [1 + seg + 1]
+    for (int i = 0; i < n; ++i) {
+        if (streams[i] < 0) continue;
+        int& sg = seg_of[(size_t)streams[i]];
+        if (sg < 0) { sg = n_seg++; count[sg + 1] = 0; }
+        count[sg + 1]++;
+    }
+    int* seg_stream = g + 2 + n_seg;
+    int* frames = g + 2 + 2 * n_seg;
+    g[0] = n_seg;
+    g[1] = 0;
+    for (int sg = 0; sg < n_seg; ++sg) g[2 + sg] += g[1 + sg];                       // inclusive scan: g[1 + sg] = offset of segment sg, g[1 + n_seg] = n_tracked
+    std::vector<int> fill((size_t)n_seg);
+    for (int sg = 0; sg < n_seg; ++sg) fill[(size_t)sg] = g[1 + sg];
+    for (int i = 0; i < n; ++i) {
+        if (streams[i] < 0) continue;
+        const int sg = seg_of[(size_t)streams[i]];
+        seg_stream[sg] = streams[i];
+        frames[fill[(size_t)sg]++] = i;
+    }
+    for (int i = 0; i < n; ++i) if (streams[i] >= 0) seg_of[(size_t)streams[i]] = -1;
+    int* dg = tk->d_grp + (size_t)r * tk->grp_ints;
+    HIP_TRY(hipMemcpyAsync(dg, g, sizeof(int) * (size_t)(2 + 2 * n_seg + n_tracked), hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_track(tk->d_state, dg, n_seg, slabs, e->cfg.max_dets, tk->cfg.max_tracks, tk->cfg.match_iou, (uint32_t)tk->cfg.max_lost, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(tk->ev[r], s), ZLY_ERR_INFERENCE);
+    tk->used[r] = true;
+    *launched = true;
+    return ZLY_OK;
+}
+
+// every tracked launch made so far has completed (under e->mu: none can be enqueued meanwhile)
+static int track_drain(Track* tk)
+{
+    for (int r = 0; r < Track::RING; ++r)
+        if (tk->used[r]) HIP_TRY(hipEventSynchronize(tk->ev[r]), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
 static int ensure_stage(zly_engine* e, size_t bytes)
 {
     if (bytes <= e->stage_bytes) return ZLY_OK;
@@ -1523,6 +1595,13 @@ static hipError_t destroy_engine(zly_engine* e)
     if (e->h_desc) note(hipHostFree(e->h_desc));
     if (e->h_stage) note(hipHostFree(e->h_stage));
     if (e->h_slabs) note(hipHostFree(e->h_slabs));
+    if (Track* tk = e->track.load()) {
+        if (tk->d_state) note(hipFree(tk->d_state));
+        if (tk->d_grp) note(hipFree(tk->d_grp));
+        if (tk->h_grp) note(hipHostFree(tk->h_grp));
+        for (int i = 0; i < Track::RING; ++i) if (tk->ev[i]) hipEventDestroy(tk->ev[i]);
+        delete tk;
+    }
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
         if (e->ev_join[i]) hipEventDestroy(e->ev_join[i]);
@@ -1563,6 +1642,8 @@ struct IngestSlot {
     int n_reserved = 0, n_committed = 0, n_consumed = 0;
     size_t bytes_used = 0;
     std::vector<int32_t> w, h, fmt;
+    std::vector<int32_t> trk;            // the frames' stream indices (zly_submit_view_tracked), -1 = untracked
+    int n_trk = 0;                       // frames of the batch with a stream
     std::vector<size_t> off;
     int level = 0;                       // the batch's format level (ZLY_FRONT_*): the highest of its frames', i.e. which front kernel serves it
     std::vector<uint8_t> consumed;
@@ -1600,7 +1681,7 @@ static bool ingest_try_open(zly_engine* e, Ingest* g)
     IngestSlot& sl = g->slots[(size_t)(g->next_batch % g->slots.size())];
     if (sl.state != SLOT_FREE) return false;
     sl.state = SLOT_OPEN; sl.batch = g->next_batch++;
-    sl.n_reserved = sl.n_committed = sl.n_consumed = 0; sl.bytes_used = 0; sl.level = 0; sl.rc = ZLY_OK; sl.err.clear();
+    sl.n_reserved = sl.n_committed = sl.n_consumed = 0; sl.bytes_used = 0; sl.level = 0; sl.n_trk = 0; sl.rc = ZLY_OK; sl.err.clear();
     std::fill(sl.consumed.begin(), sl.consumed.end(), (uint8_t)0);
     g->open = (int)(sl.batch % g->slots.size());
     (void)e;
@@ -1634,6 +1715,15 @@ static void ingest_enqueue(zly_engine* e, Ingest* g, IngestSlot& sl)
         rc = run_path(e, n, sl.d_stage, sl.d_slabs, (uint32_t)(sl.batch << 16), e->stream, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, sl.level));
         e->ingest_active = false;
         if (rc != ZLY_OK) return rc;
+        // the tracker, right behind the batch's NMS on the stream that ran it; the candidate-buffer event of a deferred NMS moves behind it, so that whatever
+        // is ordered behind this batch's NMS (a later batch's NMS into these slabs, a join) is ordered behind its tracking too
+        Track* tk = e->track.load();
+        if (tk && sl.n_trk > 0) {
+            bool launched = false;
+            rc = track_enqueue(e, tk, n, sl.trk.data(), sl.d_slabs, ns, &launched);
+            if (rc != ZLY_OK) return rc;
+            if (launched && ns != e->stream && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], ns), ZLY_ERR_INFERENCE);
+        }
         // the slabs (n x 2.6 KB) go back on the stream the NMS ran on, right behind it: a download stream of its own would be the fifth
         // stream of a three-engine process and share a hardware queue with a compute stream (ZLY_D2H_STREAM=1 restores it)
         out_stream = g->use_d2h_stream ? g->d2h_stream : ns;
@@ -1741,6 +1831,7 @@ static int ingest_start(zly_engine* e)
              hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming) == hipSuccess;
         if (ok) hipMemset(sl.d_slabs, 0, sb);
         sl.w.resize((size_t)e->cfg.max_batch); sl.h.resize((size_t)e->cfg.max_batch); sl.fmt.resize((size_t)e->cfg.max_batch); sl.off.resize((size_t)e->cfg.max_batch);
+        sl.trk.assign((size_t)e->cfg.max_batch, -1);
         sl.consumed.resize((size_t)e->cfg.max_batch);
     }
     if (!ok) { ingest_free(e, g); return fail(ZLY_ERR_SYSTEM, "allocation of the staging ring failed"); }
@@ -1788,8 +1879,9 @@ static void ingest_free(zly_engine* e, Ingest* g)
 
 // view: the request is a frame view of the buffer bgr[0 .. nbytes) (zly_submit_view): the region's rows are copied into a tight frame of the ring, and
 // from there on the request is that frame
+// track_stream: the frame's stream index (validated by the caller), -1 = untracked; it rides with the frame through the ring
 static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket, bool nonblock = false,
-                         int32_t fmt = ZLY_PIX_BGR, const zly_frame_view* view = nullptr)
+                         int32_t fmt = ZLY_PIX_BGR, const zly_frame_view* view = nullptr, int32_t track_stream = -1)
 {
     int rcv;
     if (view) {
@@ -1834,6 +1926,8 @@ static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32
             off = o.bytes_used;
             o.bytes_used += padded;
             o.w[(size_t)idx] = w; o.h[(size_t)idx] = h; o.fmt[(size_t)idx] = fmt; o.off[(size_t)idx] = off;
+            o.trk[(size_t)idx] = track_stream;
+            if (track_stream >= 0) o.n_trk++;
             o.level = std::max(o.level, front_level(fmt));
             *ticket = (o.batch << 16) | (uint64_t)idx;
             if (o.n_reserved == e->cfg.max_batch) ingest_close_open(g);
@@ -2365,6 +2459,7 @@ int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void*
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
     e->call_seq++;
+    e->last_ns = ns; e->last_deferred = ns != s;
     with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
     return ZLY_OK;
 }
@@ -2395,6 +2490,7 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
     e->call_seq++;
+    e->last_ns = ns; e->last_deferred = ns != s;
     with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
     return ZLY_OK;
 }
@@ -2441,6 +2537,149 @@ int32_t zly_read_slabs(zly_engine* e, int32_t n, void* host_slabs)
     }
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
+}
+
+// --- tracking --------------------------------------------------------------------------------------
+void zly_default_track_config(zly_track_config* c)
+{
+    if (!c) return;
+    c->max_streams = 64;
+    c->max_tracks = 64;
+    c->match_iou = 0.3f;          // reference src/game/kalman_tracker.h:173
+    c->max_lost = 6;              // the adapter's 100 ms at the reference's 60 FPS target
+}
+
+int32_t zly_track_enable(zly_engine* e, const zly_track_config* c)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!c) return fail(ZLY_ERR_INVALID_ARGUMENT, "null track config");
+    if (c->max_streams < 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "max_streams must be >= 1");
+    if (c->max_tracks < e->cfg.max_dets || c->max_tracks > ZLY_TRACK_MAX)
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "max_tracks must lie in [max_dets, 64] (max_dets = " + std::to_string(e->cfg.max_dets) + ")");
+    if (!(c->match_iou >= 0.0f && c->match_iou < 1.0f)) return fail(ZLY_ERR_INVALID_ARGUMENT, "match_iou must lie in [0, 1)");
+    if (c->max_lost < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "max_lost must be >= 0");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->track.load()) return fail(ZLY_ERR_INVALID_ARGUMENT, "tracking is already enabled on this engine");
+    ExclusiveGate gl;                                  // allocations: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    Track* tk = new Track();
+    tk->cfg = *c;
+    tk->grp_ints = 2 + 3 * (size_t)e->cfg.max_batch;
+    tk->seg_of.assign((size_t)c->max_streams, -1);
+    bool ok = hipMalloc((void**)&tk->d_state, sizeof(TrackStream) * (size_t)c->max_streams) == hipSuccess &&
+              hipMalloc((void**)&tk->d_grp, sizeof(int) * tk->grp_ints * Track::RING) == hipSuccess &&
+              hipHostMalloc((void**)&tk->h_grp, sizeof(int) * tk->grp_ints * Track::RING, hipHostMallocDefault) == hipSuccess;
+    for (int i = 0; i < Track::RING && ok; ++i) ok = hipEventCreateWithFlags(&tk->ev[i], hipEventDisableTiming) == hipSuccess;
+    ok = ok && launch_track_reset(tk->d_state, 0, c->max_streams, 1u, e->stream) == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (tk->d_state) hipFree(tk->d_state);
+        if (tk->d_grp) hipFree(tk->d_grp);
+        if (tk->h_grp) hipHostFree(tk->h_grp);
+        for (int i = 0; i < Track::RING; ++i) if (tk->ev[i]) hipEventDestroy(tk->ev[i]);
+        delete tk;
+        return fail(ZLY_ERR_SYSTEM, "allocation of the track tables failed");
+    }
+    e->track.store(tk);
+    return ZLY_OK;
+}
+
+// the engine's tracker, or null with the error set
+static Track* track_of(zly_engine* e)
+{
+    Track* tk = e->track.load();
+    if (!tk) fail(ZLY_ERR_INVALID_ARGUMENT, "tracking is not enabled on this engine (zly_track_enable)");
+    return tk;
+}
+
+int32_t zly_track_reset(zly_engine* e, int32_t stream, uint32_t first_id)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    Track* tk = track_of(e);
+    if (!tk) return ZLY_ERR_INVALID_ARGUMENT;
+    if (stream < -1 || stream >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (int rc = track_drain(tk)) return rc;
+    {
+        SharedGate gl;
+        HIP_TRY(launch_track_reset(tk->d_state, stream < 0 ? 0 : stream, stream < 0 ? tk->cfg.max_streams : 1, first_id, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_track_state_at(zly_engine* e, int32_t stream, zly_track_state* out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    Track* tk = track_of(e);
+    if (!tk) return ZLY_ERR_INVALID_ARGUMENT;
+    if (!out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    if (stream < 0 || stream >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (int rc = track_drain(tk)) return rc;
+    std::vector<unsigned char> host(sizeof(TrackStream));
+    {
+        SharedGate gl;
+        HIP_TRY(hipMemcpyAsync(host.data(), tk->d_state + stream, sizeof(TrackStream), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    const TrackStream* ts = reinterpret_cast<const TrackStream*>(host.data());
+    out->frame_no = ts->frame_no; out->next_id = ts->next_id; out->evictions = ts->evictions;
+    out->n_live = 0;
+    for (int t = 0; t < tk->cfg.max_tracks; ++t) out->n_live += ts->live[t] ? 1 : 0;
+    return ZLY_OK;
+}
+
+int32_t zly_track_slabs(zly_engine* e, int32_t n, const int32_t* streams, void* d_slabs, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    Track* tk = track_of(e);
+    if (!tk) return ZLY_ERR_INVALID_ARGUMENT;
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    if (!streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "null streams");
+    for (int i = 0; i < n; ++i)
+        if (streams[i] < -1 || streams[i] >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(streams[i]) + " out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    // behind the NMS of the most recent zly_detect_device* call, on whichever stream it ran: the engine's NMS stream when it was deferred; otherwise
+    // the caller's stream, which waits for that call's completion event where it is not the stream the call itself was given
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    const bool after_call = e->call_seq > 0;
+    if (after_call && e->last_deferred) s = e->last_ns;
+    else if (after_call && s != e->last_ns) HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1) & 1], 0), ZLY_ERR_INFERENCE);
+    bool launched = false;
+    int rc = track_enqueue(e, tk, n, streams, d_slabs ? d_slabs : e->d_slabs, s, &launched);
+    if (rc != ZLY_OK) return rc;
+    if (launched && after_call) {
+        // the call's completion events move behind its tracking: zly_join, zly_read_slabs and a later call's NMS wait for both
+        HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], s), ZLY_ERR_INFERENCE);
+        if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], s), ZLY_ERR_INFERENCE);
+    }
+    return ZLY_OK;
+}
+
+static int submit_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket, bool nonblock)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    Track* tk = track_of(e);
+    if (!tk) return ZLY_ERR_INVALID_ARGUMENT;
+    if (!v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null view");
+    if (!ticket) return fail(ZLY_ERR_INVALID_ARGUMENT, "null ticket");
+    if (stream < -1 || stream >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    return ingest_submit(e, base, buf_bytes, 0, 0, ticket, nonblock, ZLY_PIX_BGR, v, stream);
+}
+
+int32_t zly_submit_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket)
+{
+    return submit_tracked(e, base, buf_bytes, v, stream, ticket, false);
+}
+
+int32_t zly_submit_try_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket)
+{
+    return submit_tracked(e, base, buf_bytes, v, stream, ticket, true);
 }
 
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw)

@@ -325,4 +325,20 @@ hipError_t nms_init();
 hipError_t launch_nms(const Cand* cand, int* cand_count, int N, int n, float iou_thr, int nc,
                       Cand* scratch, void* slabs, int cap, uint32_t tag0, hipStream_t s, int force_general = 0);
 
+// ---- tracking (kernels_track.hip; the rule and the step: include/zly.h) ----
+#define ZLY_TRACK_MAX 64          // slots per stream as stored (max_tracks <= 64: one lane per slot)
+// The track table of one stream in HBM, structure of arrays: lane t of track_kernel's wave loads and stores element t of every array.
+struct TrackStream {
+    uint32_t frame_no, next_id, evictions, pad_;
+    uint32_t live[ZLY_TRACK_MAX];
+    float x[ZLY_TRACK_MAX], y[ZLY_TRACK_MAX], w[ZLY_TRACK_MAX], h[ZLY_TRACK_MAX];
+    int32_t cls[ZLY_TRACK_MAX];
+    uint32_t id[ZLY_TRACK_MAX], last_seen[ZLY_TRACK_MAX];
+};
+// grp (device, int32): [0] = S, the number of distinct streams of the call; [1 .. S + 1] = segment offsets into the frame list; [S + 2 .. 2S + 1] = the
+// segments' stream indices; [2S + 2 ...] = the call's tracked frame indices ordered by (first occurrence of their stream, index).  One workgroup per segment.
+hipError_t launch_track(TrackStream* states, const int* grp, int n_seg, void* slabs, int cap, int max_tracks, float match_iou, uint32_t max_lost, hipStream_t s);
+// all slots of streams [first, first + count) free, frame_no = 0, evictions = 0; next_id = first_id unless that is 0
+hipError_t launch_track_reset(TrackStream* states, int first, int count, uint32_t first_id, hipStream_t s);
+
 }  // namespace zly

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <unordered_map>
 
 // The format-taking submit calls are referenced weakly: a host build against a C ABI without them (the link-time stub of
 // tests/cpp/test_plugin_stub.cpp) still links, and initialize() refuses a YUV ZLY_INPUT_FORMAT when they are missing.
@@ -21,6 +22,12 @@
 #pragma weak zly_view_crop
 #pragma weak zly_submit_view
 #pragma weak zly_submit_try_view
+// ... and the tracking calls behind ZLY_TRACK: initialize() refuses ZLY_TRACK when they are missing
+#pragma weak zly_default_track_config
+#pragma weak zly_track_enable
+#pragma weak zly_track_reset
+#pragma weak zly_submit_view_tracked
+#pragma weak zly_submit_try_view_tracked
 
 namespace zero_latency {
 
@@ -112,6 +119,12 @@ int envInt(const char* name, int fallback)
 struct HipInferenceEngine::EngineHandle {
     zly_engine* e = nullptr;
     std::atomic<bool> replaced{false};                   // set by reloadModel / shutdown when the handle leaves engines_: its last request hands it to the reaper
+    // ZLY_TRACK: which client owns which stream slot of this engine.  A new engine (hot reload) starts empty, like its track tables.
+    struct TrackSlot { uint32_t client = 0; uint64_t last_use = 0; bool used = false; };
+    std::mutex track_mu;
+    std::vector<TrackSlot> track_slots;
+    std::unordered_map<uint32_t, int32_t> track_slot_of;
+    uint64_t track_clock = 0;
     explicit EngineHandle(zly_engine* p) : e(p) {}
     ~EngineHandle() { if (e) zly_destroy(e); }
     EngineHandle(const EngineHandle&) = delete;
@@ -153,6 +166,21 @@ Result<void> HipInferenceEngine::initialize()
     if (resize < 0)
         return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_RESIZE must be stretch or letterbox, got '") + std::getenv("ZLY_RESIZE") + "'");
     letterbox_ = resize == 1;
+    // ZLY_TRACK=1: track ids on the GPU (include/zly.h "tracking"); a client is one stream of one engine
+    track_ = envInt("ZLY_TRACK", 0) != 0;
+    if (track_) {
+        if (!zly_default_track_config || !zly_track_enable || !zly_track_reset || !zly_submit_view_tracked || !zly_submit_try_view_tracked || !zly_view_tight ||
+            !zly_view_bytes)
+            return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_TRACK: the engine library has no zly_submit_view_tracked");
+        track_streams_ = std::max(1, envInt("ZLY_TRACK_STREAMS", 64));
+        const char* iou = std::getenv("ZLY_TRACK_IOU");
+        track_iou_ = (iou && *iou) ? (float)std::atof(iou) : -1.0f;
+        track_max_lost_ = envInt("ZLY_TRACK_MAX_LOST", -1);
+        // a tracking engine stores at most 64 detections per frame (one lane per track slot): that is the default then, and a larger ZLY_MAX_DETS an error
+        const char* md = std::getenv("ZLY_MAX_DETS");
+        if (md && *md && max_dets_ > 64) return Result<void>::error(ErrorCode::INVALID_ARGUMENT, "ZLY_TRACK needs ZLY_MAX_DETS <= 64");
+        max_dets_ = std::min(max_dets_, 64);
+    }
     const int ndev = simulate_ ? 0 : std::max(1, envInt("ZLY_NUM_DEVICES", 1));
     const int dev0 = std::max(0, envInt("ZLY_FIRST_DEVICE", 0));
     first_device_ = dev0;
@@ -226,7 +254,19 @@ std::shared_ptr<HipInferenceEngine::EngineHandle> HipInferenceEngine::createEngi
     zly_engine* e = nullptr;
     *rc = zly_create(&c, &e);
     if (*rc != ZLY_OK) { *msg = zly_last_error(); return nullptr; }
-    return std::make_shared<EngineHandle>(e);
+    auto h = std::make_shared<EngineHandle>(e);
+    if (track_) {
+        zly_track_config tc;
+        zly_default_track_config(&tc);
+        tc.max_streams = track_streams_;
+        tc.max_tracks = 64;
+        if (track_iou_ >= 0.0f) tc.match_iou = track_iou_;
+        if (track_max_lost_ >= 0) tc.max_lost = track_max_lost_;
+        *rc = zly_track_enable(e, &tc);
+        if (*rc != ZLY_OK) { *msg = zly_last_error(); return nullptr; }      // h destroys the engine
+        h->track_slots.assign((size_t)track_streams_, EngineHandle::TrackSlot());
+    }
+    return h;
 }
 
 // Build the new engines first (hundreds of milliseconds: weight repack, upload, warm-up, beside the running ones), then
@@ -365,6 +405,28 @@ Result<void> HipInferenceEngine::shutdown()
     return Result<void>::ok();
 }
 
+// ZLY_TRACK: the stream slot of a client on its engine.  Known client: its slot.  New client: a slot never used, else the least recently used one,
+// whose tracks are cleared (zly_track_reset, ids go on counting) before the new client's first frame.
+int32_t HipInferenceEngine::trackSlotFor(EngineHandle& h, uint32_t client_id) const
+{
+    std::lock_guard<std::mutex> lk(h.track_mu);
+    const uint64_t now = ++h.track_clock;
+    auto it = h.track_slot_of.find(client_id);
+    if (it != h.track_slot_of.end()) { h.track_slots[(size_t)it->second].last_use = now; return it->second; }
+    int32_t pick = -1;
+    for (size_t i = 0; i < h.track_slots.size() && pick < 0; ++i) if (!h.track_slots[i].used) pick = (int32_t)i;
+    if (pick < 0) {
+        pick = 0;
+        for (size_t i = 1; i < h.track_slots.size(); ++i) if (h.track_slots[i].last_use < h.track_slots[(size_t)pick].last_use) pick = (int32_t)i;
+        h.track_slot_of.erase(h.track_slots[(size_t)pick].client);
+        if (zly_track_reset(h.e, pick, 0) != ZLY_OK) return -1;
+    }
+    EngineHandle::TrackSlot& sl = h.track_slots[(size_t)pick];
+    sl.client = client_id; sl.last_use = now; sl.used = true;
+    h.track_slot_of[client_id] = pick;
+    return pick;
+}
+
 // Runs on the caller's thread (the UDP receive thread in the reference's server, network_server.cpp:209): the request's
 // pixels are copied ONCE, into the engine's pinned staging ring; nothing of `request` is retained.
 Result<void> HipInferenceEngine::submitInference(const InferenceRequest& request)
@@ -405,7 +467,23 @@ Result<void> HipInferenceEngine::submitInference(const InferenceRequest& request
                     p.cropped = vrc == ZLY_OK;
                 }
             }
+            // ZLY_TRACK: the client's engine and its stream slot there; the request as a view (its window, or its whole tight frame)
+            int32_t track_slot = -1;
+            if (track_ && vrc == ZLY_OK) {
+                if (!p.cropped) {
+                    vrc = zly_view_tight(input_format_, request.width, request.height, &win);
+                    if (vrc == ZLY_OK && request.data.size() != zly_view_bytes(&win)) vrc = ZLY_ERR_INVALID_INPUT;
+                    else if (vrc != ZLY_OK) vrc = ZLY_ERR_INVALID_INPUT;             // a size the format does not allow: as a frame of the wrong size
+                }
+                if (vrc == ZLY_OK) {
+                    track_slot = trackSlotFor(*(*snap)[(size_t)(request.client_id % ne)], request.client_id);
+                    if (track_slot < 0) vrc = ZLY_ERR_INFERENCE;
+                }
+            }
             auto offer = [&](zly_engine* e, bool blocking) -> int32_t {
+                if (track_)
+                    return blocking ? zly_submit_view_tracked(e, request.data.data(), request.data.size(), &win, track_slot, &p.ticket)
+                                    : zly_submit_try_view_tracked(e, request.data.data(), request.data.size(), &win, track_slot, &p.ticket);
                 if (p.cropped)
                     return blocking ? zly_submit_view(e, request.data.data(), request.data.size(), &win, &p.ticket)
                                     : zly_submit_try_view(e, request.data.data(), request.data.size(), &win, &p.ticket);
@@ -416,6 +494,13 @@ Result<void> HipInferenceEngine::submitInference(const InferenceRequest& request
                                 : zly_submit_try_fmt(e, input_format_, request.data.data(), request.data.size(), request.width, request.height, &p.ticket);
             };
             if (vrc != ZLY_OK) rc = vrc;
+            if (track_ && rc == ZLY_PENDING) {
+                // a client's frames are one stream of ONE engine: no round robin and no spill-over; non-blocking first only to keep the two calls' order of the untracked path
+                p.slot = (size_t)(request.client_id % ne);
+                p.engine = (*snap)[p.slot];
+                rc = offer(p.engine->e, false);
+                if (rc == ZLY_PENDING) rc = offer(p.engine->e, true);
+            }
             for (size_t k = 0; k < ne && rc == ZLY_PENDING; ++k) {
                 p.slot = (first + k) % ne;
                 p.engine = (*snap)[p.slot];
@@ -618,6 +703,7 @@ std::unordered_map<std::string, std::string> HipInferenceEngine::getStatus() con
     s["dynamic_batching"] = "enabled";
     s["resize_mode"] = letterbox_ ? "letterbox" : "stretch";
     s["input_format"] = inputFormatName(input_format_);
+    s["tracking"] = track_ ? "on" : "off";
     s["crop"] = crop_w_ > 0 ? std::to_string(crop_w_) + "x" + std::to_string(crop_h_) : "off";
     double avg = 0, p99 = 0;
     {
@@ -654,6 +740,12 @@ std::unordered_map<std::string, std::string> HipInferenceEngine::getStatus() con
     s["avg_forward_time_ms"] = frames ? std::to_string(fwd / (double)frames) : "0";
     s["avg_postprocessing_time_ms"] = frames ? std::to_string(post / (double)frames) : "0";
     s["weight_format"] = (!engines.empty() && zly_weights_fp8(engines[0]->e)) ? "fp8_e4m3" : "fp32";      // the reference's "quantised" model claim (README.md:84)
+    size_t in_use = 0;
+    for (const auto& h : engines) {
+        std::lock_guard<std::mutex> lk(h->track_mu);
+        in_use += h->track_slot_of.size();
+    }
+    s["track_streams_in_use"] = std::to_string(in_use);
     s["worker_threads"] = std::to_string(engines.size());
     s["devices"] = std::to_string(engines.size() / (size_t)std::max(1, engines_per_gpu_));
     s["engines_per_gpu"] = std::to_string(engines_per_gpu_);

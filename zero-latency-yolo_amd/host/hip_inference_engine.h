@@ -100,6 +100,14 @@ private:
     int32_t input_format_ = 0;                             // ZLY_INPUT_FORMAT (read by initialize()): ZLY_PIX_* of every request's data (0 = BGR)
     int32_t crop_w_ = 0, crop_h_ = 0;                      // ZLY_CROP=WxH (read by initialize()): every request is detected in the centred W x H window of its frame (0 = whole frames)
     bool letterbox_ = false;                               // ZLY_RESIZE=letterbox (read by initialize()): every engine is created with ZLY_FLAG_LETTERBOX
+    // ZLY_TRACK=1 (read by initialize()): every engine tracks (zly_track_enable) and a client's frames all go to engine client_id % engines, as one
+    // stream of that engine: detections come back with track ids that persist from frame to frame.  ZLY_TRACK_STREAMS (default 64) stream slots per
+    // engine; ZLY_TRACK_IOU / ZLY_TRACK_MAX_LOST override the engine's defaults.  A hot reload's new engines start with fresh tracks.
+    bool track_ = false;
+    int track_streams_ = 64;
+    float track_iou_ = -1.0f;                              // < 0: the engine's default
+    int track_max_lost_ = -1;                              // < 0: the engine's default
+    int32_t trackSlotFor(EngineHandle& h, uint32_t client_id) const;   // the client's stream slot on this engine (a new client: a free slot, else the least recently used one, reset)
     std::thread monitor_, completer_, reaper_;
     // Engines replaced by a hot reload are destroyed on the reaper thread: zly_destroy drains the engine's streams and takes the process-wide
     // exclusive gate, which must never stall callback delivery (the completion thread) or a submitting thread.

@@ -47,6 +47,7 @@ SYMBOLS = [
     "zly_preprocess", "zly_forward", "zly_head_tensor", "zly_postprocess", "zly_debug_tap",
     "zly_view_bytes", "zly_view_tight", "zly_view_crop", "zly_detect_view", "zly_detect_batch_view", "zly_submit_view", "zly_submit_try_view",
     "zly_detect_device_view", "zly_preprocess_view",
+    "zly_default_track_config", "zly_track_enable", "zly_track_reset", "zly_track_state_at", "zly_track_slabs", "zly_submit_view_tracked", "zly_submit_try_view_tracked",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -67,6 +68,16 @@ class FrameView(C.Structure):
     """zly_frame_view: where a request's samples lie inside a larger buffer (offsets from the buffer base, row pitches)"""
     _fields_ = [("fmt", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("pad_", C.c_int32),
                 ("off", C.c_uint64 * 3), ("pitch", C.c_int32 * 3), ("pad2_", C.c_int32)]
+
+
+class TrackConfig(C.Structure):
+    """zly_track_config"""
+    _fields_ = [("max_streams", C.c_int32), ("max_tracks", C.c_int32), ("match_iou", C.c_float), ("max_lost", C.c_int32)]
+
+
+class TrackState(C.Structure):
+    """zly_track_state"""
+    _fields_ = [("frame_no", C.c_uint32), ("next_id", C.c_uint32), ("n_live", C.c_int32), ("evictions", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -143,6 +154,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_submit_try_view.argtypes = [vp, vp, sz, pv, C.POINTER(C.c_uint64)]; lib.zly_submit_try_view.restype = i32
     lib.zly_detect_device_view.argtypes = [vp, i32, vp, sz, pv, vp, u32, vp]; lib.zly_detect_device_view.restype = i32
     lib.zly_preprocess_view.argtypes = [vp, vp, sz, pv, vp]; lib.zly_preprocess_view.restype = i32
+    lib.zly_default_track_config.argtypes = [C.POINTER(TrackConfig)]; lib.zly_default_track_config.restype = None
+    lib.zly_track_enable.argtypes = [vp, C.POINTER(TrackConfig)]; lib.zly_track_enable.restype = i32
+    lib.zly_track_reset.argtypes = [vp, i32, u32]; lib.zly_track_reset.restype = i32
+    lib.zly_track_state_at.argtypes = [vp, i32, C.POINTER(TrackState)]; lib.zly_track_state_at.restype = i32
+    lib.zly_track_slabs.argtypes = [vp, i32, pi32, vp, vp]; lib.zly_track_slabs.restype = i32
+    lib.zly_submit_view_tracked.argtypes = [vp, vp, sz, pv, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_view_tracked.restype = i32
+    lib.zly_submit_try_view_tracked.argtypes = [vp, vp, sz, pv, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_try_view_tracked.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -322,6 +340,42 @@ class Engine:
         t = C.c_uint64(0)
         _check(self.lib, self.lib.zly_submit_view(self.h, buf.ctypes.data, buf.nbytes, C.byref(view), C.byref(t)))
         return t.value
+
+    def submit_view_tracked(self, buf: np.ndarray, view: FrameView, stream: int) -> int:
+        """submit_view plus the frame's stream index (-1 = untracked): its detections come back with track ids"""
+        t = C.c_uint64(0)
+        _check(self.lib, self.lib.zly_submit_view_tracked(self.h, buf.ctypes.data, buf.nbytes, C.byref(view), stream, C.byref(t)))
+        return t.value
+
+    # -- tracking (include/zly.h "tracking") ------------------------------------------------------------
+    def track_enable(self, max_streams: Optional[int] = None, max_tracks: Optional[int] = None, match_iou: Optional[float] = None,
+                     max_lost: Optional[int] = None):
+        """once per engine, before the first tracked call; arguments left out keep zly_default_track_config's values"""
+        c = TrackConfig()
+        self.lib.zly_default_track_config(C.byref(c))
+        if max_streams is not None:
+            c.max_streams = max_streams
+        if max_tracks is not None:
+            c.max_tracks = max_tracks
+        if match_iou is not None:
+            c.match_iou = match_iou
+        if max_lost is not None:
+            c.max_lost = max_lost
+        _check(self.lib, self.lib.zly_track_enable(self.h, C.byref(c)))
+
+    def track_reset(self, stream: int = -1, first_id: int = 0):
+        _check(self.lib, self.lib.zly_track_reset(self.h, stream, first_id))
+
+    def track_state(self, stream: int) -> dict:
+        s = TrackState()
+        _check(self.lib, self.lib.zly_track_state_at(self.h, stream, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in TrackState._fields_}
+
+    def track_slabs(self, streams: Sequence[int], d_slabs_ptr: int = 0, stream: int = 0):
+        """tracks, in place, the len(streams) slabs of the most recent detect_device* call (d_slabs_ptr = 0: the engine's own buffer); -1 = untouched"""
+        n = len(streams)
+        cs = (C.c_int32 * n)(*streams)
+        _check(self.lib, self.lib.zly_track_slabs(self.h, n, cs, d_slabs_ptr or None, stream or None))
 
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
