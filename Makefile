@@ -72,7 +72,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -105,6 +105,12 @@ $(OUT)/test_plugin_track_stub: tests/cpp/test_plugin_track_stub.cpp $(HOST)/hip_
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_stub.cpp -pthread
 $(OUT)/test_plugin_track_stub_nosym: tests/cpp/test_plugin_track_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -DNO_TRACK_SYMBOLS -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_stub.cpp -pthread
+
+# ... and its ZLY_TRACK_MOTION logic against a stub that records the enables; the second binary's stub has the tracking calls but not the motion model's
+$(OUT)/test_plugin_track_motion_stub: tests/cpp/test_plugin_track_motion_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_motion_stub.cpp -pthread
+$(OUT)/test_plugin_track_motion_stub_nosym: tests/cpp/test_plugin_track_motion_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -DNO_MOTION_SYMBOLS -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_motion_stub.cpp -pthread
 
 $(OUT)/test_wire: tests/cpp/test_wire.cpp $(HOST)/zly_wire.hpp $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -I$(HOST) -o $@ tests/cpp/test_wire.cpp

@@ -342,7 +342,8 @@ int32_t zly_join(zly_engine* e, void* stream, int32_t lag);
  * changes -- no extra launch, identical bytes, track_id = 0.  The reference's game step gives every detection with id 0 a fresh id on every frame
  * (cs16_game_adapter.cpp:243-262) and its client keys its Kalman filters by track_id (src/client/prediction_engine.cpp:19-72), so only a
  * tracked frame lets a client filter see a second measurement.  The association is the reference's own IoU matching (src/game/kalman_tracker.h,
- * threshold 0.3) without its motion model: no prediction, no min_hits, no re-identification -- the client filters what it gets.
+ * threshold 0.3) without its motion model: no prediction, no min_hits, no re-identification -- the client filters what it gets.  The prediction
+ * is opt-in on top of that (zly_track_motion_enable, "The motion model" below); min_hits and re-identification stay out.
  *
  * A frame may name a STREAM, an index in [0, max_streams): an ordered sequence of frames, for example one client.  The engine keeps one track
  * table per stream in HBM.
@@ -365,6 +366,24 @@ int32_t zly_join(zly_engine* e, void* stream, int32_t lag);
  *      eviction) -- becomes {live, box, class, id = next_id, last_seen = frame_no}; D[d].track_id = next_id; next_id becomes next_id + 1, or 1
  *      if that is 0.
  * So every stored detection of a tracked frame leaves with a non-zero id, and ids are per stream.
+ *
+ * The motion model (zly_track_motion_enable; off by default).  Without prediction a target that moves by more than about half its width per
+ * frame, or that reappears a few widths further on after a dropout, never matches its own track and gets a fresh id.  The reference's tracker
+ * predicts every track to the frame's time first and matches against the predicted box (src/game/kalman_tracker.cpp:273-355, :430-460); a
+ * motion engine does the same with a constant velocity per slot.  It keeps three more values per slot: vx, vy (fp32, in normalised units PER
+ * FRAME OF THE STREAM) and hits (u32).  The clock is frame_no -- frames carry no timestamps on the device path -- so a stream with irregular
+ * frame intervals gets a worse prediction; timestamps are out of scope.  All arithmetic is single IEEE fp32 operations in the order written,
+ * without contraction, as in iou.  After step 1:
+ *   P.  Predict, for every live slot: dt = frame_no - last_seen (u32); dtf = (float)dt, rounded to nearest even; px = x + vx*dtf,
+ *       py = y + vy*dtf (the product is rounded first, then the sum).  The predicted box is (px, py, w, h).
+ *   2'. Candidate pairs use iou(D[d], predicted box) instead of the stored box.  The class test, the strict > match_iou, the total order and
+ *       the greedy acceptance (steps 2-3) do not change.
+ *   4'. An accepted pair (d, t): rx = D[d].x - px, ry = D[d].y - py; g = 1.0f if hits == 1, else beta; vx = clamp(vx + g*(rx/dtf)), and
+ *       likewise vy, with clamp(v) = v < -v_max ? -v_max : (v > v_max ? v_max : v); hits becomes hits + 1, saturating at 0xFFFFFFFF.  Then, as
+ *       in step 4: the slot takes the detection's box, last_seen = frame_no, D[d].track_id = slot.id.
+ *   5, 6. Expiry, births and the eviction order do not change.  A birth sets vx = vy = 0 and hits = 1.
+ * So a track's first match takes the whole displacement as its velocity and later ones move it by beta of the residual; v_max = 0 gives the
+ * plain tracker's ids bit for bit.  THE RULE holds unchanged.
  * Not tracked: frames that go through the synchronous host calls or the _fmt submits, and engines behind host/zly_sharded*.hpp (consecutive
  * frames of a stream land on different GPUs).  A new engine (the plugin's hot reload) starts with fresh tables. */
 typedef struct zly_track_config {
@@ -391,6 +410,31 @@ int32_t zly_track_enable(zly_engine* e, const zly_track_config* cfg);
 int32_t zly_track_reset(zly_engine* e, int32_t stream, uint32_t first_id);
 /* Synchronises with the tracking enqueued so far, then reads (tests, status pages). */
 int32_t zly_track_state_at(zly_engine* e, int32_t stream, zly_track_state* out);
+
+/* The motion model ("The motion model" above).  The defaults are chosen, not tuned: nobody has measured them on real footage. */
+typedef struct zly_track_motion_config {
+    float beta;            /* in (0, 1]: the share of a match's residual that goes into the velocity; default 0.5 */
+    float v_max;           /* >= 0 and finite: |vx|, |vy| never exceed it, per frame of the stream; default 0.25 */
+} zly_track_motion_config;
+void    zly_default_track_motion_config(zly_track_motion_config* cfg);
+/* Once per engine, after zly_track_enable: allocates the motion state (a device array of its own beside the tables), waits for the tracking
+ * enqueued so far and resets every stream as zly_track_reset(e, -1, 0) does.  From then on every tracked call of the engine, on the device
+ * path or the pipelined one, runs the motion step, and zly_track_reset also clears vx, vy and hits of the streams it resets.  Errors --
+ * ZLY_ERR_INVALID_ARGUMENT for a null, out-of-range or NaN config, for an engine without tables and for a second call; ZLY_ERR_SYSTEM for a
+ * failed allocation.  An engine that never calls it runs exactly the kernels it ran before this call existed. */
+int32_t zly_track_motion_enable(zly_engine* e, const zly_track_motion_config* cfg);
+
+/* One live slot of a stream's table.  x, y, w, h: the last matched box, not the prediction; vx, vy per frame of the stream.  On an engine
+ * without the motion model vx, vy and hits are 0.  sizeof == 40. */
+typedef struct zly_track {
+    float    x, y, w, h, vx, vy;
+    int32_t  class_id;
+    uint32_t id, hits, last_seen;
+} zly_track;
+/* Synchronises like zly_track_state_at, then writes the stream's live slots in ascending slot order: min(n, cap) of them to out, and the
+ * uncapped count n to *n_out (cap = 0 with out = NULL asks for the count alone).  frame_no - last_seen (zly_track_state_at) is a slot's
+ * age: what a server needs to coast a track over frames without a detection, as the reference's predict() does. */
+int32_t zly_track_read(zly_engine* e, int32_t stream, zly_track* out, int32_t cap, int32_t* n_out);
 
 /* The device path: tracks, in place, the n slabs that the most recent zly_detect_device* call on this engine wrote.  d_slabs = NULL: the engine's
  * own slab buffer.  streams is a HOST array of n; streams[i] = -1 leaves slab i untouched, and a call with nothing but -1 launches nothing.

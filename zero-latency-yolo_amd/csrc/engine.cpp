@@ -16,6 +16,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <string>
@@ -156,6 +157,8 @@ struct Ingest;        // pipelined host-to-host path (zly_submit / zly_wait), be
 struct Track {
     zly_track_config cfg{};
     TrackStream* d_state = nullptr;   // [max_streams]
+    TrackMotion* d_motion = nullptr;  // [max_streams], allocated by zly_track_motion_enable (under mu): from then on every launch is track_motion_kernel
+    zly_track_motion_config mcfg{};
     static constexpr int RING = 8;
     size_t grp_ints = 0;              // int32 per ring entry: 2 + 3 * max_batch (zly_internal.h: launch_track)
     int* h_grp = nullptr;             // pinned [RING][grp_ints]
@@ -1430,7 +1433,11 @@ static int track_enqueue(zly_engine* e, Track* tk, int n, const int32_t* streams
     for (int i = 0; i < n; ++i) if (streams[i] >= 0) seg_of[(size_t)streams[i]] = -1;
     int* dg = tk->d_grp + (size_t)r * tk->grp_ints;
     HIP_TRY(hipMemcpyAsync(dg, g, sizeof(int) * (size_t)(2 + 2 * n_seg + n_tracked), hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(launch_track(tk->d_state, dg, n_seg, slabs, e->cfg.max_dets, tk->cfg.max_tracks, tk->cfg.match_iou, (uint32_t)tk->cfg.max_lost, s), ZLY_ERR_INFERENCE);
+    if (tk->d_motion)
+        HIP_TRY(launch_track_motion(tk->d_state, tk->d_motion, dg, n_seg, slabs, e->cfg.max_dets, tk->cfg.max_tracks, tk->cfg.match_iou, (uint32_t)tk->cfg.max_lost,
+                                    tk->mcfg.beta, tk->mcfg.v_max, s), ZLY_ERR_INFERENCE);
+    else
+        HIP_TRY(launch_track(tk->d_state, dg, n_seg, slabs, e->cfg.max_dets, tk->cfg.max_tracks, tk->cfg.match_iou, (uint32_t)tk->cfg.max_lost, s), ZLY_ERR_INFERENCE);
     HIP_TRY(hipEventRecord(tk->ev[r], s), ZLY_ERR_INFERENCE);
     tk->used[r] = true;
     *launched = true;
@@ -1597,6 +1604,7 @@ static hipError_t destroy_engine(zly_engine* e)
     if (e->h_slabs) note(hipHostFree(e->h_slabs));
     if (Track* tk = e->track.load()) {
         if (tk->d_state) note(hipFree(tk->d_state));
+        if (tk->d_motion) note(hipFree(tk->d_motion));
         if (tk->d_grp) note(hipFree(tk->d_grp));
         if (tk->h_grp) note(hipHostFree(tk->h_grp));
         for (int i = 0; i < Track::RING; ++i) if (tk->ev[i]) hipEventDestroy(tk->ev[i]);
@@ -2604,8 +2612,78 @@ int32_t zly_track_reset(zly_engine* e, int32_t stream, uint32_t first_id)
     {
         SharedGate gl;
         HIP_TRY(launch_track_reset(tk->d_state, stream < 0 ? 0 : stream, stream < 0 ? tk->cfg.max_streams : 1, first_id, e->stream), ZLY_ERR_INFERENCE);
+        if (tk->d_motion) HIP_TRY(launch_track_motion_reset(tk->d_motion, stream < 0 ? 0 : stream, stream < 0 ? tk->cfg.max_streams : 1, e->stream), ZLY_ERR_INFERENCE);
     }
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+void zly_default_track_motion_config(zly_track_motion_config* c)
+{
+    if (!c) return;
+    c->beta = 0.5f;               // chosen, not tuned
+    c->v_max = 0.25f;
+}
+
+int32_t zly_track_motion_enable(zly_engine* e, const zly_track_motion_config* c)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!c) return fail(ZLY_ERR_INVALID_ARGUMENT, "null track motion config");
+    if (!(c->beta > 0.0f && c->beta <= 1.0f)) return fail(ZLY_ERR_INVALID_ARGUMENT, "beta must lie in (0, 1]");
+    if (!(c->v_max >= 0.0f && c->v_max <= std::numeric_limits<float>::max())) return fail(ZLY_ERR_INVALID_ARGUMENT, "v_max must be >= 0 and finite");
+    Track* tk = track_of(e);
+    if (!tk) return ZLY_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (tk->d_motion) return fail(ZLY_ERR_INVALID_ARGUMENT, "the motion model is already enabled on this engine");
+    ExclusiveGate gl;                                  // an allocation: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (int rc = track_drain(tk)) return rc;
+    TrackMotion* m = nullptr;
+    bool ok = hipMalloc((void**)&m, sizeof(TrackMotion) * (size_t)tk->cfg.max_streams) == hipSuccess;
+    // every stream starts over, as after zly_track_reset(e, -1, 0): a table matched without the model has no velocities to go on with
+    ok = ok && launch_track_reset(tk->d_state, 0, tk->cfg.max_streams, 0u, e->stream) == hipSuccess &&
+         launch_track_motion_reset(m, 0, tk->cfg.max_streams, e->stream) == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (m) hipFree(m);
+        return fail(ZLY_ERR_SYSTEM, "allocation of the motion state failed");
+    }
+    tk->mcfg = *c;
+    tk->d_motion = m;
+    return ZLY_OK;
+}
+
+int32_t zly_track_read(zly_engine* e, int32_t stream, zly_track* out, int32_t cap, int32_t* n_out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    Track* tk = track_of(e);
+    if (!tk) return ZLY_ERR_INVALID_ARGUMENT;
+    if (!n_out || cap < 0 || (cap > 0 && !out)) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    if (stream < 0 || stream >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (int rc = track_drain(tk)) return rc;
+    std::vector<unsigned char> host(sizeof(TrackStream)), hostm(sizeof(TrackMotion), 0);
+    {
+        SharedGate gl;
+        HIP_TRY(hipMemcpyAsync(host.data(), tk->d_state + stream, sizeof(TrackStream), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+        if (tk->d_motion) HIP_TRY(hipMemcpyAsync(hostm.data(), tk->d_motion + stream, sizeof(TrackMotion), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    const TrackStream* ts = reinterpret_cast<const TrackStream*>(host.data());
+    const TrackMotion* tm = reinterpret_cast<const TrackMotion*>(hostm.data());      // all zero on an engine without the model
+    int32_t n = 0;
+    for (int t = 0; t < tk->cfg.max_tracks; ++t) {
+        if (!ts->live[t]) continue;
+        if (n < cap) {
+            zly_track& o = out[n];
+            o.x = ts->x[t]; o.y = ts->y[t]; o.w = ts->w[t]; o.h = ts->h[t];
+            o.vx = tm->vx[t]; o.vy = tm->vy[t];
+            o.class_id = ts->cls[t]; o.id = ts->id[t]; o.hits = tm->hits[t]; o.last_seen = ts->last_seen[t];
+        }
+        ++n;
+    }
+    *n_out = n;
     return ZLY_OK;
 }
 

@@ -335,10 +335,21 @@ struct TrackStream {
     int32_t cls[ZLY_TRACK_MAX];
     uint32_t id[ZLY_TRACK_MAX], last_seen[ZLY_TRACK_MAX];
 };
+// The motion model's state of one stream (zly_track_motion_enable), an array of its own beside TrackStream: velocities in normalised units per frame
+// of the stream, and the number of frames the track has been seen in (1 at birth).
+struct TrackMotion {
+    float vx[ZLY_TRACK_MAX], vy[ZLY_TRACK_MAX];
+    uint32_t hits[ZLY_TRACK_MAX];
+};
 // grp (device, int32): [0] = S, the number of distinct streams of the call; [1 .. S + 1] = segment offsets into the frame list; [S + 2 .. 2S + 1] = the
 // segments' stream indices; [2S + 2 ...] = the call's tracked frame indices ordered by (first occurrence of their stream, index).  One workgroup per segment.
 hipError_t launch_track(TrackStream* states, const int* grp, int n_seg, void* slabs, int cap, int max_tracks, float match_iou, uint32_t max_lost, hipStream_t s);
 // all slots of streams [first, first + count) free, frame_no = 0, evictions = 0; next_id = first_id unless that is 0
 hipError_t launch_track_reset(TrackStream* states, int first, int count, uint32_t first_id, hipStream_t s);
+// launch_track with the motion model (track_motion_kernel); motion[i] is the state of states[i]
+hipError_t launch_track_motion(TrackStream* states, TrackMotion* motion, const int* grp, int n_seg, void* slabs, int cap, int max_tracks, float match_iou,
+                               uint32_t max_lost, float beta, float v_max, hipStream_t s);
+// vx = vy = 0, hits = 0 in every slot of streams [first, first + count)
+hipError_t launch_track_motion_reset(TrackMotion* motion, int first, int count, hipStream_t s);
 
 }  // namespace zly

@@ -28,6 +28,9 @@
 #pragma weak zly_track_reset
 #pragma weak zly_submit_view_tracked
 #pragma weak zly_submit_try_view_tracked
+// ... and the motion model's calls behind ZLY_TRACK_MOTION: initialize() refuses ZLY_TRACK_MOTION when they are missing
+#pragma weak zly_default_track_motion_config
+#pragma weak zly_track_motion_enable
 
 namespace zero_latency {
 
@@ -181,6 +184,17 @@ Result<void> HipInferenceEngine::initialize()
         if (md && *md && max_dets_ > 64) return Result<void>::error(ErrorCode::INVALID_ARGUMENT, "ZLY_TRACK needs ZLY_MAX_DETS <= 64");
         max_dets_ = std::min(max_dets_, 64);
     }
+    // ZLY_TRACK_MOTION=1: the tracker's constant-velocity motion model on every engine (include/zly.h "The motion model"); only with ZLY_TRACK=1
+    track_motion_ = envInt("ZLY_TRACK_MOTION", 0) != 0;
+    if (track_motion_) {
+        if (!track_) return Result<void>::error(ErrorCode::INVALID_ARGUMENT, "ZLY_TRACK_MOTION needs ZLY_TRACK=1");
+        if (!zly_default_track_motion_config || !zly_track_motion_enable)
+            return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_TRACK_MOTION: the engine library has no zly_track_motion_enable");
+        const char* beta = std::getenv("ZLY_TRACK_BETA");
+        track_beta_ = (beta && *beta) ? (float)std::atof(beta) : -1.0f;
+        const char* vmax = std::getenv("ZLY_TRACK_VMAX");
+        track_vmax_ = (vmax && *vmax) ? (float)std::atof(vmax) : -1.0f;
+    }
     const int ndev = simulate_ ? 0 : std::max(1, envInt("ZLY_NUM_DEVICES", 1));
     const int dev0 = std::max(0, envInt("ZLY_FIRST_DEVICE", 0));
     first_device_ = dev0;
@@ -264,6 +278,14 @@ std::shared_ptr<HipInferenceEngine::EngineHandle> HipInferenceEngine::createEngi
         if (track_max_lost_ >= 0) tc.max_lost = track_max_lost_;
         *rc = zly_track_enable(e, &tc);
         if (*rc != ZLY_OK) { *msg = zly_last_error(); return nullptr; }      // h destroys the engine
+        if (track_motion_) {
+            zly_track_motion_config mc;
+            zly_default_track_motion_config(&mc);
+            if (track_beta_ >= 0.0f) mc.beta = track_beta_;
+            if (track_vmax_ >= 0.0f) mc.v_max = track_vmax_;
+            *rc = zly_track_motion_enable(e, &mc);
+            if (*rc != ZLY_OK) { *msg = zly_last_error(); return nullptr; }
+        }
         h->track_slots.assign((size_t)track_streams_, EngineHandle::TrackSlot());
     }
     return h;
@@ -704,6 +726,7 @@ std::unordered_map<std::string, std::string> HipInferenceEngine::getStatus() con
     s["resize_mode"] = letterbox_ ? "letterbox" : "stretch";
     s["input_format"] = inputFormatName(input_format_);
     s["tracking"] = track_ ? "on" : "off";
+    s["track_motion"] = track_motion_ ? "on" : "off";
     s["crop"] = crop_w_ > 0 ? std::to_string(crop_w_) + "x" + std::to_string(crop_h_) : "off";
     double avg = 0, p99 = 0;
     {

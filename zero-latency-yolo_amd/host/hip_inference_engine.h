@@ -107,6 +107,11 @@ private:
     int track_streams_ = 64;
     float track_iou_ = -1.0f;                              // < 0: the engine's default
     int track_max_lost_ = -1;                              // < 0: the engine's default
+    // ZLY_TRACK_MOTION=1 (read by initialize(), refused without ZLY_TRACK=1): every engine also enables the tracker's constant-velocity motion
+    // model (zly_track_motion_enable); ZLY_TRACK_BETA / ZLY_TRACK_VMAX override the engine's defaults.
+    bool track_motion_ = false;
+    float track_beta_ = -1.0f;                             // < 0: the engine's default
+    float track_vmax_ = -1.0f;                             // < 0: the engine's default
     int32_t trackSlotFor(EngineHandle& h, uint32_t client_id) const;   // the client's stream slot on this engine (a new client: a free slot, else the least recently used one, reset)
     std::thread monitor_, completer_, reaper_;
     // Engines replaced by a hot reload are destroyed on the reaper thread: zly_destroy drains the engine's streams and takes the process-wide

@@ -48,6 +48,7 @@ SYMBOLS = [
     "zly_view_bytes", "zly_view_tight", "zly_view_crop", "zly_detect_view", "zly_detect_batch_view", "zly_submit_view", "zly_submit_try_view",
     "zly_detect_device_view", "zly_preprocess_view",
     "zly_default_track_config", "zly_track_enable", "zly_track_reset", "zly_track_state_at", "zly_track_slabs", "zly_submit_view_tracked", "zly_submit_try_view_tracked",
+    "zly_default_track_motion_config", "zly_track_motion_enable", "zly_track_read",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -55,6 +56,10 @@ DET_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("
                       ("class_id", "<i4"), ("track_id", "<u4"), ("pad_", "<u4"), ("timestamp", "<u8")])
 assert DET_DTYPE.itemsize == 40
 SLAB_HDR_DTYPE = np.dtype([("n_kept", "<i4"), ("n_candidates", "<i4"), ("flags", "<u4"), ("frame_tag", "<u4")])
+# zly_track: one live slot of a stream's track table (zly_track_read)
+TRACK_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("vx", "<f4"), ("vy", "<f4"),
+                        ("class_id", "<i4"), ("id", "<u4"), ("hits", "<u4"), ("last_seen", "<u4")])
+assert TRACK_DTYPE.itemsize == 40
 
 
 class Config(C.Structure):
@@ -78,6 +83,17 @@ class TrackConfig(C.Structure):
 class TrackState(C.Structure):
     """zly_track_state"""
     _fields_ = [("frame_no", C.c_uint32), ("next_id", C.c_uint32), ("n_live", C.c_int32), ("evictions", C.c_uint32)]
+
+
+class TrackMotionConfig(C.Structure):
+    """zly_track_motion_config"""
+    _fields_ = [("beta", C.c_float), ("v_max", C.c_float)]
+
+
+class Track(C.Structure):
+    """zly_track (TRACK_DTYPE is its numpy twin)"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("w", C.c_float), ("h", C.c_float), ("vx", C.c_float), ("vy", C.c_float),
+                ("class_id", C.c_int32), ("id", C.c_uint32), ("hits", C.c_uint32), ("last_seen", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -161,6 +177,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_track_slabs.argtypes = [vp, i32, pi32, vp, vp]; lib.zly_track_slabs.restype = i32
     lib.zly_submit_view_tracked.argtypes = [vp, vp, sz, pv, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_view_tracked.restype = i32
     lib.zly_submit_try_view_tracked.argtypes = [vp, vp, sz, pv, i32, C.POINTER(C.c_uint64)]; lib.zly_submit_try_view_tracked.restype = i32
+    lib.zly_default_track_motion_config.argtypes = [C.POINTER(TrackMotionConfig)]; lib.zly_default_track_motion_config.restype = None
+    lib.zly_track_motion_enable.argtypes = [vp, C.POINTER(TrackMotionConfig)]; lib.zly_track_motion_enable.restype = i32
+    lib.zly_track_read.argtypes = [vp, i32, vp, i32, pi32]; lib.zly_track_read.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -370,6 +389,24 @@ class Engine:
         s = TrackState()
         _check(self.lib, self.lib.zly_track_state_at(self.h, stream, C.byref(s)))
         return {k: int(getattr(s, k)) for k, _ in TrackState._fields_}
+
+    def track_motion_enable(self, beta: Optional[float] = None, v_max: Optional[float] = None):
+        """once per engine, after track_enable: every tracked call from then on runs the constant-velocity motion step; arguments left out keep
+        zly_default_track_motion_config's values"""
+        c = TrackMotionConfig()
+        self.lib.zly_default_track_motion_config(C.byref(c))
+        if beta is not None:
+            c.beta = beta
+        if v_max is not None:
+            c.v_max = v_max
+        _check(self.lib, self.lib.zly_track_motion_enable(self.h, C.byref(c)))
+
+    def track_read(self, stream: int) -> np.ndarray:
+        """the stream's live slots in ascending slot order, as TRACK_DTYPE records (vx, vy, hits = 0 on an engine without the motion model)"""
+        out = np.zeros(64, dtype=TRACK_DTYPE)
+        n = C.c_int32(0)
+        _check(self.lib, self.lib.zly_track_read(self.h, stream, out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value].copy()
 
     def track_slabs(self, streams: Sequence[int], d_slabs_ptr: int = 0, stream: int = 0):
         """tracks, in place, the len(streams) slabs of the most recent detect_device* call (d_slabs_ptr = 0: the engine's own buffer); -1 = untouched"""
