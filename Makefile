@@ -16,7 +16,7 @@ KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_mi
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
 OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/engine.o $(OUT)/weights.o
 
-all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so oracle weights host
+all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so $(OUT)/libsppf_probe.so oracle weights host
 
 $(OUT):
 	mkdir -p $(OUT)
@@ -53,6 +53,14 @@ nms_probe: $(OUT)/libnms_probe.so
 $(OUT)/nms_probe_main.o: tests/cpp/nms_probe.hip $(CSRC)/zly_internal.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OUT)/libnms_probe.so: $(OUT)/nms_probe_main.o $(OUT)/kernels_post.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-Bsymbolic -o $@ $^
+
+# ---- test infrastructure: single launches of the shipped SPPF kernels (the two pool kernels, the fused block) on caller-made buffers
+#      (tests/test_gpu_sppf.py).  As above: the kernels_misc.o, kernels_sppf.o and weights.o of libzly.so itself, not recompilations
+sppf_probe: $(OUT)/libsppf_probe.so
+$(OUT)/sppf_probe_main.o: tests/cpp/sppf_probe.hip $(CSRC)/zly_internal.h $(CSRC)/weights.h include/zly.h | $(OUT)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OUT)/libsppf_probe.so: $(OUT)/sppf_probe_main.o $(OUT)/kernels_misc.o $(OUT)/kernels_sppf.o $(OUT)/weights.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-Bsymbolic -o $@ $^
 
 # ---- in-process RCCL gather of result slabs (include/zly_gather.h): a library of its own -- it links RCCL, and a process that already carries
@@ -144,4 +152,4 @@ $(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_
 clean:
 	rm -rf $(OUT) oracle/_build
 
-.PHONY: all host oracle weights diag diaglib nms_probe clean
+.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe clean

@@ -97,6 +97,29 @@ def test_production_selection(weights_path, oracle, monkeypatch, w, h, n):
     e.close()
 
 
+@pytest.mark.parametrize("w,h,n", [(352, 288, 5), (416, 416, 3)])
+def test_production_selection_with_fused_sppf(weights_path, oracle, monkeypatch, w, h, n):
+    """test_production_selection with ZLY_SPPF_FUSED=1: model.9 runs as one sppf_fused_kernel launch (11 x 9 and 13 x 13 maps), whose dump
+    writes y and the pooled maps to the concat buffer -- so model.9.cv1 and model.9.cv2 go through the same per-element bound as every
+    other conv, after forward() and after detect_batch() (tests/test_gpu_sppf.py drives the kernel alone)."""
+    for k, v in MIN_SWITCHES.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("ZLY_SPPF_FUSED", "1")
+    frames = zm.synth_frames(n, w, h, seed=31, rects=False)
+    x = _pre(oracle, frames, w, h)
+    e = zly.Engine(weights_path, model_w=w, model_h=h, max_batch=n, warmup_runs=0, flags=zly.FLAG_DUMP_LOGITS)
+    kn = " | ".join(e.op_kernels(n))
+    assert "sppf_fused_kernel" in kn and "sppf_pool" not in kn, kn
+    lds = lds_resident_from_kernels(e, n)
+    head = e.forward(x)
+    assert len(check_closed_loop(e, weights_path, range(n), lds_resident=lds)) == 63
+    for i in range(n):
+        check_head_decode(e, head[i], i)
+    assert len(e.detect_batch(list(frames), cap=64)) == n
+    assert len(check_closed_loop(e, weights_path, range(n), lds_resident=lds, first_input=_as_held(x))) == 63
+    e.close()
+
+
 @pytest.mark.parametrize("w,h,n", [(416, 416, 1), (96, 64, 1), (352, 288, 4), (416, 416, 4)])
 def test_latency_path(weights_path, oracle, w, h, n):
     """batch 1 and batch 4 as they run by default: the Detect convs as two merged launches (conv_igemm_multi_kernel), split-K direct kernels"""
