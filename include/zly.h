@@ -450,6 +450,93 @@ int32_t zly_track_slabs(zly_engine* e, int32_t n, const int32_t* streams, void* 
 int32_t zly_submit_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket);
 int32_t zly_submit_try_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket);
 
+/* --- Tiles -------------------------------------------------------------------------------------------------------------------------
+ * Merges, on the GPU and behind NMS, the slabs that the tiles of one surface produced into one slab in surface coordinates.  A large capture
+ * stretched to the model size makes a small target a few model pixels wide; sliced inference -- overlapping tiles (zly_detect_device_view takes
+ * them as views of one buffer), then a merge -- is how such targets are found.  An object on a seam comes back from two or four tiles; the merge
+ * maps every box to its surface and suppresses the duplicates.  Opt-in per call: an engine that never calls zly_merge_slabs or zly_detect_tiled
+ * runs exactly the kernels it ran before these calls existed.
+ *
+ * A TILE is the rectangle (x0, y0, w, h) of a W x H surface that a slab's boxes are fractions of.  A GROUP is the set of tiles of one surface in
+ * a call; a call may carry several groups (8 tiles for each of 8 clients in a batch of 64).  A whole-surface pass beside the tiles -- one more
+ * view with x0 = y0 = 0, w = W, h = H -- is just another tile of its group.
+ *
+ * The step for one group.  Its sources are the group's slabs in ascending slab index.  All arithmetic is single IEEE fp32 operations in the
+ * order written, without contraction; the (float) conversions are exact because every integer is below 2^24.
+ *   1. Candidates: the stored detections of every source i, K_i = clamp(n_kept_i, 0, cap) records each.  M = sum of K_i.
+ *   2. Map each candidate (x, y, bw, bh) of a tile (x0, y0, w, h) of a W x H surface to surface fractions:
+ *          X = (x*(float)w + (float)x0) / (float)W        Y = (y*(float)h + (float)y0) / (float)H
+ *          BW = bw*(float)w / (float)W                     BH = bh*(float)h / (float)H
+ *      (the product is rounded, then the sum, then the quotient) -- the map of INTEGRATION.md section 3 and of the plugin's ZLY_CROP.
+ *   3. The total order: class_id ascending (as int32), confidence descending (as fp32 value: -0 and +0 tie; a NaN confidence is outside the rule,
+ *      and NMS never stores one), source slab index ascending, position in the slab ascending.
+ *   4. Greedy suppression, as applyNMS (onnx_engine.cpp:837-878): go through the order; every candidate still alive suppresses every later alive
+ *      candidate of the same class for which m > thr (strict).  With a the earlier and b the later candidate, on the MAPPED boxes:
+ *          ax0 = a.X - a.BW/2, ay0 = a.Y - a.BH/2, ax1 = a.X + a.BW/2, ay1 = a.Y + a.BH/2, and b likewise
+ *          lo_x = ax0 < bx0 ? bx0 : ax0;  hi_x = bx1 < ax1 ? bx1 : ax1;  lo_y, hi_y likewise
+ *          dx = hi_x - lo_x;  dy = hi_y - lo_y;  ox = 0 < dx ? dx : 0;  oy = 0 < dy ? dy : 0;  inter = ox*oy
+ *          area_a = a.BW*a.BH;  area_b = b.BW*b.BH
+ *          ZLY_MERGE_IOU:  uni = area_a + area_b - inter;                 m = uni > 0 ? inter/uni : 0     (calculateIoU, :881-909, as NMS computes it)
+ *          ZLY_MERGE_IOS:  mn = area_a < area_b ? area_a : area_b;        m = mn > 0 ? inter/mn : 0
+ *      All pairs are tested, pairs from the same tile included.  Intersection over the smaller area is what removes the half box that a tile
+ *      border cuts from an object its neighbour sees whole; IoU alone often leaves it.
+ *   5. The group's output slab, in the engine's slab format and capacity: the survivors in the order of step 3, the first min(n_kept, cap) of
+ *      them, with the mapped box, the source's confidence and class_id, and track_id = pad_ = timestamp = 0.  Header: n_kept = survivors
+ *      (un-capped), n_candidates = M, ZLY_SLAB_OVERFLOW set when n_kept > cap or any source carries it, frame_tag = frame_tag0 + group.
+ *      Records at or beyond the stored count are NOT written.  A group without tiles gives an empty slab (the header only).
+ * Nothing else is fused: no averaging or union of matched boxes, no class-agnostic merging.
+ * Out of scope: the plugin (there is no ZLY_TILES switch), the pipelined submit path, engines behind host/zly_sharded*.hpp. */
+#define ZLY_MERGE_IOU 0
+#define ZLY_MERGE_IOS 1
+#define ZLY_MERGE_MAX_CANDIDATES 4096   /* tiles of a group x cap may not exceed it: a group's candidates are sorted in one workgroup's LDS */
+typedef struct zly_tile {
+    int32_t group;            /* -1: this slab takes no part */
+    int32_t x0, y0, w, h;     /* the tile inside its surface, pixels */
+    int32_t W, H;             /* the surface; equal for every tile of a group */
+} zly_tile;
+typedef struct zly_merge_config {
+    int32_t metric;           /* ZLY_MERGE_IOU | ZLY_MERGE_IOS */
+    float   thr;              /* in [0, 1) */
+} zly_merge_config;
+/* IoS at 0.5.  Chosen, not tuned: nobody has measured them on real footage. */
+void    zly_default_merge_config(zly_merge_config* cfg);
+
+/* The device path: merges the n slabs that the most recent zly_detect_device* call on this engine wrote (d_slabs = NULL: the engine's own slab
+ * buffer), or slabs made elsewhere on an engine that has made no call yet (tests), as zly_track_slabs allows.  tiles is a HOST array of n, one per
+ * slab; d_out receives n_groups slabs of zly_slab_bytes each (NULL: an engine-owned buffer of max_batch slabs, allocated on first use -- alone in
+ * the process, like the submit ring -- and read with zly_read_merged); it must not overlap the sources.  The sources are not modified.
+ * Enqueued, not synchronised, on exactly the stream zly_track_slabs would choose: the engine's NMS stream when the call's NMS was deferred
+ * (ZLY_FLAG_ASYNC_NMS), otherwise `stream` (NULL = the engine's own), which waits for the call's completion event.  The call's completion events
+ * move behind the merge: zly_join, zly_sync and zly_read_slabs cover it, and a following zly_track_slabs(e, n_groups, streams, d_out, stream)
+ * tracks the merged slabs with no further synchronisation.  The tile table reaches the device through a ring of pinned records, as the tracker's
+ * stream list does: after the first merge of an engine a call allocates nothing.
+ * ZLY_ERR_INVALID_ARGUMENT, with nothing enqueued: n outside 1..max_batch or n_groups outside 1..n; a group index outside -1..n_groups-1; a
+ * rectangle that is not inside its surface, has w or h < 1, or a surface with W or H >= 2^24; tiles of one group that disagree on W, H; a group
+ * with tiles x cap > ZLY_MERGE_MAX_CANDIDATES; a null or out-of-range config (NaN included); a d_out that is the engine's own slab buffer. */
+int32_t zly_merge_slabs(zly_engine* e, int32_t n, const zly_tile* tiles, int32_t n_groups, const zly_merge_config* cfg, void* d_slabs, void* d_out,
+                        uint32_t frame_tag0, void* stream);
+/* Waits for the merges enqueued so far, then copies the first n_groups slabs of the engine-owned merge buffer to the host (1..max_batch;
+ * ZLY_ERR_INVALID_ARGUMENT otherwise, and on an engine that has not merged yet). */
+int32_t zly_read_merged(zly_engine* e, int32_t n_groups, void* host_slabs);
+
+/* The tiles of a W x H surface, host only (no engine, no GPU).  Per axis, with extent E, tile size T and overlap V: step = T - V (> 0); if
+ * T >= E there is one tile and it spans the extent; otherwise count = ceil((E - T) / step) + 1 and origin_i = min(i*step, E - T), so that the
+ * last tile is shifted back and every tile is full-sized.  even != 0 (YUV 4:2:0 surfaces): origins are rounded down to even; odd tile sizes or
+ * extents are refused.  Tiles come in row-major order with group = 0 and W, H filled in; min(count, cap) of them are written and *n_out is the
+ * count (cap = 0, out = NULL asks for the count alone).  ZLY_ERR_INVALID_ARGUMENT: W, H outside 1..2^24-1, a tile size < 1, an overlap < 0 or
+ * >= the tile size, the even rule, a null n_out, cap < 0 or a null out with cap > 0. */
+int32_t zly_tile_grid(int32_t W, int32_t H, int32_t tile_w, int32_t tile_h, int32_t overlap_x, int32_t overlap_y, int32_t even, zly_tile* out,
+                      int32_t cap, int32_t* n_out);
+
+/* The synchronous host entry: one surface in host memory, detected in n tiles and merged as one group.  The surface's zly_view_bytes bytes are
+ * uploaded ONCE, as zly_preprocess_view uploads them; the tiles are zly_view_crop's of `surface` on the device-view path (the front kernel
+ * fetches through them: nothing is repacked), so letterbox engines and every pixel format are honoured because views are.  Every tile must have
+ * W = surface->w, H = surface->h and group = 0.  Writes min(n_kept, cap) merged detections to out, in surface fractions, and the un-capped count
+ * to *n_out; timestamps as zly_detect sets them.  Errors as zly_detect_view (for the surface and for every tile's view) plus those of
+ * zly_merge_slabs and zly_view_crop. */
+int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* surface, int32_t n, const zly_tile* tiles,
+                         const zly_merge_config* cfg, zly_det* out, int32_t cap, int32_t* n_out);
+
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw);

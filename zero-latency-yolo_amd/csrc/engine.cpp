@@ -169,6 +169,19 @@ struct Track {
     std::vector<int> seg_of;          // [max_streams] scratch of the grouping: a stream's segment in the current call, -1 = none yet
 };
 
+// Merging the slabs of a surface's tiles (zly_merge_slabs; include/zly.h "Tiles"): created by an engine's first merge.  The tile table of a call reaches
+// merge_kernel through a ring like the tracker's; d_out is the engine-owned output buffer (max_batch slabs), allocated with the ring.
+struct Merge {
+    static constexpr int RING = 8;
+    size_t tab_ints = 0;              // int32 per ring entry: max_batch + 1 offsets + ZLY_MERGE_TILE_INTS * max_batch (zly_internal.h: launch_merge)
+    int* h_tab = nullptr;             // pinned [RING][tab_ints]
+    int* d_tab = nullptr;             // device [RING][tab_ints]
+    hipEvent_t ev[RING] = {};         // behind the kernel that read entry r
+    bool used[RING] = {};
+    int next = 0, last = -1;          // last: the entry of the most recent merge
+    unsigned char* d_out = nullptr;   // [max_batch][slab_bytes]
+};
+
 }  // namespace zly
 
 using namespace zly;
@@ -249,6 +262,7 @@ struct zly_engine : Plan {
     uint32_t cu_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::atomic<Ingest*> ingest{nullptr};   // created by the first zly_submit (under mu), read lock-free afterwards
     std::atomic<Track*> track{nullptr};     // created by zly_track_enable (under mu), read lock-free afterwards
+    Merge* merge = nullptr;                 // created by the first zly_merge_slabs / zly_detect_tiled (under mu)
     hipStream_t last_ns = nullptr;          // the stream the most recent zly_detect_device* call's NMS ran on, and whether that was the engine's NMS stream
     bool last_deferred = false;
 
@@ -1610,6 +1624,13 @@ static hipError_t destroy_engine(zly_engine* e)
         for (int i = 0; i < Track::RING; ++i) if (tk->ev[i]) hipEventDestroy(tk->ev[i]);
         delete tk;
     }
+    if (Merge* mg = e->merge) {
+        if (mg->d_tab) note(hipFree(mg->d_tab));
+        if (mg->h_tab) note(hipHostFree(mg->h_tab));
+        if (mg->d_out) note(hipFree(mg->d_out));
+        for (int i = 0; i < Merge::RING; ++i) if (mg->ev[i]) hipEventDestroy(mg->ev[i]);
+        delete mg;
+    }
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
         if (e->ev_join[i]) hipEventDestroy(e->ev_join[i]);
@@ -2758,6 +2779,238 @@ int32_t zly_submit_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_b
 int32_t zly_submit_try_view_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket)
 {
     return submit_tracked(e, base, buf_bytes, v, stream, ticket, true);
+}
+
+// --- tiles -----------------------------------------------------------------------------------------
+void zly_default_merge_config(zly_merge_config* c)
+{
+    if (!c) return;
+    c->metric = ZLY_MERGE_IOS;    // chosen, not tuned
+    c->thr = 0.5f;
+}
+
+// one axis of zly_tile_grid: the number of tiles and their size; false when the arguments are refused
+static bool grid_axis(int32_t extent, int32_t tile, int32_t overlap, bool even, int64_t* count, int32_t* size, int32_t* step)
+{
+    if (extent < 1 || extent >= (1 << 24) || tile < 1 || overlap < 0 || overlap >= tile) return false;
+    if (even && ((extent | tile) & 1)) return false;
+    *step = tile - overlap;
+    if (tile >= extent) { *count = 1; *size = extent; return true; }
+    *size = tile;
+    *count = ((int64_t)(extent - tile) + *step - 1) / *step + 1;
+    return true;
+}
+
+int32_t zly_tile_grid(int32_t W, int32_t H, int32_t tile_w, int32_t tile_h, int32_t overlap_x, int32_t overlap_y, int32_t even, zly_tile* out,
+                      int32_t cap, int32_t* n_out)
+{
+    if (!n_out || cap < 0 || (cap > 0 && !out)) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_tile_grid: null output");
+    int64_t nx = 0, ny = 0;
+    int32_t tw = 0, th = 0, sx = 0, sy = 0;
+    if (!grid_axis(W, tile_w, overlap_x, even != 0, &nx, &tw, &sx) || !grid_axis(H, tile_h, overlap_y, even != 0, &ny, &th, &sy))
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_tile_grid: the surface must lie in 1..2^24-1, a tile be >= 1 and its overlap in [0, tile); even surfaces need even sizes");
+    if (nx * ny > 0x7fffffff) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_tile_grid: too many tiles");
+    int64_t k = 0;
+    for (int64_t j = 0; j < ny && k < cap; ++j)
+        for (int64_t i = 0; i < nx && k < cap; ++i, ++k) {
+            int64_t x0 = std::min<int64_t>(i * sx, W - tw), y0 = std::min<int64_t>(j * sy, H - th);
+            if (even) { x0 &= ~(int64_t)1; y0 &= ~(int64_t)1; }
+            zly_tile t;
+            t.group = 0; t.x0 = (int32_t)x0; t.y0 = (int32_t)y0; t.w = tw; t.h = th; t.W = W; t.H = H;
+            out[k] = t;
+        }
+    *n_out = (int32_t)(nx * ny);
+    return ZLY_OK;
+}
+
+// the argument checks of a merge (include/zly.h lists them); *max_slots = the largest tiles x cap of a group
+static int merge_check(const zly_engine* e, int n, const zly_tile* tiles, int n_groups, const zly_merge_config* c, int* max_slots)
+{
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    if (n_groups < 1 || n_groups > n) return fail(ZLY_ERR_INVALID_ARGUMENT, "n_groups must lie in 1..n");
+    if (!tiles) return fail(ZLY_ERR_INVALID_ARGUMENT, "null tiles");
+    if (!c) return fail(ZLY_ERR_INVALID_ARGUMENT, "null merge config");
+    if (c->metric != ZLY_MERGE_IOU && c->metric != ZLY_MERGE_IOS) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown merge metric " + std::to_string(c->metric));
+    if (!(c->thr >= 0.0f && c->thr < 1.0f)) return fail(ZLY_ERR_INVALID_ARGUMENT, "the merge threshold must lie in [0, 1)");
+    std::vector<int> count((size_t)n_groups, 0), first((size_t)n_groups, -1);
+    for (int i = 0; i < n; ++i) {
+        const zly_tile& t = tiles[i];
+        if (t.group < -1 || t.group >= n_groups) return fail(ZLY_ERR_INVALID_ARGUMENT, "tile " + std::to_string(i) + ": group " + std::to_string(t.group) + " out of range");
+        if (t.group < 0) continue;
+        if (t.W < 1 || t.H < 1 || t.W >= (1 << 24) || t.H >= (1 << 24)) return fail(ZLY_ERR_INVALID_ARGUMENT, "tile " + std::to_string(i) + ": the surface must lie in 1..2^24-1");
+        if (t.w < 1 || t.h < 1 || t.x0 < 0 || t.y0 < 0 || (int64_t)t.x0 + t.w > t.W || (int64_t)t.y0 + t.h > t.H)
+            return fail(ZLY_ERR_INVALID_ARGUMENT, "tile " + std::to_string(i) + ": the rectangle is not inside its surface");
+        int& f = first[(size_t)t.group];
+        if (f < 0) f = i;
+        else if (tiles[f].W != t.W || tiles[f].H != t.H) return fail(ZLY_ERR_INVALID_ARGUMENT, "tile " + std::to_string(i) + ": the tiles of group " + std::to_string(t.group) + " disagree on W, H");
+        count[(size_t)t.group]++;
+    }
+    int64_t mx = 0;
+    for (int g = 0; g < n_groups; ++g) mx = std::max<int64_t>(mx, (int64_t)count[(size_t)g] * e->cfg.max_dets);
+    if (mx > ZLY_MERGE_MAX_CANDIDATES) return fail(ZLY_ERR_INVALID_ARGUMENT, "a group's tiles x max_dets exceed ZLY_MERGE_MAX_CANDIDATES");
+    *max_slots = (int)mx;
+    return ZLY_OK;
+}
+
+// the engine's merge state, created on first use: allocations and the kernel's LDS opt-in, alone in the process.  Under e->mu, no gate held.
+static int merge_ensure(zly_engine* e)
+{
+    if (e->merge) return ZLY_OK;
+    ExclusiveGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    Merge* mg = new Merge();
+    mg->tab_ints = (size_t)e->cfg.max_batch * (1 + ZLY_MERGE_TILE_INTS) + 1;
+    bool ok = merge_init() == hipSuccess &&
+              hipMalloc((void**)&mg->d_tab, sizeof(int) * mg->tab_ints * Merge::RING) == hipSuccess &&
+              hipHostMalloc((void**)&mg->h_tab, sizeof(int) * mg->tab_ints * Merge::RING, hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void**)&mg->d_out, slab_bytes_of(e) * (size_t)e->cfg.max_batch) == hipSuccess &&
+              hipMemset(mg->d_out, 0, slab_bytes_of(e) * (size_t)e->cfg.max_batch) == hipSuccess;
+    for (int i = 0; i < Merge::RING && ok; ++i) ok = hipEventCreateWithFlags(&mg->ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (mg->d_tab) hipFree(mg->d_tab);
+        if (mg->h_tab) hipHostFree(mg->h_tab);
+        if (mg->d_out) hipFree(mg->d_out);
+        for (int i = 0; i < Merge::RING; ++i) if (mg->ev[i]) hipEventDestroy(mg->ev[i]);
+        delete mg;
+        return fail(ZLY_ERR_SYSTEM, "allocation of the merge buffers failed");
+    }
+    e->merge = mg;
+    return ZLY_OK;
+}
+
+// Builds the call's tile table in the next ring entry, uploads it and launches merge_kernel on `s` -- the stream the slabs' NMS ran on, or one already
+// ordered behind it.  Under e->mu, enqueue gate held; the arguments are validated by the caller (merge_check).
+static int merge_enqueue(zly_engine* e, int n, const zly_tile* tiles, int n_groups, const zly_merge_config* c, int max_slots, const void* src, void* dst,
+                         uint32_t tag0, hipStream_t s)
+{
+    Merge* mg = e->merge;
+    const int r = mg->next;
+    mg->next = (r + 1) % Merge::RING;
+    if (mg->used[r]) HIP_TRY(hipEventSynchronize(mg->ev[r]), ZLY_ERR_INFERENCE);      // 8 merges back: long complete
+    int* t = mg->h_tab + (size_t)r * mg->tab_ints;
+    for (int g = 0; g <= n_groups; ++g) t[g] = 0;
+    for (int i = 0; i < n; ++i) if (tiles[i].group >= 0) t[tiles[i].group + 1]++;
+    for (int g = 0; g < n_groups; ++g) t[g + 1] += t[g];                             // t[g] = offset of group g, t[n_groups] = members in all
+    const int n_members = t[n_groups];
+    int* members = t + n_groups + 1;
+    std::vector<int> fill(t, t + n_groups);
+    for (int i = 0; i < n; ++i) {                                                     // ascending slab index inside every group
+        if (tiles[i].group < 0) continue;
+        int* m = members + (size_t)fill[(size_t)tiles[i].group]++ * ZLY_MERGE_TILE_INTS;
+        m[0] = i; m[1] = tiles[i].x0; m[2] = tiles[i].y0; m[3] = tiles[i].w; m[4] = tiles[i].h; m[5] = tiles[i].W; m[6] = tiles[i].H;
+    }
+    int* dt = mg->d_tab + (size_t)r * mg->tab_ints;
+    HIP_TRY(hipMemcpyAsync(dt, t, sizeof(int) * (size_t)(n_groups + 1 + n_members * ZLY_MERGE_TILE_INTS), hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_merge(dt, n_groups, max_slots, src, dst, e->cfg.max_dets, c->metric, c->thr, tag0, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(mg->ev[r], s), ZLY_ERR_INFERENCE);
+    mg->used[r] = true;
+    mg->last = r;
+    return ZLY_OK;
+}
+
+int32_t zly_merge_slabs(zly_engine* e, int32_t n, const zly_tile* tiles, int32_t n_groups, const zly_merge_config* c, void* d_slabs, void* d_out,
+                        uint32_t frame_tag0, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    int max_slots = 0;
+    if (int rc = merge_check(e, n, tiles, n_groups, c, &max_slots)) return rc;
+    if (d_out && d_out == (void*)e->d_slabs) return fail(ZLY_ERR_INVALID_ARGUMENT, "d_out must not be the engine's own slab buffer");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (int rc = merge_ensure(e)) return rc;
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    // the stream zly_track_slabs would choose: behind the NMS of the most recent zly_detect_device* call, on whichever stream it ran
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    const bool after_call = e->call_seq > 0;
+    if (after_call && e->last_deferred) s = e->last_ns;
+    else if (after_call && s != e->last_ns) HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1) & 1], 0), ZLY_ERR_INFERENCE);
+    int rc = merge_enqueue(e, n, tiles, n_groups, c, max_slots, d_slabs ? d_slabs : e->d_slabs, d_out ? d_out : e->merge->d_out, frame_tag0, s);
+    if (rc != ZLY_OK) return rc;
+    if (after_call) {
+        // the call's completion events move behind its merge: zly_join, zly_read_slabs, a later call's NMS and a following zly_track_slabs wait for both
+        HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], s), ZLY_ERR_INFERENCE);
+        if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], s), ZLY_ERR_INFERENCE);
+    }
+    return ZLY_OK;
+}
+
+int32_t zly_read_merged(zly_engine* e, int32_t n_groups, void* host_slabs)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!host_slabs || n_groups < 1 || n_groups > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Merge* mg = e->merge;
+    if (!mg) return fail(ZLY_ERR_INVALID_ARGUMENT, "this engine has not merged yet (zly_merge_slabs)");
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    {
+        SharedGate gl;
+        if (mg->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, mg->ev[mg->last], 0), ZLY_ERR_INFERENCE);      // merges of an engine are ordered among themselves
+        int rcj = join_nms(e, e->stream);
+        if (rcj != ZLY_OK) return rcj;
+        HIP_TRY(hipMemcpyAsync(host_slabs, mg->d_out, slab_bytes_of(e) * (size_t)n_groups, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* surface, int32_t n, const zly_tile* tiles,
+                         const zly_merge_config* c, zly_det* out, int32_t cap, int32_t* n_out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!surface || !out || !n_out || cap < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    if (!fmt_known(surface->fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(surface->fmt));
+    size_t nbytes = 0;
+    if (!view_valid(surface, &nbytes)) return fail(ZLY_ERR_INVALID_INPUT, "invalid surface view");
+    if (!base || nbytes > buf_bytes) return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: the surface needs " + std::to_string(nbytes) + " bytes, got " + std::to_string(buf_bytes));
+    int max_slots = 0;
+    if (int rc = merge_check(e, n, tiles, 1, c, &max_slots)) return rc;
+    std::vector<zly_frame_view> views((size_t)n);
+    std::vector<int32_t> ws((size_t)n), hs((size_t)n), fs((size_t)n);
+    std::vector<size_t> offs((size_t)n);
+    std::vector<ViewRec> recs((size_t)n);
+    int level = ZLY_FRONT_BGR;
+    for (int i = 0; i < n; ++i) {
+        const zly_tile& t = tiles[i];
+        if (t.group != 0 || t.W != surface->w || t.H != surface->h)
+            return fail(ZLY_ERR_INVALID_ARGUMENT, "tile " + std::to_string(i) + ": zly_detect_tiled needs group = 0 and W, H = the surface's size");
+        if (int rc = zly_view_crop(surface, t.x0, t.y0, t.w, t.h, &views[(size_t)i])) return rc;
+        if (int rc = check_view(e, base, buf_bytes, &views[(size_t)i])) return rc;
+        const zly_frame_view& v = views[(size_t)i];
+        ws[(size_t)i] = v.w; hs[(size_t)i] = v.h; fs[(size_t)i] = v.fmt; offs[(size_t)i] = (size_t)v.off[0];
+        recs[(size_t)i] = view_rec(&v);
+        level = std::max(level, front_level(v.fmt));
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (int rc = merge_ensure(e)) return rc;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (nbytes > e->stage_bytes) {                                       // an allocation: alone in the process
+        ExclusiveGate x;
+        if (int rc = ensure_stage(e, nbytes)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
+    memcpy(e->h_stage, base, nbytes);                                    // the surface once, as it is: the front kernel fetches through the tiles' views
+    SharedGate gl;
+    HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, nbytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
+    int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream, fs.data(), recs.data());
+    if (rc != ZLY_OK) return rc;
+    rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, false, nullptr, front_of(e, level, true));
+    if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
+    rc = merge_enqueue(e, n, tiles, 1, c, max_slots, e->d_slabs, e->merge->d_out, 0, e->stream);
+    if (rc != ZLY_OK) return rc;
+    const size_t sb = slab_bytes_of(e);
+    HIP_TRY(hipMemcpyAsync(e->h_slabs, e->merge->d_out, sb, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    gl.release();                                                        // waiting for the device is not an enqueue section
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    const uint64_t ts = now_ms();                                        // onnx_engine.cpp:813-815
+    const zly_slab_header* hd = reinterpret_cast<const zly_slab_header*>(e->h_slabs);
+    const zly_det* d = reinterpret_cast<const zly_det*>(hd + 1);
+    int m = std::min(std::min(hd->n_kept, e->cfg.max_dets), cap);
+    for (int k = 0; k < m; ++k) { out[k] = d[k]; out[k].timestamp = ts; }
+    *n_out = hd->n_kept;
+    harvest_timing(e);
+    with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
+    return ZLY_OK;
 }
 
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw)

@@ -352,4 +352,13 @@ hipError_t launch_track_motion(TrackStream* states, TrackMotion* motion, const i
 // vx = vy = 0, hits = 0 in every slot of streams [first, first + count)
 hipError_t launch_track_motion_reset(TrackMotion* motion, int first, int count, hipStream_t s);
 
+// ---- merging the slabs of a surface's tiles (kernels_merge.hip; the rule and the step: include/zly.h, "Tiles") ----
+#define ZLY_MERGE_TILE_INTS 7     // a member of the tile table: source slab, x0, y0, w, h, W, H
+// merge_kernel's dynamic LDS holds up to ZLY_MERGE_MAX_CANDIDATES candidates (132 KB): opted in at an engine's first merge, outside capture
+hipError_t merge_init();
+// tab (device, int32): [0 .. G] = the G groups' offsets into the member list; then ZLY_MERGE_TILE_INTS per member, a group's members in ascending slab
+// index.  One workgroup per group merges its members' slabs (of `slabs`) into slab g of `out`, frame_tag = tag0 + g.  max_slots: the largest
+// members x cap of a group (<= ZLY_MERGE_MAX_CANDIDATES): it sizes the launch.  metric: ZLY_MERGE_IOU | ZLY_MERGE_IOS.
+hipError_t launch_merge(const int* tab, int n_groups, int max_slots, const void* slabs, void* out, int cap, int metric, float thr, uint32_t tag0, hipStream_t s);
+
 }  // namespace zly

@@ -37,6 +37,8 @@ LETTERBOX_MAX_DIM = 16384    # largest request side (and model side) of a letter
 # packed RGB / BGRA / RGBA (the fourth byte is never interpreted) fetched in the front kernel as the BGR frame of their B, G, R bytes
 PIX_BGR, PIX_NV12_BT601, PIX_I420_BT601, PIX_NV12_BT709, PIX_I420_BT709 = 0, 1, 2, 3, 4
 PIX_RGB, PIX_BGRA, PIX_RGBA = 16, 17, 18
+MERGE_IOU, MERGE_IOS = 0, 1          # zly_merge_config.metric (include/zly.h "Tiles")
+MERGE_MAX_CANDIDATES = 4096          # tiles of a group x max_dets may not exceed it
 _PACKED_BPP = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
 
 # every symbol include/zly.h declares (tests/test_abi.py checks the library exports them all)
@@ -49,6 +51,7 @@ SYMBOLS = [
     "zly_detect_device_view", "zly_preprocess_view",
     "zly_default_track_config", "zly_track_enable", "zly_track_reset", "zly_track_state_at", "zly_track_slabs", "zly_submit_view_tracked", "zly_submit_try_view_tracked",
     "zly_default_track_motion_config", "zly_track_motion_enable", "zly_track_read",
+    "zly_default_merge_config", "zly_merge_slabs", "zly_read_merged", "zly_tile_grid", "zly_detect_tiled",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -94,6 +97,16 @@ class Track(C.Structure):
     """zly_track (TRACK_DTYPE is its numpy twin)"""
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("w", C.c_float), ("h", C.c_float), ("vx", C.c_float), ("vy", C.c_float),
                 ("class_id", C.c_int32), ("id", C.c_uint32), ("hits", C.c_uint32), ("last_seen", C.c_uint32)]
+
+
+class Tile(C.Structure):
+    """zly_tile: the rectangle (x0, y0, w, h) of a W x H surface that a slab's boxes are fractions of, and the group it is merged in (-1 = none)"""
+    _fields_ = [("group", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("W", C.c_int32), ("H", C.c_int32)]
+
+
+class MergeConfig(C.Structure):
+    """zly_merge_config"""
+    _fields_ = [("metric", C.c_int32), ("thr", C.c_float)]
 
 
 class Stats(C.Structure):
@@ -180,6 +193,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_default_track_motion_config.argtypes = [C.POINTER(TrackMotionConfig)]; lib.zly_default_track_motion_config.restype = None
     lib.zly_track_motion_enable.argtypes = [vp, C.POINTER(TrackMotionConfig)]; lib.zly_track_motion_enable.restype = i32
     lib.zly_track_read.argtypes = [vp, i32, vp, i32, pi32]; lib.zly_track_read.restype = i32
+    lib.zly_default_merge_config.argtypes = [C.POINTER(MergeConfig)]; lib.zly_default_merge_config.restype = None
+    lib.zly_merge_slabs.argtypes = [vp, i32, C.POINTER(Tile), i32, C.POINTER(MergeConfig), vp, vp, u32, vp]; lib.zly_merge_slabs.restype = i32
+    lib.zly_read_merged.argtypes = [vp, i32, vp]; lib.zly_read_merged.restype = i32
+    lib.zly_tile_grid.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(Tile), i32, pi32]; lib.zly_tile_grid.restype = i32
+    lib.zly_detect_tiled.argtypes = [vp, vp, sz, pv, i32, C.POINTER(Tile), C.POINTER(MergeConfig), vp, i32, pi32]; lib.zly_detect_tiled.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -230,6 +248,31 @@ def view_crop(surface: FrameView, x0: int, y0: int, w: int, h: int) -> FrameView
 def view_bytes(v: FrameView) -> int:
     """the smallest buffer that holds the view; 0 for an invalid view (host only)"""
     return int(load_library().zly_view_bytes(C.byref(v)))
+
+
+def tile(x0: int, y0: int, w: int, h: int, W: int, H: int, group: int = 0) -> Tile:
+    return Tile(group, x0, y0, w, h, W, H)
+
+
+def tile_grid(W: int, H: int, tile_w: int, tile_h: int, overlap_x: int = 0, overlap_y: int = 0, even: bool = False) -> List[Tile]:
+    """the row-major tiles of a W x H surface (zly_tile_grid; host only): every tile full-sized, the last of an axis shifted back"""
+    lib = load_library()
+    n = C.c_int32(0)
+    _check(lib, lib.zly_tile_grid(W, H, tile_w, tile_h, overlap_x, overlap_y, 1 if even else 0, None, 0, C.byref(n)))
+    out = (Tile * max(n.value, 1))()
+    _check(lib, lib.zly_tile_grid(W, H, tile_w, tile_h, overlap_x, overlap_y, 1 if even else 0, out, n.value, C.byref(n)))
+    return [Tile(t.group, t.x0, t.y0, t.w, t.h, t.W, t.H) for t in out[:n.value]]
+
+
+def merge_config(metric: Optional[int] = None, thr: Optional[float] = None) -> MergeConfig:
+    """zly_default_merge_config (IoS at 0.5) with the given fields replaced"""
+    c = MergeConfig()
+    load_library().zly_default_merge_config(C.byref(c))
+    if metric is not None:
+        c.metric = metric
+    if thr is not None:
+        c.thr = thr
+    return c
 
 
 def _dims(frame: np.ndarray, fmt: int, w: Optional[int], h: Optional[int]) -> Tuple[int, int]:
@@ -413,6 +456,35 @@ class Engine:
         n = len(streams)
         cs = (C.c_int32 * n)(*streams)
         _check(self.lib, self.lib.zly_track_slabs(self.h, n, cs, d_slabs_ptr or None, stream or None))
+
+    # -- tiles (include/zly.h "Tiles") ------------------------------------------------------------------
+    def merge_slabs(self, tiles: Sequence[Tile], n_groups: int = 1, metric: Optional[int] = None, thr: Optional[float] = None, d_slabs_ptr: int = 0,
+                    d_out_ptr: int = 0, tag0: int = 0, stream: int = 0):
+        """merges the len(tiles) slabs of the most recent detect_device* call (d_slabs_ptr = 0: the engine's own buffer) into n_groups slabs at
+        d_out_ptr (0: the engine-owned merge buffer, read with read_merged); enqueued, not synchronised"""
+        n = len(tiles)
+        ct = (Tile * n)(*tiles)
+        c = merge_config(metric, thr)
+        _check(self.lib, self.lib.zly_merge_slabs(self.h, n, ct, n_groups, C.byref(c), d_slabs_ptr or None, d_out_ptr or None, tag0, stream or None))
+
+    def read_merged(self, n_groups: int = 1) -> List[Tuple[np.ndarray, np.ndarray]]:
+        raw = np.zeros(n_groups * self.slab_bytes, dtype=np.uint8)
+        _check(self.lib, self.lib.zly_read_merged(self.h, n_groups, raw.ctypes.data))
+        return parse_slabs(raw, n_groups, self.max_dets)
+
+    def detect_tiled(self, buf: np.ndarray, surface: FrameView, tiles: Sequence[Tile], metric: Optional[int] = None, thr: Optional[float] = None,
+                     cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+        """buf: the surface in host memory, uploaded once; tiles: rectangles of it, detected in one call and merged as one group
+        -> (detections[min(n, cap)] in surface fractions, n)"""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        cap = cap or self.max_dets
+        n_t = len(tiles)
+        ct = (Tile * n_t)(*tiles)
+        c = merge_config(metric, thr)
+        out = np.zeros(cap, dtype=DET_DTYPE)
+        n = C.c_int32(0)
+        _check(self.lib, self.lib.zly_detect_tiled(self.h, buf.ctypes.data, buf.nbytes, C.byref(surface), n_t, ct, C.byref(c), out.ctypes.data, cap, C.byref(n)))
+        return out[:min(n.value, cap)], n.value
 
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
