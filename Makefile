@@ -12,9 +12,9 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wal
 CXX      ?= g++
 PY       ?= python3
 
-KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_pix.hip $(CSRC)/kernels_pix_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip $(CSRC)/kernels_track.hip $(CSRC)/kernels_merge.hip
+KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_pix.hip $(CSRC)/kernels_pix_view.hip $(CSRC)/kernels_y422.hip $(CSRC)/kernels_y422_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip $(CSRC)/kernels_track.hip $(CSRC)/kernels_merge.hip
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
-OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/kernels_merge.o $(OUT)/engine.o $(OUT)/weights.o
+OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/kernels_merge.o $(OUT)/engine.o $(OUT)/weights.o
 
 all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so $(OUT)/libsppf_probe.so oracle weights host
 
@@ -28,7 +28,7 @@ $(OUT)/%.o: $(CSRC)/%.hip $(KHDRS) | $(OUT)
 # the side units of the front kernels (front_variants.h) compile the main units' text
 $(OUT)/kernels_stem_yuv.o: $(CSRC)/kernels_stem.hip
 $(OUT)/kernels_lb.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_head.hip
-$(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
+$(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
 
 $(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
@@ -60,7 +60,9 @@ $(OUT)/libnms_probe.so: $(OUT)/nms_probe_main.o $(OUT)/kernels_post.o
 sppf_probe: $(OUT)/libsppf_probe.so
 $(OUT)/sppf_probe_main.o: tests/cpp/sppf_probe.hip $(CSRC)/zly_internal.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OUT)/libsppf_probe.so: $(OUT)/sppf_probe_main.o $(OUT)/kernels_misc.o $(OUT)/kernels_sppf.o $(OUT)/weights.o
+$(OUT)/sppf_probe_y422.o: tests/cpp/sppf_probe_y422.hip $(CSRC)/zly_internal.h $(CSRC)/front_variants.h include/zly.h | $(OUT)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OUT)/libsppf_probe.so: $(OUT)/sppf_probe_main.o $(OUT)/sppf_probe_y422.o $(OUT)/kernels_misc.o $(OUT)/kernels_sppf.o $(OUT)/weights.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-Bsymbolic -o $@ $^
 
 # ---- in-process RCCL gather of result slabs (include/zly_gather.h): a library of its own -- it links RCCL, and a process that already carries
@@ -80,7 +82,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -107,6 +109,10 @@ $(OUT)/test_plugin_stub: tests/cpp/test_plugin_stub.cpp $(HOST)/hip_inference_en
 # ... and its ZLY_CROP logic against a stub that records the frame view it is handed
 $(OUT)/test_plugin_crop_stub: tests/cpp/test_plugin_crop_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_crop_stub.cpp -pthread
+
+# ... and its packed YUV 4:2:2 input formats (names, sizes, ZLY_CROP's x-only evenness rule) against a stub of the same kind
+$(OUT)/test_plugin_yuv422_stub: tests/cpp/test_plugin_yuv422_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_yuv422_stub.cpp -pthread
 
 # ... and its ZLY_TRACK logic against a stub that records (engine, stream) of every submit and every reset; the second binary's stub lacks the tracking calls
 $(OUT)/test_plugin_track_stub: tests/cpp/test_plugin_track_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)

@@ -111,8 +111,10 @@ extern "C" {
  *   ZLY_PIX_RGB          packed R,G,B, 3 bytes per pixel: nbytes = w*h*3
  *   ZLY_PIX_BGRA         packed B,G,R,X, 4 bytes per pixel: nbytes = w*h*4   (GDI 32-bit DIB, DXGI B8G8R8A8, DRM XRGB8888 / ARGB8888)
  *   ZLY_PIX_RGBA         packed R,G,B,X, 4 bytes per pixel: nbytes = w*h*4   (DXGI R8G8B8A8, DRM XBGR8888 / ABGR8888, GL_RGBA)
- * The known formats are a set, not a range: the values between the YUV formats and ZLY_PIX_RGB (5..15) are unknown, reserved for further YUV
- * layouts.
+ *   ZLY_PIX_YUY2_*       packed 4:2:2, macropixels of two pixels Y0,U,Y1,V [h][w/2][4]: nbytes = w*h*2   (YUYV; Media Foundation / V4L2 capture)
+ *   ZLY_PIX_UYVY_*       packed 4:2:2, macropixels of two pixels U,Y0,V,Y1 [h][w/2][4]: nbytes = w*h*2   (HDMI / SDI capture cards)
+ * The known formats are a set, not a range: of the values between the 4:2:0 formats and ZLY_PIX_RGB, 10..13 are the packed 4:2:2 formats;
+ * 5..9, 14 and 15 are unknown, reserved for further YUV layouts.
  * YUV frames (8-bit 4:2:0, limited range) need even w and h (>= 2).  Colour conversion happens in the front kernel: for the source pixel
  * (sx, sy) that the stretch-nearest resize picks (the BGR map, unchanged),
  *   Y = Yplane[sy*w + sx];  ci = (sy>>1)*(w/2) + (sx>>1);  NV12: U = UV[2ci], V = UV[2ci+1];  I420: U = Uplane[ci], V = Vplane[ci]
@@ -126,6 +128,14 @@ extern "C" {
  *   BT.709   1220945  1879825  -558796  -223607  2215014   (round(c x 2^20) from Kr = 0.2126, Kb = 0.0722, luma x 255/219, chroma x 255/224)
  * Those B,G,R bytes then take the BGR path exactly (resize map, /255, BGR->RGB): a YUV frame gives, bit for bit, what its converted BGR frame
  * gives.  Boxes stay normalised by the request's w, h.  (A letterbox engine converts each of its four taps this way, then interpolates.)
+ * Packed 4:2:2 frames (YUY2 / UYVY, 8-bit, limited range) need an even w >= 2; h >= 1 has no evenness rule (chroma is not subsampled
+ * vertically).  One plane; row sy holds w/2 macropixels of 4 bytes.  The fetch for the source pixel (sx, sy):
+ *   m = plane0 + sy*pitch + (sx>>1)*4        (tight frame: pitch = 2*w)
+ *   YUY2:  Y = m[(sx&1)*2]      U = m[1]  V = m[3]
+ *   UYVY:  Y = m[1 + (sx&1)*2]  U = m[0]  V = m[2]
+ * then the conversion above with the same constants.  Chroma is the pixel's own macropixel's: no interpolation between macropixels (the decision
+ * 4:2:0 made).  The rule is the same: a 4:2:2 frame gives, bit for bit, what the BGR frame made of its converted pixels gives through the same
+ * entry point -- same engine, same batch size and composition, stretch or letterbox (four taps converted, then interpolated).
  * Packed RGB / BGRA / RGBA frames follow THE SAME RULE: a frame of one of these formats gives, bit for bit, what the BGR frame made of its
  * B, G, R bytes gives through the same entry point -- same engine, same batch size and composition, stretch or letterbox.  The front kernel
  * fetches a pixel as the BGR fetch's word (B | G<<8 | R<<16) and everything behind the fetch is the BGR path.  Consequences: the fourth byte X
@@ -136,6 +146,10 @@ extern "C" {
 #define ZLY_PIX_I420_BT601   2
 #define ZLY_PIX_NV12_BT709   3
 #define ZLY_PIX_I420_BT709   4
+#define ZLY_PIX_YUY2_BT601   10
+#define ZLY_PIX_UYVY_BT601   11
+#define ZLY_PIX_YUY2_BT709   12
+#define ZLY_PIX_UYVY_BT709   13
 #define ZLY_PIX_RGB          16
 #define ZLY_PIX_BGRA         17
 #define ZLY_PIX_RGBA         18
@@ -143,13 +157,13 @@ extern "C" {
 /* A frame view: where a request's samples lie inside a larger buffer -- a decoder or capture surface with a row pitch, a region of interest of
  * one, a tile.  Plane offsets and line sizes as usual, with offsets from the buffer's base instead of pointers, so that one view serves host and
  * device memory alike.
- *   Planes.  The packed formats (BGR, RGB, BGRA, RGBA) use plane 0 only; NV12 0 = Y, 1 = interleaved UV; I420 0 = Y, 1 = U, 2 = V.  Entries of
+ *   Planes.  The packed formats (BGR, RGB, BGRA, RGBA) and packed 4:2:2 (YUY2, UYVY) use plane 0 only; NV12 0 = Y, 1 = interleaved UV; I420 0 = Y, 1 = U, 2 = V.  Entries of
  *   planes a format does not have are ignored.
  *   Rows of plane p, with cw = w/2, ch = h/2:    packed: h rows of bpp*w bytes (bpp = 3 for BGR / RGB, 4 for BGRA / RGBA);  Y: h rows of w;
- *   NV12 UV: ch rows of 2cw;  I420 U, V: ch rows of cw.
+ *   NV12 UV: ch rows of 2cw;  I420 U, V: ch rows of cw;  YUY2 / UYVY: h rows of 2*w bytes.
  *   The extent of a plane is (rows-1)*pitch + row_bytes.
- *   A view is valid when fmt is known; w, h >= 1 (YUV: even and >= 2; the packed formats have no evenness rule); every used pitch[p] >= its row bytes; every used plane's extent is < 2^31.
- *   There is no alignment requirement, no negative pitch and no overlap check.
+ *   A view is valid when fmt is known; w, h >= 1 (YUV 4:2:0: even and >= 2; packed 4:2:2: w even and >= 2, any h; the packed RGB formats have no evenness rule); every used pitch[p] >= its row bytes; every used plane's extent is < 2^31.
+ *   There is no alignment requirement (a 4:2:2 macropixel's four bytes may start at any address), no negative pitch and no overlap check.
  * THE RULE: a view gives, bit for bit, what the tight frame made of its samples gives through the _fmt entry point of the same name -- same
  * engine, same batch size and composition, stretch or letterbox.  w, h of the view are the REQUEST's size for the resize map, the letterbox geometry
  * and the box normalisation: boxes come back as fractions of the region (INTEGRATION.md section 3 has the one-line map to surface coordinates).
@@ -235,8 +249,8 @@ int32_t zly_destroy(zly_engine* e);
 const char* zly_last_error(void);          /* thread-local message of the last failing call */
 const char* zly_version(void);
 
-/* Bytes of one frame of format fmt (ZLY_PIX_*) and size w x h: w*h*3 for BGR / RGB, w*h*4 for BGRA / RGBA, w*h*3/2 for YUV 4:2:0; 0 for an unknown format or invalid
- * dimensions (w or h < 1; for YUV: odd, or < 2).  Host only: needs no engine and no GPU. */
+/* Bytes of one frame of format fmt (ZLY_PIX_*) and size w x h: w*h*3 for BGR / RGB, w*h*4 for BGRA / RGBA, w*h*3/2 for YUV 4:2:0, w*h*2 for packed 4:2:2; 0 for an unknown format or invalid
+ * dimensions (w or h < 1; for YUV 4:2:0: odd, or < 2; for packed 4:2:2: w odd or < 2).  Host only: needs no engine and no GPU. */
 size_t  zly_frame_bytes(int32_t fmt, int32_t w, int32_t h);
 
 /* Frame views, host only (no engine, no GPU).
@@ -244,8 +258,8 @@ size_t  zly_frame_bytes(int32_t fmt, int32_t w, int32_t h);
  * zly_view_tight: the view of a tight frame as defined above (its zly_view_bytes equals zly_frame_bytes); ZLY_ERR_INVALID_ARGUMENT for an unknown
  *   format, invalid dimensions or a null output.
  * zly_view_crop: the view of the sub-rectangle (x0, y0, w, h) of a view.  Pitches stay; the offset advances by y0*pitch0 + x0*bpp in plane 0
- *   (bpp = 3 for BGR / RGB, 4 for BGRA / RGBA, 1 for Y), by (y0/2)*pitch + (x0/2)*2 in the NV12 UV plane and by (y0/2)*pitch + x0/2 in the I420 chroma planes.
- *   ZLY_ERR_INVALID_ARGUMENT when the surface is invalid, the rectangle is not inside it, or -- YUV -- any of x0, y0, w, h is odd.  Crops compose
+ *   (bpp = 3 for BGR / RGB, 4 for BGRA / RGBA, 2 for YUY2 / UYVY, 1 for Y), by (y0/2)*pitch + (x0/2)*2 in the NV12 UV plane and by (y0/2)*pitch + x0/2 in the I420 chroma planes.
+ *   ZLY_ERR_INVALID_ARGUMENT when the surface is invalid, the rectangle is not inside it, -- YUV 4:2:0 -- any of x0, y0, w, h is odd, or -- packed 4:2:2 -- x0 or w is odd (y0 and h may be odd).  Crops compose
  *   (out may be the surface itself). */
 size_t  zly_view_bytes(const zly_frame_view* v);
 int32_t zly_view_tight(int32_t fmt, int32_t w, int32_t h, zly_frame_view* out);
@@ -522,7 +536,7 @@ int32_t zly_read_merged(zly_engine* e, int32_t n_groups, void* host_slabs);
 /* The tiles of a W x H surface, host only (no engine, no GPU).  Per axis, with extent E, tile size T and overlap V: step = T - V (> 0); if
  * T >= E there is one tile and it spans the extent; otherwise count = ceil((E - T) / step) + 1 and origin_i = min(i*step, E - T), so that the
  * last tile is shifted back and every tile is full-sized.  even != 0 (YUV 4:2:0 surfaces): origins are rounded down to even; odd tile sizes or
- * extents are refused.  Tiles come in row-major order with group = 0 and W, H filled in; min(count, cap) of them are written and *n_out is the
+ * extents are refused.  Its tiles are valid for packed 4:2:2 surfaces too: it rounds both axes where they need only x, which is stricter than needed.  Tiles come in row-major order with group = 0 and W, H filled in; min(count, cap) of them are written and *n_out is the
  * count (cap = 0, out = NULL asks for the count alone).  ZLY_ERR_INVALID_ARGUMENT: W, H outside 1..2^24-1, a tile size < 1, an overlap < 0 or
  * >= the tile size, the even rule, a null n_out, cap < 0 or a null out with cap > 0. */
 int32_t zly_tile_grid(int32_t W, int32_t H, int32_t tile_w, int32_t tile_h, int32_t overlap_x, int32_t overlap_y, int32_t even, zly_tile* out,

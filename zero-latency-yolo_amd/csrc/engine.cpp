@@ -1498,11 +1498,12 @@ static uint64_t now_ms()
 
 static void ingest_destroy(zly_engine* e);
 
-// the known formats are a set, not a range (include/zly.h): 5..15 lie between the YUV layouts and the packed RGB family and are unknown
-static bool fmt_yuv(int32_t fmt) { return fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709; }
-static bool fmt_known(int32_t fmt) { return fmt == ZLY_PIX_BGR || fmt_yuv(fmt) || fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA; }
-// bytes per pixel of a packed format (BGR, RGB: 3; BGRA, RGBA: 4)
-static uint32_t fmt_bpp(int32_t fmt) { return fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : 3u; }
+// the known formats are a set, not a range (include/zly.h): 5..9, 14 and 15 lie between the YUV layouts and the packed RGB family and are unknown
+static bool fmt_yuv(int32_t fmt) { return fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709; }      // YUV 4:2:0: two or three planes, even width and height
+static bool fmt_yuv422(int32_t fmt) { return fmt >= ZLY_PIX_YUY2_BT601 && fmt <= ZLY_PIX_UYVY_BT709; }   // packed YUV 4:2:2: one plane of 4-byte macropixels, even width
+static bool fmt_known(int32_t fmt) { return fmt == ZLY_PIX_BGR || fmt_yuv(fmt) || fmt_yuv422(fmt) || fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA; }
+// bytes per pixel of a one-plane format (BGR, RGB: 3; BGRA, RGBA: 4; packed 4:2:2: 2, in macropixels of two)
+static uint32_t fmt_bpp(int32_t fmt) { return fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : fmt_yuv422(fmt) ? 2u : 3u; }
 
 // the request checks of every entry point that takes host frames (onnx_engine.cpp:659-665): an unknown format is an argument error; a byte count
 // that is not zly_frame_bytes(fmt, w, h) -- odd or too small YUV sizes included -- is ZLY_ERR_INVALID_INPUT
@@ -1513,7 +1514,8 @@ static int check_frame(int32_t fmt, const uint8_t* p, size_t nbytes, int32_t w, 
     if (!p || want == 0 || nbytes != want) {
         const size_t shown = want ? want : (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * (fmt_yuv(fmt) ? 3u : 2u * fmt_bpp(fmt)) / 2u;
         return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: expected " + std::to_string(shown) + ", got " + std::to_string(nbytes) +
-                                           (fmt_yuv(fmt) && (w < 2 || h < 2 || (w | h) & 1) ? " (YUV 4:2:0 needs even width and height >= 2)" : ""));
+                                           (fmt_yuv(fmt) && (w < 2 || h < 2 || (w | h) & 1) ? " (YUV 4:2:0 needs even width and height >= 2)" :
+                                            fmt_yuv422(fmt) && (w < 2 || (w & 1)) ? " (packed YUV 4:2:2 needs even width >= 2)" : ""));
     }
     return ZLY_OK;
 }
@@ -1532,6 +1534,7 @@ static int check_frame_mode(const zly_engine* e, int32_t w, int32_t h)
 static int view_plane_shape(int32_t fmt, int32_t w, int32_t h, int64_t rows[3], int64_t row_bytes[3])
 {
     if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
+    if (fmt_yuv422(fmt) && (w < 2 || (w & 1))) return 0;          // whole macropixels; any height
     if (!fmt_yuv(fmt)) { rows[0] = h; row_bytes[0] = (int64_t)fmt_bpp(fmt) * (int64_t)w; return 1; }
     if (w < 2 || h < 2 || ((w | h) & 1)) return 0;
     rows[0] = h; row_bytes[0] = w;
@@ -1567,7 +1570,7 @@ static int check_view(const zly_engine* e, const void* base, size_t buf_bytes, c
     if (!fmt_known(v->fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(v->fmt));
     size_t need = 0;
     if (!view_valid(v, &need)) return fail(ZLY_ERR_INVALID_INPUT, "invalid frame view (size " + std::to_string(v->w) + " x " + std::to_string(v->h) +
-                                                                  ": YUV 4:2:0 needs even width and height >= 2, every pitch at least its row's bytes, every plane below 2 GiB)");
+                                                                  ": YUV 4:2:0 needs even width and height >= 2, packed 4:2:2 even width >= 2, every pitch at least its row's bytes, every plane below 2 GiB)");
     if (!base || need > buf_bytes) return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: the view needs " + std::to_string(need) + " bytes, got " + std::to_string(buf_bytes));
     return check_frame_mode(e, v->w, v->h);
 }
@@ -2283,6 +2286,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
 size_t zly_frame_bytes(int32_t fmt, int32_t w, int32_t h)
 {
     if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
+    if (fmt_yuv422(fmt) && (w < 2 || (w & 1))) return 0;               // 4:2:2: whole macropixels of two pixels; any height
     if (!fmt_yuv(fmt)) return (size_t)w * (size_t)h * fmt_bpp(fmt);
     if (w < 2 || h < 2 || (w & 1) || (h & 1)) return 0;                // 4:2:0: one chroma sample per 2 x 2 block
     return (size_t)w * (size_t)h * 3u / 2u;
@@ -2321,6 +2325,7 @@ int32_t zly_view_crop(const zly_frame_view* surface, int32_t x0, int32_t y0, int
     zly_frame_view v = *surface;                         // (out may be the surface itself: crops compose)
     v.w = w; v.h = h;
     if (!fmt_yuv(v.fmt)) {
+        if (fmt_yuv422(v.fmt) && ((x0 | w) & 1)) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: a packed YUV 4:2:2 rectangle needs even x0 and w");
         v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0 * fmt_bpp(v.fmt);
     } else {
         if ((x0 | y0 | w | h) & 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: a YUV 4:2:0 rectangle needs even x0, y0, w, h");

@@ -22,10 +22,12 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // and optionally the reference's planar fp32 [3][th][tw] layout for the parity entry point.
 // YUV, LB, VIEW, PK: the input variants (front_variants.h has what each flag selects and which object its instantiations are compiled in).  Whatever
 // the fetch, the B, G, R bytes it yields take the same path.
+// The kernel's text is preprocess_body, behind two entries: preprocess_kernel<T, YUV, LB, VIEW, PK>, whose symbols and code are what they were before
+// the packed 4:2:2 level existed, and preprocess_y422_kernel<T, LB, VIEW> for that level (Y2: every format, YUY2 / UYVY included).
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
-__global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
-                                                         T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
+template <typename T, bool YUV, bool LB, bool VIEW, bool PK, bool Y2>
+__device__ __forceinline__ void preprocess_body(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
+                                                T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
 {
     const int f = blockIdx.y;
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -36,15 +38,21 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     const float scale_h = (float)d.h / (float)th;
     int sy = (int)((float)y * scale_h); if (sy > d.h - 1) sy = d.h - 1;
     int sx = (int)((float)x * scale_w); if (sx > d.w - 1) sx = d.w - 1;
-    const Planes<VIEW> pl = frame_planes<VIEW, PK>(src, src + (YUV ? desc_off(d.src_off) : d.src_off), desc, (int)gridDim.y, f, d, YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR);
+    const Planes<VIEW> pl = frame_planes<VIEW, PK, Y2>(src, src + (YUV ? desc_off(d.src_off) : d.src_off), desc, (int)gridDim.y, f, d, YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR);
     float b, g, r;
     if constexpr (LB) {
         const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
         const LbFrame lf = lb_frame(d.w, d.h, tw, th);
         LbTaps taps;
-        lb_issue<YUV, PK>(pl, fmt, lf, x, y, taps);
-        const unsigned int px = lb_blend<YUV, PK>(taps, fmt);
+        lb_issue<YUV, PK, Y2>(pl, fmt, lf, x, y, taps);
+        const unsigned int px = lb_blend<YUV, PK, Y2>(taps, fmt);
         b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)((px >> 16) & 0xffu) / 255.0f;
+    } else
+    if (Y2 && pix_is_y422(desc_fmt(d.src_off))) {
+        unsigned int m;
+        y422_issue(pl, sx, sy, m);
+        const unsigned int px = y422_bgr_word(m, y422_sel(desc_fmt(d.src_off), sx), desc_fmt(d.src_off));
+        b = (float)(px & 0xffu) / 255.0f; g = (float)((px >> 8) & 0xffu) / 255.0f; r = (float)(px >> 16) / 255.0f;
     } else
     if (YUV && pix_yuv_frame<PK>(desc_fmt(d.src_off))) {
         unsigned int yv, uv;
@@ -77,13 +85,32 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     }
 }
 
+template <typename T, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
+__global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
+                                                         T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
+{
+    preprocess_body<T, YUV, LB, VIEW, PK, false>(src, desc, out8, out_nchw, tw, th);
+}
+template <typename T, bool LB, bool VIEW>
+__global__ __launch_bounds__(256) void preprocess_y422_kernel(const uint8_t* __restrict__ src, const FrameDesc* __restrict__ desc,
+                                                              T* __restrict__ out8, float* __restrict__ out_nchw, int tw, int th)
+{
+    preprocess_body<T, true, LB, VIEW, true, true>(src, desc, out8, out_nchw, tw, th);
+}
+// a row's entry (front_variants.h), as the kernel's host address
+template <typename T, int LEVEL, bool LB, bool VIEW> static const void* preprocess_entry()
+{
+    if constexpr (LEVEL >= ZLY_FRONT_YUV422) return (const void*)preprocess_y422_kernel<T, LB, VIEW>;
+    else return (const void*)preprocess_kernel<T, ZLY_FRONT_FLAGS(LEVEL, LB, VIEW)>;
+}
+
 // The instantiations this unit owns (front_variants.h), as the kernel's host address: dtype bf16, or fp32 for every other
 template <int TU> static const void* preprocess_own(FrontVariant v, int dtype)
 {
 #define ZLY_ROW(level, lb, view, pre_tu, stem_tu) \
     if constexpr (TU == front_owner(pre_tu)) \
         if (v == FrontVariant(level, lb, view)) \
-            return dtype == ZLY_DTYPE_BF16 ? (const void*)preprocess_kernel<bf16_t, ZLY_FRONT_FLAGS(level, lb, view)> : (const void*)preprocess_kernel<float, ZLY_FRONT_FLAGS(level, lb, view)>;
+            return dtype == ZLY_DTYPE_BF16 ? preprocess_entry<bf16_t, level, lb, view>() : preprocess_entry<float, level, lb, view>();
     ZLY_FRONT_VARIANTS(ZLY_ROW)
 #undef ZLY_ROW
     return nullptr;

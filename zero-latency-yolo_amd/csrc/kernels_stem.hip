@@ -51,9 +51,12 @@ __device__ __forceinline__ FrameDesc load_desc(const FrameDesc* p)
 // ends with 8 consecutive channels = one 16-byte store); the pixel fragments are read once for both tiles.
 // YUV, LB, VIEW, PK: the input variant (front_variants.h).  A frame that is not model-sized BGR is fetched as YUV -> BGR bytes, as a packed pixel or as
 // the letterbox's padding / bilinear blend; the bytes then take the same path.
-template <int NT, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
+// NTL: NT, plus ZLY_FRONT_Y2_TAG in the instantiations of the packed 4:2:2 level (Y2; front_variants.h has why the flag rides on this parameter).
+template <int NTL, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
 {
+    constexpr int NT = NTL & (ZLY_FRONT_Y2_TAG - 1);
+    constexpr bool Y2 = (NTL & ZLY_FRONT_Y2_TAG) != 0;
     __shared__ __attribute__((aligned(16))) bf16x4 patch[STEM_PH * STEM_PW];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
     const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
     const uint8_t* src = a.src + (YUV ? desc_off(d.src_off) : d.src_off);
     const bool same = (d.w == a.tw) & (d.h == a.th) & !pix_not_bgr(fmt);
-    const Planes<VIEW> pl = frame_planes<VIEW, PK>(a.src, src, a.desc, (int)gridDim.y, f, d, fmt);
+    const Planes<VIEW> pl = frame_planes<VIEW, PK, Y2>(a.src, src, a.desc, (int)gridDim.y, f, d, fmt);
     const auto frame_bytes = pix_end<PK>(pl, fmt);          // bound of the wide loads: the end of plane 0
     LbFrame lf;
     if constexpr (LB) lf = lb_frame(d.w, d.h, a.tw, a.th);
@@ -95,9 +98,13 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemArgs a)
             if (LB && !same) {         // (a model-sized BGR frame: the letterbox map is the identity too)
                 if constexpr (LB) {
                     LbTaps taps;
-                    lb_issue<YUV, PK>(pl, fmt, lf, ix, iy, taps);
-                    px4 = lb_blend<YUV, PK>(taps, fmt);
+                    lb_issue<YUV, PK, Y2>(pl, fmt, lf, ix, iy, taps);
+                    px4 = lb_blend<YUV, PK, Y2>(taps, fmt);
                 }
+            } else if (Y2 && pix_is_y422(fmt)) {             // wave-uniform: one format per frame
+                unsigned int m;
+                y422_issue(pl, sx, sy, m);
+                px4 = y422_bgr_word(m, y422_sel(fmt, sx), fmt);
             } else if (YUV && pix_yuv_frame<PK>(fmt)) {      // wave-uniform: one format per frame
                 unsigned int yv, uv;
                 yuv_issue(pl, fmt, sx, sy, yv, uv);
@@ -183,7 +190,7 @@ template <int TU> static stem_fused_fn stem_fused_own(FrontVariant v, int nt)
 {
 #define ZLY_ROW(level, lb, view, pre_tu, stem_tu) \
     if constexpr (TU == front_owner(stem_tu)) \
-        if (v == FrontVariant(level, lb, view)) return nt == 2 ? stem_fused_kernel<2, ZLY_FRONT_FLAGS(level, lb, view)> : stem_fused_kernel<1, ZLY_FRONT_FLAGS(level, lb, view)>;
+        if (v == FrontVariant(level, lb, view)) return nt == 2 ? stem_fused_kernel<2 | ZLY_FRONT_Y2(level), ZLY_FRONT_FLAGS(level, lb, view)> : stem_fused_kernel<1 | ZLY_FRONT_Y2(level), ZLY_FRONT_FLAGS(level, lb, view)>;
     ZLY_FRONT_VARIANTS(ZLY_ROW)
 #undef ZLY_ROW
     return nullptr;
@@ -266,10 +273,14 @@ const int* stem1_tap_slot() { return STEM1_TAP_SLOT; }
 // letterbox engine (the letterbox map is the identity for them) or as a view (a model-sized window of a larger surface, the headline use: one 12-byte load
 // per four pixels at row address iy * pitch0 + ix * 3; a quad lies inside its row, hence inside the plane).  A YUV or packed RGB / BGRA / RGBA frame never
 // counts as `same`; the per-pixel general path fetches it through yuv_device.h (all byte loads of a thread first, then the conversions), a letterbox engine's
-// other frames take the letterbox general path.
-template <int NW, int VAR, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
+// other frames take the letterbox general path.  A packed 4:2:2 frame (Y2) takes the same general paths: until the conversions raw[] holds the pixel's byte
+// selector and rawc[] its macropixel.
+// VARL: VAR, plus ZLY_FRONT_Y2_TAG in the instantiations of the packed 4:2:2 level (Y2; front_variants.h has why the flag rides on this parameter).
+template <int NW, int VARL, bool YUV, bool LB = false, bool VIEW = false, bool PK = false>
 __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem_model1_kernel(const Stem1Args a)
 {
+    constexpr int VAR = VARL & (ZLY_FRONT_Y2_TAG - 1);
+    constexpr bool Y2 = (VARL & ZLY_FRONT_Y2_TAG) != 0;
     constexpr bool NEWP = VAR >= 1, PERS = VAR >= 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem1[];
     const int RH = 2 * a.TH + 1, RW = 2 * a.TW + 1;          // stem pixels the tile needs
@@ -412,7 +423,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
     const int fmt = YUV ? desc_fmt(d.src_off) : ZLY_PIX_BGR;
     const uint8_t* src = a.st.src + (YUV ? desc_off(d.src_off) : d.src_off);
     const bool same = (d.w == a.st.tw) & (d.h == a.st.th) & !pix_not_bgr(fmt);
-    const Planes<VIEW> pl = frame_planes<VIEW, PK>(a.st.src, src, a.st.desc, a.n, f, d, fmt);
+    const Planes<VIEW> pl = frame_planes<VIEW, PK, Y2>(a.st.src, src, a.st.desc, a.n, f, d, fmt);
     const auto frame_bytes = pix_end<PK>(pl, fmt);          // bound of the wide loads: the end of plane 0
     STEMSTAMP(0);
     if (same && NEWP) {
@@ -528,7 +539,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                 if (u < PH * PWV) {
                     const int py = div_small_s(u, invPW), px = u - py * PWV;
                     const int iy = iy0 + py, ix = ix0 + px;
-                    if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) lb_issue<YUV, PK>(pl, fmt, lf, ix, iy, tp[j]);
+                    if ((unsigned)iy < (unsigned)a.st.th && (unsigned)ix < (unsigned)a.st.tw) lb_issue<YUV, PK, Y2>(pl, fmt, lf, ix, iy, tp[j]);
                 }
             }
     #pragma unroll
@@ -538,7 +549,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                     bf16x4 v = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
                     if (tp[j].m != LB_OUT) {
                         const float kk = 1.0f / 255.0f;
-                        const unsigned int px = lb_blend<YUV, PK>(tp[j], fmt);
+                        const unsigned int px = lb_blend<YUV, PK, Y2>(tp[j], fmt);
                         v[0] = (bf16_t)((float)((px >> 16) & 0xffu) * kk); v[1] = (bf16_t)((float)((px >> 8) & 0xffu) * kk); v[2] = (bf16_t)((float)(px & 0xffu) * kk);
                     }
                     const int py = div_small_s(u, invPW);
@@ -554,6 +565,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
         unsigned int raw[STEM1_MAXIT];
         unsigned int rawc[YUV ? STEM1_MAXIT : 1];                   // YUV frames: raw = the Y byte, rawc = U | V << 8
         const bool yuvf = YUV && pix_yuv_frame<PK>(fmt);            // workgroup-uniform
+        const bool y2f = Y2 && pix_is_y422(fmt);                    // workgroup-uniform: raw = the pixel's selector (bit 31 clear), rawc = its macropixel
         const unsigned int rb_sel = PK && pix_is_rgb_order(fmt) ? ZLY_PERM_SWAP_RB : ZLY_PERM_KEEP_BGR;
         const int tidg = PERS ? pin_here(tid) : tid;
     #pragma unroll
@@ -569,6 +581,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                         sy = (int)((float)iy * scale_h); if (sy > d.h - 1) sy = d.h - 1;
                         sx = (int)((float)ix * scale_w); if (sx > d.w - 1) sx = d.w - 1;
                     }
+                    if (y2f) {
+                        if constexpr (Y2) { raw[k] = y422_sel(fmt, sx); y422_issue(pl, sx, sy, rawc[k]); }
+                    } else
                     if (yuvf) {
                         yuv_issue(pl, fmt, sx, sy, raw[k], rawc[k]);
                     } else {
@@ -594,6 +609,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
                     const float kk = 1.0f / 255.0f;                  // bf16(u8 * (1/255.f)) == bf16(u8 / 255.f) for all 256 values (tests/test_model_spec.py)
                     unsigned int px = raw[k];
                     if constexpr (YUV) { if (yuvf) px = yuv_bgr_word(raw[k], rawc[k], fmt); }
+                    if constexpr (Y2) { if (y2f) px = y422_bgr_word(rawc[k], raw[k], fmt); }
                     v[0] = (bf16_t)((float)((px >> 16) & 0xffu) * kk); v[1] = (bf16_t)((float)((px >> 8) & 0xffu) * kk); v[2] = (bf16_t)((float)(px & 0xffu) * kk);
                 }
                 const int py = div_small_s(u, invPW);
@@ -761,19 +777,19 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 8 : NW == 12 ? 6 : 4) void stem
 }
 
 static constexpr int STEM1_NW = 8;
-// waves per workgroup x kernel variant of one input variant
-template <bool YUV, bool LB, bool VIEW, bool PK> static stem1_fn stem1_nw_var(int nw, int var)
+// waves per workgroup x kernel variant of one input variant (Y2T: ZLY_FRONT_Y2 of its level)
+template <int Y2T, bool YUV, bool LB, bool VIEW, bool PK> static stem1_fn stem1_nw_var(int nw, int var)
 {
-    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 2, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 2, YUV, LB, VIEW, PK>;
-    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 1, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 1, YUV, LB, VIEW, PK>;
-    return nw == 12 ? stem_model1_kernel<12, 0, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 0, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 0, YUV, LB, VIEW, PK>;
+    if (var >= 2) return nw == 12 ? stem_model1_kernel<12, 2 | Y2T, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 2 | Y2T, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 2 | Y2T, YUV, LB, VIEW, PK>;
+    if (var == 1) return nw == 12 ? stem_model1_kernel<12, 1 | Y2T, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 1 | Y2T, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 1 | Y2T, YUV, LB, VIEW, PK>;
+    return nw == 12 ? stem_model1_kernel<12, 0 | Y2T, YUV, LB, VIEW, PK> : nw == 16 ? stem_model1_kernel<16, 0 | Y2T, YUV, LB, VIEW, PK> : stem_model1_kernel<STEM1_NW, 0 | Y2T, YUV, LB, VIEW, PK>;
 }
 // The instantiations this unit owns (front_variants.h)
 template <int TU> static stem1_fn stem1_own(FrontVariant v, int nw, int var)
 {
 #define ZLY_ROW(level, lb, view, pre_tu, stem_tu) \
     if constexpr (TU == front_owner(stem_tu)) \
-        if (v == FrontVariant(level, lb, view)) return stem1_nw_var<ZLY_FRONT_FLAGS(level, lb, view)>(nw, var);
+        if (v == FrontVariant(level, lb, view)) return stem1_nw_var<ZLY_FRONT_Y2(level), ZLY_FRONT_FLAGS(level, lb, view)>(nw, var);
     ZLY_FRONT_VARIANTS(ZLY_ROW)
 #undef ZLY_ROW
     return nullptr;

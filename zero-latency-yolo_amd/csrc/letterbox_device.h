@@ -62,10 +62,13 @@ __device__ __forceinline__ void lb_coord(int d, int step, int S, int& i0, int& a
 //   BGR, RGB: t[0], t[1] = 8 bytes from (xl, y0): B G R B' | G' R' . .   t[2], t[3] = the same from (xl, y1)
 //   BGRA, RGBA: t[0], t[1] = 8 bytes from (xl, y0): B G R X | B' G' R' X' -- the two dwords ARE the two taps --   t[2], t[3] = the same from (xl, y1)
 //   YUV: t[0..3] = the four taps p00, p01, p10, p11 as Y | U << 8 | V << 16
+//   packed 4:2:2: t[0..3] = the MACROPIXELS of the four taps (xl and xl + 1 share one when xl is even and straddle two when it is odd: a dword load per
+//   tap either way, each inside its row), and bit LB_Y422_ODD of m = xl's parity, from which lb_blend makes the taps' byte selectors
 // The second column is always xl + 1: where the reference's x1 = min(x0 + 1, w - 1) is x0 itself (the last column), its weight ax is 0, so the fetch
 // steps one column back (xl = w - 2) and gives the SECOND tap the whole weight (ax = 256) -- the same products.  One (unaligned) 8-byte load per row
 // then covers both taps of a packed frame.  The R-first formats (RGB, RGBA) are loaded like their B-first twins; lb_blend exchanges the lanes.
 #define LB_PAD (-1)
+#define LB_Y422_ODD 30
 struct LbTaps { unsigned int t[4]; int m; };
 
 __device__ __forceinline__ bool lb_is_pad(const LbFrame& f, int ix, int iy)
@@ -73,7 +76,7 @@ __device__ __forceinline__ bool lb_is_pad(const LbFrame& f, int ix, int iy)
     return (unsigned)(ix - f.pad_x) >= (unsigned)f.nw || (unsigned)(iy - f.pad_y) >= (unsigned)f.nh;
 }
 
-template <bool YUV, bool PK = false, class PL>
+template <bool YUV, bool PK = false, bool Y2 = false, class PL>
 __device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f, int ix, int iy, LbTaps& o)
 {
     o.m = LB_PAD;
@@ -86,6 +89,14 @@ __device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f
     const int xl = min(x0, max(f.w - 2, 0));
     if (x0 > xl) ax = 256;
     o.m = ax | (ay << 16);
+    if constexpr (Y2) {
+        if (pix_is_y422(fmt)) {                         // uniform per frame; 4:2:2 frames are at least 2 wide: xl + 1 is a column
+            o.m |= (xl & 1) << LB_Y422_ODD;
+            y422_issue(pl, xl, y0, o.t[0]); y422_issue(pl, xl + 1, y0, o.t[1]);
+            y422_issue(pl, xl, y1, o.t[2]); y422_issue(pl, xl + 1, y1, o.t[3]);
+            return;
+        }
+    }
     if (YUV && pix_yuv_frame<PK>(fmt)) {                // uniform per frame; YUV frames are at least 2 x 2
         unsigned int y, uv;
         yuv_issue(pl, fmt, xl, y0, y, uv);         o.t[0] = y | (uv << 8);
@@ -128,13 +139,19 @@ __device__ __forceinline__ void lb_issue(const PL& pl, int fmt, const LbFrame& f
 }
 
 // taps -> B | G << 8 | R << 16 (include/zly.h "Sampling": the four products per channel, + 32768, >> 16)
-template <bool YUV, bool PK = false>
+template <bool YUV, bool PK = false, bool Y2 = false>
 __device__ __forceinline__ unsigned int lb_blend(const LbTaps& o, int fmt)
 {
     if (o.m == LB_PAD) return ZLY_LB_PAD_WORD;
-    const int ax = o.m & 0xffff, ay = o.m >> 16;
+    const int ax = o.m & 0xffff, ay = Y2 ? (o.m >> 16) & 0x1ff : o.m >> 16;
     const int w00 = __mul24(256 - ax, 256 - ay), w01 = __mul24(ax, 256 - ay), w10 = __mul24(256 - ax, ay), w11 = __mul24(ax, ay);
     unsigned int p00, p01, p10, p11;                     // B | G << 8 | R << 16 (| junk << 24)
+    if (Y2 && pix_is_y422(fmt)) {
+        const int odd = (o.m >> LB_Y422_ODD) & 1;
+        const unsigned int s0 = y422_sel(fmt, odd), s1 = y422_sel(fmt, odd ^ 1);        // columns xl and xl + 1
+        p00 = y422_bgr_word(o.t[0], s0, fmt); p01 = y422_bgr_word(o.t[1], s1, fmt);
+        p10 = y422_bgr_word(o.t[2], s0, fmt); p11 = y422_bgr_word(o.t[3], s1, fmt);
+    } else
     if (YUV && pix_yuv_frame<PK>(fmt)) {
         p00 = yuv_bgr_word(o.t[0] & 0xffu, o.t[0] >> 8, fmt); p01 = yuv_bgr_word(o.t[1] & 0xffu, o.t[1] >> 8, fmt);
         p10 = yuv_bgr_word(o.t[2] & 0xffu, o.t[2] >> 8, fmt); p11 = yuv_bgr_word(o.t[3] & 0xffu, o.t[3] >> 8, fmt);

@@ -35,6 +35,7 @@ template <> struct Planes<false> {
     __device__ __forceinline__ const uint8_t* nv12(int x, int y) const { return f + (size_t)w * h + 2 * ci(x, y); }                 // interleaved U, V
     __device__ __forceinline__ const uint8_t* cu(int x, int y) const { return f + (size_t)w * h + ci(x, y); }
     __device__ __forceinline__ const uint8_t* cv(int x, int y) const { return f + (size_t)w * h + ((size_t)(w >> 1) * (size_t)(h >> 1) + ci(x, y)); }
+    __device__ __forceinline__ const uint8_t* y422(int x, int y) const { return f + ((size_t)y * w + (size_t)(x & ~1)) * 2; }        // the 4-byte macropixel of a packed 4:2:2 pixel (w even)
 };
 
 template <> struct Planes<true> {
@@ -48,11 +49,13 @@ template <> struct Planes<true> {
     __device__ __forceinline__ const uint8_t* nv12(int x, int y) const { return p1 + ((unsigned)(y >> 1) * pitch1 + ((unsigned)x & ~1u)); }
     __device__ __forceinline__ const uint8_t* cu(int x, int y) const { return p1 + ((unsigned)(y >> 1) * pitch1 + (unsigned)(x >> 1)); }
     __device__ __forceinline__ const uint8_t* cv(int x, int y) const { return p2 + ((unsigned)(y >> 1) * pitch2 + (unsigned)(x >> 1)); }
+    __device__ __forceinline__ const uint8_t* y422(int x, int y) const { return f + ((unsigned)y * pitch0 + (((unsigned)x & ~1u) << 1)); }
 };
 
 // The layout of frame fi of a call of n frames.  src: the frame's first sample in the source buffer (base + its descriptor's offset).
 // fmt: the frame's format.  PK: the instantiation serves the packed RGB / BGRA / RGBA family (otherwise "not BGR" means YUV: one byte per pixel in plane 0).
-template <bool VIEW, bool PK = false>
+// Y2: it serves packed 4:2:2 as well (two bytes per pixel).
+template <bool VIEW, bool PK = false, bool Y2 = false>
 __device__ __forceinline__ Planes<VIEW> frame_planes(const uint8_t* base, const uint8_t* src, const FrameDesc* desc, int n, int fi, const FrameDesc& d, int fmt)
 {
     Planes<VIEW> pl;
@@ -64,6 +67,10 @@ __device__ __forceinline__ Planes<VIEW> frame_planes(const uint8_t* base, const 
         pl.p1 = base + ((unsigned long long)a[0] | ((unsigned long long)a[1] << 32));
         pl.p2 = base + ((unsigned long long)a[2] | ((unsigned long long)a[3] << 32));
         pl.pitch0 = b[0]; pl.pitch1 = b[1]; pl.pitch2 = b[2];
+        if constexpr (Y2)
+            pl.end0 = (unsigned)(d.h - 1) * pl.pitch0 + (unsigned)d.w * (fmt >= ZLY_PIX_YUY2_BT601 && fmt <= ZLY_PIX_UYVY_BT709 ? 2u :
+                                                                         fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709 ? 1u : fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : 3u);
+        else
         pl.end0 = (unsigned)(d.h - 1) * pl.pitch0 + (unsigned)d.w * (!PK ? (fmt == ZLY_PIX_BGR ? 3u : 1u) :
                                                                              fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709 ? 1u : fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : 3u);
     } else {

@@ -1,4 +1,5 @@
-// yuv_device.h -- the pixel fetch of YUV 4:2:0 frames (ZLY_PIX_NV12_* / ZLY_PIX_I420_*, include/zly.h) for the front kernels.
+// yuv_device.h -- the pixel fetch of YUV 4:2:0 frames (ZLY_PIX_NV12_* / ZLY_PIX_I420_*, include/zly.h) and of packed 4:2:2 frames (ZLY_PIX_YUY2_* /
+// ZLY_PIX_UYVY_*) for the front kernels.
 //
 // A YUV frame's source pixel (sx, sy) -- picked by the unchanged nearest-neighbour map -- becomes the same packed B | G<<8 | R<<16 word the
 // BGR fetch yields, so everything behind the fetch (/255, BGR->RGB, bf16 rounding) is the BGR path's: a YUV frame gives exactly what its
@@ -51,6 +52,27 @@ __device__ __forceinline__ void yuv_issue(const PL& pl, int fmt, int sx, int sy,
     }
 }
 
+// ---- packed 4:2:2 (YUY2: Y0 U Y1 V, UYVY: U Y0 V Y1; only the ZLY_FRONT_YUV422 instantiations, kernels_y422.hip / kernels_y422_view.hip, meet one) ----
+// The issue half is ONE (unaligned) 4-byte load of the pixel's macropixel, which lies wholly inside its row: no end-of-plane guard.  The convert half
+// picks Y, U, V out of it with one v_perm_b32 -- selector bytes, low to high: the pixel's Y, U, V, constant 0; wave-uniform per frame but for the
+// Y index, which follows the column's parity -- and hands the same (y, u | v << 8) pair to yuv_bgr_word.
+__device__ __forceinline__ bool pix_is_y422(int fmt) { return fmt >= ZLY_PIX_YUY2_BT601 && fmt <= ZLY_PIX_UYVY_BT709; }
+__device__ __forceinline__ bool pix_is_uyvy(int fmt) { return fmt == ZLY_PIX_UYVY_BT601 || fmt == ZLY_PIX_UYVY_BT709; }
+#define ZLY_PERM_YUY2 0x0c030100u        // Y0 U V 0 of the word Y0 | U<<8 | Y1<<16 | V<<24; + 2: Y1 in place of Y0
+#define ZLY_PERM_UYVY 0x0c020001u        // Y0 U V 0 of the word U | Y0<<8 | V<<16 | Y1<<24; + 2: Y1 in place of Y0
+// the selector of column sx of a frame of format fmt
+__device__ __forceinline__ unsigned int y422_sel(int fmt, int sx) { return (pix_is_uyvy(fmt) ? ZLY_PERM_UYVY : ZLY_PERM_YUY2) + (((unsigned int)sx & 1u) << 1); }
+// the load of one pixel: m = its macropixel
+template <class PL>
+__device__ __forceinline__ void y422_issue(const PL& pl, int sx, int sy, unsigned int& m)
+{
+    __builtin_memcpy(&m, pl.y422(sx, sy), 4);          // (amdhsa: unaligned global access is enabled)
+}
+// macropixel, selector -> Y | U << 8 | V << 16
+__device__ __forceinline__ unsigned int y422_yuv_word(unsigned int m, unsigned int sel) { return __builtin_amdgcn_perm(0u, m, sel); }
+// the 4:2:0 format whose matrix a 4:2:2 format shares: the 601 / 709 choice of yuv_bgr_word
+__device__ __forceinline__ int y422_matrix(int fmt) { return fmt >= ZLY_PIX_YUY2_BT709 ? ZLY_PIX_NV12_BT709 : ZLY_PIX_NV12_BT601; }
+
 // Y, U | V << 8 -> B | G << 8 | R << 16
 __device__ __forceinline__ unsigned int yuv_bgr_word(unsigned int y, unsigned int uv, int fmt)
 {
@@ -63,6 +85,13 @@ __device__ __forceinline__ unsigned int yuv_bgr_word(unsigned int y, unsigned in
     const int g = min(max((yy + __mul24(CVG, v) + __mul24(CUG, u) + (1 << 19)) >> 20, 0), 255);
     const int b = min(max((yy + __mul24(CUB, u) + (1 << 19)) >> 20, 0), 255);
     return (unsigned int)b | ((unsigned int)g << 8) | ((unsigned int)r << 16);
+}
+
+// macropixel, selector -> B | G << 8 | R << 16
+__device__ __forceinline__ unsigned int y422_bgr_word(unsigned int m, unsigned int sel, int fmt)
+{
+    const unsigned int yuv = y422_yuv_word(m, sel);
+    return yuv_bgr_word(yuv & 0xffu, yuv >> 8, y422_matrix(fmt));
 }
 
 }  // namespace zly

@@ -53,7 +53,7 @@ ErrorCode toErrorCode(int32_t rc)
         default: return ErrorCode::INFERENCE_ERROR;
     }
 }
-// ZLY_INPUT_FORMAT: bgr (default), nv12, i420 (BT.601), nv12_709, i420_709, rgb, bgra, rgba -> ZLY_PIX_*, -1 = unknown
+// ZLY_INPUT_FORMAT: bgr (default), nv12, i420 (BT.601), nv12_709, i420_709, rgb, bgra, rgba, yuy2, uyvy (BT.601), yuy2_709, uyvy_709 -> ZLY_PIX_*, -1 = unknown
 int32_t parseInputFormat(const char* v)
 {
     if (!v || !*v || std::strcmp(v, "bgr") == 0) return ZLY_PIX_BGR;
@@ -64,10 +64,16 @@ int32_t parseInputFormat(const char* v)
     if (std::strcmp(v, "rgb") == 0) return ZLY_PIX_RGB;
     if (std::strcmp(v, "bgra") == 0) return ZLY_PIX_BGRA;
     if (std::strcmp(v, "rgba") == 0) return ZLY_PIX_RGBA;
+    if (std::strcmp(v, "yuy2") == 0) return ZLY_PIX_YUY2_BT601;
+    if (std::strcmp(v, "uyvy") == 0) return ZLY_PIX_UYVY_BT601;
+    if (std::strcmp(v, "yuy2_709") == 0) return ZLY_PIX_YUY2_BT709;
+    if (std::strcmp(v, "uyvy_709") == 0) return ZLY_PIX_UYVY_BT709;
     return -1;
 }
 // YUV 4:2:0 formats: even sizes and even crop origins; the packed formats (BGR, RGB, BGRA, RGBA) have no such rule
 bool isYuvFormat(int32_t fmt) { return fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709; }
+// packed YUV 4:2:2 formats: the rule holds along x only (whole macropixels); any height, any y0
+bool isYuv422Format(int32_t fmt) { return fmt >= ZLY_PIX_YUY2_BT601 && fmt <= ZLY_PIX_UYVY_BT709; }
 const char* inputFormatName(int32_t fmt)
 {
     switch (fmt) {
@@ -78,6 +84,10 @@ const char* inputFormatName(int32_t fmt)
     case ZLY_PIX_RGB: return "rgb";
     case ZLY_PIX_BGRA: return "bgra";
     case ZLY_PIX_RGBA: return "rgba";
+    case ZLY_PIX_YUY2_BT601: return "yuy2";
+    case ZLY_PIX_UYVY_BT601: return "uyvy";
+    case ZLY_PIX_YUY2_BT709: return "yuy2_709";
+    case ZLY_PIX_UYVY_BT709: return "uyvy_709";
     default: return "bgr";
     }
 }
@@ -146,21 +156,24 @@ Result<void> HipInferenceEngine::initialize()
 {
     if (running_) return Result<void>::ok();
     simulate_ = envInt("ZLY_SIMULATE", 0) != 0;               // explicit opt-in only: a missing or bad model file is an ERROR below, never a silent fake
-    // ZLY_INPUT_FORMAT: requests carry YUV 4:2:0 frames (decoder output) or packed RGB / BGRA / RGBA frames (capture surfaces) instead of packed BGR; request.data must then hold
+    // ZLY_INPUT_FORMAT: requests carry YUV 4:2:0 frames (decoder output), packed RGB / BGRA / RGBA frames (capture surfaces) or packed YUV 4:2:2 frames (capture
+    // cards, UVC devices) instead of packed BGR; request.data must then hold
     // zly_frame_bytes(format, width, height) bytes, a request of any other size fails alone with INVALID_INPUT
     input_format_ = parseInputFormat(std::getenv("ZLY_INPUT_FORMAT"));
     if (input_format_ < 0)
-        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_INPUT_FORMAT must be bgr, nv12, i420, nv12_709, i420_709, rgb, bgra or rgba, got '") +
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_INPUT_FORMAT must be bgr, nv12, i420, nv12_709, i420_709, rgb, bgra, rgba, yuy2, uyvy, yuy2_709 or uyvy_709, got '") +
                                                                  std::getenv("ZLY_INPUT_FORMAT") + "'");
     if (input_format_ != ZLY_PIX_BGR && (!zly_submit_fmt || !zly_submit_try_fmt))
         return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_INPUT_FORMAT: the engine library has no zly_submit_fmt");
     // ZLY_CROP=WxH: every request is detected in the centred W x H window of its frame (x0 = (width - W) / 2, y0 = (height - H) / 2, both rounded down
-    // to even for a YUV ZLY_INPUT_FORMAT) -- a model-sized window around the crosshair is the engine's fast path -- and its boxes are mapped back to
+    // to even for a YUV 4:2:0 ZLY_INPUT_FORMAT, x0 alone for a packed 4:2:2 one) -- a model-sized window around the crosshair is the engine's fast path -- and its boxes are mapped back to
     // fractions of the whole frame before the callback.  A request smaller than the window on either axis is detected whole.
     if (!parseCrop(std::getenv("ZLY_CROP"), &crop_w_, &crop_h_))
         return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_CROP must be WxH with W, H >= 1, got '") + std::getenv("ZLY_CROP") + "'");
     if (crop_w_ > 0 && isYuvFormat(input_format_) && ((crop_w_ | crop_h_) & 1))
         return Result<void>::error(ErrorCode::INVALID_ARGUMENT, "ZLY_CROP: a YUV 4:2:0 ZLY_INPUT_FORMAT needs an even window size");
+    if (crop_w_ > 0 && isYuv422Format(input_format_) && (crop_w_ & 1))
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, "ZLY_CROP: a packed YUV 4:2:2 ZLY_INPUT_FORMAT needs an even window width");
     if (crop_w_ > 0 && (!zly_view_tight || !zly_view_bytes || !zly_view_crop || !zly_submit_view || !zly_submit_try_view))
         return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_CROP: the engine library has no zly_submit_view");
     // ZLY_RESIZE: how every engine of this plugin (a hot reload's new ones included) fits a request into the model's input: the reference's
@@ -484,6 +497,7 @@ Result<void> HipInferenceEngine::submitInference(const InferenceRequest& request
                 if (vrc == ZLY_OK) {
                     p.crop_x0 = (request.width - crop_w_) / 2; p.crop_y0 = (request.height - crop_h_) / 2;
                     if (isYuvFormat(input_format_)) { p.crop_x0 &= ~1; p.crop_y0 &= ~1; }
+                    if (isYuv422Format(input_format_)) p.crop_x0 &= ~1;
                     p.frame_w = request.width; p.frame_h = request.height;
                     vrc = zly_view_crop(&whole, p.crop_x0, p.crop_y0, crop_w_, crop_h_, &win);
                     p.cropped = vrc == ZLY_OK;

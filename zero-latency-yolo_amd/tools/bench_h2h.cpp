@@ -8,6 +8,7 @@
 // synthetic frames put through a float BGR -> YUV transform; cabi submits with zly_submit_fmt, plugin / lone set ZLY_INPUT_FORMAT.
 // format rgb, bgra, rgba: packed frames made by permuting the synthetic BGR frames' bytes and, for the 4-byte formats, padding every pixel with a
 // fourth byte (a 4-byte frame is 4/3 of the BGR frame's PCIe and staging bytes: the GB/s column counts them).
+// format yuy2, uyvy, yuy2_709, uyvy_709: packed YUV 4:2:2 frames (capture cards, UVC devices) from the same float transform, two bytes per pixel.
 // Without it the output is unchanged (bench.py --full parses it); with it the JSON line is the same and the format is named on stderr.
 //
 // engines > 1: that many engine instances on the GPU (ZLY_FLAG_SINGLE_CHAIN), submitting thread t feeds engine t % engines; their
@@ -76,6 +77,31 @@ static std::vector<uint8_t> toYuv420(const std::vector<uint8_t>& bgr, int W, int
     return out;
 }
 
+// BGR -> packed YUV 4:2:2 of format fmt (float, limited range, chroma = mean of each pixel pair of a row): YUY2 = Y0 U Y1 V, UYVY = U Y0 V Y1
+static std::vector<uint8_t> toYuv422(const std::vector<uint8_t>& bgr, int W, int H, int32_t fmt)
+{
+    const bool b709 = fmt == ZLY_PIX_YUY2_BT709 || fmt == ZLY_PIX_UYVY_BT709, uyvy = fmt == ZLY_PIX_UYVY_BT601 || fmt == ZLY_PIX_UYVY_BT709;
+    const double kr = b709 ? 0.2126 : 0.299, kb = b709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
+    std::vector<uint8_t> out(zly_frame_bytes(fmt, W, H));
+    auto u8 = [](double v) { return (uint8_t)std::min(255.0, std::max(0.0, v + 0.5)); };
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; x += 2) {
+            double cb = 0, cr = 0;
+            uint8_t yy[2];
+            for (int k = 0; k < 2; ++k) {
+                const uint8_t* p = &bgr[((size_t)y * W + x + k) * 3];
+                const double l = kr * p[2] + kg * p[1] + kb * p[0];
+                yy[k] = u8(16.0 + 219.0 / 255.0 * l);
+                cb += 0.5 * (128.0 + 224.0 / 255.0 * (p[0] - l) / (2.0 * (1.0 - kb)));
+                cr += 0.5 * (128.0 + 224.0 / 255.0 * (p[2] - l) / (2.0 * (1.0 - kr)));
+            }
+            uint8_t* m = &out[((size_t)y * W + x) * 2];
+            if (uyvy) { m[0] = u8(cb); m[1] = yy[0]; m[2] = u8(cr); m[3] = yy[1]; }
+            else { m[0] = yy[0]; m[1] = u8(cb); m[2] = yy[1]; m[3] = u8(cr); }
+        }
+    return out;
+}
+
 // BGR -> packed RGB / BGRA / RGBA: the same pixels, permuted and padded (the fourth byte is never interpreted: any value)
 static std::vector<uint8_t> toPacked(const std::vector<uint8_t>& bgr, int W, int H, int32_t fmt)
 {
@@ -103,7 +129,10 @@ int main(int argc, char** argv)
     const std::string fmt_name = argc > 9 ? argv[9] : "bgr";
     const int32_t fmt = fmt_name == "bgr" ? ZLY_PIX_BGR : fmt_name == "nv12" ? ZLY_PIX_NV12_BT601 : fmt_name == "i420" ? ZLY_PIX_I420_BT601
                       : fmt_name == "nv12_709" ? ZLY_PIX_NV12_BT709 : fmt_name == "i420_709" ? ZLY_PIX_I420_BT709
-                      : fmt_name == "rgb" ? ZLY_PIX_RGB : fmt_name == "bgra" ? ZLY_PIX_BGRA : fmt_name == "rgba" ? ZLY_PIX_RGBA : -1;
+                      : fmt_name == "rgb" ? ZLY_PIX_RGB : fmt_name == "bgra" ? ZLY_PIX_BGRA : fmt_name == "rgba" ? ZLY_PIX_RGBA
+                      : fmt_name == "yuy2" ? ZLY_PIX_YUY2_BT601 : fmt_name == "uyvy" ? ZLY_PIX_UYVY_BT601
+                      : fmt_name == "yuy2_709" ? ZLY_PIX_YUY2_BT709 : fmt_name == "uyvy_709" ? ZLY_PIX_UYVY_BT709 : -1;
+    const bool y422 = fmt >= ZLY_PIX_YUY2_BT601 && fmt <= ZLY_PIX_UYVY_BT709;
     const bool packed = fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA;
     if (fmt < 0 || zly_frame_bytes(fmt, W, H) == 0) { std::fprintf(stderr, "bad format '%s' for %dx%d\n", fmt_name.c_str(), W, H); return 2; }
     if (fmt != ZLY_PIX_BGR) {
@@ -121,6 +150,7 @@ int main(int argc, char** argv)
             uint32_t* p = reinterpret_cast<uint32_t*>(f.data());
             for (size_t i = 0; i < fb / 4; ++i) p[i] = rng();
             if (packed) f = toPacked(f, W, H, fmt);
+            else if (y422) f = toYuv422(f, W, H, fmt);
             else if (fmt != ZLY_PIX_BGR) f = toYuv420(f, W, H, fmt);
         }
     }

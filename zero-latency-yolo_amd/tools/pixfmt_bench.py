@@ -7,6 +7,8 @@ model-sized frames resident in HBM, once per format, the same synthetic pictures
     bgr                 the headline path (12-byte quad loads)
     nv12, i420          YUV 4:2:0 made from the pictures by a float transform (only the content of the requests matters here)
     rgb, bgra, rgba     the pictures' bytes permuted / padded with a fourth byte
+    yuy2, uyvy          packed YUV 4:2:2 (capture cards, UVC devices) holding the nv12 frame's samples, each chroma row twice: 2 bytes per pixel, one
+                        load per pixel, and exactly nv12's pixels after conversion, so that everything behind the front launch does nv12's work
 
 The formats alternate block by block (bench.py's block structure: warm-up, then timed blocks bracketed by a synchronize, the median block counts),
 so that clock ramps and neighbours on the box hit all alike.  Per format it reports the step time and the device time of the FRONT launch from the
@@ -31,7 +33,8 @@ sys.path.insert(0, HERE)
 import zly            # noqa: E402
 import zly_model as zm  # noqa: E402
 
-FORMATS = {"bgr": zly.PIX_BGR, "nv12": zly.PIX_NV12_BT601, "i420": zly.PIX_I420_BT601, "rgb": zly.PIX_RGB, "bgra": zly.PIX_BGRA, "rgba": zly.PIX_RGBA}
+FORMATS = {"bgr": zly.PIX_BGR, "nv12": zly.PIX_NV12_BT601, "i420": zly.PIX_I420_BT601, "rgb": zly.PIX_RGB, "bgra": zly.PIX_BGRA, "rgba": zly.PIX_RGBA,
+           "yuy2": zly.PIX_YUY2_BT601, "uyvy": zly.PIX_UYVY_BT601, "yuy2_709": zly.PIX_YUY2_BT709, "uyvy_709": zly.PIX_UYVY_BT709}
 
 
 def to_format(bgr, name):
@@ -49,9 +52,15 @@ def to_format(bgr, name):
     f = bgr.astype(np.float32)
     b, g, r = f[..., 0], f[..., 1], f[..., 2]
     y = 16 + 0.257 * r + 0.504 * g + 0.098 * b
+    u8 = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)     # noqa: E731
+    if name.startswith(("yuy2", "uyvy")):                          # chroma = nv12's (the mean of each 2 x 2 block) on both rows; Y0 U Y1 V or U Y0 V Y1
+        cb = np.repeat((128 - 0.148 * r - 0.291 * g + 0.439 * b).reshape(B, H // 2, 2, W // 2, 2).mean(axis=(2, 4)), 2, axis=1)
+        cr = np.repeat((128 + 0.439 * r - 0.368 * g - 0.071 * b).reshape(B, H // 2, 2, W // 2, 2).mean(axis=(2, 4)), 2, axis=1)
+        yy = u8(y).reshape(B, H, W // 2, 2)
+        order = [yy[..., 0], u8(cb), yy[..., 1], u8(cr)] if name.startswith("yuy2") else [u8(cb), yy[..., 0], u8(cr), yy[..., 1]]
+        return np.ascontiguousarray(np.stack(order, axis=-1)).reshape(-1)
     cb = (128 - 0.148 * r - 0.291 * g + 0.439 * b).reshape(B, H // 2, 2, W // 2, 2).mean(axis=(2, 4))
     cr = (128 + 0.439 * r - 0.368 * g - 0.071 * b).reshape(B, H // 2, 2, W // 2, 2).mean(axis=(2, 4))
-    u8 = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)     # noqa: E731
     chroma = np.stack([u8(cb), u8(cr)], axis=-1) if name == "nv12" else np.stack([u8(cb), u8(cr)], axis=1)
     return np.concatenate([u8(y).reshape(B, -1), chroma.reshape(B, -1)], axis=1).reshape(-1)
 

@@ -37,6 +37,7 @@ LETTERBOX_MAX_DIM = 16384    # largest request side (and model side) of a letter
 # packed RGB / BGRA / RGBA (the fourth byte is never interpreted) fetched in the front kernel as the BGR frame of their B, G, R bytes
 PIX_BGR, PIX_NV12_BT601, PIX_I420_BT601, PIX_NV12_BT709, PIX_I420_BT709 = 0, 1, 2, 3, 4
 PIX_RGB, PIX_BGRA, PIX_RGBA = 16, 17, 18
+PIX_YUY2_BT601, PIX_UYVY_BT601, PIX_YUY2_BT709, PIX_UYVY_BT709 = 10, 11, 12, 13      # packed YUV 4:2:2 (capture cards, UVC devices): 1-D u8 buffers of 2wh bytes, w even
 MERGE_IOU, MERGE_IOS = 0, 1          # zly_merge_config.metric (include/zly.h "Tiles")
 MERGE_MAX_CANDIDATES = 4096          # tiles of a group x max_dets may not exceed it
 _PACKED_BPP = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
@@ -217,7 +218,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 
 
 def frame_bytes(fmt: int, w: int, h: int) -> int:
-    """bytes of one w x h frame of format fmt (PIX_*): 3wh for BGR / RGB, 4wh for BGRA / RGBA, 3wh/2 for YUV 4:2:0; 0 for an unknown format or invalid sizes (host only)"""
+    """bytes of one w x h frame of format fmt (PIX_*): 3wh for BGR / RGB, 4wh for BGRA / RGBA, 3wh/2 for YUV 4:2:0, 2wh for packed 4:2:2; 0 for an unknown format or invalid sizes (host only)"""
     return int(load_library().zly_frame_bytes(fmt, w, h))
 
 
