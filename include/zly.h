@@ -103,6 +103,43 @@ extern "C" {
  * stage keeps its model-sized input, and the postProcess stage keeps the stretch mapping (cx / img_w) on every engine. */
 #define ZLY_LETTERBOX_MAX_DIM 16384
 
+#define ZLY_FLAG_AREA         64  /* resize FILTER of this engine: the area average (box filter) over every source pixel a model pixel stands for, instead of the
+                                   one pixel the stretch picks or the four the letterbox blends.  Combines with ZLY_FLAG_LETTERBOX, which remains the resize
+                                   GEOMETRY.  Opt-in; a large capture reduced to the model's size no longer aliases thin and small targets in and out.  Defined below. */
+
+/* Area resize (ZLY_FLAG_AREA).  Per engine, for a request of w x h and a model of tw x th, all in integers:
+ *   Content.  Without ZLY_FLAG_LETTERBOX the request is area-resized to the content size D = (tw, th).  With it, to D = (nw, nh) of "Geometry" above,
+ *     placed at (pad_x, pad_y), with 114, 114, 114 everywhere else.
+ *   Per axis, with source length S (w or h), content length D and content index d, in units of 1/D of a source pixel:
+ *       lo = d*S;  hi = (d+1)*S;  i0 = lo / D;  i1 = (hi - 1) / D
+ *     and source index i in [i0, i1] has the weight
+ *       w(d, i) = min(hi, (i+1)*D) - max(lo, i*D)
+ *     -- the overlap of the content pixel's interval [lo, hi) with the source pixel's [i*D, (i+1)*D).  Interior weights equal D, the two edge weights
+ *     are in 1..D, and the weights of one d sum to S.  The one definition serves S > D (a downscale), S == D (w = D at i = d alone: the identity) and
+ *     S < D (it degenerates to replication with blended seams): there is no special case and no fall-back to another filter.
+ *   Per channel, with the B, G, R bytes p(ix, iy) of the source pixels:
+ *       acc = sum over iy of wy(y, iy) * (sum over ix of wx(x, ix) * p(ix, iy))
+ *       T   = Sx*Sy
+ *       v   = (acc + (T >> 1)) / T
+ *     The sum is exact and / truncates: round half up.  v is a byte (255 stays 255).  acc < 255 * 2^28 needs 64 bits; everything else fits int32
+ *     for w, h <= ZLY_AREA_MAX_DIM; larger requests fail in this mode with ZLY_ERR_INVALID_INPUT (and an engine with model_w or model_h above it is
+ *     refused with ZLY_ERR_INVALID_ARGUMENT).
+ *   Source pixels that are not BGR: every source pixel is first converted to its B, G, R bytes by the existing rules, then averaged -- YUV 4:2:0 and
+ *     packed 4:2:2 by the integer conversion below with the pixel's own chroma, RGB / BGRA / RGBA as the fetch's word with X ignored.  (The decision
+ *     the letterbox made for its taps.)
+ *   Tensor.  The bytes v take the BGR path exactly (/255, BGR->RGB, bf16 rounding in the bf16 engine).
+ *   Boxes.  Box mapping, threshold, NMS and output order do not change: an area engine maps boxes as the same engine without the flag does, from the
+ *     request's w, h -- cx / w on stretch engines, the letterbox un-mapping on letterbox engines.
+ *   Consequences.  A request of exactly the content size gives, bit for bit, what the engine without the flag gives.  For S = k*D the result is the
+ *     k x k block mean, rounded half up.  A constant frame stays constant.  Equality with any library's INTER_AREA or BOX bytes is NOT claimed: their
+ *     rounding differs.
+ * Every entry point that takes frames honours the mode (the synchronous, batch, _fmt, _view, submit, device, device-view, tiled and tracked calls and
+ * zly_preprocess*); zly_forward and zly_postprocess, which take tensors, do not -- the line the letterbox draws.
+ * How: a pre-pass kernel writes one model-sized BGR frame per request into an engine-owned buffer of max_batch * model_w * model_h * 3 bytes (allocated
+ * at zly_create only with the flag), and the engine's front kernel runs on that buffer, where its own resize is the identity.  The pre-pass lies inside
+ * what zly_stats calls preprocess and is timed with the front op in zly_profile_ops; the op table of an area engine is the plain engine's. */
+#define ZLY_AREA_MAX_DIM 16384
+
 /* Pixel formats of a request frame (the *_fmt entry points; the others take ZLY_PIX_BGR).  Planes are tight: no row pitch, no padding
  * (pitched surfaces and regions of a larger buffer go through a zly_frame_view and the *_view entry points, below).
  *   ZLY_PIX_BGR          packed B,G,R, 3 bytes per pixel: nbytes = w*h*3

@@ -226,6 +226,11 @@ struct zly_engine : Plan {
     std::vector<ViewRec> view_cache;
     int last_desc_n = 0;              // frames of the upload d_desc holds
     bool desc_cache_view = false;     // what d_desc holds came from a view call: a plain call and a view call never reuse each other's upload
+    // ZLY_FLAG_AREA: the pre-pass's output, max_batch model-sized tight BGR frames, and the constant descriptor table the front kernel reads it with
+    // (frame f at f * model_w * model_h * 3, model_w x model_h, BGR; uploaded once).  Calls on an engine are stream-ordered: no ring.
+    uint8_t* d_area = nullptr;
+    FrameDesc* d_area_desc = nullptr;
+    bool area_view = false;           // the current call's request frames are frame views (set by run_path, with `front`)
     uint8_t* d_stage = nullptr;       // frame staging (host path)
     uint8_t* h_stage = nullptr;       // pinned
     size_t stage_bytes = 0;
@@ -1088,23 +1093,41 @@ static void op_writes(const zly_engine* e, const Op& op, std::vector<IoView>* ou
     }
 }
 
+// What the front kernel of a call reads.  A plain engine: the call's frames and descriptors, as they are.  An area engine (ZLY_FLAG_AREA): the pre-pass
+// (kernels_area.hip) runs here, on the call's stream ahead of the front kernel, and the front kernel reads its output -- model-sized tight BGR frames,
+// for which the engine's BGR variant (e->front: run_path, area_front) is the identity map -- through the constant table.  The Detect tail keeps reading
+// d_desc: boxes are mapped from the request's sizes.
+static hipError_t front_source(zly_engine* e, int n, const uint8_t** src, const FrameDesc** desc, hipStream_t s)
+{
+    if (!(e->cfg.flags & ZLY_FLAG_AREA)) return hipSuccess;
+    const hipError_t r = launch_area(*src, e->d_desc, n, e->area_view, e->d_area, e->cfg.model_w, e->cfg.model_h, (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0,
+                                     e->sw.num_cus, s);
+    *src = e->d_area; *desc = e->d_area_desc;
+    return r;
+}
+
 // launches what the launch table says op i launches at batch n (nothing for LK_NONE)
 static hipError_t run_op(zly_engine* e, size_t i, const Launch& L, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s)
 {
     const Op& op = e->ops[i];
+    const FrameDesc* desc = e->d_desc;
+    if (L.kind == LK_PREPROCESS || L.kind == LK_STEM || L.kind == LK_STEM1) {
+        const hipError_t r = front_source(e, n, &d_src, &desc, s);
+        if (r != hipSuccess) return r;
+    }
     switch (L.kind) {
     case LK_NONE:
         return hipSuccess;
     case LK_PREPROCESS:
-        return launch_preprocess(e->dtype, d_src, e->d_desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front);
+        return launch_preprocess(e->dtype, d_src, desc, n, e->bufs[(size_t)e->in_buf].ptr, nullptr, e->cfg.model_w, e->cfg.model_h, s, e->front);
     case LK_STEM: {
         StemArgs st = e->stem;
-        st.src = d_src; st.desc = e->d_desc;
+        st.src = d_src; st.desc = desc;
         return launch_stem_fused(st, n, s, e->front);
     }
     case LK_STEM1: {
         Stem1Args st = e->stem1a;
-        st.st.src = d_src; st.st.desc = e->d_desc;
+        st.st.src = d_src; st.st.desc = desc;
         return launch_stem_model1(st, n, s, e->front);
     }
     case LK_CONV:
@@ -1266,12 +1289,21 @@ static void harvest_timing(zly_engine* e)
 // the front-kernel variant of a call on this engine: the batch's format level (the highest front_level of its frames), tight frames or frame views
 static FrontVariant front_of(const zly_engine* e, int level, bool view = false) { return FrontVariant(level, (e->cfg.flags & ZLY_FLAG_LETTERBOX) != 0, view); }
 
+// An area engine's front kernel reads the pre-pass's output whatever the call's frames are (front_source): the variant of model-sized tight BGR frames.
+// What the request frames are -- their formats ride in d_desc -- is the pre-pass's business; it only needs to know whether view records lie behind them.
+static FrontVariant area_front(zly_engine* e, FrontVariant variant)
+{
+    if (!(e->cfg.flags & ZLY_FLAG_AREA)) return variant;
+    e->area_view = variant.view;
+    return front_of(e, ZLY_FRONT_BGR);
+}
+
 // nms_stream_out: the stream the call's NMS (its last kernel) was launched on -- `s`, or the engine's NMS stream when deferred
 // variant: the call's front-kernel variant (front_of: the batch's format level -- d_desc says which format each frame has --, and whether the frames are views, d_desc then holding their ViewRec too)
 static int run_path(zly_engine* e, int n, const uint8_t* d_src, void* d_slabs_out, uint32_t tag0, hipStream_t s, bool with_pre, bool defer_nms,
                     hipStream_t* nms_stream_out, FrontVariant variant)
 {
-    e->front = variant;
+    e->front = area_front(e, variant);
     const size_t nops = e->ops.size();
     harvest_timing(e);
     const bool sample = with_pre && !e->t_pending && (e->sample_ctr++ % zly_engine::SAMPLE_EVERY) == 0;
@@ -1526,6 +1558,10 @@ static int check_frame_mode(const zly_engine* e, int32_t w, int32_t h)
     if ((e->cfg.flags & ZLY_FLAG_LETTERBOX) && (w > ZLY_LETTERBOX_MAX_DIM || h > ZLY_LETTERBOX_MAX_DIM))
         return fail(ZLY_ERR_INVALID_INPUT, "letterbox mode takes frames of at most " + std::to_string(ZLY_LETTERBOX_MAX_DIM) + " pixels on a side, got " +
                                            std::to_string(w) + " x " + std::to_string(h));
+    // so does an area engine's exact average (the products of the footprint arithmetic stay below 2^28)
+    if ((e->cfg.flags & ZLY_FLAG_AREA) && (w > ZLY_AREA_MAX_DIM || h > ZLY_AREA_MAX_DIM))
+        return fail(ZLY_ERR_INVALID_INPUT, "area mode takes frames of at most " + std::to_string(ZLY_AREA_MAX_DIM) + " pixels on a side, got " +
+                                           std::to_string(w) + " x " + std::to_string(h));
     return ZLY_OK;
 }
 
@@ -1614,7 +1650,7 @@ static hipError_t destroy_engine(zly_engine* e)
     ExclusiveGate x;
     for (auto& kv : e->graphs) if (kv.second) note(hipGraphExecDestroy(kv.second));
     for (Buffer& b : e->bufs) if (b.ptr) note(hipFree(b.ptr));
-    void* dptrs[] = {e->d_weights, e->d_head, e->d_cand, e->d_cand_alt, e->d_count_alt, e->d_scratch, e->d_count, e->d_slabs, e->d_desc, e->d_stage, e->d_scratch_f32};
+    void* dptrs[] = {e->d_weights, e->d_head, e->d_cand, e->d_cand_alt, e->d_count_alt, e->d_scratch, e->d_count, e->d_slabs, e->d_desc, e->d_stage, e->d_scratch_f32, e->d_area, e->d_area_desc};
     for (void* p : dptrs) if (p) note(hipFree(p));
     if (e->h_desc) note(hipHostFree(e->h_desc));
     if (e->h_stage) note(hipHostFree(e->h_stage));
@@ -2099,6 +2135,8 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
     if (cfg->dtype != ZLY_DTYPE_BF16 && cfg->dtype != ZLY_DTYPE_FP32) return fail(ZLY_ERR_INVALID_ARGUMENT, "dtype must be ZLY_DTYPE_FP32 or ZLY_DTYPE_BF16");
     if ((cfg->flags & ZLY_FLAG_LETTERBOX) && (cfg->model_w > ZLY_LETTERBOX_MAX_DIM || cfg->model_h > ZLY_LETTERBOX_MAX_DIM))
         return fail(ZLY_ERR_INVALID_ARGUMENT, "ZLY_FLAG_LETTERBOX: model_w/model_h must be <= " + std::to_string(ZLY_LETTERBOX_MAX_DIM));
+    if ((cfg->flags & ZLY_FLAG_AREA) && (cfg->model_w > ZLY_AREA_MAX_DIM || cfg->model_h > ZLY_AREA_MAX_DIM))
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "ZLY_FLAG_AREA: model_w/model_h must be <= " + std::to_string(ZLY_AREA_MAX_DIM));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(ZLY_ERR_SYSTEM, "no HIP device available: this engine has no CPU fallback");
@@ -2177,6 +2215,14 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
             if (!ok) return fail(ZLY_ERR_SYSTEM, "device allocation failed (deferred NMS)");
         }
         if (!ok) return fail(ZLY_ERR_SYSTEM, "device initialisation failed");
+        if (cfg->flags & ZLY_FLAG_AREA) {
+            const size_t afb = (size_t)cfg->model_w * cfg->model_h * 3;
+            std::vector<FrameDesc> ad(B);
+            for (size_t i = 0; i < B; ++i) { ad[i].src_off = desc_pack(i * afb, ZLY_PIX_BGR); ad[i].w = cfg->model_w; ad[i].h = cfg->model_h; }
+            ok = hipMalloc((void**)&e->d_area, B * afb) == hipSuccess && hipMalloc((void**)&e->d_area_desc, B * sizeof(FrameDesc)) == hipSuccess &&
+                 hipMemcpy(e->d_area_desc, ad.data(), B * sizeof(FrameDesc), hipMemcpyHostToDevice) == hipSuccess;
+            if (!ok) return fail(ZLY_ERR_SYSTEM, "device allocation failed (area resize)");
+        }
         // staging for one frame (zly_detect) -- or, with a warm-up, for max_batch model-sized frames (warm_batch; zly_detect_batch then never allocates)
         const size_t fb = (size_t)cfg->model_w * cfg->model_h * 3;
         return ensure_stage(e, cfg->warmup_runs > 0 ? fb * B : fb);
@@ -3043,7 +3089,10 @@ int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_
     size_t off0 = 0;
     rc = set_desc(e, 1, &w, &h, &off0, e->stream, &fmt);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, front_of(e, front_level(fmt))), ZLY_ERR_INFERENCE);
+    const FrontVariant fv = area_front(e, front_of(e, front_level(fmt)));
+    const uint8_t* src = e->d_stage; const FrameDesc* desc = e->d_desc;
+    HIP_TRY(front_source(e, 1, &src, &desc, e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_preprocess(e->dtype, src, desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, fv), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
@@ -3070,7 +3119,10 @@ int32_t zly_preprocess_view(zly_engine* e, const uint8_t* base, size_t buf_bytes
     const ViewRec rec = view_rec(v);
     rc = set_desc(e, 1, &v->w, &v->h, &off0, e->stream, &v->fmt, &rec);
     if (rc != ZLY_OK) return rc;
-    HIP_TRY(launch_preprocess(e->dtype, e->d_stage, e->d_desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, front_of(e, front_level(v->fmt), true)), ZLY_ERR_INFERENCE);
+    const FrontVariant fv = area_front(e, front_of(e, front_level(v->fmt), true));
+    const uint8_t* src = e->d_stage; const FrameDesc* desc = e->d_desc;
+    HIP_TRY(front_source(e, 1, &src, &desc, e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_preprocess(e->dtype, src, desc, 1, nullptr, e->d_scratch_f32, e->cfg.model_w, e->cfg.model_h, e->stream, fv), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemcpyAsync(out_nchw, e->d_scratch_f32, elems * sizeof(float), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
@@ -3382,7 +3434,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
     std::vector<size_t> offs((size_t)n);
     for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * (size_t)w * (size_t)h * 3u;
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream);
-    e->front = front_of(e, ZLY_FRONT_BGR);         // tight BGR frames
+    e->front = area_front(e, front_of(e, ZLY_FRONT_BGR));         // tight BGR frames
     if (rc != ZLY_OK) return rc;
     const size_t nops = e->ops.size();
     const std::vector<Launch>& tab = resolve_launches(e, n);

@@ -239,6 +239,10 @@ hipError_t launch_sppf_pool(int dtype, void* buf, int cs, int c, int n, int H, i
 bool       sppf_pool16_ok(int dtype, int cs, int c, int n, int H, int W, int six_pass);                        // does launch_sppf_pool take sppf_pool16_kernel?
 hipError_t launch_tap_to_nchw(int dtype, const void* in, int cs, int co, int C, int H, int W, int idx, float* out, hipStream_t s);
 
+// kernels_area.hip -- the area-average resize filter (ZLY_FLAG_AREA) as a pre-pass: the call's n request frames (src, desc; with view set, n ViewRec lie
+// behind the n descriptors) -> n model-sized tight BGR frames at out ([n][th][tw][3]; lb: the letterbox geometry, padding included)
+hipError_t launch_area(const uint8_t* src, const FrameDesc* desc, int n, bool view, uint8_t* out, int tw, int th, bool lb, int num_cus, hipStream_t s);
+
 // kernels_stem.hip -- preprocess fused into the stem conv (bf16, 16-channel stem)
 struct StemArgs {
     const uint8_t* src; const FrameDesc* desc;

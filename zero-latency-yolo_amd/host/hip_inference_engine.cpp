@@ -91,13 +91,17 @@ const char* inputFormatName(int32_t fmt)
     default: return "bgr";
     }
 }
-// ZLY_RESIZE: stretch (default: the reference's nearest-neighbour stretch), letterbox (ZLY_FLAG_LETTERBOX) -> 0 / 1, -1 = unknown
+// ZLY_RESIZE: stretch (default: the reference's nearest-neighbour stretch), letterbox (ZLY_FLAG_LETTERBOX), area (ZLY_FLAG_AREA: the stretch geometry
+// with the area-average filter), letterbox_area (both flags) -> bit 0 = letterbox geometry, bit 1 = area filter; -1 = unknown
 int parseResizeMode(const char* v)
 {
     if (!v || !*v || std::strcmp(v, "stretch") == 0) return 0;
     if (std::strcmp(v, "letterbox") == 0) return 1;
+    if (std::strcmp(v, "area") == 0) return 2;
+    if (std::strcmp(v, "letterbox_area") == 0) return 3;
     return -1;
 }
+const char* resizeModeName(bool letterbox, bool area) { return letterbox ? (area ? "letterbox_area" : "letterbox") : (area ? "area" : "stretch"); }
 // ZLY_CROP=WxH (both >= 1) -> true; unset or empty: no crop (w = h = 0), true; anything else: false
 bool parseCrop(const char* v, int32_t* w, int32_t* h)
 {
@@ -177,11 +181,13 @@ Result<void> HipInferenceEngine::initialize()
     if (crop_w_ > 0 && (!zly_view_tight || !zly_view_bytes || !zly_view_crop || !zly_submit_view || !zly_submit_try_view))
         return Result<void>::error(ErrorCode::SYSTEM_ERROR, "ZLY_CROP: the engine library has no zly_submit_view");
     // ZLY_RESIZE: how every engine of this plugin (a hot reload's new ones included) fits a request into the model's input: the reference's
-    // stretch, or the aspect-preserving letterbox an Ultralytics-trained model expects (boxes then are normalised to the request frame itself)
+    // stretch, or the aspect-preserving letterbox an Ultralytics-trained model expects (boxes then are normalised to the request frame itself); and
+    // with which filter: one source pixel per model pixel (four in the letterbox), or -- area, letterbox_area -- the average over all of them
     const int resize = parseResizeMode(std::getenv("ZLY_RESIZE"));
     if (resize < 0)
-        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_RESIZE must be stretch or letterbox, got '") + std::getenv("ZLY_RESIZE") + "'");
-    letterbox_ = resize == 1;
+        return Result<void>::error(ErrorCode::INVALID_ARGUMENT, std::string("ZLY_RESIZE must be stretch, letterbox, area or letterbox_area, got '") + std::getenv("ZLY_RESIZE") + "'");
+    letterbox_ = (resize & 1) != 0;
+    area_ = (resize & 2) != 0;
     // ZLY_TRACK=1: track ids on the GPU (include/zly.h "tracking"); a client is one stream of one engine
     track_ = envInt("ZLY_TRACK", 0) != 0;
     if (track_) {
@@ -277,7 +283,7 @@ std::shared_ptr<HipInferenceEngine::EngineHandle> HipInferenceEngine::createEngi
     c.warmup_runs = 3;                                   // onnx_engine.cpp:919-954
     c.use_graph = 1;
     // the server only consumes detections; one engine per GPU: NMS of a batch runs beside the next one; several: one chain each
-    c.flags = ZLY_FLAG_NO_HEAD_TENSOR | (engines_per_gpu_ > 1 ? ZLY_FLAG_SINGLE_CHAIN : ZLY_FLAG_ASYNC_NMS) | (letterbox_ ? ZLY_FLAG_LETTERBOX : 0);
+    c.flags = ZLY_FLAG_NO_HEAD_TENSOR | (engines_per_gpu_ > 1 ? ZLY_FLAG_SINGLE_CHAIN : ZLY_FLAG_ASYNC_NMS) | (letterbox_ ? ZLY_FLAG_LETTERBOX : 0) | (area_ ? ZLY_FLAG_AREA : 0);
     zly_engine* e = nullptr;
     *rc = zly_create(&c, &e);
     if (*rc != ZLY_OK) { *msg = zly_last_error(); return nullptr; }
@@ -737,7 +743,7 @@ std::unordered_map<std::string, std::string> HipInferenceEngine::getStatus() con
     s["inference_errors"] = std::to_string(inference_errors_.load());
     s["dropped_frames"] = std::to_string(dropped_frames_.load());
     s["dynamic_batching"] = "enabled";
-    s["resize_mode"] = letterbox_ ? "letterbox" : "stretch";
+    s["resize_mode"] = resizeModeName(letterbox_, area_);
     s["input_format"] = inputFormatName(input_format_);
     s["tracking"] = track_ ? "on" : "off";
     s["track_motion"] = track_motion_ ? "on" : "off";

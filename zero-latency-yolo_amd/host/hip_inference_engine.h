@@ -99,7 +99,8 @@ private:
     int engines_per_gpu_ = 1;
     int32_t input_format_ = 0;                             // ZLY_INPUT_FORMAT (read by initialize()): ZLY_PIX_* of every request's data (0 = BGR)
     int32_t crop_w_ = 0, crop_h_ = 0;                      // ZLY_CROP=WxH (read by initialize()): every request is detected in the centred W x H window of its frame (0 = whole frames)
-    bool letterbox_ = false;                               // ZLY_RESIZE=letterbox (read by initialize()): every engine is created with ZLY_FLAG_LETTERBOX
+    bool letterbox_ = false;                               // ZLY_RESIZE=letterbox / letterbox_area (read by initialize()): every engine is created with ZLY_FLAG_LETTERBOX
+    bool area_ = false;                                    // ZLY_RESIZE=area / letterbox_area: every engine, a hot reload's included, is created with ZLY_FLAG_AREA
     // ZLY_TRACK=1 (read by initialize()): every engine tracks (zly_track_enable) and a client's frames all go to engine client_id % engines, as one
     // stream of that engine: detections come back with track ids that persist from frame to frame.  ZLY_TRACK_STREAMS (default 64) stream slots per
     // engine; ZLY_TRACK_IOU / ZLY_TRACK_MAX_LOST override the engine's defaults.  A hot reload's new engines start with fresh tracks.

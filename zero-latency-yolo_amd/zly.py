@@ -33,6 +33,8 @@ FLAG_ASYNC_NMS = 8
 FLAG_SINGLE_CHAIN = 16
 FLAG_LETTERBOX = 32          # per-engine resize mode: aspect-preserving bilinear letterbox (include/zly.h), boxes normalised to the request frame
 LETTERBOX_MAX_DIM = 16384    # largest request side (and model side) of a letterbox engine
+FLAG_AREA = 64               # per-engine resize filter: the exact area average over every source pixel (include/zly.h); combines with FLAG_LETTERBOX
+AREA_MAX_DIM = 16384         # largest request side (and model side) of an area engine
 # pixel formats of a request frame (include/zly.h ZLY_PIX_*): packed BGR, 8-bit YUV 4:2:0 (limited range) converted in the front kernel, or
 # packed RGB / BGRA / RGBA (the fourth byte is never interpreted) fetched in the front kernel as the BGR frame of their B, G, R bytes
 PIX_BGR, PIX_NV12_BT601, PIX_I420_BT601, PIX_NV12_BT709, PIX_I420_BT709 = 0, 1, 2, 3, 4
