@@ -30,7 +30,7 @@ $(OUT)/kernels_stem_yuv.o: $(CSRC)/kernels_stem.hip
 $(OUT)/kernels_lb.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_head.hip
 $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
 
-$(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/weights.h include/zly.h | $(OUT)
+$(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(OUT)/weights.o: $(CSRC)/weights.cpp $(CSRC)/weights.h include/zly.h | $(OUT)
@@ -42,7 +42,7 @@ $(OUT)/libzly.so: $(OBJS)
 # ---- diagnostic build of the engine (never shipped, never loaded by tests / bench.py / the plugin): the same kernels, engine.cpp with -DZLY_DIAG, which
 #      compiles in the result-changing ZLY_ABLATE_SKIP switch of tools/ablate_launches.sh (ZLY_LIB=.../libzly_diag.so python3 bench.py ...)
 diaglib: $(OUT)/libzly_diag.so
-$(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/weights.h include/zly.h | $(OUT)
+$(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -DZLY_DIAG=1 -x hip -c $< -o $@
 $(OUT)/libzly_diag.so: $(filter-out $(OUT)/engine.o,$(OBJS)) $(OUT)/engine_diag.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
@@ -82,7 +82,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_frame_rules $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -106,33 +106,43 @@ $(OUT)/test_frame_server: tests/cpp/test_frame_server.cpp $(HOST)/zly_frame_serv
 $(OUT)/test_plugin_stub: tests/cpp/test_plugin_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_stub.cpp -pthread
 
-# ... and its ZLY_CROP logic against a stub that records the frame view it is handed
-$(OUT)/test_plugin_crop_stub: tests/cpp/test_plugin_crop_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_crop_stub.cpp -pthread
+# ... and five more sides of it against one shared stub (tests/cpp/plugin_abi_stub.hpp), whose frame and view checks are the product's own (csrc/frame_rules.h):
+ABI_STUB := tests/cpp/plugin_abi_stub.hpp $(CSRC)/frame_rules.h $(CSRC)/front_variants.h $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h
+# its ZLY_CROP logic, from the frame views the stub records
+$(OUT)/test_plugin_crop_stub: tests/cpp/test_plugin_crop_stub.cpp $(ABI_STUB) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -I$(CSRC) -o $@ tests/cpp/test_plugin_crop_stub.cpp -pthread
 
 # ... and its packed YUV 4:2:2 input formats (names, sizes, ZLY_CROP's x-only evenness rule) against a stub of the same kind
-$(OUT)/test_plugin_yuv422_stub: tests/cpp/test_plugin_yuv422_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_yuv422_stub.cpp -pthread
+$(OUT)/test_plugin_yuv422_stub: tests/cpp/test_plugin_yuv422_stub.cpp $(ABI_STUB) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -I$(CSRC) -o $@ tests/cpp/test_plugin_yuv422_stub.cpp -pthread
 
 # ... and its ZLY_TRACK logic against a stub that records (engine, stream) of every submit and every reset; the second binary's stub lacks the tracking calls
-$(OUT)/test_plugin_track_stub: tests/cpp/test_plugin_track_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_stub.cpp -pthread
-$(OUT)/test_plugin_track_stub_nosym: tests/cpp/test_plugin_track_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
-	$(CXX) -O2 -std=c++17 -Wall -DNO_TRACK_SYMBOLS -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_stub.cpp -pthread
+$(OUT)/test_plugin_track_stub: tests/cpp/test_plugin_track_stub.cpp $(ABI_STUB) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -I$(CSRC) -o $@ tests/cpp/test_plugin_track_stub.cpp -pthread
+$(OUT)/test_plugin_track_stub_nosym: tests/cpp/test_plugin_track_stub.cpp $(ABI_STUB) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -DNO_TRACK_SYMBOLS -Iinclude -I$(HOST) -I$(CSRC) -o $@ tests/cpp/test_plugin_track_stub.cpp -pthread
 
 # ... and its ZLY_TRACK_MOTION logic against a stub that records the enables; the second binary's stub has the tracking calls but not the motion model's
-$(OUT)/test_plugin_track_motion_stub: tests/cpp/test_plugin_track_motion_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_motion_stub.cpp -pthread
-$(OUT)/test_plugin_track_motion_stub_nosym: tests/cpp/test_plugin_track_motion_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
-	$(CXX) -O2 -std=c++17 -Wall -DNO_MOTION_SYMBOLS -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_track_motion_stub.cpp -pthread
+$(OUT)/test_plugin_track_motion_stub: tests/cpp/test_plugin_track_motion_stub.cpp $(ABI_STUB) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -I$(CSRC) -o $@ tests/cpp/test_plugin_track_motion_stub.cpp -pthread
+$(OUT)/test_plugin_track_motion_stub_nosym: tests/cpp/test_plugin_track_motion_stub.cpp $(ABI_STUB) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -DNO_MOTION_SYMBOLS -Iinclude -I$(HOST) -I$(CSRC) -o $@ tests/cpp/test_plugin_track_motion_stub.cpp -pthread
 
 # ... and its ZLY_RESIZE names (stretch, letterbox, area, letterbox_area) against a stub that records the zly_config it is handed
-$(OUT)/test_plugin_area_stub: tests/cpp/test_plugin_area_stub.cpp $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_compat.hpp include/zly.h | $(OUT)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_plugin_area_stub.cpp -pthread
+$(OUT)/test_plugin_area_stub: tests/cpp/test_plugin_area_stub.cpp $(ABI_STUB) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -I$(CSRC) -o $@ tests/cpp/test_plugin_area_stub.cpp -pthread
 
 # the area resize filter's per-axis footprint arithmetic (csrc/area_device.h) as the pre-pass kernel computes it, printed for tests/test_area_footprint.py (test infrastructure: no GPU)
 $(OUT)/test_area_footprint: tests/cpp/test_area_footprint.cpp $(CSRC)/area_device.h | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ tests/cpp/test_area_footprint.cpp
+
+# the frame and view rules (csrc/frame_rules.h) on their own, for tests/test_frame_rules.py (test infrastructure: no GPU, nothing of the engine) ...
+$(OUT)/test_frame_rules: tests/cpp/test_frame_rules.cpp $(CSRC)/frame_rules.h $(CSRC)/front_variants.h include/zly.h | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(CSRC) -o $@ tests/cpp/test_frame_rules.cpp
+# ... and under the host sanitizers: not part of `all`; make frame_rules_san && $(OUT)/test_frame_rules_san
+frame_rules_san: $(OUT)/test_frame_rules_san
+$(OUT)/test_frame_rules_san: tests/cpp/test_frame_rules.cpp $(CSRC)/frame_rules.h $(CSRC)/front_variants.h include/zly.h | $(OUT)
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(CSRC) -o $@ tests/cpp/test_frame_rules.cpp
 
 $(OUT)/test_wire: tests/cpp/test_wire.cpp $(HOST)/zly_wire.hpp $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -I$(HOST) -o $@ tests/cpp/test_wire.cpp
@@ -166,4 +176,4 @@ $(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_
 clean:
 	rm -rf $(OUT) oracle/_build
 
-.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe clean
+.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe frame_rules_san clean

@@ -1,131 +1,10 @@
 // test_plugin_crop_stub.cpp -- the plugin's ZLY_CROP (detect every request in the centred W x H window of its frame) without a GPU: the window
 // arithmetic, the even rounding for YUV input, the small-request rule, and the map of the boxes back to fractions of the request frame.
-// TEST INFRASTRUCTURE: host/hip_inference_engine.cpp is compiled into this binary together with a link-time stub of the C-ABI entry points it
-// calls, among them the frame-view calls.  The stub is not a CPU fallback of the product.  Its fake engine records the view it is handed and
-// "detects" one fixed box (in window coordinates) per frame.
+// TEST INFRASTRUCTURE: the plugin against the link-time stub of the C ABI of plugin_abi_stub.hpp, whose fake engine records the view it is handed
+// and "detects" one fixed box (in window coordinates) per frame.
 //
 //   test_plugin_crop_stub <report.txt> <bgr|nv12>          (ZLY_CROP / ZLY_INPUT_FORMAT are set by the driver itself)
-#include "../../zero-latency-yolo_amd/host/hip_inference_engine.cpp"
-
-#include <fstream>
-#include <thread>
-
-// ------------------------------------------------------------------------------------------------ stub of the C ABI
-struct Submitted { bool view; zly_frame_view v; size_t buf_bytes; int32_t w, h, fmt; };
-struct zly_engine {
-    std::mutex mu;
-    std::map<uint64_t, Submitted> pending;
-    uint64_t next_ticket = 1;
-    std::atomic<uint64_t> frames{0};
-};
-namespace {
-std::mutex g_mu;
-std::vector<Submitted> g_log;                            // every accepted submit, in order
-thread_local std::string g_err;
-const float BOX[4] = {0.25f, 0.625f, 0.1f, 0.3f};        // what the fake engine detects: centre x, centre y, w, h as fractions of what it was handed
-
-int planes_of(int32_t fmt, int32_t w, int32_t h, int64_t rows[3], int64_t rb[3])
-{
-    if (fmt < ZLY_PIX_BGR || fmt > ZLY_PIX_I420_BT709 || w < 1 || h < 1) return 0;
-    if (fmt == ZLY_PIX_BGR) { rows[0] = h; rb[0] = 3 * (int64_t)w; return 1; }
-    if ((w | h) & 1) return 0;
-    rows[0] = h; rb[0] = w;
-    if (fmt == ZLY_PIX_NV12_BT601 || fmt == ZLY_PIX_NV12_BT709) { rows[1] = h / 2; rb[1] = w; return 2; }
-    rows[1] = rows[2] = h / 2; rb[1] = rb[2] = w / 2;
-    return 3;
-}
-int32_t accept(zly_engine* e, const Submitted& s, uint64_t* ticket)
-{
-    std::lock_guard<std::mutex> lk(e->mu);
-    *ticket = e->next_ticket++;
-    e->pending[*ticket] = s;
-    std::lock_guard<std::mutex> lg(g_mu);
-    g_log.push_back(s);
-    return ZLY_OK;
-}
-}
-
-extern "C" {
-void zly_default_config(zly_config* c) { std::memset(c, 0, sizeof *c); c->model_w = 416; c->model_h = 416; c->conf_thr = 0.5f; c->iou_thr = 0.45f; c->max_batch = 1; c->max_dets = 64; c->warmup_runs = 3; c->use_graph = 1; }
-const char* zly_last_error(void) { return g_err.c_str(); }
-int32_t zly_create(const zly_config*, zly_engine** out) { *out = new zly_engine(); return ZLY_OK; }
-int32_t zly_destroy(zly_engine* e) { delete e; return ZLY_OK; }
-size_t zly_view_bytes(const zly_frame_view* v)
-{
-    int64_t rows[3], rb[3];
-    const int np = planes_of(v->fmt, v->w, v->h, rows, rb);
-    size_t most = 0;
-    for (int p = 0; p < np; ++p) {
-        if (v->pitch[p] < rb[p]) return 0;
-        most = std::max<size_t>(most, (size_t)v->off[p] + (size_t)((rows[p] - 1) * v->pitch[p] + rb[p]));
-    }
-    return most;
-}
-int32_t zly_view_tight(int32_t fmt, int32_t w, int32_t h, zly_frame_view* out)
-{
-    int64_t rows[3], rb[3];
-    const int np = planes_of(fmt, w, h, rows, rb);
-    if (!np) return ZLY_ERR_INVALID_ARGUMENT;
-    std::memset(out, 0, sizeof *out);
-    out->fmt = fmt; out->w = w; out->h = h;
-    uint64_t off = 0;
-    for (int p = 0; p < np; ++p) { out->off[p] = off; out->pitch[p] = (int32_t)rb[p]; off += (uint64_t)(rows[p] * rb[p]); }
-    return ZLY_OK;
-}
-int32_t zly_view_crop(const zly_frame_view* s, int32_t x0, int32_t y0, int32_t w, int32_t h, zly_frame_view* out)
-{
-    if (x0 < 0 || y0 < 0 || w < 1 || h < 1 || x0 + w > s->w || y0 + h > s->h) return ZLY_ERR_INVALID_ARGUMENT;
-    zly_frame_view v = *s;
-    v.w = w; v.h = h;
-    if (v.fmt == ZLY_PIX_BGR) v.off[0] += (uint64_t)y0 * v.pitch[0] + (uint64_t)x0 * 3;
-    else {
-        if ((x0 | y0 | w | h) & 1) return ZLY_ERR_INVALID_ARGUMENT;
-        v.off[0] += (uint64_t)y0 * v.pitch[0] + (uint64_t)x0;
-        const bool nv12 = v.fmt == ZLY_PIX_NV12_BT601 || v.fmt == ZLY_PIX_NV12_BT709;
-        v.off[1] += (uint64_t)(y0 / 2) * v.pitch[1] + (uint64_t)(x0 / 2) * (nv12 ? 2 : 1);
-        if (!nv12) v.off[2] += (uint64_t)(y0 / 2) * v.pitch[2] + (uint64_t)(x0 / 2);
-    }
-    *out = v;
-    return ZLY_OK;
-}
-int32_t zly_submit_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket)
-{
-    zly_frame_view t;
-    if (!frame || zly_view_tight(fmt, w, h, &t) != ZLY_OK || nbytes != zly_view_bytes(&t)) { g_err = "Invalid image data size"; return ZLY_ERR_INVALID_INPUT; }
-    return accept(e, Submitted{false, t, nbytes, w, h, fmt}, ticket);
-}
-int32_t zly_submit_try_fmt(zly_engine* e, int32_t fmt, const uint8_t* frame, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket) { return zly_submit_fmt(e, fmt, frame, nbytes, w, h, ticket); }
-int32_t zly_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket) { return zly_submit_fmt(e, ZLY_PIX_BGR, bgr, nbytes, w, h, ticket); }
-int32_t zly_submit_try(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, uint64_t* ticket) { return zly_submit_fmt(e, ZLY_PIX_BGR, bgr, nbytes, w, h, ticket); }
-int32_t zly_submit_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, uint64_t* ticket)
-{
-    const size_t need = zly_view_bytes(v);
-    if (!base || !need || need > buf_bytes) { g_err = "Invalid image data size"; return ZLY_ERR_INVALID_INPUT; }
-    return accept(e, Submitted{true, *v, buf_bytes, v->w, v->h, v->fmt}, ticket);
-}
-int32_t zly_submit_try_view(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, uint64_t* ticket) { return zly_submit_view(e, base, buf_bytes, v, ticket); }
-int32_t zly_poll(zly_engine* e, uint64_t ticket)
-{
-    std::lock_guard<std::mutex> lk(e->mu);
-    return e->pending.count(ticket) ? ZLY_OK : ZLY_ERR_INVALID_ARGUMENT;
-}
-int32_t zly_wait(zly_engine* e, uint64_t ticket, zly_det* out, int32_t cap, int32_t* n_out)
-{
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (!e->pending.erase(ticket)) return ZLY_ERR_INVALID_ARGUMENT;
-    }
-    if (cap >= 1) {
-        std::memset(out, 0, sizeof *out);
-        out[0].x = BOX[0]; out[0].y = BOX[1]; out[0].w = BOX[2]; out[0].h = BOX[3]; out[0].confidence = 0.75f; out[0].class_id = 2;
-    }
-    *n_out = 1;
-    e->frames++;
-    return ZLY_OK;
-}
-int32_t zly_get_stats(const zly_engine* e, zly_stats* out) { std::memset(out, 0, sizeof *out); out->batches = e->frames.load(); return ZLY_OK; }
-int32_t zly_weights_fp8(const zly_engine*) { return 0; }
-}
+#include "plugin_abi_stub.hpp"
 
 // ------------------------------------------------------------------------------------------------ the test
 using namespace zero_latency;
@@ -195,9 +74,10 @@ int main(int argc, char** argv)
     std::this_thread::sleep_for(std::chrono::milliseconds(20));
     auto st = engine->getStatus();
     engine->shutdown();
+    const std::vector<stub::Event> g_log = stub::log(stub::Event::SUBMIT);      // every accepted submit, in order
     rep << "callbacks=" << seen.size() << "\nstatus_errors=" << st["inference_errors"] << "\nlogged=" << g_log.size() << "\n";
     for (size_t i = 0; i < g_log.size() && i < seen.size(); ++i) {
-        const Submitted& s = g_log[i];
+        const stub::Event& s = g_log[i];
         const Detection& d = seen[i].second;
         rep << "req[" << i << "]=" << sizes[i][0] << "," << sizes[i][1] << "," << (s.view ? 1 : 0) << "," << s.w << "," << s.h << "," << s.fmt << ","
             << s.v.off[0] << "," << s.v.off[1] << "," << s.v.pitch[0] << "," << s.v.pitch[1] << "," << s.buf_bytes << ","

@@ -9,6 +9,7 @@
 // and C2f's split never move data: producers write into channel slices of the consumer's concat
 // buffer (ConvArgs::out_cs/out_co) and consumers read channel slices (in_cs/in_co).
 #include "zly_internal.h"
+#include "frame_rules.h"
 #include "weights.h"
 
 #include <algorithm>
@@ -1530,103 +1531,11 @@ static uint64_t now_ms()
 
 static void ingest_destroy(zly_engine* e);
 
-// the known formats are a set, not a range (include/zly.h): 5..9, 14 and 15 lie between the YUV layouts and the packed RGB family and are unknown
-static bool fmt_yuv(int32_t fmt) { return fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709; }      // YUV 4:2:0: two or three planes, even width and height
-static bool fmt_yuv422(int32_t fmt) { return fmt >= ZLY_PIX_YUY2_BT601 && fmt <= ZLY_PIX_UYVY_BT709; }   // packed YUV 4:2:2: one plane of 4-byte macropixels, even width
-static bool fmt_known(int32_t fmt) { return fmt == ZLY_PIX_BGR || fmt_yuv(fmt) || fmt_yuv422(fmt) || fmt == ZLY_PIX_RGB || fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA; }
-// bytes per pixel of a one-plane format (BGR, RGB: 3; BGRA, RGBA: 4; packed 4:2:2: 2, in macropixels of two)
-static uint32_t fmt_bpp(int32_t fmt) { return fmt == ZLY_PIX_BGRA || fmt == ZLY_PIX_RGBA ? 4u : fmt_yuv422(fmt) ? 2u : 3u; }
-
-// the request checks of every entry point that takes host frames (onnx_engine.cpp:659-665): an unknown format is an argument error; a byte count
-// that is not zly_frame_bytes(fmt, w, h) -- odd or too small YUV sizes included -- is ZLY_ERR_INVALID_INPUT
-static int check_frame(int32_t fmt, const uint8_t* p, size_t nbytes, int32_t w, int32_t h)
-{
-    if (!fmt_known(fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(fmt));
-    const size_t want = zly_frame_bytes(fmt, w, h);
-    if (!p || want == 0 || nbytes != want) {
-        const size_t shown = want ? want : (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * (fmt_yuv(fmt) ? 3u : 2u * fmt_bpp(fmt)) / 2u;
-        return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: expected " + std::to_string(shown) + ", got " + std::to_string(nbytes) +
-                                           (fmt_yuv(fmt) && (w < 2 || h < 2 || (w | h) & 1) ? " (YUV 4:2:0 needs even width and height >= 2)" :
-                                            fmt_yuv422(fmt) && (w < 2 || (w & 1)) ? " (packed YUV 4:2:2 needs even width >= 2)" : ""));
-    }
-    return ZLY_OK;
-}
-
-// a letterbox engine's fixed-point resize fits int32 for requests of up to ZLY_LETTERBOX_MAX_DIM pixels on a side (include/zly.h)
-static int check_frame_mode(const zly_engine* e, int32_t w, int32_t h)
-{
-    if ((e->cfg.flags & ZLY_FLAG_LETTERBOX) && (w > ZLY_LETTERBOX_MAX_DIM || h > ZLY_LETTERBOX_MAX_DIM))
-        return fail(ZLY_ERR_INVALID_INPUT, "letterbox mode takes frames of at most " + std::to_string(ZLY_LETTERBOX_MAX_DIM) + " pixels on a side, got " +
-                                           std::to_string(w) + " x " + std::to_string(h));
-    // so does an area engine's exact average (the products of the footprint arithmetic stay below 2^28)
-    if ((e->cfg.flags & ZLY_FLAG_AREA) && (w > ZLY_AREA_MAX_DIM || h > ZLY_AREA_MAX_DIM))
-        return fail(ZLY_ERR_INVALID_INPUT, "area mode takes frames of at most " + std::to_string(ZLY_AREA_MAX_DIM) + " pixels on a side, got " +
-                                           std::to_string(w) + " x " + std::to_string(h));
-    return ZLY_OK;
-}
-
-// ---- frame views (include/zly.h zly_frame_view) ----
-// planes of a w x h frame of format fmt: rows and bytes per row of each; 0 for an unknown format or invalid dimensions
-static int view_plane_shape(int32_t fmt, int32_t w, int32_t h, int64_t rows[3], int64_t row_bytes[3])
-{
-    if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
-    if (fmt_yuv422(fmt) && (w < 2 || (w & 1))) return 0;          // whole macropixels; any height
-    if (!fmt_yuv(fmt)) { rows[0] = h; row_bytes[0] = (int64_t)fmt_bpp(fmt) * (int64_t)w; return 1; }
-    if (w < 2 || h < 2 || ((w | h) & 1)) return 0;
-    rows[0] = h; row_bytes[0] = w;
-    if (fmt == ZLY_PIX_NV12_BT601 || fmt == ZLY_PIX_NV12_BT709) { rows[1] = h / 2; row_bytes[1] = w; return 2; }      // 2 * (w/2)
-    rows[1] = rows[2] = h / 2; row_bytes[1] = row_bytes[2] = w / 2;
-    return 3;
-}
-
-// include/zly.h's validity rule; *need = the smallest buffer that holds the view
-static bool view_valid(const zly_frame_view* v, size_t* need)
-{
-    int64_t rows[3], rb[3];
-    const int np = v ? view_plane_shape(v->fmt, v->w, v->h, rows, rb) : 0;
-    if (!np) return false;
-    uint64_t most = 0;
-    for (int p = 0; p < np; ++p) {
-        if ((int64_t)v->pitch[p] < rb[p]) return false;
-        const uint64_t ext = (uint64_t)(rows[p] - 1) * (uint64_t)v->pitch[p] + (uint64_t)rb[p];
-        if (ext >= (1ull << 31)) return false;
-        if (v->off[p] > UINT64_MAX - ext) return false;
-        most = std::max<uint64_t>(most, v->off[p] + ext);
-    }
-    if (most > (uint64_t)SIZE_MAX) return false;
-    *need = (size_t)most;
-    return true;
-}
-
-// the request checks of every entry point that takes a view: an unknown format is an argument error; an otherwise invalid view, or one that does
-// not fit the caller's buffer, is ZLY_ERR_INVALID_INPUT (as a wrong byte count is); letterbox engines bound the view's size
-static int check_view(const zly_engine* e, const void* base, size_t buf_bytes, const zly_frame_view* v)
-{
-    if (!v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null view");
-    if (!fmt_known(v->fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(v->fmt));
-    size_t need = 0;
-    if (!view_valid(v, &need)) return fail(ZLY_ERR_INVALID_INPUT, "invalid frame view (size " + std::to_string(v->w) + " x " + std::to_string(v->h) +
-                                                                  ": YUV 4:2:0 needs even width and height >= 2, packed 4:2:2 even width >= 2, every pitch at least its row's bytes, every plane below 2 GiB)");
-    if (!base || need > buf_bytes) return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: the view needs " + std::to_string(need) + " bytes, got " + std::to_string(buf_bytes));
-    return check_frame_mode(e, v->w, v->h);
-}
-
-// the region's rows, plane by plane, as the tight frame of zly_frame_bytes(fmt, w, h) at dst: the one host copy of a view request
-static void copy_view_tight(uint8_t* dst, const uint8_t* base, const zly_frame_view* v)
-{
-    int64_t rows[3], rb[3];
-    const int np = view_plane_shape(v->fmt, v->w, v->h, rows, rb);
-    for (int p = 0; p < np; ++p) {
-        const uint8_t* q = base + v->off[p];
-        if ((int64_t)v->pitch[p] == rb[p]) { memcpy(dst, q, (size_t)(rows[p] * rb[p])); dst += rows[p] * rb[p]; continue; }
-        for (int64_t r = 0; r < rows[p]; ++r, q += v->pitch[p], dst += rb[p]) memcpy(dst, q, (size_t)rb[p]);
-    }
-}
-
+// what the VIEW instantiations of the front kernels read of a (checked) view
 static ViewRec view_rec(const zly_frame_view* v)
 {
     int64_t rows[3], rb[3];
-    const int np = view_plane_shape(v->fmt, v->w, v->h, rows, rb);
+    const int np = plane_shape(v->fmt, v->w, v->h, rows, rb);
     ViewRec r{};
     r.off1 = np > 1 ? v->off[1] : 0; r.off2 = np > 2 ? v->off[2] : 0;
     r.pitch0 = v->pitch[0]; r.pitch1 = np > 1 ? v->pitch[1] : 0; r.pitch2 = np > 2 ? v->pitch[2] : 0;
@@ -1953,11 +1862,11 @@ static int ingest_submit(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32
 {
     int rcv;
     if (view) {
-        rcv = check_view(e, bgr, nbytes, view);
+        rcv = check_view(e->cfg.flags, bgr, nbytes, view, &g_last_error);
         if (rcv == ZLY_OK) { fmt = view->fmt; w = view->w; h = view->h; nbytes = zly_frame_bytes(fmt, w, h); }
     } else {
-        rcv = check_frame(fmt, bgr, nbytes, w, h);
-        if (rcv == ZLY_OK) rcv = check_frame_mode(e, w, h);
+        rcv = check_frame(fmt, bgr, nbytes, w, h, &g_last_error);
+        if (rcv == ZLY_OK) rcv = check_frame_mode(e->cfg.flags, w, h, &g_last_error);
     }
     if (rcv != ZLY_OK) {
         with_stats(e, [](zly_stats& st) { st.inference_errors++; });
@@ -2276,11 +2185,11 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     for (int i = 0; i < n; ++i) {
         int rcv;
         if (views) {
-            rcv = check_view(e, bgr[i], nbytes[i], &views[i]);
+            rcv = check_view(e->cfg.flags, bgr[i], nbytes[i], &views[i], &g_last_error);
             vw[(size_t)i] = views[i].w; vh[(size_t)i] = views[i].h; vf[(size_t)i] = views[i].fmt;
         } else {
-            rcv = check_frame(fmt ? fmt[i] : ZLY_PIX_BGR, bgr[i], nbytes[i], w[i], h[i]);
-            if (rcv == ZLY_OK) rcv = check_frame_mode(e, w[i], h[i]);
+            rcv = check_frame(fmt ? fmt[i] : ZLY_PIX_BGR, bgr[i], nbytes[i], w[i], h[i], &g_last_error);
+            if (rcv == ZLY_OK) rcv = check_frame_mode(e->cfg.flags, w[i], h[i], &g_last_error);
         }
         if (rcv != ZLY_OK) {
             with_stats(e, [](zly_stats& st) { st.inference_errors++; });
@@ -2329,75 +2238,26 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     return ZLY_OK;
 }
 
-size_t zly_frame_bytes(int32_t fmt, int32_t w, int32_t h)
-{
-    if (!fmt_known(fmt) || w < 1 || h < 1) return 0;
-    if (fmt_yuv422(fmt) && (w < 2 || (w & 1))) return 0;               // 4:2:2: whole macropixels of two pixels; any height
-    if (!fmt_yuv(fmt)) return (size_t)w * (size_t)h * fmt_bpp(fmt);
-    if (w < 2 || h < 2 || (w & 1) || (h & 1)) return 0;                // 4:2:0: one chroma sample per 2 x 2 block
-    return (size_t)w * (size_t)h * 3u / 2u;
-}
+// the host-only entry points: the rules are frame_rules.h's
+size_t zly_frame_bytes(int32_t fmt, int32_t w, int32_t h) { return frame_bytes(fmt, w, h); }
 
-size_t zly_view_bytes(const zly_frame_view* v)
-{
-    size_t need = 0;
-    return view_valid(v, &need) ? need : 0;
-}
+size_t zly_view_bytes(const zly_frame_view* v) { return view_bytes(v); }
 
 int32_t zly_view_tight(int32_t fmt, int32_t w, int32_t h, zly_frame_view* out)
 {
-    int64_t rows[3], rb[3];
     if (!out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
-    const int np = view_plane_shape(fmt, w, h, rows, rb);
-    if (!np) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_tight: unknown format or invalid size");
-    zly_frame_view v{};
-    v.fmt = fmt; v.w = w; v.h = h;
-    uint64_t off = 0;
-    for (int p = 0; p < np; ++p) {                       // the planes follow each other without padding, rows without pitch
-        v.off[p] = off; v.pitch[p] = (int32_t)rb[p];
-        off += (uint64_t)rows[p] * (uint64_t)rb[p];
-    }
-    *out = v;
-    return ZLY_OK;
+    return view_tight(fmt, w, h, out, &g_last_error);
 }
 
 int32_t zly_view_crop(const zly_frame_view* surface, int32_t x0, int32_t y0, int32_t w, int32_t h, zly_frame_view* out)
 {
     if (!surface || !out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
-    size_t need = 0;
-    if (!view_valid(surface, &need)) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: invalid surface view");
-    if (x0 < 0 || y0 < 0 || w < 1 || h < 1 || (int64_t)x0 + w > surface->w || (int64_t)y0 + h > surface->h)
-        return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: the rectangle is not inside the surface");
-    zly_frame_view v = *surface;                         // (out may be the surface itself: crops compose)
-    v.w = w; v.h = h;
-    if (!fmt_yuv(v.fmt)) {
-        if (fmt_yuv422(v.fmt) && ((x0 | w) & 1)) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: a packed YUV 4:2:2 rectangle needs even x0 and w");
-        v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0 * fmt_bpp(v.fmt);
-    } else {
-        if ((x0 | y0 | w | h) & 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_view_crop: a YUV 4:2:0 rectangle needs even x0, y0, w, h");
-        v.off[0] += (uint64_t)y0 * (uint64_t)v.pitch[0] + (uint64_t)x0;
-        if (v.fmt == ZLY_PIX_NV12_BT601 || v.fmt == ZLY_PIX_NV12_BT709) {
-            v.off[1] += (uint64_t)(y0 / 2) * (uint64_t)v.pitch[1] + (uint64_t)(x0 / 2) * 2u;
-        } else {
-            v.off[1] += (uint64_t)(y0 / 2) * (uint64_t)v.pitch[1] + (uint64_t)(x0 / 2);
-            v.off[2] += (uint64_t)(y0 / 2) * (uint64_t)v.pitch[2] + (uint64_t)(x0 / 2);
-        }
-    }
-    *out = v;
-    return ZLY_OK;
+    return view_crop(surface, x0, y0, w, h, out, &g_last_error);
 }
 
 int32_t zly_letterbox_geometry(int32_t w, int32_t h, int32_t model_w, int32_t model_h, int32_t* nw, int32_t* nh, int32_t* pad_x, int32_t* pad_y)
 {
-    if (w < 1 || h < 1 || model_w < 1 || model_h < 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_letterbox_geometry: sizes must be positive");
-    if (!nw || !nh || !pad_x || !pad_y) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
-    const int64_t W = w, H = h, TW = model_w, TH = model_h;
-    int64_t cw, ch;
-    if (TW * H <= TH * W) { cw = TW; ch = std::max<int64_t>(1, (2 * H * TW + W) / (2 * W)); }      // the width binds
-    else                  { ch = TH; cw = std::max<int64_t>(1, (2 * W * TH + H) / (2 * H)); }
-    *nw = (int32_t)cw; *nh = (int32_t)ch;
-    *pad_x = (int32_t)((TW - cw) >> 1); *pad_y = (int32_t)((TH - ch) >> 1);
-    return ZLY_OK;
+    return letterbox_geometry(w, h, model_w, model_h, nw, nh, pad_x, pad_y, &g_last_error);      // null outputs are refused there, behind the sizes
 }
 
 int32_t zly_detect(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, zly_det* out, int32_t cap, int32_t* n_out)
@@ -2412,7 +2272,7 @@ int32_t zly_detect_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_t nb
     std::lock_guard<std::mutex> lk(e->mu);
     const auto t0 = std::chrono::steady_clock::now();
     const uint8_t* ptrs[1] = {bgr};
-    int rc = detect_host_locked(e, 1, ptrs, &nbytes, &w, &h, out, cap, n_out, fmt == ZLY_PIX_BGR ? nullptr : &fmt);
+    int rc = detect_host_locked(e, 1, ptrs, &nbytes, &w, &h, out, cap, n_out, &fmt);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     with_stats(e, [&](zly_stats& st) { st.last_detect_ms = ms; });
     return rc;
@@ -2520,11 +2380,11 @@ int32_t zly_detect_device(zly_engine* e, int32_t n, const void* d_frames, int32_
 int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void* d_frames, int32_t w, int32_t h, void* d_slabs, uint32_t frame_tag0, void* stream)
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
-    if (!fmt_known(fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(fmt));
+    if (!pix_format(fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(fmt));
     const size_t fb = zly_frame_bytes(fmt, w, h);
     if (!d_frames || w <= 0 || h <= 0 || fb == 0) return fail(ZLY_ERR_INVALID_INPUT, "bad frame pointer or size");
     if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
-    if (int rcm = check_frame_mode(e, w, h)) return rcm;
+    if (int rcm = check_frame_mode(e->cfg.flags, w, h, &g_last_error)) return rcm;
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
@@ -2554,7 +2414,7 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     std::vector<ViewRec> recs((size_t)n);
     int level = ZLY_FRONT_BGR;
     for (int i = 0; i < n; ++i) {
-        if (int rcv = check_view(e, d_base, buf_bytes, &v[i])) return rcv;
+        if (int rcv = check_view(e->cfg.flags, d_base, buf_bytes, &v[i], &g_last_error)) return rcv;
         ws[(size_t)i] = v[i].w; hs[(size_t)i] = v[i].h; fs[(size_t)i] = v[i].fmt; offs[(size_t)i] = (size_t)v[i].off[0];
         recs[(size_t)i] = view_rec(&v[i]);
         level = std::max(level, front_level(v[i].fmt));
@@ -2840,38 +2700,11 @@ void zly_default_merge_config(zly_merge_config* c)
     c->thr = 0.5f;
 }
 
-// one axis of zly_tile_grid: the number of tiles and their size; false when the arguments are refused
-static bool grid_axis(int32_t extent, int32_t tile, int32_t overlap, bool even, int64_t* count, int32_t* size, int32_t* step)
-{
-    if (extent < 1 || extent >= (1 << 24) || tile < 1 || overlap < 0 || overlap >= tile) return false;
-    if (even && ((extent | tile) & 1)) return false;
-    *step = tile - overlap;
-    if (tile >= extent) { *count = 1; *size = extent; return true; }
-    *size = tile;
-    *count = ((int64_t)(extent - tile) + *step - 1) / *step + 1;
-    return true;
-}
-
 int32_t zly_tile_grid(int32_t W, int32_t H, int32_t tile_w, int32_t tile_h, int32_t overlap_x, int32_t overlap_y, int32_t even, zly_tile* out,
                       int32_t cap, int32_t* n_out)
 {
     if (!n_out || cap < 0 || (cap > 0 && !out)) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_tile_grid: null output");
-    int64_t nx = 0, ny = 0;
-    int32_t tw = 0, th = 0, sx = 0, sy = 0;
-    if (!grid_axis(W, tile_w, overlap_x, even != 0, &nx, &tw, &sx) || !grid_axis(H, tile_h, overlap_y, even != 0, &ny, &th, &sy))
-        return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_tile_grid: the surface must lie in 1..2^24-1, a tile be >= 1 and its overlap in [0, tile); even surfaces need even sizes");
-    if (nx * ny > 0x7fffffff) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_tile_grid: too many tiles");
-    int64_t k = 0;
-    for (int64_t j = 0; j < ny && k < cap; ++j)
-        for (int64_t i = 0; i < nx && k < cap; ++i, ++k) {
-            int64_t x0 = std::min<int64_t>(i * sx, W - tw), y0 = std::min<int64_t>(j * sy, H - th);
-            if (even) { x0 &= ~(int64_t)1; y0 &= ~(int64_t)1; }
-            zly_tile t;
-            t.group = 0; t.x0 = (int32_t)x0; t.y0 = (int32_t)y0; t.w = tw; t.h = th; t.W = W; t.H = H;
-            out[k] = t;
-        }
-    *n_out = (int32_t)(nx * ny);
-    return ZLY_OK;
+    return tile_grid(W, H, tile_w, tile_h, overlap_x, overlap_y, even, out, cap, n_out, &g_last_error);
 }
 
 // the argument checks of a merge (include/zly.h lists them); *max_slots = the largest tiles x cap of a group
@@ -3010,7 +2843,7 @@ int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, c
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!surface || !out || !n_out || cap < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
-    if (!fmt_known(surface->fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(surface->fmt));
+    if (!pix_format(surface->fmt)) return fail(ZLY_ERR_INVALID_ARGUMENT, "unknown pixel format " + std::to_string(surface->fmt));
     size_t nbytes = 0;
     if (!view_valid(surface, &nbytes)) return fail(ZLY_ERR_INVALID_INPUT, "invalid surface view");
     if (!base || nbytes > buf_bytes) return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: the surface needs " + std::to_string(nbytes) + " bytes, got " + std::to_string(buf_bytes));
@@ -3026,7 +2859,7 @@ int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, c
         if (t.group != 0 || t.W != surface->w || t.H != surface->h)
             return fail(ZLY_ERR_INVALID_ARGUMENT, "tile " + std::to_string(i) + ": zly_detect_tiled needs group = 0 and W, H = the surface's size");
         if (int rc = zly_view_crop(surface, t.x0, t.y0, t.w, t.h, &views[(size_t)i])) return rc;
-        if (int rc = check_view(e, base, buf_bytes, &views[(size_t)i])) return rc;
+        if (int rc = check_view(e->cfg.flags, base, buf_bytes, &views[(size_t)i], &g_last_error)) return rc;
         const zly_frame_view& v = views[(size_t)i];
         ws[(size_t)i] = v.w; hs[(size_t)i] = v.h; fs[(size_t)i] = v.fmt; offs[(size_t)i] = (size_t)v.off[0];
         recs[(size_t)i] = view_rec(&v);
@@ -3073,8 +2906,8 @@ int32_t zly_preprocess_fmt(zly_engine* e, int32_t fmt, const uint8_t* bgr, size_
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!out_nchw) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
-    if (int rcv = check_frame(fmt, bgr, nbytes, w, h)) return rcv;
-    if (int rcm = check_frame_mode(e, w, h)) return rcm;
+    if (int rcv = check_frame(fmt, bgr, nbytes, w, h, &g_last_error)) return rcv;
+    if (int rcm = check_frame_mode(e->cfg.flags, w, h, &g_last_error)) return rcm;
     std::lock_guard<std::mutex> lk(e->mu);
     ExclusiveGate gl;                                    // parity / debug entry point: allocations and copies, alone in the process
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
@@ -3102,7 +2935,7 @@ int32_t zly_preprocess_view(zly_engine* e, const uint8_t* base, size_t buf_bytes
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!out_nchw) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
-    if (int rcv = check_view(e, base, buf_bytes, v)) return rcv;
+    if (int rcv = check_view(e->cfg.flags, base, buf_bytes, v, &g_last_error)) return rcv;
     const size_t nbytes = zly_view_bytes(v);             // the buffer's first bytes as they are: the kernel fetches through the view
     std::lock_guard<std::mutex> lk(e->mu);
     ExclusiveGate gl;                                    // parity / debug entry point: allocations and copies, alone in the process
@@ -3426,7 +3259,7 @@ int32_t zly_profile_ops(zly_engine* e, int32_t n, const void* d_frames, int32_t 
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!d_frames || !ms_out || reps < 1 || n < 1 || n > e->cfg.max_batch || w < 1 || h < 1) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rcm = check_frame_mode(e, w, h)) return rcm;
+    if (int rcm = check_frame_mode(e->cfg.flags, w, h, &g_last_error)) return rcm;
     std::lock_guard<std::mutex> lk(e->mu);
     ExclusiveGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);

@@ -23,13 +23,6 @@ __host__ __device__ __forceinline__ unsigned long long desc_pack(unsigned long l
 __host__ __device__ __forceinline__ unsigned long long desc_off(unsigned long long v) { return v & ((1ull << ZLY_DESC_FMT_SHIFT) - 1); }
 __host__ __device__ __forceinline__ int desc_fmt(unsigned long long v) { return (int)(v >> ZLY_DESC_FMT_SHIFT); }
 
-// The format level a frame of this format asks of the front kernels (front_variants.h: ZLY_FRONT_*)
-__host__ __device__ __forceinline__ int front_level(int fmt)
-{
-    return fmt == ZLY_PIX_BGR ? ZLY_FRONT_BGR : fmt >= ZLY_PIX_NV12_BT601 && fmt <= ZLY_PIX_I420_BT709 ? ZLY_FRONT_YUV :
-           fmt >= ZLY_PIX_YUY2_BT601 && fmt <= ZLY_PIX_UYVY_BT709 ? ZLY_FRONT_YUV422 : ZLY_FRONT_PACKED;
-}
-
 // What a frame view (zly_frame_view, include/zly.h) adds to a frame's descriptor: the offsets of planes 1 and 2 and the three row pitches; plane 0's
 // offset is FrameDesc::src_off, the view's size FrameDesc::w, h.  32 bytes = two 16-byte scalar loads, uniform per workgroup.  The n records of a
 // call lie right behind its n descriptors (desc + n), so no kernel argument changes; only the VIEW instantiations of the front kernels
