@@ -588,6 +588,73 @@ int32_t zly_tile_grid(int32_t W, int32_t H, int32_t tile_w, int32_t tile_h, int3
 int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* surface, int32_t n, const zly_tile* tiles,
                          const zly_merge_config* cfg, zly_det* out, int32_t cap, int32_t* n_out);
 
+/* --- Resident surfaces -------------------------------------------------------------------------------------------------------------
+ * Keeps the last frame of each capture stream in HBM, where the front kernel reads it, and takes "these rectangles changed" instead of the whole
+ * frame.  Every other way of handing over a frame from host memory copies all of it into pinned staging and uploads all of it, every time; screen
+ * capture knows better (DXGI desktop duplication hands out dirty rectangles with every frame, and the reference's own client computes the changed
+ * region of each capture, src/client/screen_capture.cpp:394-470, use_difference_encoding).  Opt-in per engine: an engine that never calls
+ * zly_surfaces_enable allocates nothing more and launches what it launched before.
+ *
+ * The STORE is one device allocation of max_surfaces SLOTS at a fixed stride (max_bytes_each rounded up to ZLY_SURFACE_ALIGN).  A slot that has been
+ * defined holds one tight frame (the layout of zly_view_tight) of the slot's format and size.  A slot is VALID once an update has covered it whole
+ * (the keyframe) since it was last defined.
+ * THE RULE: after any sequence of defines and updates a slot holds, byte for byte, the tight frame obtained by applying those rectangles in call
+ * order to the frame (a byte that no rectangle has written since the define is unspecified: hence the keyframe).  Detecting on it gives, bit for
+ * bit, what zly_detect_device_view gives for the same frames uploaded whole -- in a call of the same engine, batch size and composition, with
+ * stretch, letterbox or area resize.
+ * How: the calling thread copies each rectangle's rows tight into the engine's pinned staging, one copy takes pixels and job table up, and ONE
+ * launch of a patch kernel (csrc/kernels_surface.hip) writes every rectangle of the call into the store, whatever their number; it writes no byte
+ * outside a rectangle.  Detection builds frame views into the store and takes the device-view path as it is.
+ * Not covered: the pipelined submit ring (its slots are tight frames in a staging buffer of their own), the plugin and the wire format (a request
+ * carries no rectangle), engines behind host/zly_sharded*.hpp, skipping inference for unchanged tiles (results across batch sizes are not
+ * bit-identical, so it would break the rule), and move rectangles. */
+#define ZLY_SURFACE_MAX_RECTS 1024      /* rectangles per zly_surface_update / zly_detect_delta call (chosen) */
+#define ZLY_SURFACE_ALIGN     256       /* the slot stride is a multiple of it */
+#define ZLY_SURFACE_STORE_MAX (1ull << 56)   /* largest store in bytes: a view's plane-0 offset rides in 56 bits of the front kernels' frame descriptor */
+typedef struct zly_surface_rect {
+    int32_t surface;          /* slot index */
+    int32_t x0, y0;           /* where the rectangle's first pixel lies in the surface; its size and format are the source view's */
+} zly_surface_rect;
+typedef struct zly_roi {
+    int32_t x0, y0, w, h;
+} zly_roi;
+/* Once per engine: allocates the store (alone in the process, like the allocations of zly_create).  ZLY_ERR_INVALID_ARGUMENT for a non-positive
+ * argument, for a second call and for a store above ZLY_SURFACE_STORE_MAX bytes; ZLY_ERR_SYSTEM for a failed allocation.  Every other call of this
+ * section on an engine without a store, and a slot index outside 0..max_surfaces-1, fail with ZLY_ERR_INVALID_ARGUMENT and enqueue nothing. */
+int32_t zly_surfaces_enable(zly_engine* e, int32_t max_surfaces, size_t max_bytes_each);
+/* Slot s now holds a tight w x h frame of format fmt, and is NOT valid: how a stream starts, changes resolution, or recovers from a lost keyframe.
+ * Nothing is enqueued.  Unknown format: ZLY_ERR_INVALID_ARGUMENT; a size that is illegal for the format, or more than max_bytes_each bytes
+ * (zly_frame_bytes): ZLY_ERR_INVALID_INPUT. */
+int32_t zly_surface_define(zly_engine* e, int32_t s, int32_t fmt, int32_t w, int32_t h);
+/* Writes n_rects rectangles (1..ZLY_SURFACE_MAX_RECTS) into the store.  Rectangle i comes from the view src_views[i] of the HOST buffer bases[i] of
+ * buf_bytes[i] bytes (checked as zly_detect_view checks a view); the view gives its size and its format, which must be the surface's.  Its
+ * destination is what zly_view_crop gives for (x0, y0, w, h) of the surface's tight view, and it must be legal by exactly that function's rules:
+ * inside the surface, and the format's evenness of x0, y0, w, h.  Two rectangles of one call that name the same surface must be disjoint -- a caller
+ * with overlapping rectangles makes two calls.  A rectangle that covers its whole surface makes it valid.
+ * Ordering.  The call first WAITS, on the host, for the work enqueued so far on the engine's own stream (the pinned staging is single-buffered and is
+ * reused call to call, as zly_detect_tiled reuses it); it then copies the rows, enqueues the upload and the patch kernel on the engine's own stream and
+ * returns without waiting for them.  On the device the patch kernel runs behind every zly_detect_surfaces call made so far, WHICHEVER stream that call
+ * was given: it never overwrites a slot that an earlier call still reads, and a later zly_detect_surfaces on any stream runs behind it.  So the loop
+ * update k, detect k on a caller's stream, update k + 1, ... needs no synchronisation of the caller's; what it cannot do is overlap the host copy of
+ * update k + 1 with earlier work on the ENGINE's stream (with detection on a caller's stream the two overlap).
+ * ZLY_ERR_INVALID_ARGUMENT: a null argument, n_rects out of range, an undefined or out-of-range slot, an unknown or mismatching format, an illegal
+ * destination, an overlap; ZLY_ERR_INVALID_INPUT: an otherwise invalid source view, or one that does not fit its buffer.  If any rectangle is
+ * refused, nothing is enqueued and no slot changes. */
+int32_t zly_surface_update(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
+                           const zly_frame_view* src_views);
+/* Waits for the updates enqueued so far, then copies the slot's zly_frame_bytes bytes to host_out (tests, snapshots, debugging).  A defined slot
+ * need not be valid.  ZLY_ERR_INVALID_ARGUMENT: a null output, an undefined slot, cap_bytes too small. */
+int32_t zly_surface_read(zly_engine* e, int32_t s, void* host_out, size_t cap_bytes);
+/* The device path on n resident surfaces (1..max_batch; a surface may be named more than once): enqueues and returns as zly_detect_device_view does,
+ * d_slabs, frame_tag0 and stream as there, ordered behind the updates enqueued so far.  rois is NULL (whole surfaces) or a HOST array of n
+ * rectangles, each legal for zly_view_crop on its surface (ZLY_ERR_INVALID_ARGUMENT otherwise): the tiles of a resident surface are one call.  A
+ * surface that is not valid: ZLY_ERR_INVALID_INPUT.  The slabs may go to zly_merge_slabs and zly_track_slabs like any device-path slabs. */
+int32_t zly_detect_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const zly_roi* rois, void* d_slabs, uint32_t frame_tag0, void* stream);
+/* The host-memory convenience, synchronous: the update of zly_surface_update (n_rects may be 0: nothing changed), then the n named surfaces detected
+ * whole, then the read-back; out, cap and n_out as zly_detect_batch_view.  Validity is judged after the update: a call may carry its own keyframe. */
+int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
+                         const zly_frame_view* src_views, int32_t n, const int32_t* surfaces, zly_det* out, int32_t cap, int32_t* n_out);
+
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw);

@@ -10,6 +10,7 @@
 // buffer (ConvArgs::out_cs/out_co) and consumers read channel slices (in_cs/in_co).
 #include "zly_internal.h"
 #include "frame_rules.h"
+#include "surface_rules.h"
 #include "weights.h"
 
 #include <algorithm>
@@ -183,6 +184,22 @@ struct Merge {
     unsigned char* d_out = nullptr;   // [max_batch][slab_bytes]
 };
 
+// Resident surfaces (zly_surfaces_enable; include/zly.h "Resident surfaces"): the store in HBM and what the host knows of its slots.  The job table of
+// an update rides in the engine's staging buffer behind the pixels (surface_rules.h: SurfacePlan), so there is no ring: staging is reused call to call.
+struct Surfaces {
+    SurfaceStore store;
+    std::vector<SurfaceSlot> slots;   // [max_surfaces]
+    uint8_t* d_store = nullptr;       // [max_surfaces][stride]
+    hipEvent_t ev_patch = nullptr;    // behind the most recent patch kernel (on the engine's stream): a detect call on a foreign stream waits for it
+    bool patched = false;
+    // behind the most recent zly_detect_surfaces call, on the stream its last kernel ran on: the next patch kernel waits for it, so that it never
+    // overwrites a slot that a call still queued on a caller's stream reads.  Before it is recorded again the engine's stream is made to wait for
+    // the previous recording: the engine's stream collects every reader, whichever streams they ran on.
+    hipEvent_t ev_read = nullptr;
+    bool read_pending = false;
+    SurfacePlan plan;                 // scratch of the current update
+};
+
 }  // namespace zly
 
 using namespace zly;
@@ -269,6 +286,7 @@ struct zly_engine : Plan {
     std::atomic<Ingest*> ingest{nullptr};   // created by the first zly_submit (under mu), read lock-free afterwards
     std::atomic<Track*> track{nullptr};     // created by zly_track_enable (under mu), read lock-free afterwards
     Merge* merge = nullptr;                 // created by the first zly_merge_slabs / zly_detect_tiled (under mu)
+    Surfaces* surf = nullptr;               // created by zly_surfaces_enable (under mu)
     hipStream_t last_ns = nullptr;          // the stream the most recent zly_detect_device* call's NMS ran on, and whether that was the engine's NMS stream
     bool last_deferred = false;
 
@@ -1579,6 +1597,12 @@ static hipError_t destroy_engine(zly_engine* e)
         for (int i = 0; i < Merge::RING; ++i) if (mg->ev[i]) hipEventDestroy(mg->ev[i]);
         delete mg;
     }
+    if (Surfaces* sf = e->surf) {
+        if (sf->d_store) note(hipFree(sf->d_store));
+        if (sf->ev_patch) hipEventDestroy(sf->ev_patch);
+        if (sf->ev_read) hipEventDestroy(sf->ev_read);
+        delete sf;
+    }
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
         if (e->ev_join[i]) hipEventDestroy(e->ev_join[i]);
@@ -2404,11 +2428,11 @@ int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void*
     return ZLY_OK;
 }
 
-int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, void* d_slabs, uint32_t frame_tag0, void* stream)
+// The body of zly_detect_device_view, shared with zly_detect_surfaces and zly_detect_delta: n (1..max_batch) views of the device buffer d_base.
+// Under e->mu; takes the enqueue gate itself.  wait_for: an event `stream` has to wait for first when it is not the engine's own (null = none).
+static int detect_device_view_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, void* d_slabs, uint32_t frame_tag0,
+                                     void* stream, hipEvent_t wait_for = nullptr)
 {
-    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
-    if (!v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null views");
-    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
     std::vector<int32_t> ws((size_t)n), hs((size_t)n), fs((size_t)n);
     std::vector<size_t> offs((size_t)n);
     std::vector<ViewRec> recs((size_t)n);
@@ -2419,10 +2443,10 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
         recs[(size_t)i] = view_rec(&v[i]);
         level = std::max(level, front_level(v[i].fmt));
     }
-    std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
     int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data(), recs.data());
     if (rc != ZLY_OK) return rc;
     hipStream_t ns = s;
@@ -2433,6 +2457,15 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     e->last_ns = ns; e->last_deferred = ns != s;
     with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
     return ZLY_OK;
+}
+
+int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, void* d_slabs, uint32_t frame_tag0, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null views");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    return detect_device_view_locked(e, n, d_base, buf_bytes, v, d_slabs, frame_tag0, stream);
 }
 
 int32_t zly_join(zly_engine* e, void* stream, int32_t lag)
@@ -2894,6 +2927,176 @@ int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, c
     *n_out = hd->n_kept;
     harvest_timing(e);
     with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
+    return ZLY_OK;
+}
+
+// --- resident surfaces (include/zly.h "Resident surfaces"; the rules: surface_rules.h) -----------------
+int32_t zly_surfaces_enable(zly_engine* e, int32_t max_surfaces, size_t max_bytes_each)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    SurfaceStore st;
+    if (int rc = surfaces_plan_store(max_surfaces, max_bytes_each, &st, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->surf) return fail(ZLY_ERR_INVALID_ARGUMENT, "resident surfaces are already enabled on this engine");
+    ExclusiveGate gl;                                  // allocations: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    Surfaces* sf = new Surfaces();
+    sf->store = st;
+    sf->slots.resize((size_t)max_surfaces);
+    // cleared once: zly_surface_read of a slot without a keyframe never shows what the memory held before
+    const bool ok = hipMalloc((void**)&sf->d_store, st.total) == hipSuccess && hipEventCreateWithFlags(&sf->ev_patch, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&sf->ev_read, hipEventDisableTiming) == hipSuccess &&
+                    hipMemsetAsync(sf->d_store, 0, st.total, e->stream) == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (sf->d_store) hipFree(sf->d_store);
+        if (sf->ev_patch) hipEventDestroy(sf->ev_patch);
+        if (sf->ev_read) hipEventDestroy(sf->ev_read);
+        delete sf;
+        return fail(ZLY_ERR_SYSTEM, "allocation of the surface store (" + std::to_string(st.total) + " bytes) failed");
+    }
+    e->surf = sf;
+    return ZLY_OK;
+}
+
+// the engine's store (under e->mu), or null with the error set
+static Surfaces* surfaces_of(zly_engine* e)
+{
+    if (!e->surf) fail(ZLY_ERR_INVALID_ARGUMENT, "resident surfaces are not enabled on this engine (zly_surfaces_enable)");
+    return e->surf;
+}
+
+int32_t zly_surface_define(zly_engine* e, int32_t s, int32_t fmt, int32_t w, int32_t h)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    SurfaceSlot sl;
+    if (int rc = surface_define(sf->store, s, fmt, w, h, &sl, &g_last_error)) return rc;
+    sf->slots[(size_t)s] = sl;
+    return ZLY_OK;
+}
+
+// Enqueues the update that sf->plan describes (surface_plan_update has accepted it) on the engine's stream: the rectangles' rows tight into pinned staging
+// on this thread, ONE copy of pixels + band table, ONE launch.  Under e->mu; takes the gates itself.
+static int surface_enqueue_update(zly_engine* e, Surfaces* sf, int n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const zly_frame_view* src_views)
+{
+    const SurfacePlan& pl = sf->plan;
+    if (pl.bands.size() > (size_t)std::numeric_limits<int>::max()) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_surface_update: too many bands");
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (pl.stage_bytes > e->stage_bytes) {                               // an allocation: alone in the process
+        ExclusiveGate x;
+        if (int rc = ensure_stage(e, pl.stage_bytes)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
+    for (int i = 0; i < n_rects; ++i) copy_view_tight(e->h_stage + pl.stage_off[(size_t)i], bases[i], &src_views[i]);
+    memcpy(e->h_stage + pl.table_off, pl.bands.data(), pl.bands.size() * sizeof(SurfaceJob));
+    SharedGate gl;
+    if (sf->read_pending) {                                              // detect calls on other streams may still read the slots this writes
+        HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+        sf->read_pending = false;                                        // from here on the dependency is the engine stream's own order
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, pl.stage_bytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_surface_patch(e->d_stage, reinterpret_cast<const SurfaceJob*>(e->d_stage + pl.table_off), (int)pl.bands.size(), sf->d_store, e->sw.num_cus, e->stream),
+            ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(sf->ev_patch, e->stream), ZLY_ERR_INFERENCE);
+    sf->patched = true;
+    for (int i = 0; i < n_rects; ++i) if (pl.covers[(size_t)i]) sf->slots[(size_t)rects[i].surface].valid = true;
+    return ZLY_OK;
+}
+
+int32_t zly_surface_update(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
+                           const zly_frame_view* src_views)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    if (int rc = surface_plan_update(sf->store, sf->slots.data(), n_rects, rects, bases, buf_bytes, src_views, &sf->plan, &g_last_error)) return rc;
+    return surface_enqueue_update(e, sf, n_rects, rects, bases, src_views);
+}
+
+int32_t zly_surface_read(zly_engine* e, int32_t s, void* host_out, size_t cap_bytes)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!host_out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    if (int rc = surface_check_slot(sf->store, s, &g_last_error)) return rc;
+    const SurfaceSlot& sl = sf->slots[(size_t)s];
+    if (!sl.defined) return fail(ZLY_ERR_INVALID_ARGUMENT, "surface " + std::to_string(s) + " is not defined (zly_surface_define)");
+    const size_t fb = frame_bytes(sl.fmt, sl.w, sl.h);
+    if (cap_bytes < fb) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_surface_read: the surface holds " + std::to_string(fb) + " bytes, the buffer " + std::to_string(cap_bytes));
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    {
+        SharedGate gl;
+        HIP_TRY(hipMemcpyAsync(host_out, sf->d_store + (size_t)s * sf->store.stride, fb, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_detect_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const zly_roi* rois, void* d_slabs, uint32_t frame_tag0, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!surfaces) return fail(ZLY_ERR_INVALID_ARGUMENT, "null surfaces");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    std::vector<zly_frame_view> views((size_t)n);
+    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, rois, views.data(), &g_last_error)) return rc;
+    if (int rc = detect_device_view_locked(e, n, sf->d_store, sf->store.total, views.data(), d_slabs, frame_tag0, stream, sf->patched ? sf->ev_patch : nullptr)) return rc;
+    // the store has a reader now: the next update's patch kernel goes behind this call's last kernel, whichever stream that ran on
+    SharedGate gl;
+    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(sf->ev_read, e->last_ns), ZLY_ERR_INFERENCE);
+    sf->read_pending = true;
+    return ZLY_OK;
+}
+
+int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
+                         const zly_frame_view* src_views, int32_t n, const int32_t* surfaces, zly_det* out, int32_t cap, int32_t* n_out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!surfaces) return fail(ZLY_ERR_INVALID_ARGUMENT, "null surfaces");
+    if (!out || !n_out || cap < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    if (n_rects < 0) return fail(ZLY_ERR_INVALID_ARGUMENT, "negative rectangle count");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    // every check of both halves first, validity as it will be after the update: a refused call enqueues nothing
+    std::vector<SurfaceSlot> after = sf->slots;
+    if (n_rects > 0) {
+        if (int rc = surface_plan_update(sf->store, sf->slots.data(), n_rects, rects, bases, buf_bytes, src_views, &sf->plan, &g_last_error)) return rc;
+        for (int i = 0; i < n_rects; ++i) if (sf->plan.covers[(size_t)i]) after[(size_t)rects[i].surface].valid = true;
+    }
+    std::vector<zly_frame_view> views((size_t)n);
+    if (int rc = surface_detect_views(sf->store, after.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = check_view(e->cfg.flags, sf->d_store, sf->store.total, &views[(size_t)i], &g_last_error)) return rc;
+    if (n_rects > 0)
+        if (int rc = surface_enqueue_update(e, sf, n_rects, rects, bases, src_views)) return rc;
+    if (int rc = detect_device_view_locked(e, n, sf->d_store, sf->store.total, views.data(), nullptr, 0, nullptr)) return rc;
+    const size_t sb = slab_bytes_of(e);
+    {
+        SharedGate gl;
+        if (int rc = join_nms(e, e->stream)) return rc;                 // ZLY_FLAG_ASYNC_NMS: the call's NMS may run on the engine's NMS stream
+        HIP_TRY(hipMemcpyAsync(e->h_slabs, e->d_slabs, sb * (size_t)n, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    const uint64_t ts = now_ms();                                        // onnx_engine.cpp:813-815
+    for (int i = 0; i < n; ++i) {
+        const zly_slab_header* hd = reinterpret_cast<const zly_slab_header*>(e->h_slabs + sb * (size_t)i);
+        const zly_det* d = reinterpret_cast<const zly_det*>(hd + 1);
+        const int m = std::min(std::min(hd->n_kept, e->cfg.max_dets), cap);
+        for (int k = 0; k < m; ++k) { out[(size_t)i * cap + k] = d[k]; out[(size_t)i * cap + k].timestamp = ts; }
+        n_out[i] = hd->n_kept;
+    }
+    harvest_timing(e);
     return ZLY_OK;
 }
 

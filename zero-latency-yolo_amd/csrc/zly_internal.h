@@ -359,4 +359,9 @@ hipError_t merge_init();
 // members x cap of a group (<= ZLY_MERGE_MAX_CANDIDATES): it sizes the launch.  metric: ZLY_MERGE_IOU | ZLY_MERGE_IOS.
 hipError_t launch_merge(const int* tab, int n_groups, int max_slots, const void* slabs, void* out, int cap, int metric, float thr, uint32_t tag0, hipStream_t s);
 
+// ---- resident surfaces (kernels_surface.hip; the rule: include/zly.h, "Resident surfaces"; the band record: surface_device.h) ----
+struct SurfaceJob;
+// one launch: every band of `bands` (device, n_bands records, 16-byte aligned) from `stage` into `store` (16-byte aligned); no byte outside a band's rows is written
+hipError_t launch_surface_patch(const uint8_t* stage, const SurfaceJob* bands, int n_bands, uint8_t* store, int num_cus, hipStream_t s);
+
 }  // namespace zly

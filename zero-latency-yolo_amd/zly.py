@@ -42,6 +42,8 @@ PIX_RGB, PIX_BGRA, PIX_RGBA = 16, 17, 18
 PIX_YUY2_BT601, PIX_UYVY_BT601, PIX_YUY2_BT709, PIX_UYVY_BT709 = 10, 11, 12, 13      # packed YUV 4:2:2 (capture cards, UVC devices): 1-D u8 buffers of 2wh bytes, w even
 MERGE_IOU, MERGE_IOS = 0, 1          # zly_merge_config.metric (include/zly.h "Tiles")
 MERGE_MAX_CANDIDATES = 4096          # tiles of a group x max_dets may not exceed it
+SURFACE_MAX_RECTS = 1024             # rectangles per surface_update / detect_delta call (include/zly.h "Resident surfaces")
+SURFACE_ALIGN = 256                  # the store's slot stride is a multiple of it
 _PACKED_BPP = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
 
 # every symbol include/zly.h declares (tests/test_abi.py checks the library exports them all)
@@ -55,6 +57,7 @@ SYMBOLS = [
     "zly_default_track_config", "zly_track_enable", "zly_track_reset", "zly_track_state_at", "zly_track_slabs", "zly_submit_view_tracked", "zly_submit_try_view_tracked",
     "zly_default_track_motion_config", "zly_track_motion_enable", "zly_track_read",
     "zly_default_merge_config", "zly_merge_slabs", "zly_read_merged", "zly_tile_grid", "zly_detect_tiled",
+    "zly_surfaces_enable", "zly_surface_define", "zly_surface_update", "zly_surface_read", "zly_detect_surfaces", "zly_detect_delta",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -110,6 +113,16 @@ class Tile(C.Structure):
 class MergeConfig(C.Structure):
     """zly_merge_config"""
     _fields_ = [("metric", C.c_int32), ("thr", C.c_float)]
+
+
+class SurfaceRect(C.Structure):
+    """zly_surface_rect: where a rectangle's first pixel lies in which resident surface (its size and format are its source view's)"""
+    _fields_ = [("surface", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32)]
+
+
+class Roi(C.Structure):
+    """zly_roi"""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -201,6 +214,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_read_merged.argtypes = [vp, i32, vp]; lib.zly_read_merged.restype = i32
     lib.zly_tile_grid.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(Tile), i32, pi32]; lib.zly_tile_grid.restype = i32
     lib.zly_detect_tiled.argtypes = [vp, vp, sz, pv, i32, C.POINTER(Tile), C.POINTER(MergeConfig), vp, i32, pi32]; lib.zly_detect_tiled.restype = i32
+    lib.zly_surfaces_enable.argtypes = [vp, i32, sz]; lib.zly_surfaces_enable.restype = i32
+    lib.zly_surface_define.argtypes = [vp, i32, i32, i32, i32]; lib.zly_surface_define.restype = i32
+    lib.zly_surface_update.argtypes = [vp, i32, C.POINTER(SurfaceRect), C.POINTER(vp), C.POINTER(sz), pv]; lib.zly_surface_update.restype = i32
+    lib.zly_surface_read.argtypes = [vp, i32, vp, sz]; lib.zly_surface_read.restype = i32
+    lib.zly_detect_surfaces.argtypes = [vp, i32, pi32, C.POINTER(Roi), vp, u32, vp]; lib.zly_detect_surfaces.restype = i32
+    lib.zly_detect_delta.argtypes = [vp, i32, C.POINTER(SurfaceRect), C.POINTER(vp), C.POINTER(sz), pv, i32, pi32, vp, i32, pi32]; lib.zly_detect_delta.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -488,6 +507,55 @@ class Engine:
         n = C.c_int32(0)
         _check(self.lib, self.lib.zly_detect_tiled(self.h, buf.ctypes.data, buf.nbytes, C.byref(surface), n_t, ct, C.byref(c), out.ctypes.data, cap, C.byref(n)))
         return out[:min(n.value, cap)], n.value
+
+    # -- resident surfaces (include/zly.h "Resident surfaces") ---------------------------------------------
+    def surfaces_enable(self, max_surfaces: int, max_bytes_each: int):
+        """once per engine: one HBM store of max_surfaces slots"""
+        _check(self.lib, self.lib.zly_surfaces_enable(self.h, max_surfaces, max_bytes_each))
+
+    def surface_define(self, s: int, fmt: int, w: int, h: int):
+        """slot s now holds a tight w x h frame of format fmt and is not valid until a rectangle covers it whole"""
+        _check(self.lib, self.lib.zly_surface_define(self.h, s, fmt, w, h))
+
+    @staticmethod
+    def _rect_args(rects):
+        """rects: (surface, x0, y0, buf, view) each -- view (a FrameView) says where the rectangle's samples lie in the host u8 array buf"""
+        n = len(rects)
+        bufs = [np.ascontiguousarray(r[3], dtype=np.uint8) for r in rects]
+        cr = (SurfaceRect * max(n, 1))(*[SurfaceRect(r[0], r[1], r[2]) for r in rects])
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        nbytes = (C.c_size_t * max(n, 1))(*[b.nbytes for b in bufs])
+        cv = (FrameView * max(n, 1))(*[r[4] for r in rects])
+        return n, cr, ptrs, nbytes, cv, bufs
+
+    def surface_update(self, rects):
+        """writes the rectangles into the store: one staged upload, one kernel launch; enqueued, not synchronised"""
+        n, cr, ptrs, nbytes, cv, _keep = self._rect_args(rects)
+        _check(self.lib, self.lib.zly_surface_update(self.h, n, cr, ptrs, nbytes, cv))
+
+    def surface_read(self, s: int, nbytes: int) -> np.ndarray:
+        """the slot's current bytes (synchronises)"""
+        out = np.zeros(nbytes, dtype=np.uint8)
+        _check(self.lib, self.lib.zly_surface_read(self.h, s, out.ctypes.data, out.nbytes))
+        return out
+
+    def detect_surfaces(self, surfaces: Sequence[int], rois=None, d_slabs_ptr: int = 0, tag0: int = 0, stream: int = 0):
+        """the device path on resident surfaces; rois: None or one (x0, y0, w, h) per surface"""
+        n = len(surfaces)
+        cs = (C.c_int32 * n)(*surfaces)
+        cr = None if rois is None else (Roi * n)(*[Roi(*r) for r in rois])
+        _check(self.lib, self.lib.zly_detect_surfaces(self.h, n, cs, cr, d_slabs_ptr or None, tag0, stream or None))
+
+    def detect_delta(self, rects, surfaces: Sequence[int], cap: Optional[int] = None) -> List[Tuple[np.ndarray, int]]:
+        """surface_update(rects), then the named surfaces detected whole and read back (synchronous)"""
+        nr, cr, ptrs, nbytes, cv, _keep = self._rect_args(rects)
+        n = len(surfaces)
+        cs = (C.c_int32 * n)(*surfaces)
+        cap = cap or self.max_dets
+        out = np.zeros((n, cap), dtype=DET_DTYPE)
+        n_out = (C.c_int32 * n)()
+        _check(self.lib, self.lib.zly_detect_delta(self.h, nr, cr, ptrs, nbytes, cv, n, cs, out.ctypes.data, cap, n_out))
+        return [(out[i, :min(n_out[i], cap)], int(n_out[i])) for i in range(n)]
 
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
