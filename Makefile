@@ -12,9 +12,9 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wal
 CXX      ?= g++
 PY       ?= python3
 
-KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_pix.hip $(CSRC)/kernels_pix_view.hip $(CSRC)/kernels_y422.hip $(CSRC)/kernels_y422_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip $(CSRC)/kernels_track.hip $(CSRC)/kernels_merge.hip $(CSRC)/kernels_area.hip $(CSRC)/kernels_surface.hip
+KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_pix.hip $(CSRC)/kernels_pix_view.hip $(CSRC)/kernels_y422.hip $(CSRC)/kernels_y422_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip $(CSRC)/kernels_track.hip $(CSRC)/kernels_merge.hip $(CSRC)/kernels_area.hip $(CSRC)/kernels_surface.hip $(CSRC)/kernels_zoom.hip
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
-OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/kernels_merge.o $(OUT)/kernels_area.o $(OUT)/kernels_surface.o $(OUT)/engine.o $(OUT)/weights.o
+OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/kernels_merge.o $(OUT)/kernels_area.o $(OUT)/kernels_surface.o $(OUT)/kernels_zoom.o $(OUT)/engine.o $(OUT)/weights.o
 
 all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so $(OUT)/libsppf_probe.so oracle weights host
 
@@ -29,8 +29,10 @@ $(OUT)/%.o: $(CSRC)/%.hip $(KHDRS) | $(OUT)
 $(OUT)/kernels_stem_yuv.o: $(CSRC)/kernels_stem.hip
 $(OUT)/kernels_lb.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_head.hip
 $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o: $(CSRC)/kernels_misc.hip $(CSRC)/kernels_stem.hip
+# the plan kernel of the zoom regions compiles the arithmetic it shares with the host twin
+$(OUT)/kernels_zoom.o: $(CSRC)/zoom_device.h
 
-$(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/weights.h include/zly.h | $(OUT)
+$(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(OUT)/weights.o: $(CSRC)/weights.cpp $(CSRC)/weights.h include/zly.h | $(OUT)
@@ -42,7 +44,7 @@ $(OUT)/libzly.so: $(OBJS)
 # ---- diagnostic build of the engine (never shipped, never loaded by tests / bench.py / the plugin): the same kernels, engine.cpp with -DZLY_DIAG, which
 #      compiles in the result-changing ZLY_ABLATE_SKIP switch of tools/ablate_launches.sh (ZLY_LIB=.../libzly_diag.so python3 bench.py ...)
 diaglib: $(OUT)/libzly_diag.so
-$(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/weights.h include/zly.h | $(OUT)
+$(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/weights.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -DZLY_DIAG=1 -x hip -c $< -o $@
 $(OUT)/libzly_diag.so: $(filter-out $(OUT)/engine.o,$(OBJS)) $(OUT)/engine_diag.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
@@ -82,7 +84,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_frame_rules $(OUT)/test_surface_rules $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_frame_rules $(OUT)/test_surface_rules $(OUT)/test_zoom_plan $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -154,6 +156,17 @@ surface_rules_san: $(OUT)/test_surface_rules_san
 $(OUT)/test_surface_rules_san: $(SURFACE_RULES) | $(OUT)
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(CSRC) -o $@ tests/cpp/test_surface_rules.cpp
 
+# the plan of the zoom regions (csrc/zoom_device.h through the host twin of csrc/zoom_rules.h) on its own, for tests/test_zoom_plan.py: the program reads track
+# tables and prints plans, and walks the per-plane offset arithmetic against view_crop (test infrastructure: no GPU, nothing of the engine).  Contraction
+# off, as in the kernel's unit ...
+ZOOM_PLAN := tests/cpp/test_zoom_plan.cpp $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/frame_rules.h $(CSRC)/front_variants.h include/zly.h
+$(OUT)/test_zoom_plan: $(ZOOM_PLAN) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -ffp-contract=off -Iinclude -I$(CSRC) -o $@ tests/cpp/test_zoom_plan.cpp
+# ... and under the host sanitizers: not part of `all`; make zoom_plan_san && $(OUT)/test_zoom_plan_san selftest
+zoom_plan_san: $(OUT)/test_zoom_plan_san
+$(OUT)/test_zoom_plan_san: $(ZOOM_PLAN) | $(OUT)
+	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(CSRC) -o $@ tests/cpp/test_zoom_plan.cpp
+
 $(OUT)/test_wire: tests/cpp/test_wire.cpp $(HOST)/zly_wire.hpp $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -I$(HOST) -o $@ tests/cpp/test_wire.cpp
 
@@ -186,4 +199,4 @@ $(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_
 clean:
 	rm -rf $(OUT) oracle/_build
 
-.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe frame_rules_san surface_rules_san clean
+.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe frame_rules_san surface_rules_san zoom_plan_san clean

@@ -655,6 +655,77 @@ int32_t zly_detect_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, c
 int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
                          const zly_frame_view* src_views, int32_t n, const int32_t* surfaces, zly_det* out, int32_t cap, int32_t* n_out);
 
+/* --- Zoom regions ------------------------------------------------------------------------------------------------------------------
+ * Detects, in ONE batch, a whole surface and K full-resolution regions of it around the stream's tracked targets, merges the 1 + K slabs into one
+ * and tracks it.  A large capture stretched to the model size leaves a small target a few model pixels wide; a full tile grid (zly_tile_grid) finds
+ * it at a dozen or more inferences per frame, nearly all on regions with nothing in them.  The reference's client instead keeps a region of interest
+ * around its current target and sends that at full resolution (use_roi_encoding, src/client/screen_capture.cpp:102-107, :470-538); here the server
+ * does it from its own track tables.  The regions are PLANNED ON THE GPU, in stream order, by a one-wavefront kernel (csrc/kernels_zoom.hip) that
+ * reads the stream's track table where the tracker left it and writes the regions' origins into the frame descriptors, the view records and the
+ * merge's tile table: the frame needs no zly_track_read, hence no synchronisation with the previous frame's tracker, and stays enqueue-only.
+ * Opt-in per engine (zly_zoom_enable): an engine that never calls it allocates nothing more and launches exactly the kernels it launched before.
+ *
+ * The plan for one frame.  Inputs: the stream's table as left by every tracked call enqueued before -- frame_no F and the slots, with vx, vy if the
+ * engine has the motion model (vx = vy = 0 otherwise) -- and the surface size W x H, 2 <= W, H < 2^24.  All float arithmetic is single IEEE fp32
+ * operations in the order written, without contraction, as in the tracker; the (float) conversions of integers are exact.
+ *   1. Region size: rw = min(region_w, W & ~1), rh = min(region_h, H & ~1); xmax = (W - rw) & ~1, ymax = (H - rh) & ~1.  Origins are always even:
+ *      legal for every pixel format, and stricter than the packed RGB formats need -- the decision zly_tile_grid made.
+ *   2. Eligible slots: live; class_id equal to the config's, or the config's is -1; F - last_seen (u32) <= max_age; and the box fits a region:
+ *      w*(float)W <= (float)rw and h*(float)H <= (float)rh (a target larger than a region gains nothing from it).
+ *   3. Prediction to the coming frame, as the tracker's step P will compute it: dtf = (float)(F + 1 - last_seen) (u32 difference);
+ *      px = x + vx*dtf, py = y + vy*dtf (the product is rounded first).
+ *   4. Order of the eligible slots: age F - last_seen ascending; then area w*h ascending as an fp32 value (-0 and +0 tie); then slot ascending.
+ *      (A NaN area is outside the rule; the tracker stores none.)
+ *   5. Greedy choice: go through the order until K regions are chosen.  A slot is COVERED, and skipped, if for some region (x0, y0) already chosen
+ *      px - w*0.5f >= (float)x0/(float)W and px + w*0.5f <= (float)(x0 + rw)/(float)W, and likewise in y.  Otherwise it gets a region:
+ *      pxc = px > 0 ? (px < 1 ? px : 1) : 0 (a NaN gives 0); cx = (int32)(pxc*(float)W), truncating; x0 = min(max(cx - rw/2, 0), xmax) & ~1; y likewise.
+ *   6. The remaining regions are FALLBACKS (slot = -1, track_id = 0): the centred window, x0 = ((W - rw)/2) & ~1, y likewise -- where a crosshair
+ *      is, and what the plugin's ZLY_CROP looks at.  The batch size must be known on the host, so fallbacks are detected and merged like any region;
+ *      the merge removes what they duplicate.
+ *
+ * The frame.  Frame i's views are batch items i*(1 + K) + j: j = 0 the whole surface, j = 1..K its regions in the order chosen; n*(1 + K) <=
+ * max_batch.  Group i of the merge is those 1 + K tiles of the W x H surface; the n merged slabs (frame_tag0 + i) are tracked in place with
+ * streams[i], as zly_track_slabs would.
+ * THE RULE: the n slabs equal, byte for byte, what this sequence of existing calls gives on an engine in the same state: the plan above;
+ * zly_view_crop of each surface for each region; zly_detect_device_view on the n*(1 + K) views in that order; zly_merge_slabs with those tiles and
+ * n groups; zly_track_slabs on the merged slabs.  It holds for stretch, letterbox and area engines, for every pixel format, and with and without
+ * ZLY_FLAG_ASYNC_NMS.
+ * Ordering.  The plan kernel runs behind the previous call's tracking, on whichever stream that ran.  With ZLY_FLAG_ASYNC_NMS this removes the
+ * overlap of call k's NMS with call k + 1's front kernels: that is inherent -- the plan needs call k's tracks.
+ * Out of scope: the pipelined submit ring, the plugin, engines behind host/zly_sharded*.hpp, choosing regions from anything but tracks,
+ * per-region sizes, and tuning the defaults (chosen, not tuned: nobody has measured them on real footage; no accuracy claim is made). */
+typedef struct zly_zoom_config {
+    int32_t regions;              /* K: zoom regions per frame, 1..15 (chosen; default 3) */
+    int32_t region_w, region_h;   /* a region in surface pixels: even, 2..16384; default model_w, model_h (1:1: the front kernel's resize is the identity) */
+    int32_t max_age;              /* >= 0: slots with frame_no - last_seen > max_age are not zoomed; default 2 (chosen, not tuned) */
+    int32_t class_id;             /* -1: any class; otherwise only slots of this class (the reference's HEAD = 2, say) */
+} zly_zoom_config;
+typedef struct zly_zoom_region {
+    int32_t  x0, y0, w, h;        /* in surface pixels */
+    int32_t  slot;                /* the slot the region was chosen for; -1: a fallback */
+    uint32_t track_id;            /* that slot's id; 0: a fallback */
+} zly_zoom_region;
+void    zly_default_zoom_config(const zly_engine* e, zly_zoom_config* cfg);
+/* Once per engine, after zly_track_enable (zly_track_motion_enable is optional, before or after): allocates the plan buffers, alone in the process
+ * like the tracker's.  ZLY_ERR_INVALID_ARGUMENT: a null or out-of-range config, an engine without track tables, a second call,
+ * (1 + K) * max_dets > ZLY_MERGE_MAX_CANDIDATES, 1 + K > max_batch.  ZLY_ERR_SYSTEM: a failed allocation. */
+int32_t zly_zoom_enable(zly_engine* e, const zly_zoom_config* cfg);
+/* The frame, on n surfaces that are views of the device buffer d_base (HOST array surface_views[n]; checked as zly_detect_device_view checks a
+ * view, and 2 <= w, h < 2^24).  streams is a HOST array of n, every entry >= 0 and distinct within the call (two frames of one stream would be
+ * planned from the same table).  d_out receives the n merged, tracked slabs (NULL: the merge's engine-owned buffer, read with zly_read_merged).
+ * Enqueued, not synchronised; `stream` as in zly_detect_device_view; zly_join, zly_sync and zly_read_merged cover all of it.  Errors: those of
+ * zly_detect_device_view, zly_merge_slabs and zly_track_slabs plus the rules above.  A refused call enqueues nothing and leaves every table as it was. */
+int32_t zly_detect_device_zoom(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* surface_views, const int32_t* streams,
+                               const zly_merge_config* merge_cfg, void* d_out, uint32_t frame_tag0, void* stream);
+/* The same on n resident surfaces (distinct streams; a slot index may repeat), ordered with zly_surface_update as zly_detect_surfaces is. */
+int32_t zly_detect_surfaces_zoom(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, const zly_merge_config* merge_cfg, void* d_out,
+                                 uint32_t frame_tag0, void* stream);
+/* Stage level (tests, overlays, callers who drive the views themselves).  zly_zoom_plan runs the plan kernel alone for n (1..max_batch) frames
+ * of sizes W[i] x H[i] on streams[i] (>= 0; they may repeat), synchronously, and writes n*K regions; it patches nothing.  zly_zoom_read_plan waits
+ * for the most recent zoom call and writes its n*K regions (n must be that call's; ZLY_ERR_INVALID_ARGUMENT otherwise, and before any zoom call). */
+int32_t zly_zoom_plan(zly_engine* e, int32_t n, const int32_t* W, const int32_t* H, const int32_t* streams, zly_zoom_region* out);
+int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out);
+
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw);

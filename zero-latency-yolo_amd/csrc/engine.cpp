@@ -11,6 +11,7 @@
 #include "zly_internal.h"
 #include "frame_rules.h"
 #include "surface_rules.h"
+#include "zoom_rules.h"
 #include "weights.h"
 
 #include <algorithm>
@@ -200,6 +201,20 @@ struct Surfaces {
     SurfacePlan plan;                 // scratch of the current update
 };
 
+// Zoom regions (zly_zoom_enable; include/zly.h "Zoom regions"): the ring through which a call's frame records reach zoom_plan_kernel -- pinned host
+// records plus device records of their own, reused as the tracker's ring is -- and the plans the kernel writes.
+struct Zoom {
+    zly_zoom_config cfg{};
+    static constexpr int RING = 8;
+    ZoomFrame* h_frames = nullptr;    // pinned [RING][max_batch]
+    ZoomFrame* d_frames = nullptr;    // device [RING][max_batch]
+    hipEvent_t ev[RING] = {};         // behind the kernel that read entry r
+    bool used[RING] = {};
+    int next = 0, last = -1;          // last: the entry of the most recent frame call, last_n its frames
+    int last_n = 0;
+    zly_zoom_region* d_plan = nullptr;    // [max_batch] of the most recent frame call (n * K <= max_batch), then [max_batch * K] of zly_zoom_plan
+};
+
 }  // namespace zly
 
 using namespace zly;
@@ -287,6 +302,7 @@ struct zly_engine : Plan {
     std::atomic<Track*> track{nullptr};     // created by zly_track_enable (under mu), read lock-free afterwards
     Merge* merge = nullptr;                 // created by the first zly_merge_slabs / zly_detect_tiled (under mu)
     Surfaces* surf = nullptr;               // created by zly_surfaces_enable (under mu)
+    Zoom* zoom = nullptr;                   // created by zly_zoom_enable (under mu)
     hipStream_t last_ns = nullptr;          // the stream the most recent zly_detect_device* call's NMS ran on, and whether that was the engine's NMS stream
     bool last_deferred = false;
 
@@ -1603,6 +1619,13 @@ static hipError_t destroy_engine(zly_engine* e)
         if (sf->ev_read) hipEventDestroy(sf->ev_read);
         delete sf;
     }
+    if (Zoom* zm = e->zoom) {
+        if (zm->d_frames) note(hipFree(zm->d_frames));
+        if (zm->h_frames) note(hipHostFree(zm->h_frames));
+        if (zm->d_plan) note(hipFree(zm->d_plan));
+        for (int i = 0; i < Zoom::RING; ++i) if (zm->ev[i]) hipEventDestroy(zm->ev[i]);
+        delete zm;
+    }
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
         if (e->ev_join[i]) hipEventDestroy(e->ev_join[i]);
@@ -2796,10 +2819,10 @@ static int merge_ensure(zly_engine* e)
     return ZLY_OK;
 }
 
-// Builds the call's tile table in the next ring entry, uploads it and launches merge_kernel on `s` -- the stream the slabs' NMS ran on, or one already
-// ordered behind it.  Under e->mu, enqueue gate held; the arguments are validated by the caller (merge_check).
-static int merge_enqueue(zly_engine* e, int n, const zly_tile* tiles, int n_groups, const zly_merge_config* c, int max_slots, const void* src, void* dst,
-                         uint32_t tag0, hipStream_t s)
+// Builds the call's tile table in the next ring entry and uploads it on `s`; *ring = the entry.  Under e->mu, enqueue gate held; the arguments are
+// validated by the caller (merge_check).  A zoom call uploads on the call's stream, in front of the kernel that patches the table, and launches the
+// merge later, on the stream the slabs' NMS ran on.
+static int merge_upload(zly_engine* e, int n, const zly_tile* tiles, int n_groups, hipStream_t s, int* ring)
 {
     Merge* mg = e->merge;
     const int r = mg->next;
@@ -2819,11 +2842,30 @@ static int merge_enqueue(zly_engine* e, int n, const zly_tile* tiles, int n_grou
     }
     int* dt = mg->d_tab + (size_t)r * mg->tab_ints;
     HIP_TRY(hipMemcpyAsync(dt, t, sizeof(int) * (size_t)(n_groups + 1 + n_members * ZLY_MERGE_TILE_INTS), hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    *ring = r;
+    return ZLY_OK;
+}
+
+// launches merge_kernel on the uploaded table of ring entry r, on `s` -- the stream the slabs' NMS ran on, or one already ordered behind it (and behind
+// the table's upload)
+static int merge_launch(zly_engine* e, int r, int n_groups, const zly_merge_config* c, int max_slots, const void* src, void* dst, uint32_t tag0, hipStream_t s)
+{
+    Merge* mg = e->merge;
+    const int* dt = mg->d_tab + (size_t)r * mg->tab_ints;
     HIP_TRY(launch_merge(dt, n_groups, max_slots, src, dst, e->cfg.max_dets, c->metric, c->thr, tag0, s), ZLY_ERR_INFERENCE);
     HIP_TRY(hipEventRecord(mg->ev[r], s), ZLY_ERR_INFERENCE);
     mg->used[r] = true;
     mg->last = r;
     return ZLY_OK;
+}
+
+// upload and launch on one stream: the merge of zly_merge_slabs and zly_detect_tiled
+static int merge_enqueue(zly_engine* e, int n, const zly_tile* tiles, int n_groups, const zly_merge_config* c, int max_slots, const void* src, void* dst,
+                         uint32_t tag0, hipStream_t s)
+{
+    int r = 0;
+    if (int rc = merge_upload(e, n, tiles, n_groups, s, &r)) return rc;
+    return merge_launch(e, r, n_groups, c, max_slots, src, dst, tag0, s);
 }
 
 int32_t zly_merge_slabs(zly_engine* e, int32_t n, const zly_tile* tiles, int32_t n_groups, const zly_merge_config* c, void* d_slabs, void* d_out,
@@ -3097,6 +3139,245 @@ int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect*
         n_out[i] = hd->n_kept;
     }
     harvest_timing(e);
+    return ZLY_OK;
+}
+
+// --- zoom regions (include/zly.h "Zoom regions"; the rules: zoom_rules.h; the plan kernel: kernels_zoom.hip) -----------
+void zly_default_zoom_config(const zly_engine* e, zly_zoom_config* c)
+{
+    if (!c) return;
+    c->regions = 3;               // chosen, not tuned
+    c->region_w = e ? e->cfg.model_w & ~1 : 416;      // 1:1 with the model: the front kernel's resize is the identity
+    c->region_h = e ? e->cfg.model_h & ~1 : 416;
+    c->max_age = 2;
+    c->class_id = -1;
+}
+
+int32_t zly_zoom_enable(zly_engine* e, const zly_zoom_config* c)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = zoom_check_config(c, &g_last_error)) return rc;
+    if (!track_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
+    if ((int64_t)(1 + c->regions) * e->cfg.max_dets > ZLY_MERGE_MAX_CANDIDATES)
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "(1 + regions) x max_dets exceeds ZLY_MERGE_MAX_CANDIDATES");
+    if (1 + c->regions > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "1 + regions exceeds max_batch (" + std::to_string(e->cfg.max_batch) + ")");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->zoom) return fail(ZLY_ERR_INVALID_ARGUMENT, "zoom regions are already enabled on this engine");
+    ExclusiveGate gl;                                  // allocations: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    Zoom* zm = new Zoom();
+    zm->cfg = *c;
+    const size_t B = (size_t)e->cfg.max_batch, n_plan = B + B * (size_t)c->regions;
+    bool ok = hipMalloc((void**)&zm->d_frames, sizeof(ZoomFrame) * B * Zoom::RING) == hipSuccess &&
+              hipHostMalloc((void**)&zm->h_frames, sizeof(ZoomFrame) * B * Zoom::RING, hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void**)&zm->d_plan, sizeof(zly_zoom_region) * n_plan) == hipSuccess &&
+              hipMemset(zm->d_plan, 0, sizeof(zly_zoom_region) * n_plan) == hipSuccess;
+    for (int i = 0; i < Zoom::RING && ok; ++i) ok = hipEventCreateWithFlags(&zm->ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (zm->d_frames) hipFree(zm->d_frames);
+        if (zm->h_frames) hipHostFree(zm->h_frames);
+        if (zm->d_plan) hipFree(zm->d_plan);
+        for (int i = 0; i < Zoom::RING; ++i) if (zm->ev[i]) hipEventDestroy(zm->ev[i]);
+        delete zm;
+        return fail(ZLY_ERR_SYSTEM, "allocation of the zoom plan buffers failed");
+    }
+    e->zoom = zm;
+    return ZLY_OK;
+}
+
+// the engine's zoom state (under e->mu), or null with the error set
+static Zoom* zoom_of(zly_engine* e)
+{
+    if (!e->zoom) fail(ZLY_ERR_INVALID_ARGUMENT, "zoom regions are not enabled on this engine (zly_track_enable, then zly_zoom_enable)");
+    return e->zoom;
+}
+
+// Uploads the n frame records of a plan in the next ring entry and launches zoom_plan_kernel on `s`, behind the tracking enqueued so far on whichever
+// stream that ran.  desc / tab: what the kernel patches (null: the plan alone).  Under e->mu, enqueue gate held.
+static int zoom_enqueue_plan(zly_engine* e, Zoom* zm, Track* tk, int n, const ZoomFrame* zf, FrameDesc* desc, int* tab, zly_zoom_region* d_plan, hipStream_t s, int* ring)
+{
+    const int lt = (tk->next + Track::RING - 1) % Track::RING;                       // the most recent tracked launch
+    if (tk->used[lt]) HIP_TRY(hipStreamWaitEvent(s, tk->ev[lt], 0), ZLY_ERR_INFERENCE);
+    const int r = zm->next;
+    zm->next = (r + 1) % Zoom::RING;
+    if (zm->used[r]) HIP_TRY(hipEventSynchronize(zm->ev[r]), ZLY_ERR_INFERENCE);      // 8 plans back: long complete
+    ZoomFrame* hf = zm->h_frames + (size_t)r * (size_t)e->cfg.max_batch;
+    ZoomFrame* df = zm->d_frames + (size_t)r * (size_t)e->cfg.max_batch;
+    memcpy(hf, zf, sizeof(ZoomFrame) * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(df, hf, sizeof(ZoomFrame) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_zoom_plan(tk->d_state, tk->d_motion, df, n, desc, tab, d_plan, zm->cfg.regions, tk->cfg.max_tracks, zm->cfg.region_w, zm->cfg.region_h,
+                             zm->cfg.max_age, zm->cfg.class_id, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(zm->ev[r], s), ZLY_ERR_INFERENCE);
+    zm->used[r] = true;
+    *ring = r;
+    return ZLY_OK;
+}
+
+// The body of zly_detect_device_zoom and zly_detect_surfaces_zoom: n surfaces that are views of the device buffer d_base.  Under e->mu, e->zoom set; takes
+// the enqueue gate itself.  Every check comes first: a refused call enqueues nothing.  wait_for: as detect_device_view_locked's.
+static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* sv, const int32_t* streams,
+                              const zly_merge_config* mc, void* d_out, uint32_t frame_tag0, void* stream, hipEvent_t wait_for = nullptr)
+{
+    Zoom* zm = e->zoom;
+    Track* tk = e->track.load();
+    const int K = zm->cfg.regions, V = 1 + K, nb = n * V;
+    for (int i = 0; i < n; ++i) {
+        if (streams[i] < 0 || streams[i] >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(streams[i]) + " out of range (a zoomed frame names a stream)");
+        for (int k = 0; k < i; ++k)
+            if (streams[k] == streams[i]) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(streams[i]) + " occurs twice in a zoom call");
+    }
+    if (d_out && d_out == (void*)e->d_slabs) return fail(ZLY_ERR_INVALID_ARGUMENT, "d_out must not be the engine's own slab buffer");
+    std::vector<zly_frame_view> views((size_t)nb);
+    std::vector<zly_tile> tiles((size_t)nb);
+    std::vector<ZoomFrame> zf((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (int rc = zoom_check_surface(&sv[i], &g_last_error)) return rc;
+        if (int rc = check_view(e->cfg.flags, d_base, buf_bytes, &sv[i], &g_last_error)) return rc;
+        const int32_t W = sv[i].w, H = sv[i].h;
+        const ZoomSize z = zoom_size(zm->cfg.region_w, zm->cfg.region_h, W, H);
+        const int32_t fx = zoom_fallback_origin(W, z.rw), fy = zoom_fallback_origin(H, z.rh);
+        views[(size_t)i * V] = sv[i];
+        tiles[(size_t)i * V] = zly_tile{i, 0, 0, W, H, W, H};
+        for (int j = 1; j <= K; ++j) {                                              // every region at its fallback origin: the kernel patches what depends on the origin
+            zly_frame_view& rv = views[(size_t)i * V + j];
+            if (int rc = view_crop(&sv[i], fx, fy, z.rw, z.rh, &rv, &g_last_error)) return rc;
+            if (int rc = check_view(e->cfg.flags, d_base, buf_bytes, &rv, &g_last_error)) return rc;
+            tiles[(size_t)i * V + j] = zly_tile{i, fx, fy, z.rw, z.rh, W, H};
+        }
+        zf[(size_t)i] = zoom_frame_of(&sv[i], streams[i]);
+    }
+    int max_slots = 0;
+    if (int rc = merge_check(e, nb, tiles.data(), n, mc, &max_slots)) return rc;
+    std::vector<int32_t> ws((size_t)nb), hs((size_t)nb), fs((size_t)nb);
+    std::vector<size_t> offs((size_t)nb);
+    std::vector<ViewRec> recs((size_t)nb);
+    int level = ZLY_FRONT_BGR;
+    for (int b = 0; b < nb; ++b) {
+        const zly_frame_view& v = views[(size_t)b];
+        ws[(size_t)b] = v.w; hs[(size_t)b] = v.h; fs[(size_t)b] = v.fmt; offs[(size_t)b] = (size_t)v.off[0];
+        recs[(size_t)b] = view_rec(&v);
+        level = std::max(level, front_level(v.fmt));
+    }
+    if (int rc = merge_ensure(e)) return rc;
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
+    // the three tables the plan kernel patches go up first, on the call's stream; what set_desc remembers of d_desc is void from here on: a kernel writes it
+    int rc = set_desc(e, nb, ws.data(), hs.data(), offs.data(), s, fs.data(), recs.data());
+    e->desc_cache.clear(); e->view_cache.clear(); e->last_desc_n = 0;
+    if (rc != ZLY_OK) return rc;
+    int mr = 0, zr = 0;
+    if ((rc = merge_upload(e, nb, tiles.data(), n, s, &mr)) != ZLY_OK) return rc;
+    if ((rc = zoom_enqueue_plan(e, zm, tk, n, zf.data(), e->d_desc, e->merge->d_tab + (size_t)mr * e->merge->tab_ints, zm->d_plan, s, &zr)) != ZLY_OK) return rc;
+    zm->last = zr; zm->last_n = n;
+    hipStream_t ns = s;
+    rc = run_path(e, nb, (const uint8_t*)d_base, nullptr, 0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, level, true));
+    if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
+    e->call_seq++;
+    e->last_ns = ns; e->last_deferred = ns != s;
+    with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)nb; });
+    // merge, then track, on the stream the NMS ran on -- where zly_merge_slabs and zly_track_slabs would put them
+    void* dst = d_out ? d_out : (void*)e->merge->d_out;
+    if ((rc = merge_launch(e, mr, n, mc, max_slots, e->d_slabs, dst, frame_tag0, ns)) != ZLY_OK) return rc;
+    bool launched = false;
+    if ((rc = track_enqueue(e, tk, n, streams, dst, ns, &launched)) != ZLY_OK) return rc;
+    // the call's completion events lie behind its tracking: zly_join, zly_read_slabs, zly_read_merged and a later call's NMS wait for all of it
+    HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], ns), ZLY_ERR_INFERENCE);
+    if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], ns), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(e->merge->ev[mr], ns), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+// the argument checks the two frame entries share, in front of the lock
+static int zoom_check_call(const zly_engine* e, int32_t n, const void* frames, const int32_t* streams, const zly_merge_config* mc)
+{
+    if (!frames) return fail(ZLY_ERR_INVALID_ARGUMENT, "null surfaces");
+    if (!streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "null streams");
+    if (!mc) return fail(ZLY_ERR_INVALID_ARGUMENT, "null merge config");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    return ZLY_OK;
+}
+
+int32_t zly_detect_device_zoom(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* surface_views, const int32_t* streams,
+                               const zly_merge_config* merge_cfg, void* d_out, uint32_t frame_tag0, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = zoom_check_call(e, n, surface_views, streams, merge_cfg)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    Zoom* zm = zoom_of(e);
+    if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
+    if ((int64_t)n * (1 + zm->cfg.regions) > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "n x (1 + regions) exceeds max_batch");
+    return detect_zoom_locked(e, n, d_base, buf_bytes, surface_views, streams, merge_cfg, d_out, frame_tag0, stream);
+}
+
+int32_t zly_detect_surfaces_zoom(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, const zly_merge_config* merge_cfg, void* d_out,
+                                 uint32_t frame_tag0, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = zoom_check_call(e, n, surfaces, streams, merge_cfg)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    Zoom* zm = zoom_of(e);
+    if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
+    if ((int64_t)n * (1 + zm->cfg.regions) > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "n x (1 + regions) exceeds max_batch");
+    std::vector<zly_frame_view> views((size_t)n);
+    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
+    if (int rc = detect_zoom_locked(e, n, sf->d_store, sf->store.total, views.data(), streams, merge_cfg, d_out, frame_tag0, stream, sf->patched ? sf->ev_patch : nullptr)) return rc;
+    // the store has a reader now, as after zly_detect_surfaces: the next update's patch kernel goes behind this call's last kernel
+    SharedGate gl;
+    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(sf->ev_read, e->last_ns), ZLY_ERR_INFERENCE);
+    sf->read_pending = true;
+    return ZLY_OK;
+}
+
+int32_t zly_zoom_plan(zly_engine* e, int32_t n, const int32_t* W, const int32_t* H, const int32_t* streams, zly_zoom_region* out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!W || !H || !streams || !out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Zoom* zm = zoom_of(e);
+    if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
+    Track* tk = e->track.load();
+    std::vector<ZoomFrame> zf((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (W[i] < 2 || H[i] < 2 || W[i] >= (1 << 24) || H[i] >= (1 << 24)) return fail(ZLY_ERR_INVALID_ARGUMENT, "a zoomed surface must be 2..2^24-1 pixels on a side");
+        if (streams[i] < 0 || streams[i] >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(streams[i]) + " out of range");
+        ZoomFrame z{};
+        z.W = W[i]; z.H = H[i]; z.stream = streams[i]; z.planes = 1;
+        zf[(size_t)i] = z;
+    }
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    zly_zoom_region* d_plan = zm->d_plan + (size_t)e->cfg.max_batch;               // its own records: zly_zoom_read_plan keeps the last frame call's
+    {
+        SharedGate gl;
+        int zr = 0;
+        if (int rc = zoom_enqueue_plan(e, zm, tk, n, zf.data(), nullptr, nullptr, d_plan, e->stream, &zr)) return rc;
+        HIP_TRY(hipMemcpyAsync(out, d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Zoom* zm = zoom_of(e);
+    if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
+    if (zm->last < 0 || n != zm->last_n) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_zoom_read_plan: n must be the frames of the most recent zoom call");
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    {
+        SharedGate gl;
+        HIP_TRY(hipStreamWaitEvent(e->stream, zm->ev[zm->last], 0), ZLY_ERR_INFERENCE);
+        HIP_TRY(hipMemcpyAsync(out, zm->d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
 }
 

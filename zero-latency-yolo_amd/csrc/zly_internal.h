@@ -364,4 +364,12 @@ struct SurfaceJob;
 // one launch: every band of `bands` (device, n_bands records, 16-byte aligned) from `stage` into `store` (16-byte aligned); no byte outside a band's rows is written
 hipError_t launch_surface_patch(const uint8_t* stage, const SurfaceJob* bands, int n_bands, uint8_t* store, int num_cus, hipStream_t s);
 
+// ---- zoom regions (kernels_zoom.hip; the rule: include/zly.h, "Zoom regions"; the frame record and the arithmetic: zoom_device.h) ----
+struct ZoomFrame;
+// one launch, one wavefront per frame: plans K regions for each of the n frames of `frames` (device) from states[frame.stream] (and motion[...], or
+// null: vx = vy = 0) into plan[n * K].  desc / tab non-null (a frame call): the n * (1 + K) descriptors + view records and the merge table of n groups
+// of 1 + K members that the host has uploaded with every region at its fallback origin; the kernel patches the origins' offsets and x0, y0
+hipError_t launch_zoom_plan(const TrackStream* states, const TrackMotion* motion, const ZoomFrame* frames, int n, FrameDesc* desc, int* tab, zly_zoom_region* plan,
+                            int K, int max_tracks, int region_w, int region_h, int max_age, int class_id, hipStream_t s);
+
 }  // namespace zly

@@ -58,6 +58,7 @@ SYMBOLS = [
     "zly_default_track_motion_config", "zly_track_motion_enable", "zly_track_read",
     "zly_default_merge_config", "zly_merge_slabs", "zly_read_merged", "zly_tile_grid", "zly_detect_tiled",
     "zly_surfaces_enable", "zly_surface_define", "zly_surface_update", "zly_surface_read", "zly_detect_surfaces", "zly_detect_delta",
+    "zly_default_zoom_config", "zly_zoom_enable", "zly_detect_device_zoom", "zly_detect_surfaces_zoom", "zly_zoom_plan", "zly_zoom_read_plan",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -69,6 +70,9 @@ SLAB_HDR_DTYPE = np.dtype([("n_kept", "<i4"), ("n_candidates", "<i4"), ("flags",
 TRACK_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("vx", "<f4"), ("vy", "<f4"),
                         ("class_id", "<i4"), ("id", "<u4"), ("hits", "<u4"), ("last_seen", "<u4")])
 assert TRACK_DTYPE.itemsize == 40
+# zly_zoom_region: one planned region of a frame (zly_zoom_plan, zly_zoom_read_plan); slot = -1, track_id = 0: a fallback
+ZOOM_REGION_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("slot", "<i4"), ("track_id", "<u4")])
+assert ZOOM_REGION_DTYPE.itemsize == 24
 
 
 class Config(C.Structure):
@@ -123,6 +127,11 @@ class SurfaceRect(C.Structure):
 class Roi(C.Structure):
     """zly_roi"""
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class ZoomConfig(C.Structure):
+    """zly_zoom_config"""
+    _fields_ = [("regions", C.c_int32), ("region_w", C.c_int32), ("region_h", C.c_int32), ("max_age", C.c_int32), ("class_id", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -220,6 +229,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_surface_read.argtypes = [vp, i32, vp, sz]; lib.zly_surface_read.restype = i32
     lib.zly_detect_surfaces.argtypes = [vp, i32, pi32, C.POINTER(Roi), vp, u32, vp]; lib.zly_detect_surfaces.restype = i32
     lib.zly_detect_delta.argtypes = [vp, i32, C.POINTER(SurfaceRect), C.POINTER(vp), C.POINTER(sz), pv, i32, pi32, vp, i32, pi32]; lib.zly_detect_delta.restype = i32
+    lib.zly_default_zoom_config.argtypes = [vp, C.POINTER(ZoomConfig)]; lib.zly_default_zoom_config.restype = None
+    lib.zly_zoom_enable.argtypes = [vp, C.POINTER(ZoomConfig)]; lib.zly_zoom_enable.restype = i32
+    lib.zly_detect_device_zoom.argtypes = [vp, i32, vp, sz, pv, pi32, C.POINTER(MergeConfig), vp, u32, vp]; lib.zly_detect_device_zoom.restype = i32
+    lib.zly_detect_surfaces_zoom.argtypes = [vp, i32, pi32, pi32, C.POINTER(MergeConfig), vp, u32, vp]; lib.zly_detect_surfaces_zoom.restype = i32
+    lib.zly_zoom_plan.argtypes = [vp, i32, pi32, pi32, pi32, vp]; lib.zly_zoom_plan.restype = i32
+    lib.zly_zoom_read_plan.argtypes = [vp, i32, vp]; lib.zly_zoom_read_plan.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -335,6 +350,7 @@ class Engine:
         _check(self.lib, self.lib.zly_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self.model_w, self.model_h, self.max_batch, self.max_dets = model_w, model_h, max_batch, max_dets
+        self.zoom_regions = 0             # K, once zoom_enable has been called
         self.nc = self.lib.zly_num_classes(h)
         self.weights_fp8 = bool(self.lib.zly_weights_fp8(h))
         self.N = self.lib.zly_num_anchors(h)
@@ -556,6 +572,53 @@ class Engine:
         n_out = (C.c_int32 * n)()
         _check(self.lib, self.lib.zly_detect_delta(self.h, nr, cr, ptrs, nbytes, cv, n, cs, out.ctypes.data, cap, n_out))
         return [(out[i, :min(n_out[i], cap)], int(n_out[i])) for i in range(n)]
+
+    # -- zoom regions (include/zly.h "Zoom regions") ---------------------------------------------------------
+    def zoom_enable(self, regions: Optional[int] = None, region_w: Optional[int] = None, region_h: Optional[int] = None, max_age: Optional[int] = None,
+                    class_id: Optional[int] = None):
+        """once per engine, after track_enable; arguments left out keep zly_default_zoom_config's values (3 regions of the model's size, max_age 2, any class)"""
+        c = ZoomConfig()
+        self.lib.zly_default_zoom_config(self.h, C.byref(c))
+        for name, v in (("regions", regions), ("region_w", region_w), ("region_h", region_h), ("max_age", max_age), ("class_id", class_id)):
+            if v is not None:
+                setattr(c, name, v)
+        _check(self.lib, self.lib.zly_zoom_enable(self.h, C.byref(c)))
+        self.zoom_regions = c.regions
+
+    def detect_device_zoom(self, d_base_ptr: int, buf_bytes: int, surface_views: Sequence[FrameView], streams: Sequence[int], metric: Optional[int] = None,
+                           thr: Optional[float] = None, d_out_ptr: int = 0, tag0: int = 0, stream: int = 0):
+        """one frame per surface view of the device buffer: the whole surface and its planned regions detected in one batch, merged (d_out_ptr = 0: the
+        engine-owned merge buffer, read with read_merged) and tracked with streams[i]; enqueued, not synchronised"""
+        n = len(surface_views)
+        cv = (FrameView * n)(*surface_views)
+        cs = (C.c_int32 * len(streams))(*streams)
+        c = merge_config(metric, thr)
+        _check(self.lib, self.lib.zly_detect_device_zoom(self.h, n, d_base_ptr or None, buf_bytes, cv, cs, C.byref(c), d_out_ptr or None, tag0, stream or None))
+
+    def detect_surfaces_zoom(self, surfaces: Sequence[int], streams: Sequence[int], metric: Optional[int] = None, thr: Optional[float] = None,
+                             d_out_ptr: int = 0, tag0: int = 0, stream: int = 0):
+        """detect_device_zoom on resident surfaces"""
+        n = len(surfaces)
+        cf = (C.c_int32 * n)(*surfaces)
+        cs = (C.c_int32 * len(streams))(*streams)
+        c = merge_config(metric, thr)
+        _check(self.lib, self.lib.zly_detect_surfaces_zoom(self.h, n, cf, cs, C.byref(c), d_out_ptr or None, tag0, stream or None))
+
+    def zoom_plan(self, sizes: Sequence[Tuple[int, int]], streams: Sequence[int]) -> np.ndarray:
+        """the plan kernel alone (synchronous): sizes[i] = (W, H) of the frame of streams[i] -> ZOOM_REGION_DTYPE[len(sizes)][K]"""
+        n = len(sizes)
+        cw = (C.c_int32 * n)(*[s[0] for s in sizes])
+        ch = (C.c_int32 * n)(*[s[1] for s in sizes])
+        cs = (C.c_int32 * n)(*streams)
+        out = np.zeros((n, max(self.zoom_regions, 1)), dtype=ZOOM_REGION_DTYPE)
+        _check(self.lib, self.lib.zly_zoom_plan(self.h, n, cw, ch, cs, out.ctypes.data))
+        return out
+
+    def zoom_read_plan(self, n: int) -> np.ndarray:
+        """the regions of the most recent zoom call of n frames (synchronises) -> ZOOM_REGION_DTYPE[n][K]"""
+        out = np.zeros((n, max(self.zoom_regions, 1)), dtype=ZOOM_REGION_DTYPE)
+        _check(self.lib, self.lib.zly_zoom_read_plan(self.h, n, out.ctypes.data))
+        return out
 
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
