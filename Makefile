@@ -84,7 +84,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_frame_rules $(OUT)/test_surface_rules $(OUT)/test_zoom_plan $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_frame_rules $(OUT)/test_surface_rules $(OUT)/test_surface_moves $(OUT)/test_zoom_plan $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -155,6 +155,15 @@ $(OUT)/test_surface_rules: $(SURFACE_RULES) | $(OUT)
 surface_rules_san: $(OUT)/test_surface_rules_san
 $(OUT)/test_surface_rules_san: $(SURFACE_RULES) | $(OUT)
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(CSRC) -o $@ tests/cpp/test_surface_rules.cpp
+# the moves of the resident surfaces (csrc/surface_rules.h: surface_plan_moves -- refusals, phases, tables) on their own, for tests/test_surface_moves.py:
+# the program executes every launch's bands item by item as the kernels walk them, in three orders
+SURFACE_MOVES := tests/cpp/test_surface_moves.cpp $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/frame_rules.h $(CSRC)/front_variants.h include/zly.h
+$(OUT)/test_surface_moves: $(SURFACE_MOVES) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(CSRC) -o $@ tests/cpp/test_surface_moves.cpp
+# ... and under the host sanitizers: not part of `all`; make surface_moves_san, then run it on a script
+surface_moves_san: $(OUT)/test_surface_moves_san
+$(OUT)/test_surface_moves_san: $(SURFACE_MOVES) | $(OUT)
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(CSRC) -o $@ tests/cpp/test_surface_moves.cpp
 
 # the plan of the zoom regions (csrc/zoom_device.h through the host twin of csrc/zoom_rules.h) on its own, for tests/test_zoom_plan.py: the program reads track
 # tables and prints plans, and walks the per-plane offset arithmetic against view_crop (test infrastructure: no GPU, nothing of the engine).  Contraction
@@ -199,4 +208,4 @@ $(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_
 clean:
 	rm -rf $(OUT) oracle/_build
 
-.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe frame_rules_san surface_rules_san zoom_plan_san clean
+.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe frame_rules_san surface_rules_san surface_moves_san zoom_plan_san clean

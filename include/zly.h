@@ -607,7 +607,25 @@ int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, c
  * outside a rectangle.  Detection builds frame views into the store and takes the device-view path as it is.
  * Not covered: the pipelined submit ring (its slots are tight frames in a staging buffer of their own), the plugin and the wire format (a request
  * carries no rectangle), engines behind host/zly_sharded*.hpp, skipping inference for unchanged tiles (results across batch sizes are not
- * bit-identical, so it would break the rule), and move rectangles. */
+ * bit-identical, so it would break the rule), moves between two surfaces, and rectangles whose pixels lie in a caller's device buffer.
+ *
+ * MOVES (opt-in: zly_surface_moves_enable).  DXGI desktop duplication hands out, with every frame, move rectangles ("the w x h block at (sx, sy) now
+ * lies at (dx, dy)": a scrolled view, a dragged window) to be applied, in order, BEFORE the dirty rectangles, and does not report a moved region as
+ * dirty.  A MOVE is {surface, sx, sy, dx, dy, w, h}.  After a call with moves 0..n-1 every slot holds, byte for byte, the frame obtained by applying
+ * them in index order; each move acts on every plane of the format as  tmp = copy of the source rectangle; destination rectangle = tmp  -- memmove
+ * semantics: the source is read whole before the destination is written.  Both (sx, sy, w, h) and (dx, dy, w, h) must be legal for zly_view_crop on
+ * the surface's tight view: inside the surface, with the format's evenness rules (4:2:0: all even; 4:2:2: x and w even).  A move whose source equals
+ * its destination is legal and changes nothing.  No byte outside a destination rectangle is written, not even with its own value.  The slot must be
+ * defined and valid; a move never makes a slot valid.  THE RULE extends to moves: detecting on a slot after moves gives, bit for bit, what the frame
+ * so obtained gives when uploaded whole.
+ * How: two moves of a call CONFLICT when they name the same surface and the source of one intersects the destination of the other, or their
+ * destinations intersect.  The call is cut into consecutive PHASES in index order: a move joins the current phase unless it conflicts with a move
+ * already in it, or it overlaps itself (source and destination intersect) and the bounce buffer has no room left in this phase; then it opens the
+ * next phase.  A phase is at most two launches on the engine's stream: the move kernel (csrc/kernels_surface.hip) copies the moves that do not
+ * overlap themselves store -> store and gathers the others into the bounce buffer, and, if anything was gathered, the patch kernel scatters the
+ * bounce buffer into the store.  No launch reads or writes a byte that another workgroup of it writes.  A scroll is one phase of two launches, a
+ * window dragged clear of itself one phase of one launch; a chain of n moves of which each depends on the one before it is n phases -- accepted:
+ * capture APIs hand out a handful of moves per frame. */
 #define ZLY_SURFACE_MAX_RECTS 1024      /* rectangles per zly_surface_update / zly_detect_delta call (chosen) */
 #define ZLY_SURFACE_ALIGN     256       /* the slot stride is a multiple of it */
 #define ZLY_SURFACE_STORE_MAX (1ull << 56)   /* largest store in bytes: a view's plane-0 offset rides in 56 bits of the front kernels' frame descriptor */
@@ -654,6 +672,31 @@ int32_t zly_detect_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, c
  * whole, then the read-back; out, cap and n_out as zly_detect_batch_view.  Validity is judged after the update: a call may carry its own keyframe. */
 int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
                          const zly_frame_view* src_views, int32_t n, const int32_t* surfaces, zly_det* out, int32_t cap, int32_t* n_out);
+
+/* Moves inside resident surfaces (the rule: "MOVES" above). */
+#define ZLY_SURFACE_MAX_MOVES 1024      /* moves per zly_surface_move call (chosen) */
+struct zly_surface_move {     /* a struct tag only: C keeps typedef names and functions in one name space, and the call below has this name */
+    int32_t surface;          /* slot index */
+    int32_t sx, sy;           /* the source rectangle's first pixel */
+    int32_t dx, dy;           /* the destination rectangle's first pixel */
+    int32_t w, h;             /* the size of both */
+};
+/* Once per engine, after zly_surfaces_enable: allocates the bounce buffer of scratch_bytes bytes (alone in the process, like the other enables)
+ * through which moves that overlap themselves go; 0 means one slot stride (plus 48 bytes: each plane of a move starts 16-byte aligned), which holds any
+ * single move.  ZLY_ERR_INVALID_ARGUMENT for a second call
+ * and for an engine without a store; ZLY_ERR_SYSTEM for a failed allocation.  An engine that never calls it allocates nothing more and launches what
+ * it launched before. */
+int32_t zly_surface_moves_enable(zly_engine* e, size_t scratch_bytes);
+/* Applies n_moves moves (1..ZLY_SURFACE_MAX_MOVES), in index order, to the store.
+ * Ordering.  As zly_surface_update: the call first WAITS, on the host, for the work enqueued so far on the engine's own stream -- the band tables of
+ * its launches travel through the same single-buffered pinned staging --, then enqueues one copy of the tables and the phases' launches on the
+ * engine's own stream and returns without waiting for them.  On the device its kernels are ordered exactly as the patch kernel of an update is:
+ * behind every zly_detect_surfaces* call made so far, whichever stream that call was given, ahead of every later one, and in call order with
+ * zly_surface_update.  One captured frame is then zly_surface_move, zly_surface_update, zly_detect_surfaces, with no synchronisation of the caller's.
+ * ZLY_ERR_INVALID_ARGUMENT: a null argument, n_moves out of range, an undefined or out-of-range slot, an illegal source or destination rectangle, no
+ * bounce buffer (zly_surface_moves_enable), a single move that overlaps itself and is larger than the bounce buffer; ZLY_ERR_INVALID_INPUT: a slot
+ * that is not valid.  If any move is refused, nothing is enqueued and no slot changes. */
+int32_t zly_surface_move(zly_engine* e, int32_t n_moves, const struct zly_surface_move* moves);
 
 /* --- Zoom regions ------------------------------------------------------------------------------------------------------------------
  * Detects, in ONE batch, a whole surface and K full-resolution regions of it around the stream's tracked targets, merges the 1 + K slabs into one

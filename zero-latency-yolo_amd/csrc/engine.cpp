@@ -199,6 +199,10 @@ struct Surfaces {
     hipEvent_t ev_read = nullptr;
     bool read_pending = false;
     SurfacePlan plan;                 // scratch of the current update
+    // moves (zly_surface_moves_enable): the bounce buffer through which a move that overlaps itself goes, and the scratch of the current call
+    uint8_t* d_bounce = nullptr;
+    size_t bounce_bytes = 0;
+    SurfaceMovePlan mplan;
 };
 
 // Zoom regions (zly_zoom_enable; include/zly.h "Zoom regions"): the ring through which a call's frame records reach zoom_plan_kernel -- pinned host
@@ -1615,6 +1619,7 @@ static hipError_t destroy_engine(zly_engine* e)
     }
     if (Surfaces* sf = e->surf) {
         if (sf->d_store) note(hipFree(sf->d_store));
+        if (sf->d_bounce) note(hipFree(sf->d_bounce));
         if (sf->ev_patch) hipEventDestroy(sf->ev_patch);
         if (sf->ev_read) hipEventDestroy(sf->ev_read);
         delete sf;
@@ -3057,6 +3062,65 @@ int32_t zly_surface_update(zly_engine* e, int32_t n_rects, const zly_surface_rec
     if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
     if (int rc = surface_plan_update(sf->store, sf->slots.data(), n_rects, rects, bases, buf_bytes, src_views, &sf->plan, &g_last_error)) return rc;
     return surface_enqueue_update(e, sf, n_rects, rects, bases, src_views);
+}
+
+int32_t zly_surface_moves_enable(zly_engine* e, size_t scratch_bytes)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    if (sf->d_bounce) return fail(ZLY_ERR_INVALID_ARGUMENT, "surface moves are already enabled on this engine");
+    const size_t bytes = scratch_bytes ? scratch_bytes : sf->store.stride + 48;  // holds any single move: its planes' bytes, each of up to three rounded up to 16
+    ExclusiveGate gl;                                  // an allocation: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (hipMalloc((void**)&sf->d_bounce, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        sf->d_bounce = nullptr;
+        return fail(ZLY_ERR_SYSTEM, "allocation of the bounce buffer (" + std::to_string(bytes) + " bytes) failed");
+    }
+    sf->bounce_bytes = bytes;
+    return ZLY_OK;
+}
+
+// One call's moves: the phases' band tables through pinned staging in ONE copy, then per phase the move kernel and, if it gathered anything, the patch
+// kernel from the bounce buffer -- all on the engine's stream, ordered against detect calls and updates exactly as an update's patch kernel is.
+int32_t zly_surface_move(zly_engine* e, int32_t n_moves, const struct zly_surface_move* moves)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    if (int rc = surface_plan_moves(sf->store, sf->slots.data(), n_moves, moves, sf->bounce_bytes, &sf->mplan, &g_last_error)) return rc;
+    const SurfaceMovePlan& pl = sf->mplan;
+    if (pl.a_bands.empty()) return ZLY_OK;                               // identity moves only: nothing to do
+    if (pl.a_bands.size() > (size_t)std::numeric_limits<int>::max() || pl.b_bands.size() > (size_t)std::numeric_limits<int>::max())
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_surface_move: too many bands");
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    if (pl.table_bytes > e->stage_bytes) {                               // an allocation: alone in the process
+        ExclusiveGate x;
+        if (int rc = ensure_stage(e, pl.table_bytes)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
+    static_assert(sizeof(SurfaceMoveBand) == 32 && sizeof(SurfaceJob) == 32, "the band records are 32 bytes");
+    const size_t b_off = pl.a_bands.size() * sizeof(SurfaceMoveBand);
+    memcpy(e->h_stage, pl.a_bands.data(), b_off);
+    if (!pl.b_bands.empty()) memcpy(e->h_stage + b_off, pl.b_bands.data(), pl.b_bands.size() * sizeof(SurfaceJob));
+    SharedGate gl;
+    if (sf->read_pending) {                                              // detect calls on other streams may still read the slots this writes
+        HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+        sf->read_pending = false;
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, pl.table_bytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
+    const SurfaceMoveBand* d_a = reinterpret_cast<const SurfaceMoveBand*>(e->d_stage);
+    const SurfaceJob* d_b = reinterpret_cast<const SurfaceJob*>(e->d_stage + b_off);
+    for (const SurfaceMovePhase& ph : pl.phases) {
+        HIP_TRY(launch_surface_move(d_a + ph.a_first, (int)ph.a_count, sf->d_store, sf->d_bounce, e->sw.num_cus, e->stream), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_surface_patch(sf->d_bounce, d_b + ph.b_first, (int)ph.b_count, sf->d_store, e->sw.num_cus, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipEventRecord(sf->ev_patch, e->stream), ZLY_ERR_INFERENCE);
+    sf->patched = true;
+    return ZLY_OK;
 }
 
 int32_t zly_surface_read(zly_engine* e, int32_t s, void* host_out, size_t cap_bytes)

@@ -1,5 +1,6 @@
-// kernels_surface.hip -- the patch kernel of the resident surfaces (include/zly.h "Resident surfaces"): ONE launch writes every rectangle of a
-// zly_surface_update call from the staging buffer into the store.
+// kernels_surface.hip -- the kernels of the resident surfaces (include/zly.h "Resident surfaces").  The patch kernel: ONE launch writes every rectangle
+// of a zly_surface_update call from the staging buffer into the store.  The move kernel (at the end of the file): the copies inside the store of a
+// zly_surface_move call.
 //
 // The host (surface_rules.h) turns (rectangle, plane) pairs into jobs and cuts the jobs into bands of whole rows (surface_device.h); the band table
 // lies in the staging buffer behind the pixels, so one copy brings both.  A workgroup takes bands in a grid-stride loop: a 33 MB keyframe is two
@@ -73,6 +74,48 @@ hipError_t launch_surface_patch(const uint8_t* stage, const SurfaceJob* bands, i
     const int most = 8 * (num_cus > 0 ? num_cus : 256);
     const dim3 grid((unsigned)(n_bands < most ? n_bands : most));
     hipLaunchKernelGGL(surface_patch_kernel, grid, dim3(ZLY_SURFACE_THREADS), 0, s, stage, bands, n_bands, store);
+    return hipGetLastError();
+}
+
+// The move kernel (zly_surface_move): the patch kernel's scheme with a pitched source that lies in the STORE itself.  A band (surface_device.h:
+// SurfaceMoveBand) goes store -> store, or store -> bounce buffer for a move whose source and destination intersect; the bounce buffer comes back
+// through surface_patch_kernel in a launch of its own.  The host (surface_rules.h: surface_plan_moves) puts into one launch only bands of which none
+// reads or writes a byte that another one writes, so the order in which workgroups run does not matter -- which is why store and bounce carry no
+// __restrict__: a band's source and another band's destination may be neighbours in one granule, never the same byte.
+// Rows are cut at the DESTINATION's granules, loads are at any byte address, and no access leaves its row: a source row's neighbours in the store
+// are another rectangle's pixels, possibly being written by this very launch.
+__global__ void __launch_bounds__(ZLY_SURFACE_THREADS)
+surface_move_kernel(const SurfaceMoveBand* __restrict__ bands, int n_bands, uint8_t* store, uint8_t* bounce)
+{
+    for (int b = (int)blockIdx.x; b < n_bands; b += (int)gridDim.x) {
+        const SurfaceMoveBand j = bands[b];                     // uniform: scalar loads
+        const unsigned int G = surface_row_granules(j.row_bytes);
+        const unsigned long long items = (unsigned long long)j.rows * G;
+        uint8_t* const dbase = surface_move_to_bounce(j) ? bounce : store;
+        for (unsigned long long i = threadIdx.x; i < items; i += ZLY_SURFACE_THREADS) {
+            unsigned int r, g, k;
+            surface_band_item(j.rows, G, i, &r, &g);
+            uint64_t so, dof;
+            if (!surface_move_item(j, r, g, &so, &dof, &k)) continue;           // the row ends before this granule
+            const uint8_t* sp = store + so;
+            uint8_t* dp = dbase + dof;
+            if (k == 16u) {                                     // unclipped: dof is a multiple of 16, and both bases are 16-byte aligned
+                sf_u32x4 v;
+                __builtin_memcpy(&v, sp, 16);
+                *reinterpret_cast<sf_u32x4*>(dp) = v;
+            } else {
+                surface_copy_edge(dp, sp, k);
+            }
+        }
+    }
+}
+
+hipError_t launch_surface_move(const SurfaceMoveBand* bands, int n_bands, uint8_t* store, uint8_t* bounce, int num_cus, hipStream_t s)
+{
+    if (n_bands < 1) return hipSuccess;
+    const int most = 8 * (num_cus > 0 ? num_cus : 256);         // as launch_surface_patch
+    const dim3 grid((unsigned)(n_bands < most ? n_bands : most));
+    hipLaunchKernelGGL(surface_move_kernel, grid, dim3(ZLY_SURFACE_THREADS), 0, s, bands, n_bands, store, bounce);
     return hipGetLastError();
 }
 

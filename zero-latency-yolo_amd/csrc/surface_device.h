@@ -1,6 +1,6 @@
-// surface_device.h -- what the patch kernel of the resident surfaces (kernels_surface.hip; include/zly.h "Resident surfaces") and the host that
-// feeds it (surface_rules.h) agree on: the shape constants, the band record, and the kernel's index arithmetic -- which bytes of a row a lane owns and
-// how wide its stores are -- so that a host compiler can walk a band table exactly as the kernel does (tests/cpp/test_surface_rules.cpp).  Nothing
+// surface_device.h -- what the patch and move kernels of the resident surfaces (kernels_surface.hip; include/zly.h "Resident surfaces") and the host that
+// feeds them (surface_rules.h) agree on: the shape constants, the band records, and the kernels' index arithmetic -- which bytes of a row a lane owns and
+// how wide its stores are -- so that a host compiler can walk a band table exactly as the kernel does (tests/cpp/test_surface_rules.cpp, test_surface_moves.cpp).  Nothing
 // here includes a HIP header: a plain C++ compiler takes this file as it is.
 #pragma once
 #include <stdint.h>
@@ -54,6 +54,44 @@ ZLY_SURFACE_HD uint32_t surface_edge_width(uint32_t addr, uint32_t k)
     if (wd == 0u || wd > 8u) wd = 8u;
     while (wd > k) wd >>= 1;
     return wd;
+}
+
+// ---- moves (zly_surface_move; kernels_surface.hip: surface_move_kernel) ----
+// One band of a move: `rows` rows of `row_bytes` bytes from src_off + r * src_pitch in the STORE to dst_off + r * dst_pitch.  The destination is the
+// store, or -- ZLY_SURFACE_MOVE_TO_BOUNCE set in dst_off -- the bounce buffer: a store has at most 2^56 bytes (ZLY_SURFACE_STORE_MAX), so bit 63 of
+// an offset is free.  A move's JOB -- one plane of one move -- is the same record before it is cut into bands.  32 bytes, as SurfaceJob.
+#define ZLY_SURFACE_MOVE_TO_BOUNCE (1ull << 63)
+struct SurfaceMoveBand {
+    uint64_t src_off;       // from the store's base
+    uint64_t dst_off;       // from the store's base, or | ZLY_SURFACE_MOVE_TO_BOUNCE: from the bounce buffer's
+    uint32_t row_bytes;     // 1 .. 2^31 - 1
+    uint32_t rows;          // >= 1
+    uint32_t src_pitch;     // bytes from one source row to the next
+    uint32_t dst_pitch;     // ... and from one destination row to the next (the bounce buffer's rows are tight: row_bytes)
+};
+
+ZLY_SURFACE_HD bool surface_move_to_bounce(const SurfaceMoveBand& b) { return (b.dst_off & ZLY_SURFACE_MOVE_TO_BOUNCE) != 0; }
+ZLY_SURFACE_HD uint64_t surface_move_dst(const SurfaceMoveBand& b) { return b.dst_off & ~ZLY_SURFACE_MOVE_TO_BOUNCE; }
+
+// Item i of a band of `rows` rows of G granules each (i < rows * G) is granule *g of row *r.  A band of more than one row holds at most
+// ZLY_SURFACE_BAND_BYTES bytes, hence at most 2 * ZLY_SURFACE_BAND_BYTES items: the division is one of 32 bits.  A band of one row may be very long.
+ZLY_SURFACE_HD void surface_band_item(uint32_t rows, uint32_t G, uint64_t i, uint32_t* r, uint32_t* g)
+{
+    if (rows == 1u) { *r = 0u; *g = (uint32_t)i; }
+    else { *r = (uint32_t)i / G; *g = (uint32_t)i - *r * G; }
+}
+
+// Where item (r, g) of a move's band reads and writes: bytes [lo, hi) of row r, from *src (an offset into the store) to *dst (an offset into the
+// band's destination buffer).  False: the row ends before this granule.  The cut is surface_granule's, at the DESTINATION's granules.
+ZLY_SURFACE_HD bool surface_move_item(const SurfaceMoveBand& b, uint32_t r, uint32_t g, uint64_t* src, uint64_t* dst, uint32_t* k)
+{
+    const uint64_t drow = surface_move_dst(b) + (uint64_t)r * b.dst_pitch;
+    uint32_t lo, hi;
+    if (!surface_granule(drow, b.row_bytes, g, &lo, &hi)) return false;
+    *src = b.src_off + (uint64_t)r * b.src_pitch + lo;
+    *dst = drow + lo;
+    *k = hi - lo;
+    return true;
 }
 
 }  // namespace zly

@@ -1,7 +1,7 @@
 // surface_rules.h -- the host-side rules of the resident surfaces (include/zly.h "Resident surfaces"): the store's geometry, what a define and an
-// update may ask for, the table of jobs and bands an update hands to the patch kernel (kernels_surface.hip), and the views a detect call reads the
-// store through.  Like frame_rules.h, on which it builds: plain C++, nothing of HIP or the engine, so that engine.cpp and a stand-alone test program
-// (tests/cpp/test_surface_rules.cpp) compile the same text.  A refusal hands back its ZLY_ERR_* code and, through `err`, its message.
+// update may ask for, the table of jobs and bands an update hands to the patch kernel (kernels_surface.hip), the phases and tables of a call of moves,
+// and the views a detect call reads the store through.  Like frame_rules.h, on which it builds: plain C++, nothing of HIP or the engine, so that engine.cpp and a stand-alone test program
+// (tests/cpp/test_surface_rules.cpp, test_surface_moves.cpp) compile the same text.  A refusal hands back its ZLY_ERR_* code and, through `err`, its message.
 #pragma once
 #include <vector>
 #include "frame_rules.h"
@@ -161,6 +161,128 @@ inline int32_t surface_plan_update(const SurfaceStore& st, const SurfaceSlot* sl
     plan->pixel_bytes = total;
     plan->table_off = total;                                    // a multiple of 16
     plan->stage_bytes = total + plan->bands.size() * sizeof(SurfaceJob);
+    return ZLY_OK;
+}
+
+// ---- moves (include/zly.h "Resident surfaces", MOVES) ----
+typedef struct zly_surface_move SurfaceMoveReq;      // (the header keeps the plain name for the call)
+
+inline bool surface_rects_meet(int64_t ax, int64_t ay, int64_t bx, int64_t by, int64_t w_a, int64_t h_a, int64_t w_b, int64_t h_b)
+{
+    return ax < bx + w_b && bx < ax + w_a && ay < by + h_b && by < ay + h_a;
+}
+inline bool surface_move_identity(const SurfaceMoveReq& m) { return m.sx == m.dx && m.sy == m.dy; }
+// source and destination intersect (an identity move does, too; it is dropped before anyone asks)
+inline bool surface_move_self_overlaps(const SurfaceMoveReq& m) { return surface_rects_meet(m.sx, m.sy, m.dx, m.dy, m.w, m.h, m.w, m.h); }
+// two moves of one call conflict: the same surface, and a source meets the other's destination, or the destinations meet.  In surface pixels: the
+// planes follow by the formats' evenness rules.
+inline bool surface_moves_conflict(const SurfaceMoveReq& a, const SurfaceMoveReq& b)
+{
+    if (a.surface != b.surface) return false;
+    return surface_rects_meet(a.sx, a.sy, b.dx, b.dy, a.w, a.h, b.w, b.h) || surface_rects_meet(a.dx, a.dy, b.sx, b.sy, a.w, a.h, b.w, b.h) ||
+           surface_rects_meet(a.dx, a.dy, b.dx, b.dy, a.w, a.h, b.w, b.h);
+}
+
+// One phase: moves [first, first + count) of the call, launch A = a_bands [a_first, a_first + a_count) through surface_move_kernel, launch B =
+// b_bands [b_first, b_first + b_count) through surface_patch_kernel with the bounce buffer as its staging (b_count = 0: nothing was gathered, no
+// launch).  bounce_bytes: what the phase uses of the bounce buffer.  A phase of identity moves alone has no launch at all.
+struct SurfaceMovePhase {
+    int32_t first = 0, count = 0;
+    size_t a_first = 0, a_count = 0, b_first = 0, b_count = 0, bounce_bytes = 0;
+};
+
+// What a zly_surface_move call enqueues.  a_jobs / b_jobs: one per (move, plane), before they are cut into a_bands / b_bands (in job order); via[i]:
+// 0 move i is an identity and appears in no table, 1 it is copied store -> store, 2 it goes through the bounce buffer; phase_of[i]: its phase.  The
+// tables go to the device as [a_bands][b_bands], both of 32-byte records: table_bytes.
+struct SurfaceMovePlan {
+    std::vector<SurfaceMovePhase> phases;
+    std::vector<SurfaceMoveBand> a_jobs, a_bands;
+    std::vector<SurfaceJob> b_jobs, b_bands;
+    std::vector<char> via;
+    std::vector<int32_t> phase_of;
+    size_t table_bytes = 0;
+};
+
+// a move job's bands: as surface_bands cuts a patch job
+inline void surface_move_bands(const SurfaceMoveBand& j, std::vector<SurfaceMoveBand>* out)
+{
+    const uint32_t per = std::max<uint32_t>(1u, (uint32_t)ZLY_SURFACE_BAND_BYTES / j.row_bytes);
+    for (uint32_t r = 0; r < j.rows; r += per) {
+        SurfaceMoveBand b = j;
+        b.src_off = j.src_off + (uint64_t)r * j.src_pitch;
+        b.dst_off = j.dst_off + (uint64_t)r * j.dst_pitch;      // (the bounce flag rides along: the sum stays far below bit 63)
+        b.rows = std::min(per, j.rows - r);
+        out->push_back(b);
+    }
+}
+
+// zly_surface_move's checks, its phases and its tables.  bounce_bytes: the bounce buffer's size, 0 if the engine has none.  Nothing is modified.
+// A move is compared with every move of the current phase: n^2 / 2 comparisons of three rectangle pairs at worst (1024 independent moves: half a
+// million, about a millisecond), a handful for what a capture API hands out.
+inline int32_t surface_plan_moves(const SurfaceStore& st, const SurfaceSlot* slots, int32_t n_moves, const SurfaceMoveReq* moves, size_t bounce_bytes, SurfaceMovePlan* plan,
+                                  std::string* err)
+{
+    if (n_moves < 1 || n_moves > ZLY_SURFACE_MAX_MOVES)
+        return refuse(err, ZLY_ERR_INVALID_ARGUMENT, "zly_surface_move: " + std::to_string(n_moves) + " moves, a call takes 1.." + std::to_string(ZLY_SURFACE_MAX_MOVES));
+    if (!moves) return refuse(err, ZLY_ERR_INVALID_ARGUMENT, "null argument");
+    if (bounce_bytes < 1) return refuse(err, ZLY_ERR_INVALID_ARGUMENT, "zly_surface_move: the engine has no bounce buffer (zly_surface_moves_enable)");
+    plan->phases.clear(); plan->a_jobs.clear(); plan->a_bands.clear(); plan->b_jobs.clear(); plan->b_bands.clear();
+    plan->via.assign((size_t)n_moves, 0); plan->phase_of.assign((size_t)n_moves, 0);
+    SurfaceMovePhase ph;
+    auto close_phase = [&](int32_t next_first) {
+        ph.count = next_first - ph.first;
+        ph.a_count = plan->a_bands.size() - ph.a_first; ph.b_count = plan->b_bands.size() - ph.b_first;
+        plan->phases.push_back(ph);
+        ph = SurfaceMovePhase();
+        ph.first = next_first; ph.a_first = plan->a_bands.size(); ph.b_first = plan->b_bands.size();
+    };
+    for (int32_t i = 0; i < n_moves; ++i) {
+        const SurfaceMoveReq& m = moves[i];
+        const std::string who = "move " + std::to_string(i) + ": ";
+        if (int rc = surface_check_slot(st, m.surface, err)) return rc;
+        const SurfaceSlot& sl = slots[m.surface];
+        if (!sl.defined) return refuse(err, ZLY_ERR_INVALID_ARGUMENT, who + "surface " + std::to_string(m.surface) + " is not defined (zly_surface_define)");
+        if (!sl.valid) return refuse(err, ZLY_ERR_INVALID_INPUT, who + "surface " + std::to_string(m.surface) + " is not valid: it needs a rectangle that covers it whole (a keyframe)");
+        const zly_frame_view whole = surface_view(st, sl, m.surface);
+        zly_frame_view src, dst;
+        std::string why;
+        if (view_crop(&whole, m.sx, m.sy, m.w, m.h, &src, &why) != ZLY_OK) return refuse(err, ZLY_ERR_INVALID_ARGUMENT, who + "source: " + why);
+        if (view_crop(&whole, m.dx, m.dy, m.w, m.h, &dst, &why) != ZLY_OK) return refuse(err, ZLY_ERR_INVALID_ARGUMENT, who + "destination: " + why);
+        if (surface_move_identity(m)) { plan->phase_of[(size_t)i] = (int32_t)plan->phases.size(); continue; }
+        int64_t rows[3], rb[3];
+        const int np = plane_shape(sl.fmt, m.w, m.h, rows, rb);
+        const bool self = surface_move_self_overlaps(m);
+        size_t need = 0;                                        // of the bounce buffer: every job's start is 16-byte aligned
+        if (self) {
+            for (int p = 0; p < np; ++p) need += (size_t)(((uint64_t)rows[p] * (uint64_t)rb[p] + 15u) / 16u * 16u);
+            if (need > bounce_bytes)
+                return refuse(err, ZLY_ERR_INVALID_ARGUMENT, who + "it overlaps itself and needs " + std::to_string(need) + " bytes of the bounce buffer, which has " + std::to_string(bounce_bytes));
+        }
+        bool open_next = self && ph.bounce_bytes + need > bounce_bytes;
+        for (int32_t k = ph.first; k < i && !open_next; ++k)
+            open_next = plan->via[(size_t)k] != 0 && surface_moves_conflict(moves[k], m);
+        if (open_next) close_phase(i);
+        plan->phase_of[(size_t)i] = (int32_t)plan->phases.size();
+        plan->via[(size_t)i] = self ? 2 : 1;
+        for (int p = 0; p < np; ++p) {
+            SurfaceMoveBand a;
+            a.src_off = src.off[p]; a.row_bytes = (uint32_t)rb[p]; a.rows = (uint32_t)rows[p]; a.src_pitch = (uint32_t)src.pitch[p];
+            if (self) {
+                a.dst_off = ZLY_SURFACE_MOVE_TO_BOUNCE | (uint64_t)ph.bounce_bytes; a.dst_pitch = a.row_bytes;
+                SurfaceJob b;
+                b.src_off = ph.bounce_bytes; b.dst_off = dst.off[p]; b.row_bytes = a.row_bytes; b.rows = a.rows; b.pitch = (uint32_t)dst.pitch[p]; b.pad_ = 0;
+                plan->b_jobs.push_back(b);
+                surface_bands(b, &plan->b_bands);
+                ph.bounce_bytes += (size_t)(((uint64_t)rows[p] * (uint64_t)rb[p] + 15u) / 16u * 16u);
+            } else {
+                a.dst_off = dst.off[p]; a.dst_pitch = (uint32_t)dst.pitch[p];
+            }
+            plan->a_jobs.push_back(a);
+            surface_move_bands(a, &plan->a_bands);
+        }
+    }
+    close_phase(n_moves);
+    plan->table_bytes = (plan->a_bands.size() + plan->b_bands.size()) * sizeof(SurfaceJob);
     return ZLY_OK;
 }
 

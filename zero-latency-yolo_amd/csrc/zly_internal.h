@@ -363,6 +363,10 @@ hipError_t launch_merge(const int* tab, int n_groups, int max_slots, const void*
 struct SurfaceJob;
 // one launch: every band of `bands` (device, n_bands records, 16-byte aligned) from `stage` into `store` (16-byte aligned); no byte outside a band's rows is written
 hipError_t launch_surface_patch(const uint8_t* stage, const SurfaceJob* bands, int n_bands, uint8_t* store, int num_cus, hipStream_t s);
+struct SurfaceMoveBand;
+// one launch of a move's bands (device, 16-byte aligned): from `store` into `store` or, for the bands that say so, into `bounce` (16-byte aligned; may be
+// null if no band names it).  The caller guarantees that no band reads or writes a byte that another band of the launch writes.
+hipError_t launch_surface_move(const SurfaceMoveBand* bands, int n_bands, uint8_t* store, uint8_t* bounce, int num_cus, hipStream_t s);
 
 // ---- zoom regions (kernels_zoom.hip; the rule: include/zly.h, "Zoom regions"; the frame record and the arithmetic: zoom_device.h) ----
 struct ZoomFrame;

@@ -44,6 +44,7 @@ MERGE_IOU, MERGE_IOS = 0, 1          # zly_merge_config.metric (include/zly.h "T
 MERGE_MAX_CANDIDATES = 4096          # tiles of a group x max_dets may not exceed it
 SURFACE_MAX_RECTS = 1024             # rectangles per surface_update / detect_delta call (include/zly.h "Resident surfaces")
 SURFACE_ALIGN = 256                  # the store's slot stride is a multiple of it
+SURFACE_MAX_MOVES = 1024             # moves per surface_move call
 _PACKED_BPP = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
 
 # every symbol include/zly.h declares (tests/test_abi.py checks the library exports them all)
@@ -58,6 +59,7 @@ SYMBOLS = [
     "zly_default_track_motion_config", "zly_track_motion_enable", "zly_track_read",
     "zly_default_merge_config", "zly_merge_slabs", "zly_read_merged", "zly_tile_grid", "zly_detect_tiled",
     "zly_surfaces_enable", "zly_surface_define", "zly_surface_update", "zly_surface_read", "zly_detect_surfaces", "zly_detect_delta",
+    "zly_surface_moves_enable", "zly_surface_move",
     "zly_default_zoom_config", "zly_zoom_enable", "zly_detect_device_zoom", "zly_detect_surfaces_zoom", "zly_zoom_plan", "zly_zoom_read_plan",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
@@ -122,6 +124,11 @@ class MergeConfig(C.Structure):
 class SurfaceRect(C.Structure):
     """zly_surface_rect: where a rectangle's first pixel lies in which resident surface (its size and format are its source view's)"""
     _fields_ = [("surface", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32)]
+
+
+class SurfaceMove(C.Structure):
+    """struct zly_surface_move: the w x h block at (sx, sy) of a resident surface now lies at (dx, dy)"""
+    _fields_ = [("surface", C.c_int32), ("sx", C.c_int32), ("sy", C.c_int32), ("dx", C.c_int32), ("dy", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
 
 class Roi(C.Structure):
@@ -229,6 +236,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_surface_read.argtypes = [vp, i32, vp, sz]; lib.zly_surface_read.restype = i32
     lib.zly_detect_surfaces.argtypes = [vp, i32, pi32, C.POINTER(Roi), vp, u32, vp]; lib.zly_detect_surfaces.restype = i32
     lib.zly_detect_delta.argtypes = [vp, i32, C.POINTER(SurfaceRect), C.POINTER(vp), C.POINTER(sz), pv, i32, pi32, vp, i32, pi32]; lib.zly_detect_delta.restype = i32
+    lib.zly_surface_moves_enable.argtypes = [vp, sz]; lib.zly_surface_moves_enable.restype = i32
+    lib.zly_surface_move.argtypes = [vp, i32, C.POINTER(SurfaceMove)]; lib.zly_surface_move.restype = i32
     lib.zly_default_zoom_config.argtypes = [vp, C.POINTER(ZoomConfig)]; lib.zly_default_zoom_config.restype = None
     lib.zly_zoom_enable.argtypes = [vp, C.POINTER(ZoomConfig)]; lib.zly_zoom_enable.restype = i32
     lib.zly_detect_device_zoom.argtypes = [vp, i32, vp, sz, pv, pi32, C.POINTER(MergeConfig), vp, u32, vp]; lib.zly_detect_device_zoom.restype = i32
@@ -572,6 +581,16 @@ class Engine:
         n_out = (C.c_int32 * n)()
         _check(self.lib, self.lib.zly_detect_delta(self.h, nr, cr, ptrs, nbytes, cv, n, cs, out.ctypes.data, cap, n_out))
         return [(out[i, :min(n_out[i], cap)], int(n_out[i])) for i in range(n)]
+
+    def surface_moves_enable(self, scratch_bytes: int = 0):
+        """once per engine, after surfaces_enable: the bounce buffer of surface_move (0: one slot stride)"""
+        _check(self.lib, self.lib.zly_surface_moves_enable(self.h, scratch_bytes))
+
+    def surface_move(self, moves):
+        """moves: (surface, sx, sy, dx, dy, w, h) each, applied in order inside the store (memmove semantics); enqueued, not synchronised"""
+        n = len(moves)
+        cm = (SurfaceMove * max(n, 1))(*[SurfaceMove(*m) for m in moves])
+        _check(self.lib, self.lib.zly_surface_move(self.h, n, cm))
 
     # -- zoom regions (include/zly.h "Zoom regions") ---------------------------------------------------------
     def zoom_enable(self, regions: Optional[int] = None, region_w: Optional[int] = None, region_h: Optional[int] = None, max_age: Optional[int] = None,
