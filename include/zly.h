@@ -769,6 +769,95 @@ int32_t zly_detect_surfaces_zoom(zly_engine* e, int32_t n, const int32_t* surfac
 int32_t zly_zoom_plan(zly_engine* e, int32_t n, const int32_t* W, const int32_t* H, const int32_t* streams, zly_zoom_region* out);
 int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out);
 
+/* --- Chips -------------------------------------------------------------------------------------------------------------------------
+ * Cuts, on the GPU and behind NMS, a fixed-size CHIP -- an area-resized crop -- out of the frame for each of a slab's detections, reading the boxes
+ * where the slab lies in HBM.  Everything behind a detector wants a target's pixels: a second-stage classifier, an appearance descriptor for
+ * re-identification, a thumbnail for a status page, a client overlay.  Without this the only way to them is a synchronising slab read to learn
+ * where the boxes are, then -- for a resident surface -- zly_surface_read of the whole surface (8 MB for 1920 x 1080 BGRA), then a crop and a resize
+ * on the host.  With it the frame stays enqueue-only.  Opt-in per engine (zly_chips_enable): an engine that never calls it allocates nothing more
+ * and launches exactly the kernels it launched before.
+ *
+ * Inputs for one frame: a slab in the usual layout (from any zly_detect_device* call, merged by zly_merge_slabs or a zoom call, tracked or not);
+ * the frame view of W x H that the slab's boxes are fractions of, in any ZLY_PIX_* format -- the request view, or the surface for merged slabs --
+ * with 1 <= W, H <= ZLY_AREA_MAX_DIM; the engine's chip config.  All float arithmetic is single IEEE fp32 operations in the order written, without
+ * contraction, as in the zoom plan; the (float) conversions of these integers are exact.
+ *   1. K = clamp(n_kept, 0, cap).  The detections are D[0..K) in slab order.
+ *   2. Detection d is ELIGIBLE when class_id == -1 || D[d].class_id == class_id.  n_eligible counts them all.
+ *   3. SELECTED: the first n_chips = min(max_chips, n_eligible) eligible detections, in slab order.  Chip j belongs to the j-th of them.
+ *   4. The source rectangle, per axis; shown for x with the extent W, y with H likewise:
+ *          e = D.w * scale;  half = e * 0.5f;  lo = D.x - half;  hi = D.x + half
+ *          c(v) = v > 0 ? (v < 1 ? v : 1) : 0          (a NaN gives 0)
+ *          a = (int32)(c(lo) * (float)W);  b = (int32)(c(hi) * (float)W)          (truncating)
+ *          a = min(a, W - 1);  b = min(max(b, a + 1), W);  x0 = a;  rw = b - a
+ *      So every float box gives a legal rectangle with 1 <= rw <= W.  No evenness is required, for the YUV formats too.
+ *   5. The chip's pixels are the area resize of "Area resize" above with source lengths S = (rw, rh) and content size D = (chip_w, chip_h).  The
+ *      source pixel (ix, iy) of the filter is pixel (x0 + ix, y0 + iy) of the FRAME, converted to B, G, R by the existing per-format rules at its
+ *      own position in the frame: a 4:2:0 or 4:2:2 pixel uses its own chroma sample, whatever the parity of x0, y0.  The accumulation,
+ *      T = rw*rh and the round-half-up division are the same.  A rectangle smaller than the chip upscales by the same rule: no other filter.
+ *   6. Layouts (zly_chip_config.layout):
+ *          ZLY_CHIP_BGR8      u8 [chip_h][chip_w][3], B, G, R
+ *          ZLY_CHIP_RGB_F32   float [3][chip_h][chip_w], planes R, G, B, value (float)v / 255.0f -- the division zly_preprocess performs: what a
+ *                             classifier takes
+ *   7. The output per frame is a CHIP SLAB: a zly_chip_header, 16 bytes; max_chips records zly_chip_rec, 32 bytes each; padding to a multiple of 256
+ *      bytes; max_chips chips at a stride of the chip's bytes rounded up to 16.  zly_chip_layout reports the numbers.  NOTHING ELSE IS WRITTEN:
+ *      records and chips at or beyond n_chips, the padding, and the bytes between a chip's end and its stride are untouched.
+ * THE RULE: a chip equals, byte for byte, the area resize (tests/area_ref.py: area_bgr) of B[y0 : y0 + rh, x0 : x0 + rw] to chip_w x chip_h, where B
+ * is the frame's BGR image by the format's rules.  A view gives what the tight frame of its samples gives; bytes outside the view never influence a
+ * chip; no byte at or beyond a plane's extent is read.
+ * Consequences.  A rectangle of exactly the chip's size returns the source pixels.  A constant frame gives constant chips.
+ * Out of scope: frames in host memory (the synchronous calls, the pipelined ring); the plugin and the wire format; engines behind
+ * host/zly_sharded*.hpp; aspect-preserving or padded chips; chips of tracks that have no detection in the frame; per-class chip sizes; any encoder;
+ * and any accuracy claim -- weights and frames are synthetic, and the defaults are chosen, not tuned. */
+#define ZLY_CHIP_BGR8     0
+#define ZLY_CHIP_RGB_F32  1
+#define ZLY_CHIPS_SRC_SLABS  0     /* d_slabs == NULL: the engine's own slab buffer */
+#define ZLY_CHIPS_SRC_MERGED 1     /* d_slabs == NULL: the merge's engine-owned output (zly_merge_slabs and the zoom calls given NULL) */
+typedef struct zly_chip_config {
+    int32_t chip_w, chip_h;   /* 1..256; default 64, 64 (chosen, not tuned) */
+    int32_t max_chips;        /* per frame, 1..max_dets; default min(max_dets, 16) */
+    int32_t class_id;         /* -1: any */
+    float   scale;            /* finite, in [1, 4]; default 1.25 (chosen, not tuned) */
+    int32_t layout;           /* ZLY_CHIP_BGR8 (default) | ZLY_CHIP_RGB_F32 */
+} zly_chip_config;
+typedef struct zly_chip_header {
+    int32_t  n_chips, n_eligible;
+    uint32_t frame_tag;       /* copied from the slab */
+    uint32_t flags;           /* 0 */
+} zly_chip_header;
+typedef struct zly_chip_rec {
+    int32_t  det;             /* the detection's index in its slab */
+    int32_t  class_id;
+    uint32_t track_id;
+    float    confidence;
+    int32_t  x0, y0, w, h;    /* the source rectangle in frame pixels */
+} zly_chip_rec;
+void    zly_default_chip_config(const zly_engine* e, zly_chip_config* cfg);
+/* Once per engine: allocates max_batch chip slabs and a small ring of frame records (alone in the process, like the other enables).
+ * ZLY_ERR_INVALID_ARGUMENT: a null, out-of-range or NaN config, a second call; ZLY_ERR_SYSTEM: a failed allocation.  Every other call of this section
+ * on an engine without chips fails with ZLY_ERR_INVALID_ARGUMENT. */
+int32_t zly_chips_enable(zly_engine* e, const zly_chip_config* cfg);
+/* bytes of one chip slab, the offset of chip 0 in it, and the bytes from one chip to the next (any output may be null) */
+int32_t zly_chip_layout(const zly_engine* e, size_t* slab_bytes, size_t* pixels_off, size_t* chip_stride);
+/* Cuts chip slab i (i < n, 1 <= n <= max_batch) from view i of the device buffer d_base (HOST array views[n]) with the boxes of slab i.  d_slabs
+ * names the slabs (device memory, zly_slab_bytes apart); NULL: `source` picks the engine's buffer (ZLY_CHIPS_SRC_*); with a non-NULL d_slabs source
+ * must be 0.  d_chips receives the n chip slabs (device memory, 16-byte aligned; NULL: the engine-owned buffer, read with zly_read_chips).
+ * Enqueued, not synchronised, and ordered exactly as zly_track_slabs is: behind the NMS, merge and tracking enqueued so far, on whichever stream
+ * those ran -- the engine's NMS stream when the call's NMS was deferred, otherwise `stream` (NULL = the engine's own), which waits for the call's
+ * completion event.  The completion events move behind the chips: zly_join, zly_sync and zly_read_chips cover them, and a later call's kernels never
+ * overwrite slabs that the chips still read.  The frame records reach the kernels through a ring of pinned records with one copy per call: after
+ * zly_chips_enable a call allocates nothing and does not wait for the device.
+ * ZLY_ERR_INVALID_ARGUMENT, with nothing enqueued: an engine without chips, n out of range, a bad source (or ZLY_CHIPS_SRC_MERGED on an engine that
+ * has not merged), a null view array, an unknown format.  ZLY_ERR_INVALID_INPUT: a view that zly_detect_device_view would refuse, or W or H above
+ * ZLY_AREA_MAX_DIM. */
+int32_t zly_chips_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* views,
+                              const void* d_slabs, int32_t source, void* d_chips, void* stream);
+/* The same on n resident surfaces, whole (a slot index may repeat).  An undefined or invalid surface is refused as zly_detect_surfaces refuses it.
+ * The call is a reader of the store: it runs behind the updates and moves enqueued so far, and the next zly_surface_update / zly_surface_move
+ * cannot overwrite a surface while chips are still being cut from it. */
+int32_t zly_chips_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const void* d_slabs, int32_t source, void* d_chips, void* stream);
+/* Waits for the chips enqueued so far, then copies the first n chip slabs (1..max_batch) of the engine-owned buffer to host_out. */
+int32_t zly_read_chips(zly_engine* e, int32_t n, void* host_out);
+
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw);

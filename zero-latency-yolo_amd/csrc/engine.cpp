@@ -12,6 +12,7 @@
 #include "frame_rules.h"
 #include "surface_rules.h"
 #include "zoom_rules.h"
+#include "chip_rules.h"
 #include "weights.h"
 
 #include <algorithm>
@@ -219,6 +220,20 @@ struct Zoom {
     zly_zoom_region* d_plan = nullptr;    // [max_batch] of the most recent frame call (n * K <= max_batch), then [max_batch * K] of zly_zoom_plan
 };
 
+// Chips (zly_chips_enable; include/zly.h "Chips"): the ring through which a call's frame records reach the two chip kernels -- pinned host records
+// plus device records of their own, reused as the zoom plan's ring is -- and the engine-owned chip slabs.
+struct Chips {
+    zly_chip_config cfg{};
+    ChipLayout lay{};
+    static constexpr int RING = 8;
+    ChipFrame* h_frames = nullptr;    // pinned [RING][max_batch]
+    ChipFrame* d_frames = nullptr;    // device [RING][max_batch]
+    hipEvent_t ev[RING] = {};         // behind the kernels that read entry r
+    bool used[RING] = {};
+    int next = 0, last = -1;          // last: the entry of the most recent call
+    unsigned char* d_out = nullptr;   // [max_batch][lay.slab_bytes]
+};
+
 }  // namespace zly
 
 using namespace zly;
@@ -307,6 +322,7 @@ struct zly_engine : Plan {
     Merge* merge = nullptr;                 // created by the first zly_merge_slabs / zly_detect_tiled (under mu)
     Surfaces* surf = nullptr;               // created by zly_surfaces_enable (under mu)
     Zoom* zoom = nullptr;                   // created by zly_zoom_enable (under mu)
+    Chips* chips = nullptr;                 // created by zly_chips_enable (under mu)
     hipStream_t last_ns = nullptr;          // the stream the most recent zly_detect_device* call's NMS ran on, and whether that was the engine's NMS stream
     bool last_deferred = false;
 
@@ -1630,6 +1646,13 @@ static hipError_t destroy_engine(zly_engine* e)
         if (zm->d_plan) note(hipFree(zm->d_plan));
         for (int i = 0; i < Zoom::RING; ++i) if (zm->ev[i]) hipEventDestroy(zm->ev[i]);
         delete zm;
+    }
+    if (Chips* cp = e->chips) {
+        if (cp->d_frames) note(hipFree(cp->d_frames));
+        if (cp->h_frames) note(hipHostFree(cp->h_frames));
+        if (cp->d_out) note(hipFree(cp->d_out));
+        for (int i = 0; i < Chips::RING; ++i) if (cp->ev[i]) hipEventDestroy(cp->ev[i]);
+        delete cp;
     }
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
@@ -3440,6 +3463,155 @@ int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out)
         SharedGate gl;
         HIP_TRY(hipStreamWaitEvent(e->stream, zm->ev[zm->last], 0), ZLY_ERR_INFERENCE);
         HIP_TRY(hipMemcpyAsync(out, zm->d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+// --- chips (include/zly.h "Chips"; the rules: chip_rules.h; the kernels: kernels_chips.hip) -----------------------------
+void zly_default_chip_config(const zly_engine* e, zly_chip_config* c)
+{
+    if (!c) return;
+    chip_default_config(e ? e->cfg.max_dets : 16, c);
+}
+
+int32_t zly_chips_enable(zly_engine* e, const zly_chip_config* c)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = chip_check_config(c, e->cfg.max_dets, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->chips) return fail(ZLY_ERR_INVALID_ARGUMENT, "chips are already enabled on this engine");
+    ExclusiveGate gl;                                  // allocations: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    Chips* cp = new Chips();
+    cp->cfg = *c;
+    cp->lay = chip_layout(c->chip_w, c->chip_h, c->max_chips, c->layout == ZLY_CHIP_RGB_F32);
+    const size_t B = (size_t)e->cfg.max_batch;
+    bool ok = hipMalloc((void**)&cp->d_frames, sizeof(ChipFrame) * B * Chips::RING) == hipSuccess &&
+              hipHostMalloc((void**)&cp->h_frames, sizeof(ChipFrame) * B * Chips::RING, hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void**)&cp->d_out, (size_t)cp->lay.slab_bytes * B) == hipSuccess &&
+              hipMemset(cp->d_out, 0, (size_t)cp->lay.slab_bytes * B) == hipSuccess;
+    for (int i = 0; i < Chips::RING && ok; ++i) ok = hipEventCreateWithFlags(&cp->ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (cp->d_frames) hipFree(cp->d_frames);
+        if (cp->h_frames) hipHostFree(cp->h_frames);
+        if (cp->d_out) hipFree(cp->d_out);
+        for (int i = 0; i < Chips::RING; ++i) if (cp->ev[i]) hipEventDestroy(cp->ev[i]);
+        delete cp;
+        return fail(ZLY_ERR_SYSTEM, "allocation of the chip buffers failed");
+    }
+    e->chips = cp;
+    return ZLY_OK;
+}
+
+// the engine's chip state (under e->mu), or null with the error set
+static Chips* chips_of(zly_engine* e)
+{
+    if (!e->chips) fail(ZLY_ERR_INVALID_ARGUMENT, "chips are not enabled on this engine (zly_chips_enable)");
+    return e->chips;
+}
+
+int32_t zly_chip_layout(const zly_engine* e, size_t* slab_bytes, size_t* pixels_off, size_t* chip_stride)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    const Chips* cp = e->chips;
+    if (!cp) return fail(ZLY_ERR_INVALID_ARGUMENT, "chips are not enabled on this engine (zly_chips_enable)");
+    if (slab_bytes) *slab_bytes = (size_t)cp->lay.slab_bytes;
+    if (pixels_off) *pixels_off = (size_t)cp->lay.pixels_off;
+    if (chip_stride) *chip_stride = (size_t)cp->lay.chip_stride;
+    return ZLY_OK;
+}
+
+// The body of zly_chips_device_view and zly_chips_surfaces: n checked views of the device buffer d_base.  Under e->mu, e->chips set; takes the enqueue
+// gate itself.  wait_for: an event the chosen stream has to wait for first when it is not the engine's own (null = none).  *ran_on: the stream the
+// kernels went to.
+static int chips_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, const void* d_slabs, int32_t source, void* d_chips,
+                        void* stream, hipEvent_t wait_for, hipStream_t* ran_on)
+{
+    Chips* cp = e->chips;
+    if (!d_slabs && source == ZLY_CHIPS_SRC_MERGED && !e->merge) return fail(ZLY_ERR_INVALID_ARGUMENT, "ZLY_CHIPS_SRC_MERGED: this engine has not merged yet (zly_merge_slabs)");
+    std::vector<ChipFrame> cf((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (int rc = chip_check_view(e->cfg.flags, d_base, buf_bytes, &v[i], &g_last_error)) return rc;
+        cf[(size_t)i] = chip_frame_of(&v[i]);
+    }
+    const void* slabs = d_slabs ? d_slabs : source == ZLY_CHIPS_SRC_MERGED ? (const void*)e->merge->d_out : (const void*)e->d_slabs;
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    // the stream zly_track_slabs would choose: behind the NMS, merge and tracking of the most recent zly_detect_device* call, on whichever stream they ran
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    const bool after_call = e->call_seq > 0;
+    if (after_call && e->last_deferred) s = e->last_ns;
+    else if (after_call && s != e->last_ns) HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1) & 1], 0), ZLY_ERR_INFERENCE);
+    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
+    // merges of an engine made before any detect call (slabs made elsewhere) are ordered by their own ring event
+    if (!d_slabs && source == ZLY_CHIPS_SRC_MERGED && e->merge->last >= 0) HIP_TRY(hipStreamWaitEvent(s, e->merge->ev[e->merge->last], 0), ZLY_ERR_INFERENCE);
+    const int r = cp->next;
+    cp->next = (r + 1) % Chips::RING;
+    if (cp->used[r]) HIP_TRY(hipEventSynchronize(cp->ev[r]), ZLY_ERR_INFERENCE);      // 8 calls back: long complete
+    // chip calls of an engine are ordered among themselves: they may share the engine-owned output
+    if (cp->last >= 0) HIP_TRY(hipStreamWaitEvent(s, cp->ev[cp->last], 0), ZLY_ERR_INFERENCE);
+    ChipFrame* hf = cp->h_frames + (size_t)r * (size_t)e->cfg.max_batch;
+    ChipFrame* df = cp->d_frames + (size_t)r * (size_t)e->cfg.max_batch;
+    memcpy(hf, cf.data(), sizeof(ChipFrame) * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(df, hf, sizeof(ChipFrame) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_chips((const uint8_t*)d_base, df, n, slabs, slab_bytes_of(e), e->cfg.max_dets, d_chips ? d_chips : (void*)cp->d_out, cp->cfg, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(cp->ev[r], s), ZLY_ERR_INFERENCE);
+    cp->used[r] = true;
+    cp->last = r;
+    if (after_call) {
+        // the call's completion events move behind its chips: zly_join, zly_read_slabs and a later call's NMS wait for both
+        HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], s), ZLY_ERR_INFERENCE);
+        if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], s), ZLY_ERR_INFERENCE);
+    }
+    *ran_on = s;
+    return ZLY_OK;
+}
+
+int32_t zly_chips_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* views, const void* d_slabs, int32_t source,
+                              void* d_chips, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = chip_check_call(n, e->cfg.max_batch, views, d_slabs, source, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!chips_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
+    hipStream_t ran = nullptr;
+    return chips_locked(e, n, d_base, buf_bytes, views, d_slabs, source, d_chips, stream, nullptr, &ran);
+}
+
+int32_t zly_chips_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const void* d_slabs, int32_t source, void* d_chips, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = chip_check_call(n, e->cfg.max_batch, surfaces, d_slabs, source, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!chips_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    std::vector<zly_frame_view> views((size_t)n);
+    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
+    hipStream_t ran = nullptr;
+    if (int rc = chips_locked(e, n, sf->d_store, sf->store.total, views.data(), d_slabs, source, d_chips, stream, sf->patched ? sf->ev_patch : nullptr, &ran)) return rc;
+    // the store has a reader now, as after zly_detect_surfaces: the next update's patch kernel goes behind the cut kernel, whichever stream it ran on
+    SharedGate gl;
+    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(sf->ev_read, ran), ZLY_ERR_INFERENCE);
+    sf->read_pending = true;
+    return ZLY_OK;
+}
+
+int32_t zly_read_chips(zly_engine* e, int32_t n, void* host_out)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!host_out || n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Chips* cp = chips_of(e);
+    if (!cp) return ZLY_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    {
+        SharedGate gl;
+        if (cp->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, cp->ev[cp->last], 0), ZLY_ERR_INFERENCE);
+        HIP_TRY(hipMemcpyAsync(host_out, cp->d_out, (size_t)cp->lay.slab_bytes * (size_t)n, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     }
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;

@@ -376,4 +376,11 @@ struct ZoomFrame;
 hipError_t launch_zoom_plan(const TrackStream* states, const TrackMotion* motion, const ZoomFrame* frames, int n, FrameDesc* desc, int* tab, zly_zoom_region* plan,
                             int K, int max_tracks, int region_w, int region_h, int max_age, int class_id, hipStream_t s);
 
+// ---- chips (kernels_chips.hip; the rule: include/zly.h, "Chips"; the frame record and the arithmetic: chip_device.h) ----
+struct ChipFrame;
+// two launches: chip_select_kernel (one wavefront per frame) writes header and records of the n chip slabs at `chips` from the n slabs at `slabs`
+// (slab_bytes apart, capacity cap); chip_cut_kernel then cuts the chips out of the frames `frames` (device, n records) of the buffer `src`
+hipError_t launch_chips(const uint8_t* src, const ChipFrame* frames, int n, const void* slabs, size_t slab_bytes, int cap, void* chips, const zly_chip_config& cfg,
+                        hipStream_t s);
+
 }  // namespace zly

@@ -45,6 +45,8 @@ MERGE_MAX_CANDIDATES = 4096          # tiles of a group x max_dets may not excee
 SURFACE_MAX_RECTS = 1024             # rectangles per surface_update / detect_delta call (include/zly.h "Resident surfaces")
 SURFACE_ALIGN = 256                  # the store's slot stride is a multiple of it
 SURFACE_MAX_MOVES = 1024             # moves per surface_move call
+CHIP_BGR8, CHIP_RGB_F32 = 0, 1      # zly_chip_config.layout (include/zly.h "Chips")
+CHIPS_SRC_SLABS, CHIPS_SRC_MERGED = 0, 1     # which engine-owned slab buffer a chips call reads when it is given none
 _PACKED_BPP = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
 
 # every symbol include/zly.h declares (tests/test_abi.py checks the library exports them all)
@@ -61,6 +63,7 @@ SYMBOLS = [
     "zly_surfaces_enable", "zly_surface_define", "zly_surface_update", "zly_surface_read", "zly_detect_surfaces", "zly_detect_delta",
     "zly_surface_moves_enable", "zly_surface_move",
     "zly_default_zoom_config", "zly_zoom_enable", "zly_detect_device_zoom", "zly_detect_surfaces_zoom", "zly_zoom_plan", "zly_zoom_read_plan",
+    "zly_default_chip_config", "zly_chips_enable", "zly_chip_layout", "zly_chips_device_view", "zly_chips_surfaces", "zly_read_chips",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -75,6 +78,12 @@ assert TRACK_DTYPE.itemsize == 40
 # zly_zoom_region: one planned region of a frame (zly_zoom_plan, zly_zoom_read_plan); slot = -1, track_id = 0: a fallback
 ZOOM_REGION_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("slot", "<i4"), ("track_id", "<u4")])
 assert ZOOM_REGION_DTYPE.itemsize == 24
+# zly_chip_header / zly_chip_rec: the head of a chip slab and one chip's record (zly_read_chips)
+CHIP_HDR_DTYPE = np.dtype([("n_chips", "<i4"), ("n_eligible", "<i4"), ("frame_tag", "<u4"), ("flags", "<u4")])
+assert CHIP_HDR_DTYPE.itemsize == 16
+CHIP_REC_DTYPE = np.dtype([("det", "<i4"), ("class_id", "<i4"), ("track_id", "<u4"), ("confidence", "<f4"),
+                           ("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4")])
+assert CHIP_REC_DTYPE.itemsize == 32
 
 
 class Config(C.Structure):
@@ -139,6 +148,11 @@ class Roi(C.Structure):
 class ZoomConfig(C.Structure):
     """zly_zoom_config"""
     _fields_ = [("regions", C.c_int32), ("region_w", C.c_int32), ("region_h", C.c_int32), ("max_age", C.c_int32), ("class_id", C.c_int32)]
+
+
+class ChipConfig(C.Structure):
+    """zly_chip_config"""
+    _fields_ = [("chip_w", C.c_int32), ("chip_h", C.c_int32), ("max_chips", C.c_int32), ("class_id", C.c_int32), ("scale", C.c_float), ("layout", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -244,6 +258,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_detect_surfaces_zoom.argtypes = [vp, i32, pi32, pi32, C.POINTER(MergeConfig), vp, u32, vp]; lib.zly_detect_surfaces_zoom.restype = i32
     lib.zly_zoom_plan.argtypes = [vp, i32, pi32, pi32, pi32, vp]; lib.zly_zoom_plan.restype = i32
     lib.zly_zoom_read_plan.argtypes = [vp, i32, vp]; lib.zly_zoom_read_plan.restype = i32
+    psz = C.POINTER(sz)
+    lib.zly_default_chip_config.argtypes = [vp, C.POINTER(ChipConfig)]; lib.zly_default_chip_config.restype = None
+    lib.zly_chips_enable.argtypes = [vp, C.POINTER(ChipConfig)]; lib.zly_chips_enable.restype = i32
+    lib.zly_chip_layout.argtypes = [vp, psz, psz, psz]; lib.zly_chip_layout.restype = i32
+    lib.zly_chips_device_view.argtypes = [vp, i32, vp, sz, pv, vp, i32, vp, vp]; lib.zly_chips_device_view.restype = i32
+    lib.zly_chips_surfaces.argtypes = [vp, i32, pi32, vp, i32, vp, vp]; lib.zly_chips_surfaces.restype = i32
+    lib.zly_read_chips.argtypes = [vp, i32, vp]; lib.zly_read_chips.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -639,6 +660,45 @@ class Engine:
         _check(self.lib, self.lib.zly_zoom_read_plan(self.h, n, out.ctypes.data))
         return out
 
+    # -- chips (include/zly.h "Chips") -----------------------------------------------------------------------
+    def chips_enable(self, chip_w: Optional[int] = None, chip_h: Optional[int] = None, max_chips: Optional[int] = None, class_id: Optional[int] = None,
+                     scale: Optional[float] = None, layout: Optional[int] = None):
+        """once per engine; arguments left out keep zly_default_chip_config's values (64 x 64 BGR8 chips, min(max_dets, 16) per frame, any class, scale 1.25)"""
+        c = ChipConfig()
+        self.lib.zly_default_chip_config(self.h, C.byref(c))
+        for name, v in (("chip_w", chip_w), ("chip_h", chip_h), ("max_chips", max_chips), ("class_id", class_id), ("scale", scale), ("layout", layout)):
+            if v is not None:
+                setattr(c, name, v)
+        _check(self.lib, self.lib.zly_chips_enable(self.h, C.byref(c)))
+        self.chip_cfg = c
+
+    def chip_layout(self) -> Tuple[int, int, int]:
+        """(bytes of a chip slab, offset of chip 0 in it, bytes from one chip to the next)"""
+        o = [C.c_size_t() for _ in range(3)]
+        _check(self.lib, self.lib.zly_chip_layout(self.h, *[C.byref(x) for x in o]))
+        return tuple(int(x.value) for x in o)
+
+    def chips_device_view(self, d_base_ptr: int, buf_bytes: int, views: Sequence[FrameView], d_slabs_ptr: int = 0, source: int = CHIPS_SRC_SLABS,
+                          d_chips_ptr: int = 0, stream: int = 0):
+        """chip slab i from view i of the device buffer with the boxes of slab i (d_slabs_ptr = 0: the engine-owned buffer `source` names;
+        d_chips_ptr = 0: the engine-owned chip slabs, read with read_chips); enqueued, not synchronised"""
+        n = len(views)
+        cv = (FrameView * max(n, 1))(*views)
+        _check(self.lib, self.lib.zly_chips_device_view(self.h, n, d_base_ptr or None, buf_bytes, cv, d_slabs_ptr or None, source, d_chips_ptr or None, stream or None))
+
+    def chips_surfaces(self, surfaces: Sequence[int], d_slabs_ptr: int = 0, source: int = CHIPS_SRC_SLABS, d_chips_ptr: int = 0, stream: int = 0):
+        """chips_device_view on resident surfaces, whole"""
+        n = len(surfaces)
+        cs = (C.c_int32 * max(n, 1))(*surfaces)
+        _check(self.lib, self.lib.zly_chips_surfaces(self.h, n, cs, d_slabs_ptr or None, source, d_chips_ptr or None, stream or None))
+
+    def read_chips(self, n: int) -> np.ndarray:
+        """the first n chip slabs of the engine-owned buffer (synchronises) -> u8 [n][slab_bytes]; parse_chip_slab takes one apart"""
+        sb = self.chip_layout()[0]
+        raw = np.zeros((n, sb), dtype=np.uint8)
+        _check(self.lib, self.lib.zly_read_chips(self.h, n, raw.ctypes.data))
+        return raw
+
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
         """copies the frame into the engine's pinned staging ring (on this thread) and returns a ticket"""
@@ -790,3 +850,20 @@ def parse_slabs(raw: np.ndarray, n: int, cap: int) -> List[Tuple[np.ndarray, np.
         dets = raw[i, SLAB_HDR_DTYPE.itemsize:].view(DET_DTYPE)
         out.append((hdr, dets[:min(int(hdr["n_kept"]), cap)].copy()))
     return out
+
+
+def parse_chip_slab(raw: np.ndarray, chip_w: int, chip_h: int, max_chips: int, layout: int, pixels_off: int, chip_stride: int):
+    """one chip slab (u8 [slab_bytes]) -> (header record, records[n_chips], chips[n_chips]): chips are u8 [chip_h][chip_w][3] B, G, R for CHIP_BGR8
+    and float32 [3][chip_h][chip_w] R, G, B planes for CHIP_RGB_F32"""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    hdr = raw[:CHIP_HDR_DTYPE.itemsize].view(CHIP_HDR_DTYPE)[0]
+    n = int(hdr["n_chips"])
+    recs = raw[CHIP_HDR_DTYPE.itemsize:CHIP_HDR_DTYPE.itemsize + max_chips * CHIP_REC_DTYPE.itemsize].view(CHIP_REC_DTYPE)[:n].copy()
+    chips = []
+    for j in range(n):
+        o = pixels_off + j * chip_stride
+        if layout == CHIP_RGB_F32:
+            chips.append(raw[o:o + chip_w * chip_h * 12].view(np.float32).reshape(3, chip_h, chip_w).copy())
+        else:
+            chips.append(raw[o:o + chip_w * chip_h * 3].reshape(chip_h, chip_w, 3).copy())
+    return hdr, recs, chips
