@@ -56,6 +56,19 @@ import zly_model as zm
 #   * the oracle in fp32 mode (stands in for the fp32 engine; n and s, the models that engine loads): 6.51, at 3x3 convs of 576 .. 1152 products --
 #     fp32 inputs and weights carry 24-bit mantissas, so unlike in bf16 mode no product is exact in fp32, and a 2^-24 |y| store hides nothing anywhere.
 # C_ACC = 16 x the floor of the engine's dtype, rounded up to a power of two.
+#
+# The smallest and thinnest maps (tests/small_map_cases.py: yolov8n at 32x32, 64x32, 32x64, 96x32, 32x96, 96x96, 416x32, 32x416 and 64x64, n = 3;
+# tests/test_small_map_cases.py asserts the 16 x rule there) were measured with the stand-in built inside torch.backends.mkldnn.flags(enabled=False):
+#   * bf16 mode: 0.52 (32x32) .. 1.12 (64x32), at the final 1x1 Detect convs model.22.cv2.L.2 -- below 1.59;
+#   * fp32 mode: 2.26 (32x32) .. 4.13 (96x96), at model.1 / model.2 / model.4 / model.12 convs -- below 6.51;
+#   * decode: at most 5.4e-5 px and 2.8e-8 -- below the decode floors.
+# So the constants stay as they are.  Two observations about the STAND-IN there, neither of which says anything about an engine:
+#   1. with torch's defaults (oneDNN on) the stand-in misses the 16 x rule at 32x32: at n >= 2 its floor is 6.3 - 6.9 (bf16 mode) and 9.4 - 9.9 (fp32 mode), at
+#      the six final Detect convs -- oneDNN's choice of algorithm for those tiny batched convs (at n = 1 the floor is 0.28).  It produces no violation either
+#      way, but a stand-in for these shapes is built with oneDNN off, where the plain CPU conv shows the figures above;
+#   2. at n = 64 (32x32, all frames) torch's CPU conv shows floors of 8.8 with oneDNN and 24 without (bf16 mode), 13 and 111 (fp32 mode) -- its blocking over a
+#      large batch of tiny maps sums in an order of its own; figures of 10.8 and 60 have been seen on another run.  The stand-in is not used at large n.  The
+#      64-frame GPU cases need no stand-in -- their reference is float64 on the engine's own taps.
 C_ACC_CPU_FLOOR, C_ACC_FP32_CPU_FLOOR = 1.59, 6.51
 C_ACC = 32.0                  # bf16 engine
 C_ACC_FP32_ENGINE = 128.0     # fp32 engine
