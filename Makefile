@@ -16,7 +16,7 @@ KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_mi
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
 OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/kernels_merge.o $(OUT)/kernels_area.o $(OUT)/kernels_surface.o $(OUT)/kernels_zoom.o $(OUT)/kernels_chips.o $(OUT)/engine.o $(OUT)/weights.o
 
-all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so $(OUT)/libsppf_probe.so oracle weights host
+all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so $(OUT)/libsppf_probe.so $(OUT)/libtrack_probe.so oracle weights host
 
 $(OUT):
 	mkdir -p $(OUT)
@@ -65,6 +65,14 @@ $(OUT)/sppf_probe_main.o: tests/cpp/sppf_probe.hip $(CSRC)/zly_internal.h $(CSRC
 $(OUT)/sppf_probe_y422.o: tests/cpp/sppf_probe_y422.hip $(CSRC)/zly_internal.h $(CSRC)/front_variants.h include/zly.h | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OUT)/libsppf_probe.so: $(OUT)/sppf_probe_main.o $(OUT)/sppf_probe_y422.o $(OUT)/kernels_misc.o $(OUT)/kernels_sppf.o $(OUT)/weights.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-Bsymbolic -o $@ $^
+
+# ---- test infrastructure: single launches of the shipped zoom plan kernel and the two tracking kernels on caller-made track tables, descriptor blocks,
+#      merge tables and slabs (tests/test_gpu_track_tables.py).  As above: the kernels_track.o and kernels_zoom.o of libzly.so itself, not recompilations
+track_probe: $(OUT)/libtrack_probe.so
+$(OUT)/track_probe_main.o: tests/cpp/track_probe.hip $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/frame_rules.h include/zly.h | $(OUT)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OUT)/libtrack_probe.so: $(OUT)/track_probe_main.o $(OUT)/kernels_track.o $(OUT)/kernels_zoom.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-Bsymbolic -o $@ $^
 
 # ---- in-process RCCL gather of result slabs (include/zly_gather.h): a library of its own -- it links RCCL, and a process that already carries
@@ -220,4 +228,4 @@ $(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_
 clean:
 	rm -rf $(OUT) oracle/_build
 
-.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe frame_rules_san surface_rules_san surface_moves_san zoom_plan_san chip_rules chip_rules_san clean
+.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe track_probe frame_rules_san surface_rules_san surface_moves_san zoom_plan_san chip_rules chip_rules_san clean

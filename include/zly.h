@@ -417,6 +417,10 @@ int32_t zly_join(zly_engine* e, void* stream, int32_t lag);
  *      eviction) -- becomes {live, box, class, id = next_id, last_seen = frame_no}; D[d].track_id = next_id; next_id becomes next_id + 1, or 1
  *      if that is 0.
  * So every stored detection of a tracked frame leaves with a non-zero id, and ids are per stream.
+ * frame_no wraps at 2^32.  Ages (step 5, the motion model's dt, the zoom regions' age) are u32 differences and stay right across the wrap; the
+ * eviction order of step 6 compares last_seen as stored, so for the few frames in which a table holds values from both sides of the wrap a slot
+ * seen after it is evicted before one seen before it.  A table as stored always has 64 slots; those at and beyond T are never live, matched or born
+ * into (the kernels write their live flag as 0 and leave their other fields alone).
  *
  * The motion model (zly_track_motion_enable; off by default).  Without prediction a target that moves by more than about half its width per
  * frame, or that reappears a few widths further on after a dropout, never matches its own track and gets a fresh id.  The reference's tracker

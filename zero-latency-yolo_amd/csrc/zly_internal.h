@@ -326,6 +326,8 @@ hipError_t launch_nms(const Cand* cand, int* cand_count, int N, int n, float iou
 // ---- tracking (kernels_track.hip; the rule and the step: include/zly.h) ----
 #define ZLY_TRACK_MAX 64          // slots per stream as stored (max_tracks <= 64: one lane per slot)
 // The track table of one stream in HBM, structure of arrays: lane t of track_kernel's wave loads and stores element t of every array.
+// With max_tracks T < 64 the slots at and beyond T take no part: the tracking kernels store their live flag as 0 and every other field as they loaded
+// it, and the plan kernel of the zoom regions reads them as not live (tests/test_gpu_track_tables.py pins both).
 struct TrackStream {
     uint32_t frame_no, next_id, evictions, pad_;
     uint32_t live[ZLY_TRACK_MAX];
