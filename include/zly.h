@@ -739,8 +739,9 @@ int32_t zly_surface_move(zly_engine* e, int32_t n_moves, const struct zly_surfac
  * ZLY_FLAG_ASYNC_NMS.
  * Ordering.  The plan kernel runs behind the previous call's tracking, on whichever stream that ran.  With ZLY_FLAG_ASYNC_NMS this removes the
  * overlap of call k's NMS with call k + 1's front kernels: that is inherent -- the plan needs call k's tracks.
- * Out of scope: the pipelined submit ring, the plugin, engines behind host/zly_sharded*.hpp, choosing regions from anything but tracks,
- * per-region sizes, and tuning the defaults (chosen, not tuned: nobody has measured them on real footage; no accuracy claim is made). */
+ * Out of scope: the pipelined submit ring, the plugin, engines behind host/zly_sharded*.hpp, choosing regions from anything but tracks
+ * (the fallback regions alone can follow what moved: "Change map", zly_zoom_use_change), per-region sizes, and tuning the defaults (chosen, not
+ * tuned: nobody has measured them on real footage; no accuracy claim is made). */
 typedef struct zly_zoom_config {
     int32_t regions;              /* K: zoom regions per frame, 1..15 (chosen; default 3) */
     int32_t region_w, region_h;   /* a region in surface pixels: even, 2..16384; default model_w, model_h (1:1: the front kernel's resize is the identity) */
@@ -861,6 +862,106 @@ int32_t zly_chips_device_view(zly_engine* e, int32_t n, const void* d_base, size
 int32_t zly_chips_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const void* d_slabs, int32_t source, void* d_chips, void* stream);
 /* Waits for the chips enqueued so far, then copies the first n chip slabs (1..max_batch) of the engine-owned buffer to host_out. */
 int32_t zly_read_chips(zly_engine* e, int32_t n, void* host_out);
+
+/* --- Change map --------------------------------------------------------------------------------------------------------------------
+ * Finds, on the GPU, WHAT MOVED between two frames of a stream: a coarse grid of luma sums per stream, kept in HBM and compared with the previous
+ * frame's grid, gives a per-cell activity grid and up to max_peaks windows around the cells that changed most.  Zoom regions give a small target full
+ * resolution, but only once it has a track, and a target a few model pixels wide is never found, never tracked and never zoomed: every region the
+ * plan cannot fill from a track goes to the centred window.  The reference's client computes which part of its capture changed
+ * (use_difference_encoding, src/client/screen_capture.cpp:394-470); here the server does it on frames that are already in HBM, without a byte
+ * crossing PCIe and without a synchronisation, and a zoom call can put its fallback regions on those windows (zly_zoom_use_change).
+ * Opt-in per engine (zly_change_enable): an engine that never calls it allocates nothing more and launches exactly the kernels it launched before.
+ * What it is for: captures with a mostly static camera -- a desktop, a spectator or overview camera, surveillance-like footage.  When the whole scene
+ * moves (a first-person camera turning) the map reports ZLY_CHANGE_GLOBAL and a zoom call behaves exactly as without it.
+ *
+ * Per-stream state: a grid geometry (W, H, C), the grid of the previous frame's sums, a step counter and a have_prev bit.
+ * Inputs for one frame: a frame view of W x H in any ZLY_PIX_* format, 1 <= W, H <= ZLY_AREA_MAX_DIM; a stream index; the engine's change config.
+ * All arithmetic is unsigned 32-bit integer arithmetic: everything below is exact (the oracle: tests/change_ref.py).
+ *   1. Luma.  B is the frame's BGR image by the format's existing rules -- the image the chips rule names, every pixel with its own chroma sample.
+ *      Y(x, y) = (29*B + 150*G + 77*R + 128) >> 8.
+ *   2. Cells.  C = cell, one of 8, 16, 32, 64; gw = ceil(W / C), gh = ceil(H / C); cells are row-major, index = cy*gw + cx.  Cell (cx, cy) covers the
+ *      pixels [cx*C, min((cx+1)*C, W)) x [cy*C, min((cy+1)*C, H)); npix is their number and S(c) the sum of Y over them.  A call whose gw*gh exceeds
+ *      ZLY_CHANGE_MAX_CELLS is refused (one workgroup's grid in 32 KB of LDS; 3840 x 2160 at C = 32 is 8160 cells).
+ *   3. FIRST.  ZLY_CHANGE_FIRST is set when the stream has no previous grid: after zly_change_enable or zly_change_reset, and when W, H or C differ
+ *      from the stored geometry.  Then every A(c) = 0 and there are no peaks.  In every case the stream's stored grid becomes S, its geometry
+ *      (W, H, C), and its counter advances by one; `step` is the counter after that (1 for the first frame after enable or reset).
+ *   4. Activity.  A(c) = |S(c) - S_prev(c)|.  Cell c is ACTIVE when 16*A(c) > threshold_q4 * npix(c): threshold_q4 is in sixteenths of a luma level
+ *      per pixel, and equality is not active.  n_active counts the active cells.
+ *   5. GLOBAL.  If n_active * 1000 > max_active_permille * gw*gh, ZLY_CHANGE_GLOBAL is set and there are no peaks.  The activity grid is still written.
+ *   6. Window size, as zoom step 1 from window_w, window_h: rw = min(window_w, W & ~1), rh = min(window_h, H & ~1); xmax = (W - rw) & ~1,
+ *      ymax = (H - rh) & ~1.  Surfaces with W < 2 or H < 2 get no peaks.  The centre pixel of cell column cx is pcx = min(cx*C + C/2, W - 1); rows
+ *      likewise.
+ *   7. Peaks, greedily, over a set of LIVE cells that starts as the active cells.  Initial suppression (a zoom call's track regions, below): for each
+ *      given rectangle (x0, y0, rw, rh) every cell whose centre pixel lies in [x0, x0+rw) x [y0, y0+rh) leaves the set.  Then, until max_peaks peaks
+ *      are chosen or no cell is live: take the live cell with the largest A, on a tie the lowest index; its window is
+ *      x0 = min(max(pcx - rw/2, 0), xmax) & ~1, y likewise; record {x0, y0, rw, rh, cx, cy, A}; remove the peak cell itself from the set, ALWAYS,
+ *      and every cell whose centre pixel lies in the window.  (The clamp to xmax and the & ~1 can leave a peak's own centre outside its window --
+ *      at rw = 2, and in the last column when W - rw is odd -- which is why the peak cell is removed unconditionally: the loop terminates.)
+ *   8. The record of a stream: a zly_change_header, 32 bytes (pad = 0); max_peaks records zly_change_peak of 32 bytes each (pad = 0), of which those
+ *      at or beyond n_peaks are UNTOUCHED; then the activity grid A[gw*gh], u32, with room for ZLY_CHANGE_MAX_CELLS cells, of which those at or
+ *      beyond gw*gh are untouched.  zly_change_layout reports the offsets.  zly_change_enable zeroes the records.
+ * Consequences.  A view gives what the tight frame of its samples gives; bytes outside the view never influence a sum; no byte at or beyond a plane's
+ * extent is read; two identical frames give n_active = 0.
+ *
+ * Zoom (zly_zoom_use_change).  THE RULE of "Zoom regions", extended: with it on, the slabs of a zoom call equal, byte for byte, the explicit sequence
+ * zly_change_device_view (or zly_change_surfaces) on the surfaces with streams[i]; the plan of "Zoom regions" steps 1-6; the FILL: step 7 above with
+ * the plan's track regions (slot >= 0) as initial suppression, and peak p put on the p-th fallback region (slot == -1, in region order) until either
+ * runs out -- that region's origin becomes the peak's window and its record {slot = -2, track_id = 0}; fallbacks left over keep the centred window;
+ * then crops, detect, merge and track as before.  On a FIRST or GLOBAL frame nothing is filled.  streams[i] names both the track table and the
+ * change map.  With it off, a zoom call enqueues exactly what it enqueues without a change map.
+ * Out of scope: the pipelined submit ring, the plugin, the wire format, engines behind host/zly_sharded*.hpp, change maps of regions rather than whole
+ * frames, and tuning the defaults (chosen, not tuned; weights and frames are synthetic: no accuracy claim is made). */
+#define ZLY_CHANGE_MAX_CELLS 8192
+#define ZLY_CHANGE_FIRST     1u
+#define ZLY_CHANGE_GLOBAL    2u
+typedef struct zly_change_config {
+    int32_t cell;                 /* C: 8, 16, 32 or 64; default 32 */
+    int32_t threshold_q4;         /* 0..4080, sixteenths of a luma level per pixel; default 32 (chosen, not tuned) */
+    int32_t max_active_permille;  /* 0..1000; default 250 (chosen, not tuned) */
+    int32_t max_peaks;            /* 1..15; default 3 */
+    int32_t window_w, window_h;   /* even, 2..16384; default model_w & ~1, model_h & ~1 */
+} zly_change_config;
+typedef struct zly_change_header {
+    int32_t  n_cells, n_active, n_peaks;
+    uint32_t flags;               /* ZLY_CHANGE_FIRST | ZLY_CHANGE_GLOBAL */
+    int32_t  gw, gh;
+    uint32_t step;                /* the stream's counter */
+    uint32_t pad;                 /* 0 */
+} zly_change_header;
+typedef struct zly_change_peak {
+    int32_t  x0, y0, w, h;        /* the window in frame pixels */
+    int32_t  cx, cy;              /* the peak cell */
+    uint32_t activity;            /* its A */
+    uint32_t pad;                 /* 0 */
+} zly_change_peak;
+void    zly_default_change_config(const zly_engine* e, zly_change_config* cfg);
+/* Once per engine, alone in the process like the other enables: allocates max_streams (>= 1) grids and records and max_batch scratch grids.
+ * ZLY_ERR_INVALID_ARGUMENT: a null or out-of-range config, max_streams < 1, a second call; ZLY_ERR_SYSTEM: a failed allocation.  Every other call
+ * of this section on an engine without a change map fails with ZLY_ERR_INVALID_ARGUMENT. */
+int32_t zly_change_enable(zly_engine* e, const zly_change_config* cfg, int32_t max_streams);
+/* bytes of one stream's record, and the offsets of the peaks and of the activity grid in it (any output may be null) */
+int32_t zly_change_layout(const zly_engine* e, size_t* rec_bytes, size_t* peaks_off, size_t* activity_off);
+/* One frame for each of n streams (1 <= n <= max_batch): view i of the device buffer d_base (HOST array views[n]) is the next frame of streams[i]
+ * (HOST array; 0 <= streams[i] < max_streams, distinct within the call).  Enqueued, not synchronised, on `stream` (NULL = the engine's own); the
+ * change calls of an engine, zoom calls with zly_zoom_use_change among them, are ordered among themselves on whichever streams they run.  After
+ * zly_change_enable a call allocates nothing and does not wait for the device.
+ * ZLY_ERR_INVALID_ARGUMENT, with nothing enqueued and no stream changed: an engine without a change map, n out of range, a null array, an unknown
+ * format, a stream out of range or twice.  ZLY_ERR_INVALID_INPUT: a view that zly_detect_device_view would refuse, W or H above ZLY_AREA_MAX_DIM,
+ * more than ZLY_CHANGE_MAX_CELLS cells. */
+int32_t zly_change_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* views, const int32_t* streams, void* stream);
+/* The same on n resident surfaces, whole (a slot index may repeat).  An undefined or invalid surface is refused as zly_detect_surfaces refuses it.
+ * The call is a reader of the store: it runs behind the updates and moves enqueued so far, and the next zly_surface_update / zly_surface_move waits
+ * for it. */
+int32_t zly_change_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, void* stream);
+/* Waits for the change calls enqueued so far, then copies min(cap_bytes, record bytes) of the stream's record -- header, peaks, activity grid -- to
+ * host_out.  ZLY_ERR_INVALID_ARGUMENT: a stream out of range, cap_bytes below the header and the peaks. */
+int32_t zly_change_read(zly_engine* e, int32_t stream, void* host_out, size_t cap_bytes);
+/* Enqueued behind the change calls so far: the stream (-1: every stream) has no previous grid and its counter is 0.  The record is left as it is. */
+int32_t zly_change_reset(zly_engine* e, int32_t stream);
+/* on != 0: zoom calls fill their fallback regions from the change map (above).  ZLY_ERR_INVALID_ARGUMENT: an engine without zoom regions or without
+ * a change map, or window_w, window_h != region_w, region_h.  A zoom call then also refuses (nothing enqueued) a stream at or beyond the change map's
+ * max_streams (ZLY_ERR_INVALID_ARGUMENT) and a surface above ZLY_AREA_MAX_DIM or with more than ZLY_CHANGE_MAX_CELLS cells (ZLY_ERR_INVALID_INPUT). */
+int32_t zly_zoom_use_change(zly_engine* e, int32_t on);
 
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */

@@ -13,6 +13,7 @@
 #include "surface_rules.h"
 #include "zoom_rules.h"
 #include "chip_rules.h"
+#include "change_rules.h"
 #include "weights.h"
 
 #include <algorithm>
@@ -234,9 +235,43 @@ struct Chips {
     unsigned char* d_out = nullptr;   // [max_batch][lay.slab_bytes]
 };
 
+// Change map (zly_change_enable; include/zly.h "Change map"): the streams' states, grids and records in HBM, the scratch grids of a call, and the ring
+// through which a call's frame records reach the two kernels -- pinned host records plus device records of their own, reused as the chips' ring is.
+struct Change {
+    zly_change_config cfg{};
+    ChangeLayout lay{};
+    int max_streams = 0;
+    bool zoom_on = false;             // zly_zoom_use_change
+    static constexpr int RING = 8;
+    ChipFrame* h_frames = nullptr;    // pinned [RING][max_batch]
+    ChipFrame* d_frames = nullptr;    // device [RING][max_batch]
+    ChangeItem* h_items = nullptr;    // pinned [RING][max_batch]
+    ChangeItem* d_items = nullptr;    // device [RING][max_batch]
+    hipEvent_t ev[RING] = {};         // behind the kernels that read entry r
+    bool used[RING] = {};
+    int next = 0, last = -1;          // last: the entry of the most recent call (or reset)
+    uint32_t* d_sums = nullptr;       // [max_batch][ZLY_CHANGE_MAX_CELLS]: the scratch grids
+    ChangeStream* d_state = nullptr;  // [max_streams]
+    uint32_t* d_prev = nullptr;       // [max_streams][ZLY_CHANGE_MAX_CELLS]
+    unsigned char* d_recs = nullptr;  // [max_streams][lay.rec_bytes]
+};
+
 }  // namespace zly
 
 using namespace zly;
+
+static void change_free(Change* ch)
+{
+    if (ch->d_frames) (void)hipFree(ch->d_frames);
+    if (ch->h_frames) (void)hipHostFree(ch->h_frames);
+    if (ch->d_items) (void)hipFree(ch->d_items);
+    if (ch->h_items) (void)hipHostFree(ch->h_items);
+    if (ch->d_sums) (void)hipFree(ch->d_sums);
+    if (ch->d_state) (void)hipFree(ch->d_state);
+    if (ch->d_prev) (void)hipFree(ch->d_prev);
+    if (ch->d_recs) (void)hipFree(ch->d_recs);
+    for (int i = 0; i < Change::RING; ++i) if (ch->ev[i]) (void)hipEventDestroy(ch->ev[i]);
+}
 
 struct zly_engine : Plan {
     zly_config cfg;
@@ -323,6 +358,7 @@ struct zly_engine : Plan {
     Surfaces* surf = nullptr;               // created by zly_surfaces_enable (under mu)
     Zoom* zoom = nullptr;                   // created by zly_zoom_enable (under mu)
     Chips* chips = nullptr;                 // created by zly_chips_enable (under mu)
+    Change* change = nullptr;               // created by zly_change_enable (under mu)
     hipStream_t last_ns = nullptr;          // the stream the most recent zly_detect_device* call's NMS ran on, and whether that was the engine's NMS stream
     bool last_deferred = false;
 
@@ -1653,6 +1689,10 @@ static hipError_t destroy_engine(zly_engine* e)
         if (cp->d_out) note(hipFree(cp->d_out));
         for (int i = 0; i < Chips::RING; ++i) if (cp->ev[i]) hipEventDestroy(cp->ev[i]);
         delete cp;
+    }
+    if (Change* ch = e->change) {
+        change_free(ch);
+        delete ch;
     }
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
@@ -3229,6 +3269,206 @@ int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect*
     return ZLY_OK;
 }
 
+// --- change map (include/zly.h "Change map"; the rules: change_rules.h; the kernels: kernels_change.hip) ----------------
+void zly_default_change_config(const zly_engine* e, zly_change_config* c)
+{
+    if (!c) return;
+    change_default_config(e ? e->cfg.model_w : 416, e ? e->cfg.model_h : 416, c);
+}
+
+int32_t zly_change_enable(zly_engine* e, const zly_change_config* c, int32_t max_streams)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = change_check_config(c, max_streams, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->change) return fail(ZLY_ERR_INVALID_ARGUMENT, "the change map is already enabled on this engine");
+    ExclusiveGate gl;                                  // allocations: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    Change* ch = new Change();
+    ch->cfg = *c;
+    ch->lay = change_layout(c->max_peaks);
+    ch->max_streams = max_streams;
+    const size_t B = (size_t)e->cfg.max_batch, NS = (size_t)max_streams, grid = sizeof(uint32_t) * ZLY_CHANGE_MAX_CELLS;
+    bool ok = hipMalloc((void**)&ch->d_frames, sizeof(ChipFrame) * B * Change::RING) == hipSuccess &&
+              hipHostMalloc((void**)&ch->h_frames, sizeof(ChipFrame) * B * Change::RING, hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void**)&ch->d_items, sizeof(ChangeItem) * B * Change::RING) == hipSuccess &&
+              hipHostMalloc((void**)&ch->h_items, sizeof(ChangeItem) * B * Change::RING, hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void**)&ch->d_sums, grid * B) == hipSuccess &&
+              hipMalloc((void**)&ch->d_state, sizeof(ChangeStream) * NS) == hipSuccess &&
+              hipMalloc((void**)&ch->d_prev, grid * NS) == hipSuccess &&
+              hipMalloc((void**)&ch->d_recs, (size_t)ch->lay.rec_bytes * NS) == hipSuccess &&
+              hipMemset(ch->d_sums, 0, grid * B) == hipSuccess &&
+              hipMemset(ch->d_state, 0, sizeof(ChangeStream) * NS) == hipSuccess &&
+              hipMemset(ch->d_prev, 0, grid * NS) == hipSuccess &&
+              hipMemset(ch->d_recs, 0, (size_t)ch->lay.rec_bytes * NS) == hipSuccess;
+    for (int i = 0; i < Change::RING && ok; ++i) ok = hipEventCreateWithFlags(&ch->ev[i], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        change_free(ch);
+        delete ch;
+        return fail(ZLY_ERR_SYSTEM, "allocation of the change map's buffers failed");
+    }
+    e->change = ch;
+    return ZLY_OK;
+}
+
+// the engine's change map (under e->mu), or null with the error set
+static Change* change_of(zly_engine* e)
+{
+    if (!e->change) fail(ZLY_ERR_INVALID_ARGUMENT, "the change map is not enabled on this engine (zly_change_enable)");
+    return e->change;
+}
+
+int32_t zly_change_layout(const zly_engine* e, size_t* rec_bytes, size_t* peaks_off, size_t* activity_off)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(const_cast<zly_engine*>(e)->mu);
+    const Change* ch = e->change;
+    if (!ch) return fail(ZLY_ERR_INVALID_ARGUMENT, "the change map is not enabled on this engine (zly_change_enable)");
+    if (rec_bytes) *rec_bytes = (size_t)ch->lay.rec_bytes;
+    if (peaks_off) *peaks_off = (size_t)ch->lay.peaks_off;
+    if (activity_off) *activity_off = (size_t)ch->lay.activity_off;
+    return ZLY_OK;
+}
+
+// The first half of a change call on n checked views v of the device buffer d_base: takes the next ring entry, orders the stream `s` behind the
+// change calls so far (they share the scratch grids and the streams' states), uploads the frame records and launches change_sums_kernel.  *ring: the
+// entry, for change_enqueue_pick.  Under e->mu, enqueue gate held; every check has been made.
+static int change_enqueue_sums(zly_engine* e, Change* ch, int n, const void* d_base, const zly_frame_view* v, const int32_t* streams, hipStream_t s, int* ring)
+{
+    const int r = ch->next;
+    if (ch->used[r]) HIP_TRY(hipEventSynchronize(ch->ev[r]), ZLY_ERR_INFERENCE);      // 8 calls back: long complete
+    if (ch->last >= 0) HIP_TRY(hipStreamWaitEvent(s, ch->ev[ch->last], 0), ZLY_ERR_INFERENCE);
+    ch->next = (r + 1) % Change::RING;
+    const int rc = [&]() -> int {
+        ChipFrame* hf = ch->h_frames + (size_t)r * (size_t)e->cfg.max_batch;
+        ChipFrame* df = ch->d_frames + (size_t)r * (size_t)e->cfg.max_batch;
+        ChangeItem* hi = ch->h_items + (size_t)r * (size_t)e->cfg.max_batch;
+        ChangeItem* di = ch->d_items + (size_t)r * (size_t)e->cfg.max_batch;
+        int max_w = 1, max_h = 1;
+        for (int i = 0; i < n; ++i) {
+            hf[i] = chip_frame_of(&v[i]);
+            hi[i] = ChangeItem{v[i].w, v[i].h, streams[i], 0};
+            max_w = std::max(max_w, (int)v[i].w); max_h = std::max(max_h, (int)v[i].h);
+        }
+        HIP_TRY(hipMemcpyAsync(df, hf, sizeof(ChipFrame) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(hipMemcpyAsync(di, hi, sizeof(ChangeItem) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_change_sums((const uint8_t*)d_base, df, n, max_w, max_h, ch->cfg.cell, ch->d_sums, s), ZLY_ERR_INFERENCE);
+        return ZLY_OK;
+    }();
+    // The entry's event goes behind whatever has been enqueued, a failed call's too, and behind the sums kernel even if the caller fails before its
+    // pick kernel: the next change call, on whichever stream, is ordered behind every user of the entry and of the scratch grids.
+    if (hipEventRecord(ch->ev[r], s) == hipSuccess) { ch->used[r] = true; ch->last = r; }
+    else if (rc == ZLY_OK) return fail(ZLY_ERR_INFERENCE, "hipEventRecord failed behind the change map's sums kernel");
+    *ring = r;
+    return rc;
+}
+
+// The second half: change_pick_kernel on the ring entry r, and the entry's event once more, behind it.  zf, desc, tab, plan, K: a zoom call's (null, 0: none)
+static int change_enqueue_pick(zly_engine* e, Change* ch, int n, int r, const ZoomFrame* zf, FrameDesc* desc, int* tab, zly_zoom_region* plan, int K, hipStream_t s)
+{
+    const ChangeItem* di = ch->d_items + (size_t)r * (size_t)e->cfg.max_batch;
+    HIP_TRY(launch_change_pick(di, n, ch->d_sums, ch->d_state, ch->d_prev, ch->d_recs, ch->cfg, zf, desc, tab, plan, K, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(ch->ev[r], s), ZLY_ERR_INFERENCE);
+    ch->used[r] = true;
+    ch->last = r;
+    return ZLY_OK;
+}
+
+// The body of zly_change_device_view and zly_change_surfaces.  Under e->mu, e->change set; takes the enqueue gate itself.  Every check comes first: a
+// refused call enqueues nothing.  wait_for: an event the chosen stream has to wait for first when it is not the engine's own (null = none)
+static int change_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, const int32_t* streams, void* stream,
+                         hipEvent_t wait_for, hipStream_t* ran_on)
+{
+    Change* ch = e->change;
+    if (int rc = change_check_streams(n, streams, ch->max_streams, &g_last_error)) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (int rc = chip_check_view(e->cfg.flags, d_base, buf_bytes, &v[i], &g_last_error)) return rc;
+        if (int rc = change_check_size(v[i].w, v[i].h, ch->cfg.cell, &g_last_error)) return rc;
+    }
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
+    int r = 0;
+    if (int rc = change_enqueue_sums(e, ch, n, d_base, v, streams, s, &r)) return rc;
+    if (int rc = change_enqueue_pick(e, ch, n, r, nullptr, nullptr, nullptr, nullptr, 0, s)) return rc;
+    *ran_on = s;
+    return ZLY_OK;
+}
+
+int32_t zly_change_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* views, const int32_t* streams, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = change_check_call(n, e->cfg.max_batch, views, streams, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!change_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
+    hipStream_t ran = nullptr;
+    return change_locked(e, n, d_base, buf_bytes, views, streams, stream, nullptr, &ran);
+}
+
+int32_t zly_change_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = change_check_call(n, e->cfg.max_batch, surfaces, streams, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!change_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
+    Surfaces* sf = surfaces_of(e);
+    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    std::vector<zly_frame_view> views((size_t)n);
+    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
+    hipStream_t ran = nullptr;
+    if (int rc = change_locked(e, n, sf->d_store, sf->store.total, views.data(), streams, stream, sf->patched ? sf->ev_patch : nullptr, &ran)) return rc;
+    // the store has a reader now, as after zly_detect_surfaces: the next update's patch kernel goes behind the sums kernel, whichever stream it ran on
+    SharedGate gl;
+    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(sf->ev_read, ran), ZLY_ERR_INFERENCE);
+    sf->read_pending = true;
+    return ZLY_OK;
+}
+
+int32_t zly_change_read(zly_engine* e, int32_t stream, void* host_out, size_t cap_bytes)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!host_out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Change* ch = change_of(e);
+    if (!ch) return ZLY_ERR_INVALID_ARGUMENT;
+    if (stream < 0 || stream >= ch->max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    if (cap_bytes < (size_t)ch->lay.activity_off) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_change_read: the header and the peaks are " + std::to_string(ch->lay.activity_off) + " bytes");
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    {
+        SharedGate gl;
+        if (ch->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, ch->ev[ch->last], 0), ZLY_ERR_INFERENCE);
+        HIP_TRY(hipMemcpyAsync(host_out, ch->d_recs + (size_t)stream * (size_t)ch->lay.rec_bytes, std::min(cap_bytes, (size_t)ch->lay.rec_bytes), hipMemcpyDeviceToHost,
+                               e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_change_reset(zly_engine* e, int32_t stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Change* ch = change_of(e);
+    if (!ch) return ZLY_ERR_INVALID_ARGUMENT;
+    if (stream < -1 || stream >= ch->max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    SharedGate gl;
+    // a ring entry of its own orders the reset among the change calls: behind the last one, in front of the next
+    const int r = ch->next;
+    ch->next = (r + 1) % Change::RING;
+    if (ch->used[r]) HIP_TRY(hipEventSynchronize(ch->ev[r]), ZLY_ERR_INFERENCE);
+    if (ch->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, ch->ev[ch->last], 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipMemsetAsync(ch->d_state + (stream < 0 ? 0 : stream), 0, sizeof(ChangeStream) * (size_t)(stream < 0 ? ch->max_streams : 1), e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(ch->ev[r], e->stream), ZLY_ERR_INFERENCE);
+    ch->used[r] = true;
+    ch->last = r;
+    return ZLY_OK;
+}
+
 // --- zoom regions (include/zly.h "Zoom regions"; the rules: zoom_rules.h; the plan kernel: kernels_zoom.hip) -----------
 void zly_default_zoom_config(const zly_engine* e, zly_zoom_config* c)
 {
@@ -3315,6 +3555,9 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
             if (streams[k] == streams[i]) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(streams[i]) + " occurs twice in a zoom call");
     }
     if (d_out && d_out == (void*)e->d_slabs) return fail(ZLY_ERR_INVALID_ARGUMENT, "d_out must not be the engine's own slab buffer");
+    Change* ch = e->change && e->change->zoom_on ? e->change : nullptr;      // zly_zoom_use_change: the fallback regions follow the change map
+    if (ch)
+        if (int rc = change_check_streams(n, streams, ch->max_streams, &g_last_error)) return rc;
     std::vector<zly_frame_view> views((size_t)nb);
     std::vector<zly_tile> tiles((size_t)nb);
     std::vector<ZoomFrame> zf((size_t)n);
@@ -3333,6 +3576,8 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
             tiles[(size_t)i * V + j] = zly_tile{i, fx, fy, z.rw, z.rh, W, H};
         }
         zf[(size_t)i] = zoom_frame_of(&sv[i], streams[i]);
+        if (ch)
+            if (int rc = change_check_size(W, H, ch->cfg.cell, &g_last_error)) return rc;
     }
     int max_slots = 0;
     if (int rc = merge_check(e, nb, tiles.data(), n, mc, &max_slots)) return rc;
@@ -3357,7 +3602,12 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
     if (rc != ZLY_OK) return rc;
     int mr = 0, zr = 0;
     if ((rc = merge_upload(e, nb, tiles.data(), n, s, &mr)) != ZLY_OK) return rc;
+    int cr = 0;
+    if (ch && (rc = change_enqueue_sums(e, ch, n, d_base, sv, streams, s, &cr)) != ZLY_OK) return rc;
     if ((rc = zoom_enqueue_plan(e, zm, tk, n, zf.data(), e->d_desc, e->merge->d_tab + (size_t)mr * e->merge->tab_ints, zm->d_plan, s, &zr)) != ZLY_OK) return rc;
+    if (ch && (rc = change_enqueue_pick(e, ch, n, cr, zm->d_frames + (size_t)zr * (size_t)e->cfg.max_batch, e->d_desc,
+                                        e->merge->d_tab + (size_t)mr * e->merge->tab_ints, zm->d_plan, zm->cfg.regions, s)) != ZLY_OK) return rc;
+    if (ch) HIP_TRY(hipEventRecord(zm->ev[zr], s), ZLY_ERR_INFERENCE);      // zly_zoom_read_plan reads the plan as the pick kernel left it
     zm->last = zr; zm->last_n = n;
     hipStream_t ns = s;
     rc = run_path(e, nb, (const uint8_t*)d_base, nullptr, 0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, level, true));
@@ -3465,6 +3715,21 @@ int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out)
         HIP_TRY(hipMemcpyAsync(out, zm->d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     }
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_zoom_use_change(zly_engine* e, int32_t on)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Zoom* zm = zoom_of(e);
+    if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
+    Change* ch = change_of(e);
+    if (!ch) return ZLY_ERR_INVALID_ARGUMENT;
+    if (ch->cfg.window_w != zm->cfg.region_w || ch->cfg.window_h != zm->cfg.region_h)
+        return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_zoom_use_change: the change map's window (" + std::to_string(ch->cfg.window_w) + " x " + std::to_string(ch->cfg.window_h) +
+                                              ") must be the zoom region (" + std::to_string(zm->cfg.region_w) + " x " + std::to_string(zm->cfg.region_h) + ")");
+    ch->zoom_on = on != 0;
     return ZLY_OK;
 }
 

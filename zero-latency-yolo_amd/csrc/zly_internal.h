@@ -385,4 +385,16 @@ struct ChipFrame;
 hipError_t launch_chips(const uint8_t* src, const ChipFrame* frames, int n, const void* slabs, size_t slab_bytes, int cap, void* chips, const zly_chip_config& cfg,
                         hipStream_t s);
 
+// ---- change map (kernels_change.hip; the rule: include/zly.h, "Change map"; the records and the arithmetic: change_device.h) ----
+struct ChangeItem;
+struct ChangeStream;
+// change_sums_kernel: the luma sums of the cells of the n frames `frames` (device) of the buffer `src` into sums[n][ZLY_CHANGE_MAX_CELLS]; max_w, max_h:
+// the largest width and height among the frames (the grid's size)
+hipError_t launch_change_sums(const uint8_t* src, const ChipFrame* frames, int n, int max_w, int max_h, int cell, uint32_t* sums, hipStream_t s);
+// change_pick_kernel, one workgroup per frame: sums against prev[items[i].stream] -> the stream's record in recs (change_layout apart), its state and
+// its grid.  plan non-null (a zoom call): the K regions per frame that zoom_plan_kernel wrote, its frame records zf, and desc / tab as it was given them
+// (either may be null); the fallback regions take the peaks
+hipError_t launch_change_pick(const ChangeItem* items, int n, const uint32_t* sums, ChangeStream* state, uint32_t* prev, void* recs, const zly_change_config& cfg,
+                              const ZoomFrame* zf, FrameDesc* desc, int* tab, zly_zoom_region* plan, int K, hipStream_t s);
+
 }  // namespace zly

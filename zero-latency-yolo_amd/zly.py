@@ -64,6 +64,8 @@ SYMBOLS = [
     "zly_surface_moves_enable", "zly_surface_move",
     "zly_default_zoom_config", "zly_zoom_enable", "zly_detect_device_zoom", "zly_detect_surfaces_zoom", "zly_zoom_plan", "zly_zoom_read_plan",
     "zly_default_chip_config", "zly_chips_enable", "zly_chip_layout", "zly_chips_device_view", "zly_chips_surfaces", "zly_read_chips",
+    "zly_default_change_config", "zly_change_enable", "zly_change_layout", "zly_change_device_view", "zly_change_surfaces", "zly_change_read", "zly_change_reset",
+    "zly_zoom_use_change",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -84,6 +86,11 @@ assert CHIP_HDR_DTYPE.itemsize == 16
 CHIP_REC_DTYPE = np.dtype([("det", "<i4"), ("class_id", "<i4"), ("track_id", "<u4"), ("confidence", "<f4"),
                            ("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4")])
 assert CHIP_REC_DTYPE.itemsize == 32
+# zly_change_header / zly_change_peak: the head of a stream's change record and one peak (zly_change_read)
+CHANGE_FIRST, CHANGE_GLOBAL, CHANGE_MAX_CELLS = 1, 2, 8192
+CHANGE_HDR_DTYPE = np.dtype([("n_cells", "<i4"), ("n_active", "<i4"), ("n_peaks", "<i4"), ("flags", "<u4"), ("gw", "<i4"), ("gh", "<i4"), ("step", "<u4"), ("pad", "<u4")])
+CHANGE_PEAK_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("cx", "<i4"), ("cy", "<i4"), ("activity", "<u4"), ("pad", "<u4")])
+assert CHANGE_HDR_DTYPE.itemsize == 32 and CHANGE_PEAK_DTYPE.itemsize == 32
 
 
 class Config(C.Structure):
@@ -148,6 +155,12 @@ class Roi(C.Structure):
 class ZoomConfig(C.Structure):
     """zly_zoom_config"""
     _fields_ = [("regions", C.c_int32), ("region_w", C.c_int32), ("region_h", C.c_int32), ("max_age", C.c_int32), ("class_id", C.c_int32)]
+
+
+class ChangeConfig(C.Structure):
+    """zly_change_config"""
+    _fields_ = [("cell", C.c_int32), ("threshold_q4", C.c_int32), ("max_active_permille", C.c_int32), ("max_peaks", C.c_int32), ("window_w", C.c_int32),
+                ("window_h", C.c_int32)]
 
 
 class ChipConfig(C.Structure):
@@ -265,6 +278,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_chips_device_view.argtypes = [vp, i32, vp, sz, pv, vp, i32, vp, vp]; lib.zly_chips_device_view.restype = i32
     lib.zly_chips_surfaces.argtypes = [vp, i32, pi32, vp, i32, vp, vp]; lib.zly_chips_surfaces.restype = i32
     lib.zly_read_chips.argtypes = [vp, i32, vp]; lib.zly_read_chips.restype = i32
+    lib.zly_default_change_config.argtypes = [vp, C.POINTER(ChangeConfig)]; lib.zly_default_change_config.restype = None
+    lib.zly_change_enable.argtypes = [vp, C.POINTER(ChangeConfig), i32]; lib.zly_change_enable.restype = i32
+    lib.zly_change_layout.argtypes = [vp, psz, psz, psz]; lib.zly_change_layout.restype = i32
+    lib.zly_change_device_view.argtypes = [vp, i32, vp, sz, pv, pi32, vp]; lib.zly_change_device_view.restype = i32
+    lib.zly_change_surfaces.argtypes = [vp, i32, pi32, pi32, vp]; lib.zly_change_surfaces.restype = i32
+    lib.zly_change_read.argtypes = [vp, i32, vp, sz]; lib.zly_change_read.restype = i32
+    lib.zly_change_reset.argtypes = [vp, i32]; lib.zly_change_reset.restype = i32
+    lib.zly_zoom_use_change.argtypes = [vp, i32]; lib.zly_zoom_use_change.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -699,6 +720,54 @@ class Engine:
         _check(self.lib, self.lib.zly_read_chips(self.h, n, raw.ctypes.data))
         return raw
 
+    # -- change map (include/zly.h "Change map") -------------------------------------------------------------
+    def change_enable(self, max_streams: int = 8, cell: Optional[int] = None, threshold_q4: Optional[int] = None, max_active_permille: Optional[int] = None,
+                      max_peaks: Optional[int] = None, window_w: Optional[int] = None, window_h: Optional[int] = None):
+        """once per engine; arguments left out keep zly_default_change_config's values (cells of 32, 2 luma levels per pixel, 25 % of the cells, 3 peaks,
+        windows of the model's size)"""
+        c = ChangeConfig()
+        self.lib.zly_default_change_config(self.h, C.byref(c))
+        for name, v in (("cell", cell), ("threshold_q4", threshold_q4), ("max_active_permille", max_active_permille), ("max_peaks", max_peaks),
+                        ("window_w", window_w), ("window_h", window_h)):
+            if v is not None:
+                setattr(c, name, v)
+        _check(self.lib, self.lib.zly_change_enable(self.h, C.byref(c), max_streams))
+        self.change_cfg = c
+
+    def change_layout(self) -> Tuple[int, int, int]:
+        """(bytes of a stream's change record, offset of the peaks in it, offset of the activity grid)"""
+        o = [C.c_size_t() for _ in range(3)]
+        _check(self.lib, self.lib.zly_change_layout(self.h, *[C.byref(x) for x in o]))
+        return tuple(int(x.value) for x in o)
+
+    def change_device_view(self, d_base_ptr: int, buf_bytes: int, views: Sequence[FrameView], streams: Sequence[int], stream: int = 0):
+        """view i of the device buffer is the next frame of streams[i]; enqueued, not synchronised"""
+        n = len(views)
+        cv = (FrameView * max(n, 1))(*views)
+        cs = (C.c_int32 * max(len(streams), 1))(*streams)
+        _check(self.lib, self.lib.zly_change_device_view(self.h, n, d_base_ptr or None, buf_bytes, cv, cs, stream or None))
+
+    def change_surfaces(self, surfaces: Sequence[int], streams: Sequence[int], stream: int = 0):
+        """change_device_view on resident surfaces, whole"""
+        n = len(surfaces)
+        cf = (C.c_int32 * max(n, 1))(*surfaces)
+        cs = (C.c_int32 * max(len(streams), 1))(*streams)
+        _check(self.lib, self.lib.zly_change_surfaces(self.h, n, cf, cs, stream or None))
+
+    def change_read(self, stream: int) -> np.ndarray:
+        """the stream's whole record (synchronises) -> u8 [rec_bytes]; parse_change_record takes it apart"""
+        raw = np.zeros(self.change_layout()[0], dtype=np.uint8)
+        _check(self.lib, self.lib.zly_change_read(self.h, stream, raw.ctypes.data, raw.nbytes))
+        return raw
+
+    def change_reset(self, stream: int = -1):
+        """the stream (-1: every stream) has no previous grid; enqueued"""
+        _check(self.lib, self.lib.zly_change_reset(self.h, stream))
+
+    def zoom_use_change(self, on: bool = True):
+        """zoom calls fill their fallback regions from the change map"""
+        _check(self.lib, self.lib.zly_zoom_use_change(self.h, 1 if on else 0))
+
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
         """copies the frame into the engine's pinned staging ring (on this thread) and returns a ticket"""
@@ -867,3 +936,14 @@ def parse_chip_slab(raw: np.ndarray, chip_w: int, chip_h: int, max_chips: int, l
         else:
             chips.append(raw[o:o + chip_w * chip_h * 3].reshape(chip_h, chip_w, 3).copy())
     return hdr, recs, chips
+
+
+def parse_change_record(raw: np.ndarray, max_peaks: int):
+    """one stream's change record (u8 [rec_bytes]) -> (header record, peaks[n_peaks], activity u32 [gh][gw])"""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+    hdr = raw[:CHANGE_HDR_DTYPE.itemsize].view(CHANGE_HDR_DTYPE)[0]
+    po = CHANGE_HDR_DTYPE.itemsize
+    ao = po + max_peaks * CHANGE_PEAK_DTYPE.itemsize
+    peaks = raw[po:ao].view(CHANGE_PEAK_DTYPE)[:int(hdr["n_peaks"])].copy()
+    act = raw[ao:ao + 4 * int(hdr["n_cells"])].view(np.uint32).reshape(int(hdr["gh"]), int(hdr["gw"])).copy()
+    return hdr, peaks, act
