@@ -34,7 +34,8 @@ $(OUT)/kernels_zoom.o: $(CSRC)/zoom_device.h
 # ... and the change map's kernels the arithmetic of the zoom regions' size and plane offsets
 $(OUT)/kernels_change.o: $(CSRC)/zoom_device.h
 
-$(OUT)/engine.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/chip_rules.h $(CSRC)/chip_device.h $(CSRC)/change_rules.h $(CSRC)/change_device.h $(CSRC)/weights.h include/zly.h | $(OUT)
+ENGINE_DEPS := $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/chip_rules.h $(CSRC)/chip_device.h $(CSRC)/change_rules.h $(CSRC)/change_device.h $(CSRC)/upload_ring.h $(CSRC)/weights.h include/zly.h
+$(OUT)/engine.o: $(ENGINE_DEPS) | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(OUT)/weights.o: $(CSRC)/weights.cpp $(CSRC)/weights.h include/zly.h | $(OUT)
@@ -46,7 +47,7 @@ $(OUT)/libzly.so: $(OBJS)
 # ---- diagnostic build of the engine (never shipped, never loaded by tests / bench.py / the plugin): the same kernels, engine.cpp with -DZLY_DIAG, which
 #      compiles in the result-changing ZLY_ABLATE_SKIP switch of tools/ablate_launches.sh (ZLY_LIB=.../libzly_diag.so python3 bench.py ...)
 diaglib: $(OUT)/libzly_diag.so
-$(OUT)/engine_diag.o: $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/chip_rules.h $(CSRC)/chip_device.h $(CSRC)/change_rules.h $(CSRC)/change_device.h $(CSRC)/weights.h include/zly.h | $(OUT)
+$(OUT)/engine_diag.o: $(ENGINE_DEPS) | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -DZLY_DIAG=1 -x hip -c $< -o $@
 $(OUT)/libzly_diag.so: $(filter-out $(OUT)/engine.o,$(OBJS)) $(OUT)/engine_diag.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^

@@ -14,6 +14,7 @@
 #include "zoom_rules.h"
 #include "chip_rules.h"
 #include "change_rules.h"
+#include "upload_ring.h"
 #include "weights.h"
 
 #include <algorithm>
@@ -156,34 +157,21 @@ struct Launch {
 
 struct Ingest;        // pipelined host-to-host path (zly_submit / zly_wait), below
 
-// Tracking (zly_track_enable; include/zly.h "Tracking"): the streams' track tables in HBM, and the ring through which a call's grouping of its
-// frames by stream reaches track_kernel.  A ring entry is a pinned host record plus a device record of its own; it follows h_desc's reuse
-// discipline -- rewritten only after the work that read it has completed (its event, recorded behind the kernel) -- so no call waits for the device.
+// Tracking (zly_track_enable; include/zly.h "Tracking"): the streams' track tables in HBM, and the ring (upload_ring.h) through which a call's grouping
+// of its frames by stream reaches track_kernel.
 struct Track {
     zly_track_config cfg{};
     TrackStream* d_state = nullptr;   // [max_streams]
     TrackMotion* d_motion = nullptr;  // [max_streams], allocated by zly_track_motion_enable (under mu): from then on every launch is track_motion_kernel
     zly_track_motion_config mcfg{};
-    static constexpr int RING = 8;
-    size_t grp_ints = 0;              // int32 per ring entry: 2 + 3 * max_batch (zly_internal.h: launch_track)
-    int* h_grp = nullptr;             // pinned [RING][grp_ints]
-    int* d_grp = nullptr;             // device [RING][grp_ints]
-    hipEvent_t ev[RING] = {};         // behind the kernel that read entry r
-    bool used[RING] = {};
-    int next = 0;
+    UploadRing ring;                  // an entry: 2 + 3 * max_batch int32 (zly_internal.h: launch_track)
     std::vector<int> seg_of;          // [max_streams] scratch of the grouping: a stream's segment in the current call, -1 = none yet
 };
 
 // Merging the slabs of a surface's tiles (zly_merge_slabs; include/zly.h "Tiles"): created by an engine's first merge.  The tile table of a call reaches
-// merge_kernel through a ring like the tracker's; d_out is the engine-owned output buffer (max_batch slabs), allocated with the ring.
+// merge_kernel through a ring (upload_ring.h); d_out is the engine-owned output buffer (max_batch slabs), allocated with the ring.
 struct Merge {
-    static constexpr int RING = 8;
-    size_t tab_ints = 0;              // int32 per ring entry: max_batch + 1 offsets + ZLY_MERGE_TILE_INTS * max_batch (zly_internal.h: launch_merge)
-    int* h_tab = nullptr;             // pinned [RING][tab_ints]
-    int* d_tab = nullptr;             // device [RING][tab_ints]
-    hipEvent_t ev[RING] = {};         // behind the kernel that read entry r
-    bool used[RING] = {};
-    int next = 0, last = -1;          // last: the entry of the most recent merge
+    UploadRing ring;                  // an entry: max_batch + 1 offsets + ZLY_MERGE_TILE_INTS * max_batch int32 (zly_internal.h: launch_merge)
     unsigned char* d_out = nullptr;   // [max_batch][slab_bytes]
 };
 
@@ -207,49 +195,35 @@ struct Surfaces {
     SurfaceMovePlan mplan;
 };
 
-// Zoom regions (zly_zoom_enable; include/zly.h "Zoom regions"): the ring through which a call's frame records reach zoom_plan_kernel -- pinned host
-// records plus device records of their own, reused as the tracker's ring is -- and the plans the kernel writes.
+// Zoom regions (zly_zoom_enable; include/zly.h "Zoom regions"): the ring (upload_ring.h) through which a call's frame records reach zoom_plan_kernel,
+// and the plans the kernel writes.
 struct Zoom {
     zly_zoom_config cfg{};
-    static constexpr int RING = 8;
-    ZoomFrame* h_frames = nullptr;    // pinned [RING][max_batch]
-    ZoomFrame* d_frames = nullptr;    // device [RING][max_batch]
-    hipEvent_t ev[RING] = {};         // behind the kernel that read entry r
-    bool used[RING] = {};
-    int next = 0, last = -1;          // last: the entry of the most recent frame call, last_n its frames
+    UploadRing ring;                  // an entry: max_batch ZoomFrame
+    int last_frames = -1;             // the entry of the most recent frame call (-1: none yet), last_n its frames
     int last_n = 0;
     zly_zoom_region* d_plan = nullptr;    // [max_batch] of the most recent frame call (n * K <= max_batch), then [max_batch * K] of zly_zoom_plan
 };
 
-// Chips (zly_chips_enable; include/zly.h "Chips"): the ring through which a call's frame records reach the two chip kernels -- pinned host records
-// plus device records of their own, reused as the zoom plan's ring is -- and the engine-owned chip slabs.
+// Chips (zly_chips_enable; include/zly.h "Chips"): the ring (upload_ring.h) through which a call's frame records reach the two chip kernels, and the
+// engine-owned chip slabs.
 struct Chips {
     zly_chip_config cfg{};
     ChipLayout lay{};
-    static constexpr int RING = 8;
-    ChipFrame* h_frames = nullptr;    // pinned [RING][max_batch]
-    ChipFrame* d_frames = nullptr;    // device [RING][max_batch]
-    hipEvent_t ev[RING] = {};         // behind the kernels that read entry r
-    bool used[RING] = {};
-    int next = 0, last = -1;          // last: the entry of the most recent call
+    UploadRing ring;                  // an entry: max_batch ChipFrame
     unsigned char* d_out = nullptr;   // [max_batch][lay.slab_bytes]
 };
 
 // Change map (zly_change_enable; include/zly.h "Change map"): the streams' states, grids and records in HBM, the scratch grids of a call, and the ring
-// through which a call's frame records reach the two kernels -- pinned host records plus device records of their own, reused as the chips' ring is.
+// (upload_ring.h) through which a call's frame records and items reach the two kernels.  zly_change_reset marks an entry too, without filling it.
 struct Change {
     zly_change_config cfg{};
     ChangeLayout lay{};
     int max_streams = 0;
     bool zoom_on = false;             // zly_zoom_use_change
-    static constexpr int RING = 8;
-    ChipFrame* h_frames = nullptr;    // pinned [RING][max_batch]
-    ChipFrame* d_frames = nullptr;    // device [RING][max_batch]
-    ChangeItem* h_items = nullptr;    // pinned [RING][max_batch]
-    ChangeItem* d_items = nullptr;    // device [RING][max_batch]
-    hipEvent_t ev[RING] = {};         // behind the kernels that read entry r
-    bool used[RING] = {};
-    int next = 0, last = -1;          // last: the entry of the most recent call (or reset)
+    UploadRing ring;                  // an entry: max_batch ChipFrame, then (at items_off) max_batch ChangeItem
+    size_t items_off = 0;
+    ChangeItem* items(unsigned char* entry) const { return reinterpret_cast<ChangeItem*>(entry + items_off); }
     uint32_t* d_sums = nullptr;       // [max_batch][ZLY_CHANGE_MAX_CELLS]: the scratch grids
     ChangeStream* d_state = nullptr;  // [max_streams]
     uint32_t* d_prev = nullptr;       // [max_streams][ZLY_CHANGE_MAX_CELLS]
@@ -260,17 +234,26 @@ struct Change {
 
 using namespace zly;
 
-static void change_free(Change* ch)
+static hipError_t first_error(std::initializer_list<hipError_t> rs) { for (hipError_t r : rs) if (r != hipSuccess) return r; return hipSuccess; }
+
+// One release function per feature state, for the failure path of its *_enable (which ignores the error) and for destroy_engine: frees whatever the state
+// owns so far (hipFree takes a null pointer) and the state itself; returns the first HIP error met.
+static hipError_t track_free(Track* tk) { const hipError_t r = first_error({hipFree(tk->d_state), hipFree(tk->d_motion), tk->ring.destroy()}); delete tk; return r; }
+static hipError_t merge_free(Merge* mg) { const hipError_t r = first_error({mg->ring.destroy(), hipFree(mg->d_out)}); delete mg; return r; }
+static hipError_t surfaces_free(Surfaces* sf)
 {
-    if (ch->d_frames) (void)hipFree(ch->d_frames);
-    if (ch->h_frames) (void)hipHostFree(ch->h_frames);
-    if (ch->d_items) (void)hipFree(ch->d_items);
-    if (ch->h_items) (void)hipHostFree(ch->h_items);
-    if (ch->d_sums) (void)hipFree(ch->d_sums);
-    if (ch->d_state) (void)hipFree(ch->d_state);
-    if (ch->d_prev) (void)hipFree(ch->d_prev);
-    if (ch->d_recs) (void)hipFree(ch->d_recs);
-    for (int i = 0; i < Change::RING; ++i) if (ch->ev[i]) (void)hipEventDestroy(ch->ev[i]);
+    const hipError_t r = first_error({hipFree(sf->d_store), hipFree(sf->d_bounce), sf->ev_patch ? hipEventDestroy(sf->ev_patch) : hipSuccess,
+                                      sf->ev_read ? hipEventDestroy(sf->ev_read) : hipSuccess});
+    delete sf;
+    return r;
+}
+static hipError_t zoom_free(Zoom* zm) { const hipError_t r = first_error({zm->ring.destroy(), hipFree(zm->d_plan)}); delete zm; return r; }
+static hipError_t chips_free(Chips* cp) { const hipError_t r = first_error({cp->ring.destroy(), hipFree(cp->d_out)}); delete cp; return r; }
+static hipError_t change_free(Change* ch)
+{
+    const hipError_t r = first_error({ch->ring.destroy(), hipFree(ch->d_sums), hipFree(ch->d_state), hipFree(ch->d_prev), hipFree(ch->d_recs)});
+    delete ch;
+    return r;
 }
 
 struct zly_engine : Plan {
@@ -299,14 +282,11 @@ struct zly_engine : Plan {
     int last_async = -1;              // parity of the last deferred NMS, -1 = none outstanding
     unsigned char* d_slabs = nullptr; // [max_batch][slab_bytes]
     FrameDesc* d_desc = nullptr;      // [max_batch]
-    // per-call descriptor ring (pinned): a call whose frame sizes differ from the previous call's writes the next ring entry and
-    // uploads it in stream order; an entry is rewritten only after the upload that read it has completed (its event), so no
-    // call ever waits for the device -- a mixed-client stream (800x600 next to 416x416) used to cost a hipDeviceSynchronize
-    static constexpr int DESC_RING = 8;
-    FrameDesc* h_desc = nullptr;      // pinned [DESC_RING][max_batch]
-    hipEvent_t ev_desc[DESC_RING] = {};
-    bool desc_used[DESC_RING] = {};
-    int desc_next = 0;
+    // per-call descriptor ring (pinned; the slot discipline of upload_ring.h over the one device copy d_desc): a call whose frame sizes differ from
+    // the previous call's writes the next ring entry and uploads it in stream order, so no call ever waits for the device -- a mixed-client stream
+    // (800x600 next to 416x416) used to cost a hipDeviceSynchronize
+    FrameDesc* h_desc = nullptr;      // pinned [SlotRing::DEPTH][max_batch]
+    SlotRing desc_ring;               // an entry's event: behind the upload that read it
     std::vector<FrameDesc> desc_cache;
     // a call on frame views (zly_*_view) uploads n ViewRec behind its n descriptors (zly_internal.h); a ring entry and d_desc hold both
     static constexpr size_t DESC_SLOT = sizeof(FrameDesc) + sizeof(ViewRec);      // bytes per frame
@@ -1507,9 +1487,8 @@ static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, co
     // frame sizes / offsets changed: next entry of the pinned ring, uploaded in stream order.  Calls on one engine are
     // stream-ordered by contract (they share every activation buffer), so the upload cannot overtake a kernel of the
     // previous call that still reads d_desc; the ring entry itself is only reused once ITS upload has completed.
-    const int r = e->desc_next;
-    e->desc_next = (r + 1) % zly_engine::DESC_RING;
-    if (e->desc_used[r]) HIP_TRY(hipEventSynchronize(e->ev_desc[r]), ZLY_ERR_INFERENCE);     // 8 uploads back: long complete
+    int r = 0;
+    HIP_TRY(e->desc_ring.claim(&r), ZLY_ERR_INFERENCE);
     FrameDesc* hd = reinterpret_cast<FrameDesc*>(reinterpret_cast<unsigned char*>(e->h_desc) + (size_t)r * (size_t)e->cfg.max_batch * zly_engine::DESC_SLOT);
     if ((int)e->desc_cache.size() < n) e->desc_cache.resize((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -1527,8 +1506,7 @@ static int set_desc(zly_engine* e, int n, const int32_t* w, const int32_t* h, co
     e->desc_cache_view = views != nullptr;
     e->last_desc_n = n;
     HIP_TRY(hipMemcpyAsync(e->d_desc, hd, bytes, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(e->ev_desc[r], s), ZLY_ERR_INFERENCE);
-    e->desc_used[r] = true;
+    HIP_TRY(e->desc_ring.mark(r, s), ZLY_ERR_INFERENCE);
     return ZLY_OK;
 }
 
@@ -1541,10 +1519,9 @@ static int track_enqueue(zly_engine* e, Track* tk, int n, const int32_t* streams
     int n_tracked = 0, n_seg = 0;
     for (int i = 0; i < n; ++i) if (streams[i] >= 0) ++n_tracked;
     if (n_tracked == 0) return ZLY_OK;
-    const int r = tk->next;
-    tk->next = (r + 1) % Track::RING;
-    if (tk->used[r]) HIP_TRY(hipEventSynchronize(tk->ev[r]), ZLY_ERR_INFERENCE);      // 8 tracked calls back: long complete
-    int* g = tk->h_grp + (size_t)r * tk->grp_ints;
+    int r = 0;
+    HIP_TRY(tk->ring.claim(&r), ZLY_ERR_INFERENCE);
+    int* g = tk->ring.host<int>(r);
     // segments in the order of their stream's first occurrence; frames of a segment in index order
     std::vector<int>& seg_of = tk->seg_of;
     int* count = g + 1;                                                              // first: frames per segment, at [1 + seg + 1]
@@ -1568,15 +1545,14 @@ static int track_enqueue(zly_engine* e, Track* tk, int n, const int32_t* streams
         frames[fill[(size_t)sg]++] = i;
     }
     for (int i = 0; i < n; ++i) if (streams[i] >= 0) seg_of[(size_t)streams[i]] = -1;
-    int* dg = tk->d_grp + (size_t)r * tk->grp_ints;
-    HIP_TRY(hipMemcpyAsync(dg, g, sizeof(int) * (size_t)(2 + 2 * n_seg + n_tracked), hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    const int* dg = tk->ring.dev<int>(r);
+    HIP_TRY(tk->ring.upload(r, sizeof(int) * (size_t)(2 + 2 * n_seg + n_tracked), s), ZLY_ERR_INFERENCE);
     if (tk->d_motion)
         HIP_TRY(launch_track_motion(tk->d_state, tk->d_motion, dg, n_seg, slabs, e->cfg.max_dets, tk->cfg.max_tracks, tk->cfg.match_iou, (uint32_t)tk->cfg.max_lost,
                                     tk->mcfg.beta, tk->mcfg.v_max, s), ZLY_ERR_INFERENCE);
     else
         HIP_TRY(launch_track(tk->d_state, dg, n_seg, slabs, e->cfg.max_dets, tk->cfg.max_tracks, tk->cfg.match_iou, (uint32_t)tk->cfg.max_lost, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(tk->ev[r], s), ZLY_ERR_INFERENCE);
-    tk->used[r] = true;
+    HIP_TRY(tk->ring.mark(r, s), ZLY_ERR_INFERENCE);
     *launched = true;
     return ZLY_OK;
 }
@@ -1584,8 +1560,28 @@ static int track_enqueue(zly_engine* e, Track* tk, int n, const int32_t* streams
 // every tracked launch made so far has completed (under e->mu: none can be enqueued meanwhile)
 static int track_drain(Track* tk)
 {
-    for (int r = 0; r < Track::RING; ++r)
-        if (tk->used[r]) HIP_TRY(hipEventSynchronize(tk->ev[r]), ZLY_ERR_INFERENCE);
+    HIP_TRY(tk->ring.drain(), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+// Where work on the slabs of the most recent zly_detect_device* call goes (tracking, a merge, chips): behind that call's NMS, on whichever stream it
+// ran.  s: the caller's choice on entry.  It becomes the engine's NMS stream when the NMS was deferred; otherwise it stays, and waits for the call's
+// completion event where it is not the stream the call itself was given.  Before any such call: s as it is.
+static int stream_after_detect(zly_engine* e, hipStream_t& s)
+{
+    if (e->call_seq == 0) return ZLY_OK;
+    if (e->last_deferred) s = e->last_ns;
+    else if (s != e->last_ns) HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1) & 1], 0), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+// ... and once that work is enqueued on s, the call's completion events move behind it: zly_join, zly_read_slabs, a later call's NMS and whatever
+// stream_after_detect orders next wait for both
+static int detect_events_behind(zly_engine* e, hipStream_t s)
+{
+    if (e->call_seq == 0) return ZLY_OK;
+    HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], s), ZLY_ERR_INFERENCE);
+    if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], s), ZLY_ERR_INFERENCE);
     return ZLY_OK;
 }
 
@@ -1654,46 +1650,12 @@ static hipError_t destroy_engine(zly_engine* e)
     if (e->h_desc) note(hipHostFree(e->h_desc));
     if (e->h_stage) note(hipHostFree(e->h_stage));
     if (e->h_slabs) note(hipHostFree(e->h_slabs));
-    if (Track* tk = e->track.load()) {
-        if (tk->d_state) note(hipFree(tk->d_state));
-        if (tk->d_motion) note(hipFree(tk->d_motion));
-        if (tk->d_grp) note(hipFree(tk->d_grp));
-        if (tk->h_grp) note(hipHostFree(tk->h_grp));
-        for (int i = 0; i < Track::RING; ++i) if (tk->ev[i]) hipEventDestroy(tk->ev[i]);
-        delete tk;
-    }
-    if (Merge* mg = e->merge) {
-        if (mg->d_tab) note(hipFree(mg->d_tab));
-        if (mg->h_tab) note(hipHostFree(mg->h_tab));
-        if (mg->d_out) note(hipFree(mg->d_out));
-        for (int i = 0; i < Merge::RING; ++i) if (mg->ev[i]) hipEventDestroy(mg->ev[i]);
-        delete mg;
-    }
-    if (Surfaces* sf = e->surf) {
-        if (sf->d_store) note(hipFree(sf->d_store));
-        if (sf->d_bounce) note(hipFree(sf->d_bounce));
-        if (sf->ev_patch) hipEventDestroy(sf->ev_patch);
-        if (sf->ev_read) hipEventDestroy(sf->ev_read);
-        delete sf;
-    }
-    if (Zoom* zm = e->zoom) {
-        if (zm->d_frames) note(hipFree(zm->d_frames));
-        if (zm->h_frames) note(hipHostFree(zm->h_frames));
-        if (zm->d_plan) note(hipFree(zm->d_plan));
-        for (int i = 0; i < Zoom::RING; ++i) if (zm->ev[i]) hipEventDestroy(zm->ev[i]);
-        delete zm;
-    }
-    if (Chips* cp = e->chips) {
-        if (cp->d_frames) note(hipFree(cp->d_frames));
-        if (cp->h_frames) note(hipHostFree(cp->h_frames));
-        if (cp->d_out) note(hipFree(cp->d_out));
-        for (int i = 0; i < Chips::RING; ++i) if (cp->ev[i]) hipEventDestroy(cp->ev[i]);
-        delete cp;
-    }
-    if (Change* ch = e->change) {
-        change_free(ch);
-        delete ch;
-    }
+    if (Track* tk = e->track.load()) note(track_free(tk));
+    if (e->merge) note(merge_free(e->merge));
+    if (e->surf) note(surfaces_free(e->surf));
+    if (e->zoom) note(zoom_free(e->zoom));
+    if (e->chips) note(chips_free(e->chips));
+    if (e->change) note(change_free(e->change));
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
         if (e->ev_join[i]) hipEventDestroy(e->ev_join[i]);
@@ -1701,7 +1663,7 @@ static hipError_t destroy_engine(zly_engine* e)
     }
     if (e->ev_head) hipEventDestroy(e->ev_head);
     for (int i = 0; i < 2; ++i) if (e->ev_nms[i]) hipEventDestroy(e->ev_nms[i]);
-    for (int i = 0; i < zly_engine::DESC_RING; ++i) if (e->ev_desc[i]) hipEventDestroy(e->ev_desc[i]);
+    note(e->desc_ring.destroy());
     for (int i = 0; i < 4; ++i) if (e->ev_t[i]) hipEventDestroy(e->ev_t[i]);
     for (int i = 0; i < 2; ++i) if (e->ev_call[i]) hipEventDestroy(e->ev_call[i]);
     if (e->nms_stream) hipStreamDestroy(e->nms_stream);
@@ -2221,8 +2183,8 @@ int32_t zly_create(const zly_config* cfg, zly_engine** out)
         ok = ok && hipMalloc((void**)&e->d_count, B * sizeof(int)) == hipSuccess;
         ok = ok && hipMalloc((void**)&e->d_slabs, B * slab_bytes_of(e)) == hipSuccess;
         ok = ok && hipMalloc((void**)&e->d_desc, B * zly_engine::DESC_SLOT) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)&e->h_desc, zly_engine::DESC_RING * B * zly_engine::DESC_SLOT, hipHostMallocDefault) == hipSuccess;
-        for (int i = 0; i < zly_engine::DESC_RING && ok; ++i) ok = hipEventCreateWithFlags(&e->ev_desc[i], hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipHostMalloc((void**)&e->h_desc, SlotRing::DEPTH * B * zly_engine::DESC_SLOT, hipHostMallocDefault) == hipSuccess;
+        ok = ok && e->desc_ring.create() == hipSuccess;
         for (int i = 0; i < 4 && ok; ++i) ok = hipEventCreate(&e->ev_t[i]) == hipSuccess;
         for (int i = 0; i < 2 && ok; ++i) ok = hipEventCreateWithFlags(&e->ev_call[i], hipEventDisableTiming) == hipSuccess;
         ok = ok && hipHostMalloc((void**)&e->h_slabs, B * slab_bytes_of(e), hipHostMallocDefault) == hipSuccess;
@@ -2628,20 +2590,13 @@ int32_t zly_track_enable(zly_engine* e, const zly_track_config* c)
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     Track* tk = new Track();
     tk->cfg = *c;
-    tk->grp_ints = 2 + 3 * (size_t)e->cfg.max_batch;
     tk->seg_of.assign((size_t)c->max_streams, -1);
-    bool ok = hipMalloc((void**)&tk->d_state, sizeof(TrackStream) * (size_t)c->max_streams) == hipSuccess &&
-              hipMalloc((void**)&tk->d_grp, sizeof(int) * tk->grp_ints * Track::RING) == hipSuccess &&
-              hipHostMalloc((void**)&tk->h_grp, sizeof(int) * tk->grp_ints * Track::RING, hipHostMallocDefault) == hipSuccess;
-    for (int i = 0; i < Track::RING && ok; ++i) ok = hipEventCreateWithFlags(&tk->ev[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && launch_track_reset(tk->d_state, 0, c->max_streams, 1u, e->stream) == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess;
+    const bool ok = hipMalloc((void**)&tk->d_state, sizeof(TrackStream) * (size_t)c->max_streams) == hipSuccess &&
+                    tk->ring.create(sizeof(int) * (2 + 3 * (size_t)e->cfg.max_batch)) == hipSuccess &&
+                    launch_track_reset(tk->d_state, 0, c->max_streams, 1u, e->stream) == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        if (tk->d_state) hipFree(tk->d_state);
-        if (tk->d_grp) hipFree(tk->d_grp);
-        if (tk->h_grp) hipHostFree(tk->h_grp);
-        for (int i = 0; i < Track::RING; ++i) if (tk->ev[i]) hipEventDestroy(tk->ev[i]);
-        delete tk;
+        (void)track_free(tk);
         return fail(ZLY_ERR_SYSTEM, "allocation of the track tables failed");
     }
     e->track.store(tk);
@@ -2778,21 +2733,12 @@ int32_t zly_track_slabs(zly_engine* e, int32_t n, const int32_t* streams, void* 
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    // behind the NMS of the most recent zly_detect_device* call, on whichever stream it ran: the engine's NMS stream when it was deferred; otherwise
-    // the caller's stream, which waits for that call's completion event where it is not the stream the call itself was given
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    const bool after_call = e->call_seq > 0;
-    if (after_call && e->last_deferred) s = e->last_ns;
-    else if (after_call && s != e->last_ns) HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1) & 1], 0), ZLY_ERR_INFERENCE);
+    if (int rc = stream_after_detect(e, s)) return rc;
     bool launched = false;
     int rc = track_enqueue(e, tk, n, streams, d_slabs ? d_slabs : e->d_slabs, s, &launched);
     if (rc != ZLY_OK) return rc;
-    if (launched && after_call) {
-        // the call's completion events move behind its tracking: zly_join, zly_read_slabs and a later call's NMS wait for both
-        HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], s), ZLY_ERR_INFERENCE);
-        if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], s), ZLY_ERR_INFERENCE);
-    }
-    return ZLY_OK;
+    return launched ? detect_events_behind(e, s) : ZLY_OK;
 }
 
 static int submit_tracked(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* v, int32_t stream, uint64_t* ticket, bool nonblock)
@@ -2867,20 +2813,13 @@ static int merge_ensure(zly_engine* e)
     ExclusiveGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     Merge* mg = new Merge();
-    mg->tab_ints = (size_t)e->cfg.max_batch * (1 + ZLY_MERGE_TILE_INTS) + 1;
-    bool ok = merge_init() == hipSuccess &&
-              hipMalloc((void**)&mg->d_tab, sizeof(int) * mg->tab_ints * Merge::RING) == hipSuccess &&
-              hipHostMalloc((void**)&mg->h_tab, sizeof(int) * mg->tab_ints * Merge::RING, hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void**)&mg->d_out, slab_bytes_of(e) * (size_t)e->cfg.max_batch) == hipSuccess &&
-              hipMemset(mg->d_out, 0, slab_bytes_of(e) * (size_t)e->cfg.max_batch) == hipSuccess;
-    for (int i = 0; i < Merge::RING && ok; ++i) ok = hipEventCreateWithFlags(&mg->ev[i], hipEventDisableTiming) == hipSuccess;
+    const bool ok = merge_init() == hipSuccess &&
+                    mg->ring.create(sizeof(int) * ((size_t)e->cfg.max_batch * (1 + ZLY_MERGE_TILE_INTS) + 1)) == hipSuccess &&
+                    hipMalloc((void**)&mg->d_out, slab_bytes_of(e) * (size_t)e->cfg.max_batch) == hipSuccess &&
+                    hipMemset(mg->d_out, 0, slab_bytes_of(e) * (size_t)e->cfg.max_batch) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        if (mg->d_tab) hipFree(mg->d_tab);
-        if (mg->h_tab) hipHostFree(mg->h_tab);
-        if (mg->d_out) hipFree(mg->d_out);
-        for (int i = 0; i < Merge::RING; ++i) if (mg->ev[i]) hipEventDestroy(mg->ev[i]);
-        delete mg;
+        (void)merge_free(mg);
         return fail(ZLY_ERR_SYSTEM, "allocation of the merge buffers failed");
     }
     e->merge = mg;
@@ -2893,10 +2832,9 @@ static int merge_ensure(zly_engine* e)
 static int merge_upload(zly_engine* e, int n, const zly_tile* tiles, int n_groups, hipStream_t s, int* ring)
 {
     Merge* mg = e->merge;
-    const int r = mg->next;
-    mg->next = (r + 1) % Merge::RING;
-    if (mg->used[r]) HIP_TRY(hipEventSynchronize(mg->ev[r]), ZLY_ERR_INFERENCE);      // 8 merges back: long complete
-    int* t = mg->h_tab + (size_t)r * mg->tab_ints;
+    int r = 0;
+    HIP_TRY(mg->ring.claim(&r), ZLY_ERR_INFERENCE);
+    int* t = mg->ring.host<int>(r);
     for (int g = 0; g <= n_groups; ++g) t[g] = 0;
     for (int i = 0; i < n; ++i) if (tiles[i].group >= 0) t[tiles[i].group + 1]++;
     for (int g = 0; g < n_groups; ++g) t[g + 1] += t[g];                             // t[g] = offset of group g, t[n_groups] = members in all
@@ -2908,8 +2846,7 @@ static int merge_upload(zly_engine* e, int n, const zly_tile* tiles, int n_group
         int* m = members + (size_t)fill[(size_t)tiles[i].group]++ * ZLY_MERGE_TILE_INTS;
         m[0] = i; m[1] = tiles[i].x0; m[2] = tiles[i].y0; m[3] = tiles[i].w; m[4] = tiles[i].h; m[5] = tiles[i].W; m[6] = tiles[i].H;
     }
-    int* dt = mg->d_tab + (size_t)r * mg->tab_ints;
-    HIP_TRY(hipMemcpyAsync(dt, t, sizeof(int) * (size_t)(n_groups + 1 + n_members * ZLY_MERGE_TILE_INTS), hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(mg->ring.upload(r, sizeof(int) * (size_t)(n_groups + 1 + n_members * ZLY_MERGE_TILE_INTS), s), ZLY_ERR_INFERENCE);
     *ring = r;
     return ZLY_OK;
 }
@@ -2919,11 +2856,8 @@ static int merge_upload(zly_engine* e, int n, const zly_tile* tiles, int n_group
 static int merge_launch(zly_engine* e, int r, int n_groups, const zly_merge_config* c, int max_slots, const void* src, void* dst, uint32_t tag0, hipStream_t s)
 {
     Merge* mg = e->merge;
-    const int* dt = mg->d_tab + (size_t)r * mg->tab_ints;
-    HIP_TRY(launch_merge(dt, n_groups, max_slots, src, dst, e->cfg.max_dets, c->metric, c->thr, tag0, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(mg->ev[r], s), ZLY_ERR_INFERENCE);
-    mg->used[r] = true;
-    mg->last = r;
+    HIP_TRY(launch_merge(mg->ring.dev<int>(r), n_groups, max_slots, src, dst, e->cfg.max_dets, c->metric, c->thr, tag0, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(mg->ring.mark(r, s), ZLY_ERR_INFERENCE);
     return ZLY_OK;
 }
 
@@ -2947,19 +2881,11 @@ int32_t zly_merge_slabs(zly_engine* e, int32_t n, const zly_tile* tiles, int32_t
     if (int rc = merge_ensure(e)) return rc;
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    // the stream zly_track_slabs would choose: behind the NMS of the most recent zly_detect_device* call, on whichever stream it ran
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    const bool after_call = e->call_seq > 0;
-    if (after_call && e->last_deferred) s = e->last_ns;
-    else if (after_call && s != e->last_ns) HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1) & 1], 0), ZLY_ERR_INFERENCE);
+    if (int rc = stream_after_detect(e, s)) return rc;
     int rc = merge_enqueue(e, n, tiles, n_groups, c, max_slots, d_slabs ? d_slabs : e->d_slabs, d_out ? d_out : e->merge->d_out, frame_tag0, s);
     if (rc != ZLY_OK) return rc;
-    if (after_call) {
-        // the call's completion events move behind its merge: zly_join, zly_read_slabs, a later call's NMS and a following zly_track_slabs wait for both
-        HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], s), ZLY_ERR_INFERENCE);
-        if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], s), ZLY_ERR_INFERENCE);
-    }
-    return ZLY_OK;
+    return detect_events_behind(e, s);
 }
 
 int32_t zly_read_merged(zly_engine* e, int32_t n_groups, void* host_slabs)
@@ -2972,7 +2898,7 @@ int32_t zly_read_merged(zly_engine* e, int32_t n_groups, void* host_slabs)
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     {
         SharedGate gl;
-        if (mg->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, mg->ev[mg->last], 0), ZLY_ERR_INFERENCE);      // merges of an engine are ordered among themselves
+        HIP_TRY(mg->ring.wait_last(e->stream), ZLY_ERR_INFERENCE);      // merges of an engine are ordered among themselves
         int rcj = join_nms(e, e->stream);
         if (rcj != ZLY_OK) return rcj;
         HIP_TRY(hipMemcpyAsync(host_slabs, mg->d_out, slab_bytes_of(e) * (size_t)n_groups, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
@@ -3059,10 +2985,7 @@ int32_t zly_surfaces_enable(zly_engine* e, int32_t max_surfaces, size_t max_byte
                     hipMemsetAsync(sf->d_store, 0, st.total, e->stream) == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        if (sf->d_store) hipFree(sf->d_store);
-        if (sf->ev_patch) hipEventDestroy(sf->ev_patch);
-        if (sf->ev_read) hipEventDestroy(sf->ev_read);
-        delete sf;
+        (void)surfaces_free(sf);
         return fail(ZLY_ERR_SYSTEM, "allocation of the surface store (" + std::to_string(st.total) + " bytes) failed");
     }
     e->surf = sf;
@@ -3074,6 +2997,17 @@ static Surfaces* surfaces_of(zly_engine* e)
 {
     if (!e->surf) fail(ZLY_ERR_INVALID_ARGUMENT, "resident surfaces are not enabled on this engine (zly_surfaces_enable)");
     return e->surf;
+}
+
+// The store has a reader now: a call that read its slots has been enqueued, and its last kernel went to `ran`.  The next update's patch kernel goes
+// behind it, whichever stream that is (Surfaces::ev_read).  Under e->mu; takes the enqueue gate itself.
+static int surfaces_note_reader(zly_engine* e, Surfaces* sf, hipStream_t ran)
+{
+    SharedGate gl;
+    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(sf->ev_read, ran), ZLY_ERR_INFERENCE);
+    sf->read_pending = true;
+    return ZLY_OK;
 }
 
 int32_t zly_surface_define(zly_engine* e, int32_t s, int32_t fmt, int32_t w, int32_t h)
@@ -3218,12 +3152,7 @@ int32_t zly_detect_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, c
     std::vector<zly_frame_view> views((size_t)n);
     if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, rois, views.data(), &g_last_error)) return rc;
     if (int rc = detect_device_view_locked(e, n, sf->d_store, sf->store.total, views.data(), d_slabs, frame_tag0, stream, sf->patched ? sf->ev_patch : nullptr)) return rc;
-    // the store has a reader now: the next update's patch kernel goes behind this call's last kernel, whichever stream that ran on
-    SharedGate gl;
-    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(sf->ev_read, e->last_ns), ZLY_ERR_INFERENCE);
-    sf->read_pending = true;
-    return ZLY_OK;
+    return surfaces_note_reader(e, sf, e->last_ns);
 }
 
 int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
@@ -3289,10 +3218,10 @@ int32_t zly_change_enable(zly_engine* e, const zly_change_config* c, int32_t max
     ch->lay = change_layout(c->max_peaks);
     ch->max_streams = max_streams;
     const size_t B = (size_t)e->cfg.max_batch, NS = (size_t)max_streams, grid = sizeof(uint32_t) * ZLY_CHANGE_MAX_CELLS;
-    bool ok = hipMalloc((void**)&ch->d_frames, sizeof(ChipFrame) * B * Change::RING) == hipSuccess &&
-              hipHostMalloc((void**)&ch->h_frames, sizeof(ChipFrame) * B * Change::RING, hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void**)&ch->d_items, sizeof(ChangeItem) * B * Change::RING) == hipSuccess &&
-              hipHostMalloc((void**)&ch->h_items, sizeof(ChangeItem) * B * Change::RING, hipHostMallocDefault) == hipSuccess &&
+    // both arrays 16-byte aligned in every entry
+    static_assert(sizeof(ChangeItem) == 16 && alignof(ChipFrame) <= 16 && alignof(ChangeItem) <= 16, "the entry's layout assumes 16-byte items");
+    ch->items_off = (sizeof(ChipFrame) * B + 15) / 16 * 16;
+    bool ok = ch->ring.create(ch->items_off + sizeof(ChangeItem) * B) == hipSuccess &&
               hipMalloc((void**)&ch->d_sums, grid * B) == hipSuccess &&
               hipMalloc((void**)&ch->d_state, sizeof(ChangeStream) * NS) == hipSuccess &&
               hipMalloc((void**)&ch->d_prev, grid * NS) == hipSuccess &&
@@ -3300,13 +3229,11 @@ int32_t zly_change_enable(zly_engine* e, const zly_change_config* c, int32_t max
               hipMemset(ch->d_sums, 0, grid * B) == hipSuccess &&
               hipMemset(ch->d_state, 0, sizeof(ChangeStream) * NS) == hipSuccess &&
               hipMemset(ch->d_prev, 0, grid * NS) == hipSuccess &&
-              hipMemset(ch->d_recs, 0, (size_t)ch->lay.rec_bytes * NS) == hipSuccess;
-    for (int i = 0; i < Change::RING && ok; ++i) ok = hipEventCreateWithFlags(&ch->ev[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipDeviceSynchronize() == hipSuccess;
+              hipMemset(ch->d_recs, 0, (size_t)ch->lay.rec_bytes * NS) == hipSuccess &&
+              hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        change_free(ch);
-        delete ch;
+        (void)change_free(ch);
         return fail(ZLY_ERR_SYSTEM, "allocation of the change map's buffers failed");
     }
     e->change = ch;
@@ -3337,30 +3264,28 @@ int32_t zly_change_layout(const zly_engine* e, size_t* rec_bytes, size_t* peaks_
 // entry, for change_enqueue_pick.  Under e->mu, enqueue gate held; every check has been made.
 static int change_enqueue_sums(zly_engine* e, Change* ch, int n, const void* d_base, const zly_frame_view* v, const int32_t* streams, hipStream_t s, int* ring)
 {
-    const int r = ch->next;
-    if (ch->used[r]) HIP_TRY(hipEventSynchronize(ch->ev[r]), ZLY_ERR_INFERENCE);      // 8 calls back: long complete
-    if (ch->last >= 0) HIP_TRY(hipStreamWaitEvent(s, ch->ev[ch->last], 0), ZLY_ERR_INFERENCE);
-    ch->next = (r + 1) % Change::RING;
+    // not claim(): synchronise the entry, wait for the last, and only then advance -- a call that fails here leaves the ring as it found it
+    const int r = ch->ring.next;
+    if (ch->ring.used[r]) HIP_TRY(hipEventSynchronize(ch->ring.ev[r]), ZLY_ERR_INFERENCE);
+    HIP_TRY(ch->ring.wait_last(s), ZLY_ERR_INFERENCE);
+    ch->ring.next = (r + 1) % SlotRing::DEPTH;
     const int rc = [&]() -> int {
-        ChipFrame* hf = ch->h_frames + (size_t)r * (size_t)e->cfg.max_batch;
-        ChipFrame* df = ch->d_frames + (size_t)r * (size_t)e->cfg.max_batch;
-        ChangeItem* hi = ch->h_items + (size_t)r * (size_t)e->cfg.max_batch;
-        ChangeItem* di = ch->d_items + (size_t)r * (size_t)e->cfg.max_batch;
+        ChipFrame* hf = ch->ring.host<ChipFrame>(r);
+        ChangeItem* hi = ch->items(ch->ring.host<unsigned char>(r));
         int max_w = 1, max_h = 1;
         for (int i = 0; i < n; ++i) {
             hf[i] = chip_frame_of(&v[i]);
             hi[i] = ChangeItem{v[i].w, v[i].h, streams[i], 0};
             max_w = std::max(max_w, (int)v[i].w); max_h = std::max(max_h, (int)v[i].h);
         }
-        HIP_TRY(hipMemcpyAsync(df, hf, sizeof(ChipFrame) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
-        HIP_TRY(hipMemcpyAsync(di, hi, sizeof(ChangeItem) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
-        HIP_TRY(launch_change_sums((const uint8_t*)d_base, df, n, max_w, max_h, ch->cfg.cell, ch->d_sums, s), ZLY_ERR_INFERENCE);
+        // one copy: the frame records (all max_batch of the entry; the n first matter) and the n items behind them
+        HIP_TRY(ch->ring.upload(r, ch->items_off + sizeof(ChangeItem) * (size_t)n, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_change_sums((const uint8_t*)d_base, ch->ring.dev<ChipFrame>(r), n, max_w, max_h, ch->cfg.cell, ch->d_sums, s), ZLY_ERR_INFERENCE);
         return ZLY_OK;
     }();
     // The entry's event goes behind whatever has been enqueued, a failed call's too, and behind the sums kernel even if the caller fails before its
     // pick kernel: the next change call, on whichever stream, is ordered behind every user of the entry and of the scratch grids.
-    if (hipEventRecord(ch->ev[r], s) == hipSuccess) { ch->used[r] = true; ch->last = r; }
-    else if (rc == ZLY_OK) return fail(ZLY_ERR_INFERENCE, "hipEventRecord failed behind the change map's sums kernel");
+    if (ch->ring.mark(r, s) != hipSuccess && rc == ZLY_OK) return fail(ZLY_ERR_INFERENCE, "hipEventRecord failed behind the change map's sums kernel");
     *ring = r;
     return rc;
 }
@@ -3368,11 +3293,9 @@ static int change_enqueue_sums(zly_engine* e, Change* ch, int n, const void* d_b
 // The second half: change_pick_kernel on the ring entry r, and the entry's event once more, behind it.  zf, desc, tab, plan, K: a zoom call's (null, 0: none)
 static int change_enqueue_pick(zly_engine* e, Change* ch, int n, int r, const ZoomFrame* zf, FrameDesc* desc, int* tab, zly_zoom_region* plan, int K, hipStream_t s)
 {
-    const ChangeItem* di = ch->d_items + (size_t)r * (size_t)e->cfg.max_batch;
+    const ChangeItem* di = ch->items(ch->ring.dev<unsigned char>(r));
     HIP_TRY(launch_change_pick(di, n, ch->d_sums, ch->d_state, ch->d_prev, ch->d_recs, ch->cfg, zf, desc, tab, plan, K, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(ch->ev[r], s), ZLY_ERR_INFERENCE);
-    ch->used[r] = true;
-    ch->last = r;
+    HIP_TRY(ch->ring.mark(r, s), ZLY_ERR_INFERENCE);
     return ZLY_OK;
 }
 
@@ -3420,12 +3343,7 @@ int32_t zly_change_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, c
     if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
     hipStream_t ran = nullptr;
     if (int rc = change_locked(e, n, sf->d_store, sf->store.total, views.data(), streams, stream, sf->patched ? sf->ev_patch : nullptr, &ran)) return rc;
-    // the store has a reader now, as after zly_detect_surfaces: the next update's patch kernel goes behind the sums kernel, whichever stream it ran on
-    SharedGate gl;
-    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(sf->ev_read, ran), ZLY_ERR_INFERENCE);
-    sf->read_pending = true;
-    return ZLY_OK;
+    return surfaces_note_reader(e, sf, ran);
 }
 
 int32_t zly_change_read(zly_engine* e, int32_t stream, void* host_out, size_t cap_bytes)
@@ -3440,7 +3358,7 @@ int32_t zly_change_read(zly_engine* e, int32_t stream, void* host_out, size_t ca
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     {
         SharedGate gl;
-        if (ch->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, ch->ev[ch->last], 0), ZLY_ERR_INFERENCE);
+        HIP_TRY(ch->ring.wait_last(e->stream), ZLY_ERR_INFERENCE);
         HIP_TRY(hipMemcpyAsync(host_out, ch->d_recs + (size_t)stream * (size_t)ch->lay.rec_bytes, std::min(cap_bytes, (size_t)ch->lay.rec_bytes), hipMemcpyDeviceToHost,
                                e->stream), ZLY_ERR_INFERENCE);
     }
@@ -3458,14 +3376,11 @@ int32_t zly_change_reset(zly_engine* e, int32_t stream)
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     SharedGate gl;
     // a ring entry of its own orders the reset among the change calls: behind the last one, in front of the next
-    const int r = ch->next;
-    ch->next = (r + 1) % Change::RING;
-    if (ch->used[r]) HIP_TRY(hipEventSynchronize(ch->ev[r]), ZLY_ERR_INFERENCE);
-    if (ch->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, ch->ev[ch->last], 0), ZLY_ERR_INFERENCE);
+    int r = 0;
+    HIP_TRY(ch->ring.claim(&r), ZLY_ERR_INFERENCE);
+    HIP_TRY(ch->ring.wait_last(e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(hipMemsetAsync(ch->d_state + (stream < 0 ? 0 : stream), 0, sizeof(ChangeStream) * (size_t)(stream < 0 ? ch->max_streams : 1), e->stream), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(ch->ev[r], e->stream), ZLY_ERR_INFERENCE);
-    ch->used[r] = true;
-    ch->last = r;
+    HIP_TRY(ch->ring.mark(r, e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
 }
 
@@ -3495,18 +3410,12 @@ int32_t zly_zoom_enable(zly_engine* e, const zly_zoom_config* c)
     Zoom* zm = new Zoom();
     zm->cfg = *c;
     const size_t B = (size_t)e->cfg.max_batch, n_plan = B + B * (size_t)c->regions;
-    bool ok = hipMalloc((void**)&zm->d_frames, sizeof(ZoomFrame) * B * Zoom::RING) == hipSuccess &&
-              hipHostMalloc((void**)&zm->h_frames, sizeof(ZoomFrame) * B * Zoom::RING, hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void**)&zm->d_plan, sizeof(zly_zoom_region) * n_plan) == hipSuccess &&
-              hipMemset(zm->d_plan, 0, sizeof(zly_zoom_region) * n_plan) == hipSuccess;
-    for (int i = 0; i < Zoom::RING && ok; ++i) ok = hipEventCreateWithFlags(&zm->ev[i], hipEventDisableTiming) == hipSuccess;
+    const bool ok = zm->ring.create(sizeof(ZoomFrame) * B) == hipSuccess &&
+                    hipMalloc((void**)&zm->d_plan, sizeof(zly_zoom_region) * n_plan) == hipSuccess &&
+                    hipMemset(zm->d_plan, 0, sizeof(zly_zoom_region) * n_plan) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        if (zm->d_frames) hipFree(zm->d_frames);
-        if (zm->h_frames) hipHostFree(zm->h_frames);
-        if (zm->d_plan) hipFree(zm->d_plan);
-        for (int i = 0; i < Zoom::RING; ++i) if (zm->ev[i]) hipEventDestroy(zm->ev[i]);
-        delete zm;
+        (void)zoom_free(zm);
         return fail(ZLY_ERR_SYSTEM, "allocation of the zoom plan buffers failed");
     }
     e->zoom = zm;
@@ -3524,19 +3433,14 @@ static Zoom* zoom_of(zly_engine* e)
 // stream that ran.  desc / tab: what the kernel patches (null: the plan alone).  Under e->mu, enqueue gate held.
 static int zoom_enqueue_plan(zly_engine* e, Zoom* zm, Track* tk, int n, const ZoomFrame* zf, FrameDesc* desc, int* tab, zly_zoom_region* d_plan, hipStream_t s, int* ring)
 {
-    const int lt = (tk->next + Track::RING - 1) % Track::RING;                       // the most recent tracked launch
-    if (tk->used[lt]) HIP_TRY(hipStreamWaitEvent(s, tk->ev[lt], 0), ZLY_ERR_INFERENCE);
-    const int r = zm->next;
-    zm->next = (r + 1) % Zoom::RING;
-    if (zm->used[r]) HIP_TRY(hipEventSynchronize(zm->ev[r]), ZLY_ERR_INFERENCE);      // 8 plans back: long complete
-    ZoomFrame* hf = zm->h_frames + (size_t)r * (size_t)e->cfg.max_batch;
-    ZoomFrame* df = zm->d_frames + (size_t)r * (size_t)e->cfg.max_batch;
-    memcpy(hf, zf, sizeof(ZoomFrame) * (size_t)n);
-    HIP_TRY(hipMemcpyAsync(df, hf, sizeof(ZoomFrame) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(launch_zoom_plan(tk->d_state, tk->d_motion, df, n, desc, tab, d_plan, zm->cfg.regions, tk->cfg.max_tracks, zm->cfg.region_w, zm->cfg.region_h,
-                             zm->cfg.max_age, zm->cfg.class_id, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(zm->ev[r], s), ZLY_ERR_INFERENCE);
-    zm->used[r] = true;
+    HIP_TRY(tk->ring.wait_last(s), ZLY_ERR_INFERENCE);                               // the most recent tracked launch
+    int r = 0;
+    HIP_TRY(zm->ring.claim(&r), ZLY_ERR_INFERENCE);
+    memcpy(zm->ring.host<ZoomFrame>(r), zf, sizeof(ZoomFrame) * (size_t)n);
+    HIP_TRY(zm->ring.upload(r, sizeof(ZoomFrame) * (size_t)n, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_zoom_plan(tk->d_state, tk->d_motion, zm->ring.dev<ZoomFrame>(r), n, desc, tab, d_plan, zm->cfg.regions, tk->cfg.max_tracks, zm->cfg.region_w,
+                             zm->cfg.region_h, zm->cfg.max_age, zm->cfg.class_id, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(zm->ring.mark(r, s), ZLY_ERR_INFERENCE);
     *ring = r;
     return ZLY_OK;
 }
@@ -3604,11 +3508,11 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
     if ((rc = merge_upload(e, nb, tiles.data(), n, s, &mr)) != ZLY_OK) return rc;
     int cr = 0;
     if (ch && (rc = change_enqueue_sums(e, ch, n, d_base, sv, streams, s, &cr)) != ZLY_OK) return rc;
-    if ((rc = zoom_enqueue_plan(e, zm, tk, n, zf.data(), e->d_desc, e->merge->d_tab + (size_t)mr * e->merge->tab_ints, zm->d_plan, s, &zr)) != ZLY_OK) return rc;
-    if (ch && (rc = change_enqueue_pick(e, ch, n, cr, zm->d_frames + (size_t)zr * (size_t)e->cfg.max_batch, e->d_desc,
-                                        e->merge->d_tab + (size_t)mr * e->merge->tab_ints, zm->d_plan, zm->cfg.regions, s)) != ZLY_OK) return rc;
-    if (ch) HIP_TRY(hipEventRecord(zm->ev[zr], s), ZLY_ERR_INFERENCE);      // zly_zoom_read_plan reads the plan as the pick kernel left it
-    zm->last = zr; zm->last_n = n;
+    int* d_tab = e->merge->ring.dev<int>(mr);
+    if ((rc = zoom_enqueue_plan(e, zm, tk, n, zf.data(), e->d_desc, d_tab, zm->d_plan, s, &zr)) != ZLY_OK) return rc;
+    if (ch && (rc = change_enqueue_pick(e, ch, n, cr, zm->ring.dev<ZoomFrame>(zr), e->d_desc, d_tab, zm->d_plan, zm->cfg.regions, s)) != ZLY_OK) return rc;
+    if (ch) HIP_TRY(zm->ring.mark(zr, s), ZLY_ERR_INFERENCE);      // zly_zoom_read_plan reads the plan as the pick kernel left it
+    zm->last_frames = zr; zm->last_n = n;
     hipStream_t ns = s;
     rc = run_path(e, nb, (const uint8_t*)d_base, nullptr, 0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, level, true));
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
@@ -3621,9 +3525,8 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
     bool launched = false;
     if ((rc = track_enqueue(e, tk, n, streams, dst, ns, &launched)) != ZLY_OK) return rc;
     // the call's completion events lie behind its tracking: zly_join, zly_read_slabs, zly_read_merged and a later call's NMS wait for all of it
-    HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], ns), ZLY_ERR_INFERENCE);
-    if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], ns), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(e->merge->ev[mr], ns), ZLY_ERR_INFERENCE);
+    if ((rc = detect_events_behind(e, ns)) != ZLY_OK) return rc;
+    HIP_TRY(e->merge->ring.mark(mr, ns), ZLY_ERR_INFERENCE);
     return ZLY_OK;
 }
 
@@ -3663,12 +3566,7 @@ int32_t zly_detect_surfaces_zoom(zly_engine* e, int32_t n, const int32_t* surfac
     std::vector<zly_frame_view> views((size_t)n);
     if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
     if (int rc = detect_zoom_locked(e, n, sf->d_store, sf->store.total, views.data(), streams, merge_cfg, d_out, frame_tag0, stream, sf->patched ? sf->ev_patch : nullptr)) return rc;
-    // the store has a reader now, as after zly_detect_surfaces: the next update's patch kernel goes behind this call's last kernel
-    SharedGate gl;
-    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(sf->ev_read, e->last_ns), ZLY_ERR_INFERENCE);
-    sf->read_pending = true;
-    return ZLY_OK;
+    return surfaces_note_reader(e, sf, e->last_ns);
 }
 
 int32_t zly_zoom_plan(zly_engine* e, int32_t n, const int32_t* W, const int32_t* H, const int32_t* streams, zly_zoom_region* out)
@@ -3707,11 +3605,11 @@ int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out)
     std::lock_guard<std::mutex> lk(e->mu);
     Zoom* zm = zoom_of(e);
     if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
-    if (zm->last < 0 || n != zm->last_n) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_zoom_read_plan: n must be the frames of the most recent zoom call");
+    if (zm->last_frames < 0 || n != zm->last_n) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_zoom_read_plan: n must be the frames of the most recent zoom call");
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     {
         SharedGate gl;
-        HIP_TRY(hipStreamWaitEvent(e->stream, zm->ev[zm->last], 0), ZLY_ERR_INFERENCE);
+        HIP_TRY(hipStreamWaitEvent(e->stream, zm->ring.ev[zm->last_frames], 0), ZLY_ERR_INFERENCE);      // not wait_last: zly_zoom_plan marks entries too
         HIP_TRY(hipMemcpyAsync(out, zm->d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     }
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
@@ -3752,18 +3650,12 @@ int32_t zly_chips_enable(zly_engine* e, const zly_chip_config* c)
     cp->cfg = *c;
     cp->lay = chip_layout(c->chip_w, c->chip_h, c->max_chips, c->layout == ZLY_CHIP_RGB_F32);
     const size_t B = (size_t)e->cfg.max_batch;
-    bool ok = hipMalloc((void**)&cp->d_frames, sizeof(ChipFrame) * B * Chips::RING) == hipSuccess &&
-              hipHostMalloc((void**)&cp->h_frames, sizeof(ChipFrame) * B * Chips::RING, hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void**)&cp->d_out, (size_t)cp->lay.slab_bytes * B) == hipSuccess &&
-              hipMemset(cp->d_out, 0, (size_t)cp->lay.slab_bytes * B) == hipSuccess;
-    for (int i = 0; i < Chips::RING && ok; ++i) ok = hipEventCreateWithFlags(&cp->ev[i], hipEventDisableTiming) == hipSuccess;
+    const bool ok = cp->ring.create(sizeof(ChipFrame) * B) == hipSuccess &&
+                    hipMalloc((void**)&cp->d_out, (size_t)cp->lay.slab_bytes * B) == hipSuccess &&
+                    hipMemset(cp->d_out, 0, (size_t)cp->lay.slab_bytes * B) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        if (cp->d_frames) hipFree(cp->d_frames);
-        if (cp->h_frames) hipHostFree(cp->h_frames);
-        if (cp->d_out) hipFree(cp->d_out);
-        for (int i = 0; i < Chips::RING; ++i) if (cp->ev[i]) hipEventDestroy(cp->ev[i]);
-        delete cp;
+        (void)chips_free(cp);
         return fail(ZLY_ERR_SYSTEM, "allocation of the chip buffers failed");
     }
     e->chips = cp;
@@ -3804,32 +3696,22 @@ static int chips_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf
     const void* slabs = d_slabs ? d_slabs : source == ZLY_CHIPS_SRC_MERGED ? (const void*)e->merge->d_out : (const void*)e->d_slabs;
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    // the stream zly_track_slabs would choose: behind the NMS, merge and tracking of the most recent zly_detect_device* call, on whichever stream they ran
+    // behind the NMS, merge and tracking of the most recent zly_detect_device* call, on whichever stream they ran
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    const bool after_call = e->call_seq > 0;
-    if (after_call && e->last_deferred) s = e->last_ns;
-    else if (after_call && s != e->last_ns) HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1) & 1], 0), ZLY_ERR_INFERENCE);
+    if (int rc = stream_after_detect(e, s)) return rc;
     if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
     // merges of an engine made before any detect call (slabs made elsewhere) are ordered by their own ring event
-    if (!d_slabs && source == ZLY_CHIPS_SRC_MERGED && e->merge->last >= 0) HIP_TRY(hipStreamWaitEvent(s, e->merge->ev[e->merge->last], 0), ZLY_ERR_INFERENCE);
-    const int r = cp->next;
-    cp->next = (r + 1) % Chips::RING;
-    if (cp->used[r]) HIP_TRY(hipEventSynchronize(cp->ev[r]), ZLY_ERR_INFERENCE);      // 8 calls back: long complete
+    if (!d_slabs && source == ZLY_CHIPS_SRC_MERGED) HIP_TRY(e->merge->ring.wait_last(s), ZLY_ERR_INFERENCE);
+    int r = 0;
+    HIP_TRY(cp->ring.claim(&r), ZLY_ERR_INFERENCE);
     // chip calls of an engine are ordered among themselves: they may share the engine-owned output
-    if (cp->last >= 0) HIP_TRY(hipStreamWaitEvent(s, cp->ev[cp->last], 0), ZLY_ERR_INFERENCE);
-    ChipFrame* hf = cp->h_frames + (size_t)r * (size_t)e->cfg.max_batch;
-    ChipFrame* df = cp->d_frames + (size_t)r * (size_t)e->cfg.max_batch;
-    memcpy(hf, cf.data(), sizeof(ChipFrame) * (size_t)n);
-    HIP_TRY(hipMemcpyAsync(df, hf, sizeof(ChipFrame) * (size_t)n, hipMemcpyHostToDevice, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(launch_chips((const uint8_t*)d_base, df, n, slabs, slab_bytes_of(e), e->cfg.max_dets, d_chips ? d_chips : (void*)cp->d_out, cp->cfg, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(cp->ev[r], s), ZLY_ERR_INFERENCE);
-    cp->used[r] = true;
-    cp->last = r;
-    if (after_call) {
-        // the call's completion events move behind its chips: zly_join, zly_read_slabs and a later call's NMS wait for both
-        HIP_TRY(hipEventRecord(e->ev_call[(e->call_seq - 1) & 1], s), ZLY_ERR_INFERENCE);
-        if (e->last_deferred && e->last_async >= 0) HIP_TRY(hipEventRecord(e->ev_nms[e->last_async], s), ZLY_ERR_INFERENCE);
-    }
+    HIP_TRY(cp->ring.wait_last(s), ZLY_ERR_INFERENCE);
+    memcpy(cp->ring.host<ChipFrame>(r), cf.data(), sizeof(ChipFrame) * (size_t)n);
+    HIP_TRY(cp->ring.upload(r, sizeof(ChipFrame) * (size_t)n, s), ZLY_ERR_INFERENCE);
+    HIP_TRY(launch_chips((const uint8_t*)d_base, cp->ring.dev<ChipFrame>(r), n, slabs, slab_bytes_of(e), e->cfg.max_dets, d_chips ? d_chips : (void*)cp->d_out, cp->cfg, s),
+            ZLY_ERR_INFERENCE);
+    HIP_TRY(cp->ring.mark(r, s), ZLY_ERR_INFERENCE);
+    if (int rc = detect_events_behind(e, s)) return rc;
     *ran_on = s;
     return ZLY_OK;
 }
@@ -3857,12 +3739,7 @@ int32_t zly_chips_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, co
     if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
     hipStream_t ran = nullptr;
     if (int rc = chips_locked(e, n, sf->d_store, sf->store.total, views.data(), d_slabs, source, d_chips, stream, sf->patched ? sf->ev_patch : nullptr, &ran)) return rc;
-    // the store has a reader now, as after zly_detect_surfaces: the next update's patch kernel goes behind the cut kernel, whichever stream it ran on
-    SharedGate gl;
-    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(sf->ev_read, ran), ZLY_ERR_INFERENCE);
-    sf->read_pending = true;
-    return ZLY_OK;
+    return surfaces_note_reader(e, sf, ran);
 }
 
 int32_t zly_read_chips(zly_engine* e, int32_t n, void* host_out)
@@ -3875,7 +3752,7 @@ int32_t zly_read_chips(zly_engine* e, int32_t n, void* host_out)
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     {
         SharedGate gl;
-        if (cp->last >= 0) HIP_TRY(hipStreamWaitEvent(e->stream, cp->ev[cp->last], 0), ZLY_ERR_INFERENCE);
+        HIP_TRY(cp->ring.wait_last(e->stream), ZLY_ERR_INFERENCE);
         HIP_TRY(hipMemcpyAsync(host_out, cp->d_out, (size_t)cp->lay.slab_bytes * (size_t)n, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     }
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
