@@ -1628,6 +1628,198 @@ static ViewRec view_rec(const zly_frame_view* v)
     return r;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the scaffold of a call: what the device entries and the read-backs of the C ABI share
+// ------------------------------------------------------------------------------------------------
+
+// An engine's feature state, or null with the error set: one message per feature, stated here once.  All but track_of under e->mu.
+static const char* const NO_TRACK = "tracking is not enabled on this engine (zly_track_enable)";
+static const char* const NO_MERGE = "this engine has not merged yet (zly_merge_slabs)";
+static const char* const NO_STORE = "resident surfaces are not enabled on this engine (zly_surfaces_enable)";
+static const char* const NO_ZOOM = "zoom regions are not enabled on this engine (zly_track_enable, then zly_zoom_enable)";
+static const char* const NO_CHIPS = "chips are not enabled on this engine (zly_chips_enable)";
+static const char* const NO_CHANGE = "the change map is not enabled on this engine (zly_change_enable)";
+template <typename T> static T* enabled(T* state, const char* or_else)
+{
+    if (!state) fail(ZLY_ERR_INVALID_ARGUMENT, or_else);
+    return state;
+}
+static Track* track_of(zly_engine* e) { return enabled(e->track.load(), NO_TRACK); }
+static Surfaces* surfaces_of(zly_engine* e) { return enabled(e->surf, NO_STORE); }
+static Zoom* zoom_of(zly_engine* e) { return enabled(e->zoom, NO_ZOOM); }
+static Chips* chips_of(zly_engine* e) { return enabled(e->chips, NO_CHIPS); }
+static Change* change_of(zly_engine* e) { return enabled(e->change, NO_CHANGE); }
+
+// The stream a device entry enqueues on: the caller's, or the engine's own where the caller names none.  wait_for: an event the caller's stream has to
+// wait for first (null = none); the engine's own stream lies behind it already.  Enqueue gate held.
+static int wait_if_foreign(zly_engine* e, hipStream_t s, hipEvent_t wait_for)
+{
+    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+static int call_stream(zly_engine* e, void* stream, hipStream_t* s, hipEvent_t wait_for = nullptr)
+{
+    *s = stream ? (hipStream_t)stream : e->stream;
+    return wait_if_foreign(e, *s, wait_for);
+}
+
+// Where a call's frames lie: views v[] of the device buffer [base, base + bytes), and the event a caller's stream waits for before it reads them
+struct FrameSource {
+    const void* base;
+    size_t bytes;
+    const zly_frame_view* v;
+    hipEvent_t wait_for = nullptr;
+};
+
+// The frame table of a call -- what set_desc uploads and run_path's front kernel reads: per frame size, format, offset and (a call on frame views)
+// the ViewRec, and the batch's format level.  Appended to view by view, or made of n tight frames; five allocations at the most, as many as the
+// arrays it holds.
+struct FrameTable {
+    std::vector<int32_t> w, h, fmt;
+    std::vector<size_t> off;
+    std::vector<ViewRec> recs;        // a call on frame views; empty: tight frames
+    bool views;
+    int level = ZLY_FRONT_BGR;        // the highest front_level of the frames
+    FrameTable(int n, bool of_views) : views(of_views)
+    {
+        w.reserve((size_t)n); h.reserve((size_t)n); fmt.reserve((size_t)n); off.reserve((size_t)n);
+        if (views) recs.reserve((size_t)n);
+    }
+    // n tight w x h frames of one format, frame_bytes apart
+    static FrameTable tight(int32_t fmt, int32_t w, int32_t h, size_t frame_bytes, int n)
+    {
+        FrameTable t(n, false);
+        for (int i = 0; i < n; ++i) t.add(fmt, w, h, (size_t)i * frame_bytes);
+        return t;
+    }
+    void add(int32_t f, int32_t fw, int32_t fh, size_t o)
+    {
+        w.push_back(fw); h.push_back(fh); fmt.push_back(f); off.push_back(o);
+        level = std::max(level, front_level(f));
+    }
+    void add(const zly_frame_view& v) { add(v.fmt, v.w, v.h, (size_t)v.off[0]); recs.push_back(view_rec(&v)); }      // v: checked (check_view)
+    int n() const { return (int)w.size(); }
+    FrontVariant front(const zly_engine* e) const { return front_of(e, level, views); }
+};
+static int set_desc(zly_engine* e, const FrameTable& t, hipStream_t s)
+{
+    return set_desc(e, t.n(), t.w.data(), t.h.data(), t.off.data(), s, t.fmt.data(), t.views ? t.recs.data() : nullptr);
+}
+
+// The tail of every device detect entry, behind set_desc: the path on `s` with the engine's NMS mode, then the call's completion event behind its NMS,
+// the call counted and remembered (last_ns, last_deferred: stream_after_detect).  record_call = false: a call that enqueues more behind its NMS and
+// moves the completion events there itself (detect_events_behind) records none here.  Under e->mu, enqueue gate held.
+static int detect_run(zly_engine* e, const FrameTable& t, const void* d_src, void* d_slabs, uint32_t frame_tag0, hipStream_t s, bool record_call = true)
+{
+    hipStream_t ns = s;
+    const int rc = run_path(e, t.n(), (const uint8_t*)d_src, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, t.front(e));
+    if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
+    if (record_call) HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
+    e->call_seq++;
+    e->last_ns = ns; e->last_deferred = ns != s;
+    with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)t.n(); });
+    return ZLY_OK;
+}
+static int detect_enqueue(zly_engine* e, const FrameTable& t, const void* d_src, void* d_slabs, uint32_t frame_tag0, hipStream_t s)
+{
+    if (int rc = set_desc(e, t, s)) return rc;
+    return detect_run(e, t, d_src, d_slabs, frame_tag0, s);
+}
+
+// The resident store's side of the reader / writer protocol (Surfaces::ev_read, ev_patch), three halves.  Under e->mu.
+// 1. The store has a reader now: a call that read its slots has been enqueued, and its last kernel went to `ran`.  The next writer goes behind it,
+//    whichever stream that is.  Takes the enqueue gate itself.
+static int surfaces_note_reader(zly_engine* e, Surfaces* sf, hipStream_t ran)
+{
+    SharedGate gl;
+    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipEventRecord(sf->ev_read, ran), ZLY_ERR_INFERENCE);
+    sf->read_pending = true;
+    return ZLY_OK;
+}
+// 2. In front of a writer's kernels on the engine's stream: detect calls on other streams may still read the slots it writes.  Enqueue gate held.
+static int surfaces_begin_write(zly_engine* e, Surfaces* sf)
+{
+    if (!sf->read_pending) return ZLY_OK;
+    HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
+    sf->read_pending = false;                                            // from here on the dependency is the engine stream's own order
+    return ZLY_OK;
+}
+// 3. ... and behind them: a reader on a caller's stream waits for ev_patch (StoreFrames::read_by).  Enqueue gate held.
+static int surfaces_end_write(zly_engine* e, Surfaces* sf)
+{
+    HIP_TRY(hipEventRecord(sf->ev_patch, e->stream), ZLY_ERR_INFERENCE);
+    sf->patched = true;
+    return ZLY_OK;
+}
+
+// Frames that come from the resident store: open() asks for the store, frames() resolves n slots (and regions of them) to views of it, and read_by
+// hands them to the body of a call -- body(const FrameSource&, hipStream_t* ran), *ran the stream its last kernel went to -- and tells the store of its
+// reader once the body has enqueued.  The store's base, size and patch event leave this object in no other way: a reader cannot forget the note.
+class StoreFrames {
+    zly_engine* e = nullptr;
+    Surfaces* sf = nullptr;
+    std::vector<zly_frame_view> views;
+public:
+    int open(zly_engine* engine) { e = engine; sf = surfaces_of(e); return sf ? ZLY_OK : ZLY_ERR_INVALID_ARGUMENT; }
+    int frames(int n, const int32_t* surfaces, const zly_roi* rois = nullptr)
+    {
+        views.resize((size_t)n);
+        return surface_detect_views(sf->store, sf->slots.data(), n, surfaces, rois, views.data(), &g_last_error);
+    }
+    template <typename Body> int read_by(Body&& body)
+    {
+        hipStream_t ran = nullptr;
+        if (int rc = body(FrameSource{sf->d_store, sf->store.total, views.data(), sf->patched ? sf->ev_patch : nullptr}, &ran)) return rc;
+        return surfaces_note_reader(e, sf, ran);
+    }
+};
+
+// A read-back to host memory: the copies enqueued on the engine's stream behind whatever `behind` enqueues there first (a ring's wait_last, one ring
+// event, join_nms; it is handed the engine's stream, the only one a read-back uses), then the stream synchronised.  The gate is held over the
+// enqueue only: waiting for the device is not an enqueue section.  Under e->mu.
+struct HostCopy { void* dst; const void* src; size_t bytes; };             // bytes = 0: no copy
+template <typename Behind> static int read_back(zly_engine* e, Behind&& behind, std::initializer_list<HostCopy> copies)
+{
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    {
+        SharedGate gl;
+        if (int rc = behind(e->stream)) return rc;
+        for (const HostCopy& c : copies)
+            if (c.bytes) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+static int behind_nothing(hipStream_t) { return ZLY_OK; }
+static auto behind_ring(const SlotRing& ring)
+{
+    return [&ring](hipStream_t s) -> int { HIP_TRY(ring.wait_last(s), ZLY_ERR_INFERENCE); return ZLY_OK; };
+}
+
+// In front of a host-synchronous call's copy into pinned staging: room for `bytes` -- growth beyond what zly_create staged is an allocation, alone in
+// the process --, then the engine's stream drained, because pinned staging is reused call to call.  Waiting for the device is not an enqueue section:
+// no gate is held across it (other engines keep enqueuing).  Under e->mu, no gate held.
+static int stage_for(zly_engine* e, size_t bytes)
+{
+    if (bytes > e->stage_bytes) {
+        ExclusiveGate x;
+        if (int rc = ensure_stage(e, bytes)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+// One result slab on the host to the caller's records: the first min(n_kept, max_dets, cap) detections, stamped ts; returns n_kept
+static int unpack_slab(const unsigned char* slab, int cap, int max_dets, uint64_t ts, zly_det* out)
+{
+    const zly_slab_header* hd = reinterpret_cast<const zly_slab_header*>(slab);
+    const zly_det* d = reinterpret_cast<const zly_det*>(hd + 1);
+    const int m = std::min(std::min(hd->n_kept, max_dets), cap);
+    for (int k = 0; k < m; ++k) { out[k] = d[k]; out[k].timestamp = ts; }
+    return hd->n_kept;
+}
+
 // Returns the first HIP error met while draining / releasing (the engine is gone either way).
 static hipError_t destroy_engine(zly_engine* e)
 {
@@ -2037,14 +2229,8 @@ static int ingest_wait(zly_engine* e, uint64_t ticket, zly_det* out, int32_t cap
     const uint64_t ts = sl->ts_ms;
     lk.unlock();
     int kept = 0;
-    if (rc == ZLY_OK) {                                    // the slot cannot be recycled before this ticket is consumed below
-        const size_t sb = slab_bytes_of(e);
-        const zly_slab_header* hd = reinterpret_cast<const zly_slab_header*>(sl->h_slabs + sb * (size_t)idx);
-        const zly_det* d = reinterpret_cast<const zly_det*>(hd + 1);
-        kept = hd->n_kept;
-        int m = std::min(std::min(kept, e->cfg.max_dets), (int)cap);
-        for (int k = 0; k < m; ++k) { out[k] = d[k]; out[k].timestamp = ts; }
-    }
+    if (rc == ZLY_OK)                                      // the slot cannot be recycled before this ticket is consumed below
+        kept = unpack_slab(sl->h_slabs + slab_bytes_of(e) * (size_t)idx, cap, e->cfg.max_dets, ts, out);
     lk.lock();
     sl->consumed[(size_t)idx] = 1;
     if (++sl->n_consumed == sl->n_reserved) {
@@ -2278,15 +2464,9 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
         total += ((views ? zly_frame_bytes(fi, views[i].w, views[i].h) : nbytes[i]) + 15) / 16 * 16;
     }
     if (views) { w = vw.data(); h = vh.data(); fmt = vf.data(); }
-    int rc = ZLY_OK;
-    if (total > e->stage_bytes) {                                        // growth beyond what zly_create staged (frames larger than the model input): an allocation, alone in the process
-        ExclusiveGate x;
-        rc = ensure_stage(e, total);
-        if (rc != ZLY_OK) return rc;
-    }
-    // waiting for the device and the host copy are not enqueue sections: no gate is held across them (other engines keep enqueuing)
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
-    for (int i = 0; i < n; ++i) {
+    int rc = stage_for(e, total);                                        // frames larger than the model input grow the staging
+    if (rc != ZLY_OK) return rc;
+    for (int i = 0; i < n; ++i) {                                        // the host copy is no enqueue section either: no gate yet
         if (views) copy_view_tight(e->h_stage + offs[(size_t)i], bgr[i], &views[i]);
         else memcpy(e->h_stage + offs[(size_t)i], bgr[i], nbytes[i]);
     }
@@ -2301,15 +2481,7 @@ static int detect_host_locked(zly_engine* e, int32_t n, const uint8_t* const* bg
     gl.release();                                                        // waiting for the device is not an enqueue section
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     const uint64_t ts = now_ms();                                        // onnx_engine.cpp:813-815
-    for (int i = 0; i < n; ++i) {
-        const zly_slab_header* hd = reinterpret_cast<const zly_slab_header*>(e->h_slabs + sb * (size_t)i);
-        const zly_det* d = reinterpret_cast<const zly_det*>(hd + 1);
-        int m = hd->n_kept;
-        if (m > e->cfg.max_dets) m = e->cfg.max_dets;
-        if (m > cap) m = cap;
-        for (int k = 0; k < m; ++k) { out[(size_t)i * cap + k] = d[k]; out[(size_t)i * cap + k].timestamp = ts; }
-        n_out[i] = hd->n_kept;
-    }
+    for (int i = 0; i < n; ++i) n_out[i] = unpack_slab(e->h_slabs + sb * (size_t)i, cap, e->cfg.max_dets, ts, out + (size_t)i * cap);
     harvest_timing(e);                                                   // the stream is idle: a sampled call's events are complete
     with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
     return ZLY_OK;
@@ -2465,50 +2637,26 @@ int32_t zly_detect_device_fmt(zly_engine* e, int32_t fmt, int32_t n, const void*
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    std::vector<int32_t> ws((size_t)n, w), hs((size_t)n, h), fs((size_t)n, fmt);
-    std::vector<size_t> offs((size_t)n);
-    for (int i = 0; i < n; ++i) offs[(size_t)i] = (size_t)i * fb;
-    int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data());
-    if (rc != ZLY_OK) return rc;
-    hipStream_t ns = s;
-    rc = run_path(e, n, (const uint8_t*)d_frames, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, front_level(fmt)));
-    if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
-    HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
-    e->call_seq++;
-    e->last_ns = ns; e->last_deferred = ns != s;
-    with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
-    return ZLY_OK;
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s)) return rc;
+    return detect_enqueue(e, FrameTable::tight(fmt, w, h, fb, n), d_frames, d_slabs, frame_tag0, s);
 }
 
-// The body of zly_detect_device_view, shared with zly_detect_surfaces and zly_detect_delta: n (1..max_batch) views of the device buffer d_base.
-// Under e->mu; takes the enqueue gate itself.  wait_for: an event `stream` has to wait for first when it is not the engine's own (null = none).
-static int detect_device_view_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, void* d_slabs, uint32_t frame_tag0,
-                                     void* stream, hipEvent_t wait_for = nullptr)
+// The body of zly_detect_device_view, shared with zly_detect_surfaces and zly_detect_delta: the n (1..max_batch) views of the source.  Under e->mu;
+// takes the enqueue gate itself.  *ran_on (if asked for): the stream the call's last kernel went to.
+static int detect_device_view_locked(zly_engine* e, int32_t n, const FrameSource& f, void* d_slabs, uint32_t frame_tag0, void* stream, hipStream_t* ran_on = nullptr)
 {
-    std::vector<int32_t> ws((size_t)n), hs((size_t)n), fs((size_t)n);
-    std::vector<size_t> offs((size_t)n);
-    std::vector<ViewRec> recs((size_t)n);
-    int level = ZLY_FRONT_BGR;
+    FrameTable t(n, true);
     for (int i = 0; i < n; ++i) {
-        if (int rcv = check_view(e->cfg.flags, d_base, buf_bytes, &v[i], &g_last_error)) return rcv;
-        ws[(size_t)i] = v[i].w; hs[(size_t)i] = v[i].h; fs[(size_t)i] = v[i].fmt; offs[(size_t)i] = (size_t)v[i].off[0];
-        recs[(size_t)i] = view_rec(&v[i]);
-        level = std::max(level, front_level(v[i].fmt));
+        if (int rcv = check_view(e->cfg.flags, f.base, f.bytes, &f.v[i], &g_last_error)) return rcv;
+        t.add(f.v[i]);
     }
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
-    int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), s, fs.data(), recs.data());
-    if (rc != ZLY_OK) return rc;
-    hipStream_t ns = s;
-    rc = run_path(e, n, (const uint8_t*)d_base, d_slabs, frame_tag0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, level, true));
-    if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
-    HIP_TRY(hipEventRecord(e->ev_call[e->call_seq & 1], ns), ZLY_ERR_INFERENCE);
-    e->call_seq++;
-    e->last_ns = ns; e->last_deferred = ns != s;
-    with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s, f.wait_for)) return rc;
+    if (int rc = detect_enqueue(e, t, f.base, d_slabs, frame_tag0, s)) return rc;
+    if (ran_on) *ran_on = e->last_ns;
     return ZLY_OK;
 }
 
@@ -2518,7 +2666,7 @@ int32_t zly_detect_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     if (!v) return fail(ZLY_ERR_INVALID_ARGUMENT, "null views");
     if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
     std::lock_guard<std::mutex> lk(e->mu);
-    return detect_device_view_locked(e, n, d_base, buf_bytes, v, d_slabs, frame_tag0, stream);
+    return detect_device_view_locked(e, n, FrameSource{d_base, buf_bytes, v}, d_slabs, frame_tag0, stream);
 }
 
 int32_t zly_join(zly_engine* e, void* stream, int32_t lag)
@@ -2529,7 +2677,8 @@ int32_t zly_join(zly_engine* e, void* stream, int32_t lag)
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s)) return rc;
     // every call but the last `lag`: calls are stream-ordered among themselves, so waiting for call (last - lag) covers all earlier ones
     if (e->call_seq > (uint64_t)lag)
         HIP_TRY(hipStreamWaitEvent(s, e->ev_call[(e->call_seq - 1 - (uint64_t)lag) & 1], 0), ZLY_ERR_INFERENCE);
@@ -2554,15 +2703,7 @@ int32_t zly_read_slabs(zly_engine* e, int32_t n, void* host_slabs)
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!host_slabs || n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    {
-        SharedGate gl;
-        int rcj = join_nms(e, e->stream);
-        if (rcj != ZLY_OK) return rcj;
-        HIP_TRY(hipMemcpyAsync(host_slabs, e->d_slabs, slab_bytes_of(e) * (size_t)n, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    return ZLY_OK;
+    return read_back(e, [&](hipStream_t s) { return join_nms(e, s); }, {{host_slabs, e->d_slabs, slab_bytes_of(e) * (size_t)n}});
 }
 
 // --- tracking --------------------------------------------------------------------------------------
@@ -2601,14 +2742,6 @@ int32_t zly_track_enable(zly_engine* e, const zly_track_config* c)
     }
     e->track.store(tk);
     return ZLY_OK;
-}
-
-// the engine's tracker, or null with the error set
-static Track* track_of(zly_engine* e)
-{
-    Track* tk = e->track.load();
-    if (!tk) fail(ZLY_ERR_INVALID_ARGUMENT, "tracking is not enabled on this engine (zly_track_enable)");
-    return tk;
 }
 
 int32_t zly_track_reset(zly_engine* e, int32_t stream, uint32_t first_id)
@@ -2672,15 +2805,10 @@ int32_t zly_track_read(zly_engine* e, int32_t stream, zly_track* out, int32_t ca
     if (!n_out || cap < 0 || (cap > 0 && !out)) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
     if (stream < 0 || stream >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
     std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     if (int rc = track_drain(tk)) return rc;
     std::vector<unsigned char> host(sizeof(TrackStream)), hostm(sizeof(TrackMotion), 0);
-    {
-        SharedGate gl;
-        HIP_TRY(hipMemcpyAsync(host.data(), tk->d_state + stream, sizeof(TrackStream), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-        if (tk->d_motion) HIP_TRY(hipMemcpyAsync(hostm.data(), tk->d_motion + stream, sizeof(TrackMotion), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    if (int rc = read_back(e, behind_nothing, {{host.data(), tk->d_state + stream, sizeof(TrackStream)},
+                                               {hostm.data(), tk->d_motion ? tk->d_motion + stream : nullptr, tk->d_motion ? sizeof(TrackMotion) : 0}})) return rc;
     const TrackStream* ts = reinterpret_cast<const TrackStream*>(host.data());
     const TrackMotion* tm = reinterpret_cast<const TrackMotion*>(hostm.data());      // all zero on an engine without the model
     int32_t n = 0;
@@ -2706,14 +2834,9 @@ int32_t zly_track_state_at(zly_engine* e, int32_t stream, zly_track_state* out)
     if (!out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
     if (stream < 0 || stream >= tk->cfg.max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
     std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     if (int rc = track_drain(tk)) return rc;
     std::vector<unsigned char> host(sizeof(TrackStream));
-    {
-        SharedGate gl;
-        HIP_TRY(hipMemcpyAsync(host.data(), tk->d_state + stream, sizeof(TrackStream), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
+    if (int rc = read_back(e, behind_nothing, {{host.data(), tk->d_state + stream, sizeof(TrackStream)}})) return rc;
     const TrackStream* ts = reinterpret_cast<const TrackStream*>(host.data());
     out->frame_no = ts->frame_no; out->next_id = ts->next_id; out->evictions = ts->evictions;
     out->n_live = 0;
@@ -2733,7 +2856,8 @@ int32_t zly_track_slabs(zly_engine* e, int32_t n, const int32_t* streams, void* 
     std::lock_guard<std::mutex> lk(e->mu);
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s)) return rc;
     if (int rc = stream_after_detect(e, s)) return rc;
     bool launched = false;
     int rc = track_enqueue(e, tk, n, streams, d_slabs ? d_slabs : e->d_slabs, s, &launched);
@@ -2881,7 +3005,8 @@ int32_t zly_merge_slabs(zly_engine* e, int32_t n, const zly_tile* tiles, int32_t
     if (int rc = merge_ensure(e)) return rc;
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s)) return rc;
     if (int rc = stream_after_detect(e, s)) return rc;
     int rc = merge_enqueue(e, n, tiles, n_groups, c, max_slots, d_slabs ? d_slabs : e->d_slabs, d_out ? d_out : e->merge->d_out, frame_tag0, s);
     if (rc != ZLY_OK) return rc;
@@ -2893,18 +3018,13 @@ int32_t zly_read_merged(zly_engine* e, int32_t n_groups, void* host_slabs)
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (!host_slabs || n_groups < 1 || n_groups > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "bad argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    Merge* mg = e->merge;
-    if (!mg) return fail(ZLY_ERR_INVALID_ARGUMENT, "this engine has not merged yet (zly_merge_slabs)");
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    {
-        SharedGate gl;
-        HIP_TRY(mg->ring.wait_last(e->stream), ZLY_ERR_INFERENCE);      // merges of an engine are ordered among themselves
-        int rcj = join_nms(e, e->stream);
-        if (rcj != ZLY_OK) return rcj;
-        HIP_TRY(hipMemcpyAsync(host_slabs, mg->d_out, slab_bytes_of(e) * (size_t)n_groups, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    return ZLY_OK;
+    Merge* mg = enabled(e->merge, NO_MERGE);
+    if (!mg) return ZLY_ERR_INVALID_ARGUMENT;
+    auto behind = [&](hipStream_t s) -> int {
+        HIP_TRY(mg->ring.wait_last(s), ZLY_ERR_INFERENCE);               // merges of an engine are ordered among themselves
+        return join_nms(e, s);
+    };
+    return read_back(e, behind, {{host_slabs, mg->d_out, slab_bytes_of(e) * (size_t)n_groups}});
 }
 
 int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, const zly_frame_view* surface, int32_t n, const zly_tile* tiles,
@@ -2918,49 +3038,34 @@ int32_t zly_detect_tiled(zly_engine* e, const uint8_t* base, size_t buf_bytes, c
     if (!base || nbytes > buf_bytes) return fail(ZLY_ERR_INVALID_INPUT, "Invalid image data size: the surface needs " + std::to_string(nbytes) + " bytes, got " + std::to_string(buf_bytes));
     int max_slots = 0;
     if (int rc = merge_check(e, n, tiles, 1, c, &max_slots)) return rc;
-    std::vector<zly_frame_view> views((size_t)n);
-    std::vector<int32_t> ws((size_t)n), hs((size_t)n), fs((size_t)n);
-    std::vector<size_t> offs((size_t)n);
-    std::vector<ViewRec> recs((size_t)n);
-    int level = ZLY_FRONT_BGR;
+    FrameTable ft(n, true);
     for (int i = 0; i < n; ++i) {
         const zly_tile& t = tiles[i];
         if (t.group != 0 || t.W != surface->w || t.H != surface->h)
             return fail(ZLY_ERR_INVALID_ARGUMENT, "tile " + std::to_string(i) + ": zly_detect_tiled needs group = 0 and W, H = the surface's size");
-        if (int rc = zly_view_crop(surface, t.x0, t.y0, t.w, t.h, &views[(size_t)i])) return rc;
-        if (int rc = check_view(e->cfg.flags, base, buf_bytes, &views[(size_t)i], &g_last_error)) return rc;
-        const zly_frame_view& v = views[(size_t)i];
-        ws[(size_t)i] = v.w; hs[(size_t)i] = v.h; fs[(size_t)i] = v.fmt; offs[(size_t)i] = (size_t)v.off[0];
-        recs[(size_t)i] = view_rec(&v);
-        level = std::max(level, front_level(v.fmt));
+        zly_frame_view v;
+        if (int rc = zly_view_crop(surface, t.x0, t.y0, t.w, t.h, &v)) return rc;
+        if (int rc = check_view(e->cfg.flags, base, buf_bytes, &v, &g_last_error)) return rc;
+        ft.add(v);
     }
     std::lock_guard<std::mutex> lk(e->mu);
     if (int rc = merge_ensure(e)) return rc;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    if (nbytes > e->stage_bytes) {                                       // an allocation: alone in the process
-        ExclusiveGate x;
-        if (int rc = ensure_stage(e, nbytes)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
+    if (int rc = stage_for(e, nbytes)) return rc;
     memcpy(e->h_stage, base, nbytes);                                    // the surface once, as it is: the front kernel fetches through the tiles' views
     SharedGate gl;
     HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, nbytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
-    int rc = set_desc(e, n, ws.data(), hs.data(), offs.data(), e->stream, fs.data(), recs.data());
+    // not detect_run: a host-synchronous call never defers its NMS and is no call that zly_join or stream_after_detect could order anything behind
+    int rc = set_desc(e, ft, e->stream);
     if (rc != ZLY_OK) return rc;
-    rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, false, nullptr, front_of(e, level, true));
+    rc = run_path(e, n, e->d_stage, nullptr, 0, e->stream, true, false, nullptr, ft.front(e));
     if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
     rc = merge_enqueue(e, n, tiles, 1, c, max_slots, e->d_slabs, e->merge->d_out, 0, e->stream);
     if (rc != ZLY_OK) return rc;
-    const size_t sb = slab_bytes_of(e);
-    HIP_TRY(hipMemcpyAsync(e->h_slabs, e->merge->d_out, sb, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(hipMemcpyAsync(e->h_slabs, e->merge->d_out, slab_bytes_of(e), hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
     gl.release();                                                        // waiting for the device is not an enqueue section
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    const uint64_t ts = now_ms();                                        // onnx_engine.cpp:813-815
-    const zly_slab_header* hd = reinterpret_cast<const zly_slab_header*>(e->h_slabs);
-    const zly_det* d = reinterpret_cast<const zly_det*>(hd + 1);
-    int m = std::min(std::min(hd->n_kept, e->cfg.max_dets), cap);
-    for (int k = 0; k < m; ++k) { out[k] = d[k]; out[k].timestamp = ts; }
-    *n_out = hd->n_kept;
+    *n_out = unpack_slab(e->h_slabs, cap, e->cfg.max_dets, now_ms(), out);          // the timestamp: onnx_engine.cpp:813-815
     harvest_timing(e);
     with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)n; });
     return ZLY_OK;
@@ -2992,24 +3097,6 @@ int32_t zly_surfaces_enable(zly_engine* e, int32_t max_surfaces, size_t max_byte
     return ZLY_OK;
 }
 
-// the engine's store (under e->mu), or null with the error set
-static Surfaces* surfaces_of(zly_engine* e)
-{
-    if (!e->surf) fail(ZLY_ERR_INVALID_ARGUMENT, "resident surfaces are not enabled on this engine (zly_surfaces_enable)");
-    return e->surf;
-}
-
-// The store has a reader now: a call that read its slots has been enqueued, and its last kernel went to `ran`.  The next update's patch kernel goes
-// behind it, whichever stream that is (Surfaces::ev_read).  Under e->mu; takes the enqueue gate itself.
-static int surfaces_note_reader(zly_engine* e, Surfaces* sf, hipStream_t ran)
-{
-    SharedGate gl;
-    if (sf->read_pending) HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(sf->ev_read, ran), ZLY_ERR_INFERENCE);
-    sf->read_pending = true;
-    return ZLY_OK;
-}
-
 int32_t zly_surface_define(zly_engine* e, int32_t s, int32_t fmt, int32_t w, int32_t h)
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
@@ -3029,23 +3116,15 @@ static int surface_enqueue_update(zly_engine* e, Surfaces* sf, int n_rects, cons
     const SurfacePlan& pl = sf->plan;
     if (pl.bands.size() > (size_t)std::numeric_limits<int>::max()) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_surface_update: too many bands");
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    if (pl.stage_bytes > e->stage_bytes) {                               // an allocation: alone in the process
-        ExclusiveGate x;
-        if (int rc = ensure_stage(e, pl.stage_bytes)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
+    if (int rc = stage_for(e, pl.stage_bytes)) return rc;
     for (int i = 0; i < n_rects; ++i) copy_view_tight(e->h_stage + pl.stage_off[(size_t)i], bases[i], &src_views[i]);
     memcpy(e->h_stage + pl.table_off, pl.bands.data(), pl.bands.size() * sizeof(SurfaceJob));
     SharedGate gl;
-    if (sf->read_pending) {                                              // detect calls on other streams may still read the slots this writes
-        HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
-        sf->read_pending = false;                                        // from here on the dependency is the engine stream's own order
-    }
+    if (int rc = surfaces_begin_write(e, sf)) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, pl.stage_bytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(launch_surface_patch(e->d_stage, reinterpret_cast<const SurfaceJob*>(e->d_stage + pl.table_off), (int)pl.bands.size(), sf->d_store, e->sw.num_cus, e->stream),
             ZLY_ERR_INFERENCE);
-    HIP_TRY(hipEventRecord(sf->ev_patch, e->stream), ZLY_ERR_INFERENCE);
-    sf->patched = true;
+    if (int rc = surfaces_end_write(e, sf)) return rc;
     for (int i = 0; i < n_rects; ++i) if (pl.covers[(size_t)i]) sf->slots[(size_t)rects[i].surface].valid = true;
     return ZLY_OK;
 }
@@ -3094,20 +3173,13 @@ int32_t zly_surface_move(zly_engine* e, int32_t n_moves, const struct zly_surfac
     if (pl.a_bands.size() > (size_t)std::numeric_limits<int>::max() || pl.b_bands.size() > (size_t)std::numeric_limits<int>::max())
         return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_surface_move: too many bands");
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    if (pl.table_bytes > e->stage_bytes) {                               // an allocation: alone in the process
-        ExclusiveGate x;
-        if (int rc = ensure_stage(e, pl.table_bytes)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);        // pinned staging is reused call to call
+    if (int rc = stage_for(e, pl.table_bytes)) return rc;
     static_assert(sizeof(SurfaceMoveBand) == 32 && sizeof(SurfaceJob) == 32, "the band records are 32 bytes");
     const size_t b_off = pl.a_bands.size() * sizeof(SurfaceMoveBand);
     memcpy(e->h_stage, pl.a_bands.data(), b_off);
     if (!pl.b_bands.empty()) memcpy(e->h_stage + b_off, pl.b_bands.data(), pl.b_bands.size() * sizeof(SurfaceJob));
     SharedGate gl;
-    if (sf->read_pending) {                                              // detect calls on other streams may still read the slots this writes
-        HIP_TRY(hipStreamWaitEvent(e->stream, sf->ev_read, 0), ZLY_ERR_INFERENCE);
-        sf->read_pending = false;
-    }
+    if (int rc = surfaces_begin_write(e, sf)) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_stage, e->h_stage, pl.table_bytes, hipMemcpyHostToDevice, e->stream), ZLY_ERR_INFERENCE);
     const SurfaceMoveBand* d_a = reinterpret_cast<const SurfaceMoveBand*>(e->d_stage);
     const SurfaceJob* d_b = reinterpret_cast<const SurfaceJob*>(e->d_stage + b_off);
@@ -3115,9 +3187,7 @@ int32_t zly_surface_move(zly_engine* e, int32_t n_moves, const struct zly_surfac
         HIP_TRY(launch_surface_move(d_a + ph.a_first, (int)ph.a_count, sf->d_store, sf->d_bounce, e->sw.num_cus, e->stream), ZLY_ERR_INFERENCE);
         HIP_TRY(launch_surface_patch(sf->d_bounce, d_b + ph.b_first, (int)ph.b_count, sf->d_store, e->sw.num_cus, e->stream), ZLY_ERR_INFERENCE);
     }
-    HIP_TRY(hipEventRecord(sf->ev_patch, e->stream), ZLY_ERR_INFERENCE);
-    sf->patched = true;
-    return ZLY_OK;
+    return surfaces_end_write(e, sf);
 }
 
 int32_t zly_surface_read(zly_engine* e, int32_t s, void* host_out, size_t cap_bytes)
@@ -3132,13 +3202,7 @@ int32_t zly_surface_read(zly_engine* e, int32_t s, void* host_out, size_t cap_by
     if (!sl.defined) return fail(ZLY_ERR_INVALID_ARGUMENT, "surface " + std::to_string(s) + " is not defined (zly_surface_define)");
     const size_t fb = frame_bytes(sl.fmt, sl.w, sl.h);
     if (cap_bytes < fb) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_surface_read: the surface holds " + std::to_string(fb) + " bytes, the buffer " + std::to_string(cap_bytes));
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    {
-        SharedGate gl;
-        HIP_TRY(hipMemcpyAsync(host_out, sf->d_store + (size_t)s * sf->store.stride, fb, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    return ZLY_OK;
+    return read_back(e, behind_nothing, {{host_out, sf->d_store + (size_t)s * sf->store.stride, fb}});      // the patch kernels ran on the engine's stream
 }
 
 int32_t zly_detect_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const zly_roi* rois, void* d_slabs, uint32_t frame_tag0, void* stream)
@@ -3147,12 +3211,10 @@ int32_t zly_detect_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, c
     if (!surfaces) return fail(ZLY_ERR_INVALID_ARGUMENT, "null surfaces");
     if (n < 1 || n > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "batch size out of range");
     std::lock_guard<std::mutex> lk(e->mu);
-    Surfaces* sf = surfaces_of(e);
-    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
-    std::vector<zly_frame_view> views((size_t)n);
-    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, rois, views.data(), &g_last_error)) return rc;
-    if (int rc = detect_device_view_locked(e, n, sf->d_store, sf->store.total, views.data(), d_slabs, frame_tag0, stream, sf->patched ? sf->ev_patch : nullptr)) return rc;
-    return surfaces_note_reader(e, sf, e->last_ns);
+    StoreFrames src;
+    if (int rc = src.open(e)) return rc;
+    if (int rc = src.frames(n, surfaces, rois)) return rc;
+    return src.read_by([&](const FrameSource& f, hipStream_t* ran) { return detect_device_view_locked(e, n, f, d_slabs, frame_tag0, stream, ran); });
 }
 
 int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect* rects, const uint8_t* const* bases, const size_t* buf_bytes,
@@ -3178,7 +3240,8 @@ int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect*
         if (int rc = check_view(e->cfg.flags, sf->d_store, sf->store.total, &views[(size_t)i], &g_last_error)) return rc;
     if (n_rects > 0)
         if (int rc = surface_enqueue_update(e, sf, n_rects, rects, bases, src_views)) return rc;
-    if (int rc = detect_device_view_locked(e, n, sf->d_store, sf->store.total, views.data(), nullptr, 0, nullptr)) return rc;
+    // Not StoreFrames: the views are made against `after`, and the call is on the engine's own stream and waited for below, so the store is told of no reader
+    if (int rc = detect_device_view_locked(e, n, FrameSource{sf->d_store, sf->store.total, views.data()}, nullptr, 0, nullptr)) return rc;
     const size_t sb = slab_bytes_of(e);
     {
         SharedGate gl;
@@ -3187,13 +3250,7 @@ int32_t zly_detect_delta(zly_engine* e, int32_t n_rects, const zly_surface_rect*
     }
     HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
     const uint64_t ts = now_ms();                                        // onnx_engine.cpp:813-815
-    for (int i = 0; i < n; ++i) {
-        const zly_slab_header* hd = reinterpret_cast<const zly_slab_header*>(e->h_slabs + sb * (size_t)i);
-        const zly_det* d = reinterpret_cast<const zly_det*>(hd + 1);
-        const int m = std::min(std::min(hd->n_kept, e->cfg.max_dets), cap);
-        for (int k = 0; k < m; ++k) { out[(size_t)i * cap + k] = d[k]; out[(size_t)i * cap + k].timestamp = ts; }
-        n_out[i] = hd->n_kept;
-    }
+    for (int i = 0; i < n; ++i) n_out[i] = unpack_slab(e->h_slabs + sb * (size_t)i, cap, e->cfg.max_dets, ts, out + (size_t)i * cap);
     harvest_timing(e);
     return ZLY_OK;
 }
@@ -3240,19 +3297,12 @@ int32_t zly_change_enable(zly_engine* e, const zly_change_config* c, int32_t max
     return ZLY_OK;
 }
 
-// the engine's change map (under e->mu), or null with the error set
-static Change* change_of(zly_engine* e)
-{
-    if (!e->change) fail(ZLY_ERR_INVALID_ARGUMENT, "the change map is not enabled on this engine (zly_change_enable)");
-    return e->change;
-}
-
 int32_t zly_change_layout(const zly_engine* e, size_t* rec_bytes, size_t* peaks_off, size_t* activity_off)
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     std::lock_guard<std::mutex> lk(const_cast<zly_engine*>(e)->mu);
-    const Change* ch = e->change;
-    if (!ch) return fail(ZLY_ERR_INVALID_ARGUMENT, "the change map is not enabled on this engine (zly_change_enable)");
+    const Change* ch = enabled(e->change, NO_CHANGE);
+    if (!ch) return ZLY_ERR_INVALID_ARGUMENT;
     if (rec_bytes) *rec_bytes = (size_t)ch->lay.rec_bytes;
     if (peaks_off) *peaks_off = (size_t)ch->lay.peaks_off;
     if (activity_off) *activity_off = (size_t)ch->lay.activity_off;
@@ -3299,25 +3349,24 @@ static int change_enqueue_pick(zly_engine* e, Change* ch, int n, int r, const Zo
     return ZLY_OK;
 }
 
-// The body of zly_change_device_view and zly_change_surfaces.  Under e->mu, e->change set; takes the enqueue gate itself.  Every check comes first: a
-// refused call enqueues nothing.  wait_for: an event the chosen stream has to wait for first when it is not the engine's own (null = none)
-static int change_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, const int32_t* streams, void* stream,
-                         hipEvent_t wait_for, hipStream_t* ran_on)
+// The body of zly_change_device_view and zly_change_surfaces: the n views of the source.  Under e->mu, e->change set; takes the enqueue gate itself.
+// Every check comes first: a refused call enqueues nothing.  *ran_on (if asked for): the stream the kernels went to.
+static int change_locked(zly_engine* e, int32_t n, const FrameSource& f, const int32_t* streams, void* stream, hipStream_t* ran_on = nullptr)
 {
     Change* ch = e->change;
     if (int rc = change_check_streams(n, streams, ch->max_streams, &g_last_error)) return rc;
     for (int i = 0; i < n; ++i) {
-        if (int rc = chip_check_view(e->cfg.flags, d_base, buf_bytes, &v[i], &g_last_error)) return rc;
-        if (int rc = change_check_size(v[i].w, v[i].h, ch->cfg.cell, &g_last_error)) return rc;
+        if (int rc = chip_check_view(e->cfg.flags, f.base, f.bytes, &f.v[i], &g_last_error)) return rc;
+        if (int rc = change_check_size(f.v[i].w, f.v[i].h, ch->cfg.cell, &g_last_error)) return rc;
     }
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s, f.wait_for)) return rc;
     int r = 0;
-    if (int rc = change_enqueue_sums(e, ch, n, d_base, v, streams, s, &r)) return rc;
+    if (int rc = change_enqueue_sums(e, ch, n, f.base, f.v, streams, s, &r)) return rc;
     if (int rc = change_enqueue_pick(e, ch, n, r, nullptr, nullptr, nullptr, nullptr, 0, s)) return rc;
-    *ran_on = s;
+    if (ran_on) *ran_on = s;
     return ZLY_OK;
 }
 
@@ -3327,8 +3376,7 @@ int32_t zly_change_device_view(zly_engine* e, int32_t n, const void* d_base, siz
     if (int rc = change_check_call(n, e->cfg.max_batch, views, streams, &g_last_error)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
     if (!change_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
-    hipStream_t ran = nullptr;
-    return change_locked(e, n, d_base, buf_bytes, views, streams, stream, nullptr, &ran);
+    return change_locked(e, n, FrameSource{d_base, buf_bytes, views}, streams, stream);
 }
 
 int32_t zly_change_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, void* stream)
@@ -3337,13 +3385,10 @@ int32_t zly_change_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, c
     if (int rc = change_check_call(n, e->cfg.max_batch, surfaces, streams, &g_last_error)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
     if (!change_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
-    Surfaces* sf = surfaces_of(e);
-    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
-    std::vector<zly_frame_view> views((size_t)n);
-    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
-    hipStream_t ran = nullptr;
-    if (int rc = change_locked(e, n, sf->d_store, sf->store.total, views.data(), streams, stream, sf->patched ? sf->ev_patch : nullptr, &ran)) return rc;
-    return surfaces_note_reader(e, sf, ran);
+    StoreFrames src;
+    if (int rc = src.open(e)) return rc;
+    if (int rc = src.frames(n, surfaces)) return rc;
+    return src.read_by([&](const FrameSource& f, hipStream_t* ran) { return change_locked(e, n, f, streams, stream, ran); });
 }
 
 int32_t zly_change_read(zly_engine* e, int32_t stream, void* host_out, size_t cap_bytes)
@@ -3355,15 +3400,7 @@ int32_t zly_change_read(zly_engine* e, int32_t stream, void* host_out, size_t ca
     if (!ch) return ZLY_ERR_INVALID_ARGUMENT;
     if (stream < 0 || stream >= ch->max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
     if (cap_bytes < (size_t)ch->lay.activity_off) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_change_read: the header and the peaks are " + std::to_string(ch->lay.activity_off) + " bytes");
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    {
-        SharedGate gl;
-        HIP_TRY(ch->ring.wait_last(e->stream), ZLY_ERR_INFERENCE);
-        HIP_TRY(hipMemcpyAsync(host_out, ch->d_recs + (size_t)stream * (size_t)ch->lay.rec_bytes, std::min(cap_bytes, (size_t)ch->lay.rec_bytes), hipMemcpyDeviceToHost,
-                               e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    return ZLY_OK;
+    return read_back(e, behind_ring(ch->ring), {{host_out, ch->d_recs + (size_t)stream * (size_t)ch->lay.rec_bytes, std::min(cap_bytes, (size_t)ch->lay.rec_bytes)}});
 }
 
 int32_t zly_change_reset(zly_engine* e, int32_t stream)
@@ -3422,13 +3459,6 @@ int32_t zly_zoom_enable(zly_engine* e, const zly_zoom_config* c)
     return ZLY_OK;
 }
 
-// the engine's zoom state (under e->mu), or null with the error set
-static Zoom* zoom_of(zly_engine* e)
-{
-    if (!e->zoom) fail(ZLY_ERR_INVALID_ARGUMENT, "zoom regions are not enabled on this engine (zly_track_enable, then zly_zoom_enable)");
-    return e->zoom;
-}
-
 // Uploads the n frame records of a plan in the next ring entry and launches zoom_plan_kernel on `s`, behind the tracking enqueued so far on whichever
 // stream that ran.  desc / tab: what the kernel patches (null: the plan alone).  Under e->mu, enqueue gate held.
 static int zoom_enqueue_plan(zly_engine* e, Zoom* zm, Track* tk, int n, const ZoomFrame* zf, FrameDesc* desc, int* tab, zly_zoom_region* d_plan, hipStream_t s, int* ring)
@@ -3445,11 +3475,12 @@ static int zoom_enqueue_plan(zly_engine* e, Zoom* zm, Track* tk, int n, const Zo
     return ZLY_OK;
 }
 
-// The body of zly_detect_device_zoom and zly_detect_surfaces_zoom: n surfaces that are views of the device buffer d_base.  Under e->mu, e->zoom set; takes
-// the enqueue gate itself.  Every check comes first: a refused call enqueues nothing.  wait_for: as detect_device_view_locked's.
-static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* sv, const int32_t* streams,
-                              const zly_merge_config* mc, void* d_out, uint32_t frame_tag0, void* stream, hipEvent_t wait_for = nullptr)
+// The body of zly_detect_device_zoom and zly_detect_surfaces_zoom: n surfaces that are the views of the source.  Under e->mu, e->zoom set; takes the
+// enqueue gate itself.  Every check comes first: a refused call enqueues nothing.  *ran_on (if asked for): the stream the call's last kernel went to.
+static int detect_zoom_locked(zly_engine* e, int32_t n, const FrameSource& f, const int32_t* streams, const zly_merge_config* mc, void* d_out, uint32_t frame_tag0,
+                              void* stream, hipStream_t* ran_on = nullptr)
 {
+    const zly_frame_view* sv = f.v;
     Zoom* zm = e->zoom;
     Track* tk = e->track.load();
     const int K = zm->cfg.regions, V = 1 + K, nb = n * V;
@@ -3462,21 +3493,22 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
     Change* ch = e->change && e->change->zoom_on ? e->change : nullptr;      // zly_zoom_use_change: the fallback regions follow the change map
     if (ch)
         if (int rc = change_check_streams(n, streams, ch->max_streams, &g_last_error)) return rc;
-    std::vector<zly_frame_view> views((size_t)nb);
+    FrameTable t(nb, true);                                                          // the n x (1 + K) views of the batch: frame i's surface, then its regions
     std::vector<zly_tile> tiles((size_t)nb);
     std::vector<ZoomFrame> zf((size_t)n);
     for (int i = 0; i < n; ++i) {
         if (int rc = zoom_check_surface(&sv[i], &g_last_error)) return rc;
-        if (int rc = check_view(e->cfg.flags, d_base, buf_bytes, &sv[i], &g_last_error)) return rc;
+        if (int rc = check_view(e->cfg.flags, f.base, f.bytes, &sv[i], &g_last_error)) return rc;
         const int32_t W = sv[i].w, H = sv[i].h;
         const ZoomSize z = zoom_size(zm->cfg.region_w, zm->cfg.region_h, W, H);
         const int32_t fx = zoom_fallback_origin(W, z.rw), fy = zoom_fallback_origin(H, z.rh);
-        views[(size_t)i * V] = sv[i];
+        t.add(sv[i]);
         tiles[(size_t)i * V] = zly_tile{i, 0, 0, W, H, W, H};
         for (int j = 1; j <= K; ++j) {                                              // every region at its fallback origin: the kernel patches what depends on the origin
-            zly_frame_view& rv = views[(size_t)i * V + j];
+            zly_frame_view rv;
             if (int rc = view_crop(&sv[i], fx, fy, z.rw, z.rh, &rv, &g_last_error)) return rc;
-            if (int rc = check_view(e->cfg.flags, d_base, buf_bytes, &rv, &g_last_error)) return rc;
+            if (int rc = check_view(e->cfg.flags, f.base, f.bytes, &rv, &g_last_error)) return rc;
+            t.add(rv);
             tiles[(size_t)i * V + j] = zly_tile{i, fx, fy, z.rw, z.rh, W, H};
         }
         zf[(size_t)i] = zoom_frame_of(&sv[i], streams[i]);
@@ -3485,40 +3517,27 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
     }
     int max_slots = 0;
     if (int rc = merge_check(e, nb, tiles.data(), n, mc, &max_slots)) return rc;
-    std::vector<int32_t> ws((size_t)nb), hs((size_t)nb), fs((size_t)nb);
-    std::vector<size_t> offs((size_t)nb);
-    std::vector<ViewRec> recs((size_t)nb);
-    int level = ZLY_FRONT_BGR;
-    for (int b = 0; b < nb; ++b) {
-        const zly_frame_view& v = views[(size_t)b];
-        ws[(size_t)b] = v.w; hs[(size_t)b] = v.h; fs[(size_t)b] = v.fmt; offs[(size_t)b] = (size_t)v.off[0];
-        recs[(size_t)b] = view_rec(&v);
-        level = std::max(level, front_level(v.fmt));
-    }
     if (int rc = merge_ensure(e)) return rc;
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s, f.wait_for)) return rc;
     // the three tables the plan kernel patches go up first, on the call's stream; what set_desc remembers of d_desc is void from here on: a kernel writes it
-    int rc = set_desc(e, nb, ws.data(), hs.data(), offs.data(), s, fs.data(), recs.data());
+    int rc = set_desc(e, t, s);
     e->desc_cache.clear(); e->view_cache.clear(); e->last_desc_n = 0;
     if (rc != ZLY_OK) return rc;
     int mr = 0, zr = 0;
     if ((rc = merge_upload(e, nb, tiles.data(), n, s, &mr)) != ZLY_OK) return rc;
     int cr = 0;
-    if (ch && (rc = change_enqueue_sums(e, ch, n, d_base, sv, streams, s, &cr)) != ZLY_OK) return rc;
+    if (ch && (rc = change_enqueue_sums(e, ch, n, f.base, sv, streams, s, &cr)) != ZLY_OK) return rc;
     int* d_tab = e->merge->ring.dev<int>(mr);
     if ((rc = zoom_enqueue_plan(e, zm, tk, n, zf.data(), e->d_desc, d_tab, zm->d_plan, s, &zr)) != ZLY_OK) return rc;
     if (ch && (rc = change_enqueue_pick(e, ch, n, cr, zm->ring.dev<ZoomFrame>(zr), e->d_desc, d_tab, zm->d_plan, zm->cfg.regions, s)) != ZLY_OK) return rc;
     if (ch) HIP_TRY(zm->ring.mark(zr, s), ZLY_ERR_INFERENCE);      // zly_zoom_read_plan reads the plan as the pick kernel left it
     zm->last_frames = zr; zm->last_n = n;
-    hipStream_t ns = s;
-    rc = run_path(e, nb, (const uint8_t*)d_base, nullptr, 0, s, true, (e->cfg.flags & ZLY_FLAG_ASYNC_NMS) != 0, &ns, front_of(e, level, true));
-    if (rc != ZLY_OK) { with_stats(e, [](zly_stats& st) { st.inference_errors++; }); return rc; }
-    e->call_seq++;
-    e->last_ns = ns; e->last_deferred = ns != s;
-    with_stats(e, [&](zly_stats& st) { st.inference_count += (uint64_t)nb; });
+    // the nb views counted; no completion event yet: the call's events go behind its tracking, below
+    if ((rc = detect_run(e, t, f.base, nullptr, 0, s, false)) != ZLY_OK) return rc;
+    const hipStream_t ns = e->last_ns;
     // merge, then track, on the stream the NMS ran on -- where zly_merge_slabs and zly_track_slabs would put them
     void* dst = d_out ? d_out : (void*)e->merge->d_out;
     if ((rc = merge_launch(e, mr, n, mc, max_slots, e->d_slabs, dst, frame_tag0, ns)) != ZLY_OK) return rc;
@@ -3527,6 +3546,7 @@ static int detect_zoom_locked(zly_engine* e, int32_t n, const void* d_base, size
     // the call's completion events lie behind its tracking: zly_join, zly_read_slabs, zly_read_merged and a later call's NMS wait for all of it
     if ((rc = detect_events_behind(e, ns)) != ZLY_OK) return rc;
     HIP_TRY(e->merge->ring.mark(mr, ns), ZLY_ERR_INFERENCE);
+    if (ran_on) *ran_on = ns;
     return ZLY_OK;
 }
 
@@ -3549,7 +3569,7 @@ int32_t zly_detect_device_zoom(zly_engine* e, int32_t n, const void* d_base, siz
     Zoom* zm = zoom_of(e);
     if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
     if ((int64_t)n * (1 + zm->cfg.regions) > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "n x (1 + regions) exceeds max_batch");
-    return detect_zoom_locked(e, n, d_base, buf_bytes, surface_views, streams, merge_cfg, d_out, frame_tag0, stream);
+    return detect_zoom_locked(e, n, FrameSource{d_base, buf_bytes, surface_views}, streams, merge_cfg, d_out, frame_tag0, stream);
 }
 
 int32_t zly_detect_surfaces_zoom(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, const zly_merge_config* merge_cfg, void* d_out,
@@ -3558,15 +3578,13 @@ int32_t zly_detect_surfaces_zoom(zly_engine* e, int32_t n, const int32_t* surfac
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
     if (int rc = zoom_check_call(e, n, surfaces, streams, merge_cfg)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
-    Surfaces* sf = surfaces_of(e);
-    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
+    StoreFrames src;
+    if (int rc = src.open(e)) return rc;                                // the store before the feature: the other store entries ask the other way round
     Zoom* zm = zoom_of(e);
     if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
     if ((int64_t)n * (1 + zm->cfg.regions) > e->cfg.max_batch) return fail(ZLY_ERR_INVALID_ARGUMENT, "n x (1 + regions) exceeds max_batch");
-    std::vector<zly_frame_view> views((size_t)n);
-    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
-    if (int rc = detect_zoom_locked(e, n, sf->d_store, sf->store.total, views.data(), streams, merge_cfg, d_out, frame_tag0, stream, sf->patched ? sf->ev_patch : nullptr)) return rc;
-    return surfaces_note_reader(e, sf, e->last_ns);
+    if (int rc = src.frames(n, surfaces)) return rc;
+    return src.read_by([&](const FrameSource& f, hipStream_t* ran) { return detect_zoom_locked(e, n, f, streams, merge_cfg, d_out, frame_tag0, stream, ran); });
 }
 
 int32_t zly_zoom_plan(zly_engine* e, int32_t n, const int32_t* W, const int32_t* H, const int32_t* streams, zly_zoom_region* out)
@@ -3586,16 +3604,11 @@ int32_t zly_zoom_plan(zly_engine* e, int32_t n, const int32_t* W, const int32_t*
         z.W = W[i]; z.H = H[i]; z.stream = streams[i]; z.planes = 1;
         zf[(size_t)i] = z;
     }
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
     zly_zoom_region* d_plan = zm->d_plan + (size_t)e->cfg.max_batch;               // its own records: zly_zoom_read_plan keeps the last frame call's
-    {
-        SharedGate gl;
-        int zr = 0;
-        if (int rc = zoom_enqueue_plan(e, zm, tk, n, zf.data(), nullptr, nullptr, d_plan, e->stream, &zr)) return rc;
-        HIP_TRY(hipMemcpyAsync(out, d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    return ZLY_OK;
+    int zr = 0;
+    // `behind` is the plan kernel itself here, no wait: the copy goes behind it in the engine stream's own order
+    return read_back(e, [&](hipStream_t s) { return zoom_enqueue_plan(e, zm, tk, n, zf.data(), nullptr, nullptr, d_plan, s, &zr); },
+                     {{out, d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions}});
 }
 
 int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out)
@@ -3606,14 +3619,11 @@ int32_t zly_zoom_read_plan(zly_engine* e, int32_t n, zly_zoom_region* out)
     Zoom* zm = zoom_of(e);
     if (!zm) return ZLY_ERR_INVALID_ARGUMENT;
     if (zm->last_frames < 0 || n != zm->last_n) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_zoom_read_plan: n must be the frames of the most recent zoom call");
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    {
-        SharedGate gl;
-        HIP_TRY(hipStreamWaitEvent(e->stream, zm->ring.ev[zm->last_frames], 0), ZLY_ERR_INFERENCE);      // not wait_last: zly_zoom_plan marks entries too
-        HIP_TRY(hipMemcpyAsync(out, zm->d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    return ZLY_OK;
+    auto behind = [&](hipStream_t s) -> int {                            // the frame call's own entry, not wait_last: zly_zoom_plan marks entries too
+        HIP_TRY(hipStreamWaitEvent(s, zm->ring.ev[zm->last_frames], 0), ZLY_ERR_INFERENCE);
+        return ZLY_OK;
+    };
+    return read_back(e, behind, {{out, zm->d_plan, sizeof(zly_zoom_region) * (size_t)n * (size_t)zm->cfg.regions}});
 }
 
 int32_t zly_zoom_use_change(zly_engine* e, int32_t on)
@@ -3662,44 +3672,37 @@ int32_t zly_chips_enable(zly_engine* e, const zly_chip_config* c)
     return ZLY_OK;
 }
 
-// the engine's chip state (under e->mu), or null with the error set
-static Chips* chips_of(zly_engine* e)
-{
-    if (!e->chips) fail(ZLY_ERR_INVALID_ARGUMENT, "chips are not enabled on this engine (zly_chips_enable)");
-    return e->chips;
-}
-
 int32_t zly_chip_layout(const zly_engine* e, size_t* slab_bytes, size_t* pixels_off, size_t* chip_stride)
 {
     if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
-    const Chips* cp = e->chips;
-    if (!cp) return fail(ZLY_ERR_INVALID_ARGUMENT, "chips are not enabled on this engine (zly_chips_enable)");
+    const Chips* cp = enabled(e->chips, NO_CHIPS);
+    if (!cp) return ZLY_ERR_INVALID_ARGUMENT;
     if (slab_bytes) *slab_bytes = (size_t)cp->lay.slab_bytes;
     if (pixels_off) *pixels_off = (size_t)cp->lay.pixels_off;
     if (chip_stride) *chip_stride = (size_t)cp->lay.chip_stride;
     return ZLY_OK;
 }
 
-// The body of zly_chips_device_view and zly_chips_surfaces: n checked views of the device buffer d_base.  Under e->mu, e->chips set; takes the enqueue
-// gate itself.  wait_for: an event the chosen stream has to wait for first when it is not the engine's own (null = none).  *ran_on: the stream the
-// kernels went to.
-static int chips_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* v, const void* d_slabs, int32_t source, void* d_chips,
-                        void* stream, hipEvent_t wait_for, hipStream_t* ran_on)
+// The body of zly_chips_device_view and zly_chips_surfaces: the n views of the source.  Under e->mu, e->chips set; takes the enqueue gate itself.
+// *ran_on (if asked for): the stream the kernels went to.
+static int chips_locked(zly_engine* e, int32_t n, const FrameSource& f, const void* d_slabs, int32_t source, void* d_chips, void* stream, hipStream_t* ran_on = nullptr)
 {
     Chips* cp = e->chips;
-    if (!d_slabs && source == ZLY_CHIPS_SRC_MERGED && !e->merge) return fail(ZLY_ERR_INVALID_ARGUMENT, "ZLY_CHIPS_SRC_MERGED: this engine has not merged yet (zly_merge_slabs)");
+    if (!d_slabs && source == ZLY_CHIPS_SRC_MERGED && !e->merge) return fail(ZLY_ERR_INVALID_ARGUMENT, std::string("ZLY_CHIPS_SRC_MERGED: ") + NO_MERGE);
     std::vector<ChipFrame> cf((size_t)n);
     for (int i = 0; i < n; ++i) {
-        if (int rc = chip_check_view(e->cfg.flags, d_base, buf_bytes, &v[i], &g_last_error)) return rc;
-        cf[(size_t)i] = chip_frame_of(&v[i]);
+        if (int rc = chip_check_view(e->cfg.flags, f.base, f.bytes, &f.v[i], &g_last_error)) return rc;
+        cf[(size_t)i] = chip_frame_of(&f.v[i]);
     }
     const void* slabs = d_slabs ? d_slabs : source == ZLY_CHIPS_SRC_MERGED ? (const void*)e->merge->d_out : (const void*)e->d_slabs;
     SharedGate gl;
     HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    // behind the NMS, merge and tracking of the most recent zly_detect_device* call, on whichever stream they ran
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    // behind the NMS, merge and tracking of the most recent zly_detect_device* call, on whichever stream they ran: the stream chosen there is the one
+    // that waits for the source
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s)) return rc;
     if (int rc = stream_after_detect(e, s)) return rc;
-    if (wait_for && s != e->stream) HIP_TRY(hipStreamWaitEvent(s, wait_for, 0), ZLY_ERR_INFERENCE);
+    if (int rc = wait_if_foreign(e, s, f.wait_for)) return rc;
     // merges of an engine made before any detect call (slabs made elsewhere) are ordered by their own ring event
     if (!d_slabs && source == ZLY_CHIPS_SRC_MERGED) HIP_TRY(e->merge->ring.wait_last(s), ZLY_ERR_INFERENCE);
     int r = 0;
@@ -3708,11 +3711,11 @@ static int chips_locked(zly_engine* e, int32_t n, const void* d_base, size_t buf
     HIP_TRY(cp->ring.wait_last(s), ZLY_ERR_INFERENCE);
     memcpy(cp->ring.host<ChipFrame>(r), cf.data(), sizeof(ChipFrame) * (size_t)n);
     HIP_TRY(cp->ring.upload(r, sizeof(ChipFrame) * (size_t)n, s), ZLY_ERR_INFERENCE);
-    HIP_TRY(launch_chips((const uint8_t*)d_base, cp->ring.dev<ChipFrame>(r), n, slabs, slab_bytes_of(e), e->cfg.max_dets, d_chips ? d_chips : (void*)cp->d_out, cp->cfg, s),
+    HIP_TRY(launch_chips((const uint8_t*)f.base, cp->ring.dev<ChipFrame>(r), n, slabs, slab_bytes_of(e), e->cfg.max_dets, d_chips ? d_chips : (void*)cp->d_out, cp->cfg, s),
             ZLY_ERR_INFERENCE);
     HIP_TRY(cp->ring.mark(r, s), ZLY_ERR_INFERENCE);
     if (int rc = detect_events_behind(e, s)) return rc;
-    *ran_on = s;
+    if (ran_on) *ran_on = s;
     return ZLY_OK;
 }
 
@@ -3723,8 +3726,7 @@ int32_t zly_chips_device_view(zly_engine* e, int32_t n, const void* d_base, size
     if (int rc = chip_check_call(n, e->cfg.max_batch, views, d_slabs, source, &g_last_error)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
     if (!chips_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
-    hipStream_t ran = nullptr;
-    return chips_locked(e, n, d_base, buf_bytes, views, d_slabs, source, d_chips, stream, nullptr, &ran);
+    return chips_locked(e, n, FrameSource{d_base, buf_bytes, views}, d_slabs, source, d_chips, stream);
 }
 
 int32_t zly_chips_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const void* d_slabs, int32_t source, void* d_chips, void* stream)
@@ -3733,13 +3735,10 @@ int32_t zly_chips_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, co
     if (int rc = chip_check_call(n, e->cfg.max_batch, surfaces, d_slabs, source, &g_last_error)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
     if (!chips_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
-    Surfaces* sf = surfaces_of(e);
-    if (!sf) return ZLY_ERR_INVALID_ARGUMENT;
-    std::vector<zly_frame_view> views((size_t)n);
-    if (int rc = surface_detect_views(sf->store, sf->slots.data(), n, surfaces, nullptr, views.data(), &g_last_error)) return rc;
-    hipStream_t ran = nullptr;
-    if (int rc = chips_locked(e, n, sf->d_store, sf->store.total, views.data(), d_slabs, source, d_chips, stream, sf->patched ? sf->ev_patch : nullptr, &ran)) return rc;
-    return surfaces_note_reader(e, sf, ran);
+    StoreFrames src;
+    if (int rc = src.open(e)) return rc;
+    if (int rc = src.frames(n, surfaces)) return rc;
+    return src.read_by([&](const FrameSource& f, hipStream_t* ran) { return chips_locked(e, n, f, d_slabs, source, d_chips, stream, ran); });
 }
 
 int32_t zly_read_chips(zly_engine* e, int32_t n, void* host_out)
@@ -3749,14 +3748,7 @@ int32_t zly_read_chips(zly_engine* e, int32_t n, void* host_out)
     std::lock_guard<std::mutex> lk(e->mu);
     Chips* cp = chips_of(e);
     if (!cp) return ZLY_ERR_INVALID_ARGUMENT;
-    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
-    {
-        SharedGate gl;
-        HIP_TRY(cp->ring.wait_last(e->stream), ZLY_ERR_INFERENCE);
-        HIP_TRY(hipMemcpyAsync(host_out, cp->d_out, (size_t)cp->lay.slab_bytes * (size_t)n, hipMemcpyDeviceToHost, e->stream), ZLY_ERR_INFERENCE);
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), ZLY_ERR_INFERENCE);
-    return ZLY_OK;
+    return read_back(e, behind_ring(cp->ring), {{host_out, cp->d_out, (size_t)cp->lay.slab_bytes * (size_t)n}});
 }
 
 int32_t zly_preprocess(zly_engine* e, const uint8_t* bgr, size_t nbytes, int32_t w, int32_t h, float* out_nchw)
