@@ -12,16 +12,16 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wal
 CXX      ?= g++
 PY       ?= python3
 
-KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_pix.hip $(CSRC)/kernels_pix_view.hip $(CSRC)/kernels_y422.hip $(CSRC)/kernels_y422_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip $(CSRC)/kernels_track.hip $(CSRC)/kernels_merge.hip $(CSRC)/kernels_area.hip $(CSRC)/kernels_surface.hip $(CSRC)/kernels_zoom.hip $(CSRC)/kernels_chips.hip $(CSRC)/kernels_change.hip
+KERNELS  := $(CSRC)/kernels_conv.hip $(CSRC)/kernels_pair.hip $(CSRC)/kernels_misc.hip $(CSRC)/kernels_head.hip $(CSRC)/kernels_stem.hip $(CSRC)/kernels_stem_yuv.hip $(CSRC)/kernels_lb.hip $(CSRC)/kernels_view.hip $(CSRC)/kernels_pix.hip $(CSRC)/kernels_pix_view.hip $(CSRC)/kernels_y422.hip $(CSRC)/kernels_y422_view.hip $(CSRC)/kernels_post.hip $(CSRC)/kernels_c2f64.hip $(CSRC)/kernels_sppf.hip $(CSRC)/kernels_track.hip $(CSRC)/kernels_merge.hip $(CSRC)/kernels_area.hip $(CSRC)/kernels_surface.hip $(CSRC)/kernels_zoom.hip $(CSRC)/kernels_chips.hip $(CSRC)/kernels_change.hip $(CSRC)/kernels_camera.hip
 ENGINE   := $(CSRC)/engine.cpp $(CSRC)/weights.cpp
-OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/kernels_merge.o $(OUT)/kernels_area.o $(OUT)/kernels_surface.o $(OUT)/kernels_zoom.o $(OUT)/kernels_chips.o $(OUT)/kernels_change.o $(OUT)/engine.o $(OUT)/weights.o
+OBJS     := $(OUT)/kernels_conv.o $(OUT)/kernels_pair.o $(OUT)/kernels_misc.o $(OUT)/kernels_head.o $(OUT)/kernels_stem.o $(OUT)/kernels_stem_yuv.o $(OUT)/kernels_lb.o $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kernels_y422.o $(OUT)/kernels_y422_view.o $(OUT)/kernels_post.o $(OUT)/kernels_c2f64.o $(OUT)/kernels_sppf.o $(OUT)/kernels_track.o $(OUT)/kernels_merge.o $(OUT)/kernels_area.o $(OUT)/kernels_surface.o $(OUT)/kernels_zoom.o $(OUT)/kernels_chips.o $(OUT)/kernels_change.o $(OUT)/kernels_camera.o $(OUT)/engine.o $(OUT)/weights.o
 
 all: $(OUT)/libzly.so $(OUT)/libzly_gather.so $(OUT)/test_gather $(OUT)/zly_sharded_bench $(OUT)/libnms_probe.so $(OUT)/libsppf_probe.so $(OUT)/libtrack_probe.so oracle weights host
 
 $(OUT):
 	mkdir -p $(OUT)
 
-KHDRS    := $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h $(CSRC)/letterbox_device.h $(CSRC)/planes_device.h $(CSRC)/area_device.h $(CSRC)/surface_device.h $(CSRC)/chip_device.h $(CSRC)/change_device.h $(CSRC)/head_skip.h include/zly.h
+KHDRS    := $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/conv_device.h $(CSRC)/yuv_device.h $(CSRC)/letterbox_device.h $(CSRC)/planes_device.h $(CSRC)/area_device.h $(CSRC)/surface_device.h $(CSRC)/chip_device.h $(CSRC)/change_device.h $(CSRC)/camera_device.h $(CSRC)/head_skip.h include/zly.h
 $(OUT)/%.o: $(CSRC)/%.hip $(KHDRS) | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -33,8 +33,10 @@ $(OUT)/kernels_view.o $(OUT)/kernels_pix.o $(OUT)/kernels_pix_view.o $(OUT)/kern
 $(OUT)/kernels_zoom.o: $(CSRC)/zoom_device.h
 # ... and the change map's kernels the arithmetic of the zoom regions' size and plane offsets
 $(OUT)/kernels_change.o: $(CSRC)/zoom_device.h
+# ... and the camera motion's kernels the change map's arithmetic, which includes it
+$(OUT)/kernels_camera.o: $(CSRC)/zoom_device.h
 
-ENGINE_DEPS := $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/chip_rules.h $(CSRC)/chip_device.h $(CSRC)/change_rules.h $(CSRC)/change_device.h $(CSRC)/upload_ring.h $(CSRC)/weights.h include/zly.h
+ENGINE_DEPS := $(CSRC)/engine.cpp $(CSRC)/zly_internal.h $(CSRC)/front_variants.h $(CSRC)/frame_rules.h $(CSRC)/surface_rules.h $(CSRC)/surface_device.h $(CSRC)/zoom_rules.h $(CSRC)/zoom_device.h $(CSRC)/chip_rules.h $(CSRC)/chip_device.h $(CSRC)/change_rules.h $(CSRC)/change_device.h $(CSRC)/camera_rules.h $(CSRC)/camera_device.h $(CSRC)/upload_ring.h $(CSRC)/weights.h include/zly.h
 $(OUT)/engine.o: $(ENGINE_DEPS) | $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -95,7 +97,7 @@ $(OUT)/test_sharded_stub: tests/cpp/test_sharded_stub.cpp $(HOST)/zly_sharded.hp
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -I$(HOST) -o $@ tests/cpp/test_sharded_stub.cpp
 
 # ---- host side: the reference's IInferenceEngine plugin interface over the C ABI -----------------
-host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_frame_rules $(OUT)/test_surface_rules $(OUT)/test_surface_moves $(OUT)/test_zoom_plan $(OUT)/test_chip_rules $(OUT)/test_change_rules $(OUT)/test_sharded_stub
+host: $(OUT)/libzly_plugin.so $(OUT)/test_hip_engine $(OUT)/test_hip_engine_yuv $(OUT)/test_hip_engine_pix $(OUT)/test_wire $(OUT)/test_game_step $(OUT)/test_head_skip $(OUT)/test_frame_server $(OUT)/zly_h2h_bench $(OUT)/test_plugin_stub $(OUT)/test_plugin_crop_stub $(OUT)/test_plugin_yuv422_stub $(OUT)/test_plugin_track_stub $(OUT)/test_plugin_track_stub_nosym $(OUT)/test_plugin_track_motion_stub $(OUT)/test_plugin_track_motion_stub_nosym $(OUT)/test_plugin_area_stub $(OUT)/test_area_footprint $(OUT)/test_frame_rules $(OUT)/test_surface_rules $(OUT)/test_surface_moves $(OUT)/test_zoom_plan $(OUT)/test_chip_rules $(OUT)/test_change_rules $(OUT)/test_camera_rules $(OUT)/test_sharded_stub
 
 $(OUT)/libzly_plugin.so: $(HOST)/hip_inference_engine.cpp $(HOST)/hip_inference_engine.h $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp include/zly.h $(OUT)/libzly.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Iinclude -I$(HOST) -o $@ $(HOST)/hip_inference_engine.cpp -L$(OUT) -lzly -pthread -Wl,-rpath,'$$ORIGIN'
@@ -211,6 +213,18 @@ change_rules_san: $(OUT)/test_change_rules_san
 $(OUT)/test_change_rules_san: $(CHANGE_RULES) | $(OUT)
 	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(CSRC) -o $@ tests/cpp/test_change_rules.cpp
 
+# the camera motion's rules (csrc/camera_device.h, csrc/camera_rules.h) on their own, for tests/test_camera_rules.py: the program reads (view, config)
+# scripts, computes the sums through the change map's host twin and prints the records of the host twin of the search, pick and apply kernels
+# (test infrastructure: no GPU, nothing of the engine).  Contraction off, as in the kernels' unit ...
+CAMERA_RULES := tests/cpp/test_camera_rules.cpp $(CSRC)/camera_rules.h $(CSRC)/camera_device.h $(filter-out tests/cpp/test_change_rules.cpp,$(CHANGE_RULES))
+camera_rules: $(OUT)/test_camera_rules
+$(OUT)/test_camera_rules: $(CAMERA_RULES) | $(OUT)
+	$(CXX) -O2 -std=c++17 -Wall -ffp-contract=off -Iinclude -I$(CSRC) -o $@ tests/cpp/test_camera_rules.cpp
+# ... and under the host sanitizers: not part of `all`; make camera_rules_san, then run it on a script
+camera_rules_san: $(OUT)/test_camera_rules_san
+$(OUT)/test_camera_rules_san: $(CAMERA_RULES) | $(OUT)
+	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(CSRC) -o $@ tests/cpp/test_camera_rules.cpp
+
 $(OUT)/test_wire: tests/cpp/test_wire.cpp $(HOST)/zly_wire.hpp $(HOST)/zly_sha256.hpp $(HOST)/zly_compat.hpp | $(OUT)
 	$(CXX) -O2 -std=c++17 -Wall -I$(HOST) -o $@ tests/cpp/test_wire.cpp
 
@@ -243,4 +257,4 @@ $(OUT)/diag_lds: $(PKG)/tools/diag_lds.hip $(CSRC)/kernels_conv.hip $(CSRC)/zly_
 clean:
 	rm -rf $(OUT) oracle/_build
 
-.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe track_probe frame_rules_san surface_rules_san surface_moves_san zoom_plan_san chip_rules chip_rules_san change_rules change_rules_san clean
+.PHONY: all host oracle weights diag diaglib nms_probe sppf_probe track_probe frame_rules_san surface_rules_san surface_moves_san zoom_plan_san chip_rules chip_rules_san change_rules change_rules_san camera_rules camera_rules_san clean

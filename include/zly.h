@@ -439,6 +439,10 @@ int32_t zly_join(zly_engine* e, void* stream, int32_t lag);
  *   5, 6. Expiry, births and the eviction order do not change.  A birth sets vx = vy = 0 and hits = 1.
  * So a track's first match takes the whole displacement as its velocity and later ones move it by beta of the residual; v_max = 0 gives the
  * plain tracker's ids bit for bit.  THE RULE holds unchanged.
+ * Camera motion (zly_camera_apply_tracks, "Camera motion" below; opt-in).  THE RULE, extended: a stream's ids are a function of its own sequence
+ * of detection lists and of the SHIFTS applied between them -- each one pair (nx, ny) of fp32 values added to x and y of every live slot -- and of
+ * nothing else.  With the motion model on, the velocities then become SCENE-RELATIVE: a match's residual is taken against the shifted box, so
+ * vx, vy hold what a target moves beyond the camera's own motion, and the prediction of step P needs the shift of the coming frame applied first.
  * Not tracked: frames that go through the synchronous host calls or the _fmt submits, and engines behind host/zly_sharded*.hpp (consecutive
  * frames of a stream land on different GPUs).  A new engine (the plugin's hot reload) starts with fresh tables. */
 typedef struct zly_track_config {
@@ -962,6 +966,114 @@ int32_t zly_change_reset(zly_engine* e, int32_t stream);
  * a change map, or window_w, window_h != region_w, region_h.  A zoom call then also refuses (nothing enqueued) a stream at or beyond the change map's
  * max_streams (ZLY_ERR_INVALID_ARGUMENT) and a surface above ZLY_AREA_MAX_DIM or with more than ZLY_CHANGE_MAX_CELLS cells (ZLY_ERR_INVALID_INPUT). */
 int32_t zly_zoom_use_change(zly_engine* e, int32_t on);
+
+/* --- Camera motion -----------------------------------------------------------------------------------------------------------------
+ * Estimates, on the GPU, ONE TRANSLATION between two consecutive frames of a stream -- how far the whole picture moved, as under a turning
+ * first-person camera -- and moves the stream's tracks by it before the next frame is matched ("camera motion compensation").  The tracker
+ * matches by IoU: a pan of more than about half a box width per frame leaves every track unmatched and every target with a fresh id, and the
+ * motion model needs two matched frames before it helps, which are the frames the pan takes away; zoom regions are planned from the same
+ * table, so under a pan every region sits where its target was one frame ago; and the change map reports ZLY_CHANGE_GLOBAL and steps aside.
+ * The reference's tracker (src/game/kalman_tracker.cpp) has no answer to this either.  Here the estimate is a block-matching search over the
+ * change map's coarse grids of luma sums of the two frames, which are already in HBM; nothing synchronises and nothing crosses PCIe.
+ * Opt-in per engine (zly_camera_enable): an engine that never calls it allocates nothing more and launches exactly the kernels it launched before.
+ *
+ * Config: cell C, one of 8, 16, 32, 64; radius R, 1..8 cells: the search covers displacements of up to R cells per axis; max_residual_q4,
+ * 0..4080, sixteenths of a luma level per pixel: a best match worse than that is LOST.
+ * Per-stream state: the geometry (W, H, C); the grid of the previous frame's sums; a have_prev bit; the counter `step`; pend_x_q4, pend_y_q4
+ * (int64): the shift, in sixteenths of a pixel, accumulated since it was last applied; the counters n_lost and n_applied.
+ * All arithmetic is integer and exact, except the two fp32 operations of step A (the oracle: tests/camera_ref.py).
+ * One frame of a stream, a frame view of W x H in any ZLY_PIX_* format:
+ *   1. Grid.  S is exactly steps 1-2 of "Change map": the same luma of the format's BGR image, the same cells, gw = ceil(W / C),
+ *      gh = ceil(H / C), gw*gh <= ZLY_CHANGE_MAX_CELLS.  Also required: gw >= 2R + 1 and gh >= 2R + 1.
+ *   2. FIRST.  When the stream has no previous grid (after zly_camera_enable or zly_camera_reset) or W, H or C differ from the stored geometry:
+ *      ZLY_CAMERA_FIRST is set, d = f = 0, sx_q4 = sy_q4 = 0, sad_min = sad_zero = 0, the pending shift is SET TO 0, there is no search and the
+ *      SAD table is left untouched.  Steps 3-7 are skipped.
+ *   3. Search.  The window is the cells cx in [R, gw - R), cy in [R, gh - R): whole cells all of them, because only the last column and row can
+ *      be partial.  For every (dx, dy) in [-R, R]^2:  SAD(dx, dy) = sum over the window of |S(cx, cy) - S_prev(cx - dx, cy - dy)|,  a u64
+ *      (255*W*H exceeds 2^32 from 16.8 M pixels on).  (dx, dy) is the displacement, in cells, of the content from the previous frame to this one.
+ *   4. Best: the candidate least in the order (SAD ascending, |dx| + |dy| ascending, dy ascending, dx ascending).  A flat or unchanged scene
+ *      gives (0, 0).  sad_min is its SAD, sad_zero = SAD(0, 0).
+ *   5. Sub-cell, an equiangular fit per axis, in sixteenths of a cell.  On an axis where |d| = R: f = 0 and ZLY_CAMERA_CLIPPED is set.
+ *      Otherwise s0 = sad_min, and sm, sp = the SADs at d - 1 and d + 1 on that axis with the other axis at its best.  If s0 = 0 or
+ *      max(sm, sp) = s0: f = 0.  Otherwise num = 16*(sm - sp) (signed), den = 2*(max(sm, sp) - s0), q = min(floor(|num| / den), 8) and
+ *      f = sign(num)*q.
+ *   6. The shift in sixteenths of a pixel: sx_q4 = (16*dx + fx)*C, sy_q4 = (16*dy + fy)*C.
+ *   7. LOST.  npix = (gw - 2R)*(gh - 2R)*C*C.  If 16*sad_min > max_residual_q4*npix (64-bit; equality is not lost), ZLY_CAMERA_LOST is set and
+ *      n_lost advances; the frame then adds nothing to the pending shift.  d, f, sx_q4 and sy_q4 are still reported.
+ *   8. Update.  Unless FIRST or LOST, pend += (sx_q4, sy_q4).  The stored grid becomes S, with its geometry, and `step` advances (1 for the
+ *      first frame after enable or reset).
+ *   9. The record of a stream, kept in HBM and zeroed by zly_camera_enable: a zly_camera_header, ZLY_CAMERA_HDR_BYTES bytes (pad = 0), written
+ *      whole by every frame; then the SAD table, u64, row-major by (dy, dx): entry (dy + R)*(2R + 1) + (dx + R), with room for 17 x 17 entries,
+ *      of which those at and beyond (2R + 1)^2 are UNTOUCHED.  zly_camera_layout reports sizes and offsets.
+ *   A. Applying it to tracks (zly_camera_apply_tracks), for each named stream that has a geometry (a stream has none before its first frame
+ *      and after zly_camera_reset; it is then skipped whole):
+ *        nx = (float)pend_x_q4 / (float)(16*W),  ny = (float)pend_y_q4 / (float)(16*H)
+ *      -- each an int -> float conversion rounded to nearest even (16*W is exact) and one fp32 division, without contraction.  Every LIVE slot
+ *      of the stream's track table gets x = x + nx, y = y + ny.  Slots that are not live, and w, h, class, id, last_seen, frame_no and the
+ *      motion model's vx, vy and hits stay as they are.  Then pend = 0 and n_applied advances: the apply writes those three fields of the
+ *      record and no other byte of it.
+ * The tracking section states what this means for ids and velocities ("Camera motion" there).
+ * There is no integration into the zoom or track entry points: a caller composes zly_camera_surfaces -> zly_camera_apply_tracks ->
+ * zly_detect_surfaces_zoom.
+ * Out of scope: rotation, zoom and parallax (the estimate is one translation per frame); a pyramid for pans beyond R cells; compensating the
+ * change map with the shift; the pipelined submit ring, the plugin, the wire format, engines behind host/zly_sharded*.hpp; and tuning the
+ * defaults (max_residual_q4's is chosen, not tuned; weights and frames are synthetic: no accuracy claim is made). */
+#define ZLY_CAMERA_MAX_RADIUS 8
+#define ZLY_CAMERA_HDR_BYTES  96
+#define ZLY_CAMERA_SAD_ROOM   289     /* (2*ZLY_CAMERA_MAX_RADIUS + 1)^2 entries */
+#define ZLY_CAMERA_FIRST      1u
+#define ZLY_CAMERA_LOST       2u
+#define ZLY_CAMERA_CLIPPED    4u
+typedef struct zly_camera_config {
+    int32_t cell;                 /* C: 8, 16, 32 or 64; default 16 */
+    int32_t radius;               /* R: 1..8 cells; default 4 */
+    int32_t max_residual_q4;      /* 0..4080, sixteenths of a luma level per pixel; default 64 (chosen, not tuned) */
+} zly_camera_config;
+typedef struct zly_camera_header {
+    uint32_t flags;               /* ZLY_CAMERA_FIRST | ZLY_CAMERA_LOST | ZLY_CAMERA_CLIPPED */
+    uint32_t step;                /* the stream's counter */
+    int32_t  gw, gh;
+    int32_t  dx, dy;              /* the best displacement in cells */
+    int32_t  fx, fy;              /* the sub-cell parts, sixteenths of a cell, -8..8 */
+    int32_t  sx_q4, sy_q4;        /* this frame's shift, sixteenths of a pixel */
+    uint32_t n_lost, n_applied;
+    uint64_t sad_min, sad_zero;
+    int64_t  pend_x_q4, pend_y_q4;
+    uint32_t pad[4];              /* 0 */
+} zly_camera_header;
+void    zly_default_camera_config(zly_camera_config* cfg);
+/* Once per engine, alone in the process like the other enables: allocates max_streams (>= 1) grids and records and max_batch scratch grids.
+ * ZLY_ERR_INVALID_ARGUMENT: a null or out-of-range config, max_streams < 1, a second call; ZLY_ERR_SYSTEM: a failed allocation.  Every other call
+ * of this section on an engine without the feature fails with ZLY_ERR_INVALID_ARGUMENT.  After the enable, no call of this section allocates or
+ * waits for the device (the reads excepted: they wait). */
+int32_t zly_camera_enable(zly_engine* e, const zly_camera_config* cfg, int32_t max_streams);
+/* bytes of one stream's record, the offset of the SAD table in it and the table's room in entries (any output may be null) */
+int32_t zly_camera_layout(const zly_engine* e, size_t* rec_bytes, size_t* sad_off, size_t* sad_room);
+/* One frame for each of n streams (1 <= n <= max_batch): view i of the device buffer d_base (HOST array views[n]) is the next frame of streams[i]
+ * (HOST array; 0 <= streams[i] < max_streams, distinct within the call).  Enqueued, not synchronised, on `stream` (NULL = the engine's own); the
+ * calls of this section are ordered among themselves on whichever streams they run.  Three launches: the change map's sums kernel into the
+ * camera's own scratch grids, the search, the pick.
+ * ZLY_ERR_INVALID_ARGUMENT, with nothing enqueued and no stream changed: an engine without the feature, n out of range, a null array, an unknown
+ * format, a stream out of range or twice.  ZLY_ERR_INVALID_INPUT: a view that zly_detect_device_view would refuse, W or H above ZLY_AREA_MAX_DIM,
+ * more than ZLY_CHANGE_MAX_CELLS cells, gw or gh below 2R + 1. */
+int32_t zly_camera_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* views, const int32_t* streams, void* stream);
+/* The same on n resident surfaces, whole (a slot index may repeat).  An undefined or invalid surface is refused as zly_detect_surfaces refuses it.
+ * The call is a reader of the store, with the protocol of zly_change_surfaces. */
+int32_t zly_camera_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, void* stream);
+/* Waits for the calls of this section enqueued so far, then copies min(cap_bytes, record bytes) of the stream's record to host_out.
+ * ZLY_ERR_INVALID_ARGUMENT: a null output, a stream out of range, cap_bytes below ZLY_CAMERA_HDR_BYTES. */
+int32_t zly_camera_read(zly_engine* e, int32_t stream, void* host_out, size_t cap_bytes);
+/* Enqueued behind the calls of this section so far: the stream (-1: every stream) has no previous grid and no geometry, its counter is 0 and its
+ * pending shift is 0 -- pend_x_q4 and pend_y_q4 of the record are zeroed; the rest of the record, n_lost and n_applied included, is left as it is. */
+int32_t zly_camera_reset(zly_engine* e, int32_t stream);
+/* Step A for the n named streams (HOST array; 1 <= n <= the camera's max_streams; distinct).  Needs zly_track_enable: camera stream i is track
+ * stream i, as with the change map.  Enqueued, not synchronised, on `stream` (NULL = the engine's own): behind the camera calls and the tracked
+ * calls enqueued so far, on whichever streams those ran, and ahead of every later zly_track_slabs and zoom call -- on an engine with the feature
+ * the tracking kernels and the zoom plan wait for the most recent apply.  One launch, one wavefront per stream.  The call takes an entry of the
+ * camera's ring and one of the tracker's; like every ring of the engine, taking an entry waits for the work that used it eight calls ago.
+ * ZLY_ERR_INVALID_ARGUMENT, with nothing enqueued: an engine without the feature or without track tables, a null array, n out of range, a stream
+ * named twice or at or beyond either table's max_streams. */
+int32_t zly_camera_apply_tracks(zly_engine* e, int32_t n, const int32_t* streams, void* stream);
 
 /* --- stage-level entry points (parity tests) ------------------------------------------------- */
 /* preProcess: out_nchw is host fp32 [3][model_h][model_w]. */

@@ -14,6 +14,7 @@
 #include "zoom_rules.h"
 #include "chip_rules.h"
 #include "change_rules.h"
+#include "camera_rules.h"
 #include "upload_ring.h"
 #include "weights.h"
 
@@ -230,6 +231,22 @@ struct Change {
     unsigned char* d_recs = nullptr;  // [max_streams][lay.rec_bytes]
 };
 
+// Camera motion (zly_camera_enable; include/zly.h "Camera motion"): the streams' states, grids and records in HBM, the scratch grids of a call, and the
+// ring (upload_ring.h) through which a call's frame records and items -- or an apply's stream indices -- reach the kernels.  zly_camera_reset marks an
+// entry too, without filling it.
+struct Camera {
+    zly_camera_config cfg{};
+    CameraLayout lay{};
+    int max_streams = 0;
+    UploadRing ring;                  // an entry: max_batch ChipFrame, then (at items_off) max_batch CameraItem; an apply's: max_streams int32
+    size_t items_off = 0;
+    CameraItem* items(unsigned char* entry) const { return reinterpret_cast<CameraItem*>(entry + items_off); }
+    uint32_t* d_sums = nullptr;       // [max_batch][ZLY_CHANGE_MAX_CELLS]: the scratch grids
+    CameraStream* d_state = nullptr;  // [max_streams]
+    uint32_t* d_prev = nullptr;       // [max_streams][ZLY_CHANGE_MAX_CELLS]
+    unsigned char* d_recs = nullptr;  // [max_streams][lay.rec_bytes]
+};
+
 }  // namespace zly
 
 using namespace zly;
@@ -253,6 +270,12 @@ static hipError_t change_free(Change* ch)
 {
     const hipError_t r = first_error({ch->ring.destroy(), hipFree(ch->d_sums), hipFree(ch->d_state), hipFree(ch->d_prev), hipFree(ch->d_recs)});
     delete ch;
+    return r;
+}
+static hipError_t camera_free(Camera* cm)
+{
+    const hipError_t r = first_error({cm->ring.destroy(), hipFree(cm->d_sums), hipFree(cm->d_state), hipFree(cm->d_prev), hipFree(cm->d_recs)});
+    delete cm;
     return r;
 }
 
@@ -339,6 +362,7 @@ struct zly_engine : Plan {
     Zoom* zoom = nullptr;                   // created by zly_zoom_enable (under mu)
     Chips* chips = nullptr;                 // created by zly_chips_enable (under mu)
     Change* change = nullptr;               // created by zly_change_enable (under mu)
+    Camera* camera = nullptr;               // created by zly_camera_enable (under mu)
     hipStream_t last_ns = nullptr;          // the stream the most recent zly_detect_device* call's NMS ran on, and whether that was the engine's NMS stream
     bool last_deferred = false;
 
@@ -1519,6 +1543,8 @@ static int track_enqueue(zly_engine* e, Track* tk, int n, const int32_t* streams
     int n_tracked = 0, n_seg = 0;
     for (int i = 0; i < n; ++i) if (streams[i] >= 0) ++n_tracked;
     if (n_tracked == 0) return ZLY_OK;
+    // an engine with camera motion: behind the most recent zly_camera_apply_tracks, which marks an entry of this ring, on whichever stream it ran
+    if (e->camera) HIP_TRY(tk->ring.wait_last(s), ZLY_ERR_INFERENCE);
     int r = 0;
     HIP_TRY(tk->ring.claim(&r), ZLY_ERR_INFERENCE);
     int* g = tk->ring.host<int>(r);
@@ -1639,6 +1665,7 @@ static const char* const NO_STORE = "resident surfaces are not enabled on this e
 static const char* const NO_ZOOM = "zoom regions are not enabled on this engine (zly_track_enable, then zly_zoom_enable)";
 static const char* const NO_CHIPS = "chips are not enabled on this engine (zly_chips_enable)";
 static const char* const NO_CHANGE = "the change map is not enabled on this engine (zly_change_enable)";
+static const char* const NO_CAMERA = "camera motion is not enabled on this engine (zly_camera_enable)";
 template <typename T> static T* enabled(T* state, const char* or_else)
 {
     if (!state) fail(ZLY_ERR_INVALID_ARGUMENT, or_else);
@@ -1649,6 +1676,7 @@ static Surfaces* surfaces_of(zly_engine* e) { return enabled(e->surf, NO_STORE);
 static Zoom* zoom_of(zly_engine* e) { return enabled(e->zoom, NO_ZOOM); }
 static Chips* chips_of(zly_engine* e) { return enabled(e->chips, NO_CHIPS); }
 static Change* change_of(zly_engine* e) { return enabled(e->change, NO_CHANGE); }
+static Camera* camera_of(zly_engine* e) { return enabled(e->camera, NO_CAMERA); }
 
 // The stream a device entry enqueues on: the caller's, or the engine's own where the caller names none.  wait_for: an event the caller's stream has to
 // wait for first (null = none); the engine's own stream lies behind it already.  Enqueue gate held.
@@ -1848,6 +1876,7 @@ static hipError_t destroy_engine(zly_engine* e)
     if (e->zoom) note(zoom_free(e->zoom));
     if (e->chips) note(chips_free(e->chips));
     if (e->change) note(change_free(e->change));
+    if (e->camera) note(camera_free(e->camera));
     for (int i = 0; i < 2; ++i) {
         if (e->ev_fork[i]) hipEventDestroy(e->ev_fork[i]);
         if (e->ev_join[i]) hipEventDestroy(e->ev_join[i]);
@@ -3314,11 +3343,8 @@ int32_t zly_change_layout(const zly_engine* e, size_t* rec_bytes, size_t* peaks_
 // entry, for change_enqueue_pick.  Under e->mu, enqueue gate held; every check has been made.
 static int change_enqueue_sums(zly_engine* e, Change* ch, int n, const void* d_base, const zly_frame_view* v, const int32_t* streams, hipStream_t s, int* ring)
 {
-    // not claim(): synchronise the entry, wait for the last, and only then advance -- a call that fails here leaves the ring as it found it
-    const int r = ch->ring.next;
-    if (ch->ring.used[r]) HIP_TRY(hipEventSynchronize(ch->ring.ev[r]), ZLY_ERR_INFERENCE);
-    HIP_TRY(ch->ring.wait_last(s), ZLY_ERR_INFERENCE);
-    ch->ring.next = (r + 1) % SlotRing::DEPTH;
+    int r = 0;
+    HIP_TRY(ch->ring.claim_behind_last(s, &r), ZLY_ERR_INFERENCE);
     const int rc = [&]() -> int {
         ChipFrame* hf = ch->ring.host<ChipFrame>(r);
         ChangeItem* hi = ch->items(ch->ring.host<unsigned char>(r));
@@ -3419,6 +3445,181 @@ int32_t zly_change_reset(zly_engine* e, int32_t stream)
     HIP_TRY(hipMemsetAsync(ch->d_state + (stream < 0 ? 0 : stream), 0, sizeof(ChangeStream) * (size_t)(stream < 0 ? ch->max_streams : 1), e->stream), ZLY_ERR_INFERENCE);
     HIP_TRY(ch->ring.mark(r, e->stream), ZLY_ERR_INFERENCE);
     return ZLY_OK;
+}
+
+// --- camera motion (include/zly.h "Camera motion"; the rules: camera_rules.h; the kernels: kernels_camera.hip) ---------
+void zly_default_camera_config(zly_camera_config* c)
+{
+    if (!c) return;
+    camera_default_config(c);
+}
+
+int32_t zly_camera_enable(zly_engine* e, const zly_camera_config* c, int32_t max_streams)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = camera_check_config(c, max_streams, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->camera) return fail(ZLY_ERR_INVALID_ARGUMENT, "camera motion is already enabled on this engine");
+    ExclusiveGate gl;                                  // allocations: alone in the process
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    Camera* cm = new Camera();
+    cm->cfg = *c;
+    cm->lay = camera_layout();
+    cm->max_streams = max_streams;
+    const size_t B = (size_t)e->cfg.max_batch, NS = (size_t)max_streams, grid = sizeof(uint32_t) * ZLY_CHANGE_MAX_CELLS;
+    // both arrays 16-byte aligned in every entry
+    static_assert(sizeof(CameraItem) == 16 && alignof(ChipFrame) <= 16 && alignof(CameraItem) <= 16, "the entry's layout assumes 16-byte items");
+    cm->items_off = (sizeof(ChipFrame) * B + 15) / 16 * 16;
+    bool ok = cm->ring.create(std::max(cm->items_off + sizeof(CameraItem) * B, sizeof(int32_t) * NS)) == hipSuccess &&
+              hipMalloc((void**)&cm->d_sums, grid * B) == hipSuccess &&
+              hipMalloc((void**)&cm->d_state, sizeof(CameraStream) * NS) == hipSuccess &&
+              hipMalloc((void**)&cm->d_prev, grid * NS) == hipSuccess &&
+              hipMalloc((void**)&cm->d_recs, (size_t)cm->lay.rec_bytes * NS) == hipSuccess &&
+              hipMemset(cm->d_sums, 0, grid * B) == hipSuccess &&
+              hipMemset(cm->d_state, 0, sizeof(CameraStream) * NS) == hipSuccess &&
+              hipMemset(cm->d_prev, 0, grid * NS) == hipSuccess &&
+              hipMemset(cm->d_recs, 0, (size_t)cm->lay.rec_bytes * NS) == hipSuccess &&
+              hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        (void)camera_free(cm);
+        return fail(ZLY_ERR_SYSTEM, "allocation of the camera motion's buffers failed");
+    }
+    e->camera = cm;
+    return ZLY_OK;
+}
+
+int32_t zly_camera_layout(const zly_engine* e, size_t* rec_bytes, size_t* sad_off, size_t* sad_room)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(const_cast<zly_engine*>(e)->mu);
+    const Camera* cm = enabled(e->camera, NO_CAMERA);
+    if (!cm) return ZLY_ERR_INVALID_ARGUMENT;
+    if (rec_bytes) *rec_bytes = (size_t)cm->lay.rec_bytes;
+    if (sad_off) *sad_off = (size_t)cm->lay.sad_off;
+    if (sad_room) *sad_room = (size_t)cm->lay.sad_room;
+    return ZLY_OK;
+}
+
+// The body of zly_camera_device_view and zly_camera_surfaces: the n views of the source.  Under e->mu, e->camera set; takes the enqueue gate itself.
+// Every check comes first: a refused call enqueues nothing.  *ran_on (if asked for): the stream the kernels went to.
+static int camera_locked(zly_engine* e, int32_t n, const FrameSource& f, const int32_t* streams, void* stream, hipStream_t* ran_on = nullptr)
+{
+    Camera* cm = e->camera;
+    if (int rc = camera_check_streams(n, streams, cm->max_streams, cm->max_streams, &g_last_error)) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (int rc = chip_check_view(e->cfg.flags, f.base, f.bytes, &f.v[i], &g_last_error)) return rc;
+        if (int rc = camera_check_size(f.v[i].w, f.v[i].h, cm->cfg.cell, cm->cfg.radius, &g_last_error)) return rc;
+    }
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s, f.wait_for)) return rc;
+    int r = 0;
+    HIP_TRY(cm->ring.claim_behind_last(s, &r), ZLY_ERR_INFERENCE);      // behind the camera calls so far: they share scratch grids, states and records
+    const int rc = [&]() -> int {
+        ChipFrame* hf = cm->ring.host<ChipFrame>(r);
+        CameraItem* hi = cm->items(cm->ring.host<unsigned char>(r));
+        int max_w = 1, max_h = 1;
+        for (int i = 0; i < n; ++i) {
+            hf[i] = chip_frame_of(&f.v[i]);
+            hi[i] = CameraItem{f.v[i].w, f.v[i].h, streams[i], 0};
+            max_w = std::max(max_w, (int)f.v[i].w); max_h = std::max(max_h, (int)f.v[i].h);
+        }
+        // one copy: the frame records (all max_batch of the entry; the n first matter) and the n items behind them
+        HIP_TRY(cm->ring.upload(r, cm->items_off + sizeof(CameraItem) * (size_t)n, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_change_sums((const uint8_t*)f.base, cm->ring.dev<ChipFrame>(r), n, max_w, max_h, cm->cfg.cell, cm->d_sums, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_camera(cm->items(cm->ring.dev<unsigned char>(r)), n, cm->d_sums, cm->d_state, cm->d_prev, cm->d_recs, cm->cfg, s), ZLY_ERR_INFERENCE);
+        return ZLY_OK;
+    }();
+    // the entry's event goes behind whatever has been enqueued, a failed call's too: the next camera call, on whichever stream, is ordered behind it
+    if (cm->ring.mark(r, s) != hipSuccess && rc == ZLY_OK) return fail(ZLY_ERR_INFERENCE, "hipEventRecord failed behind the camera motion's kernels");
+    if (ran_on) *ran_on = s;
+    return rc;
+}
+
+int32_t zly_camera_device_view(zly_engine* e, int32_t n, const void* d_base, size_t buf_bytes, const zly_frame_view* views, const int32_t* streams, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = camera_check_call(n, e->cfg.max_batch, views, streams, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!camera_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
+    return camera_locked(e, n, FrameSource{d_base, buf_bytes, views}, streams, stream);
+}
+
+int32_t zly_camera_surfaces(zly_engine* e, int32_t n, const int32_t* surfaces, const int32_t* streams, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (int rc = camera_check_call(n, e->cfg.max_batch, surfaces, streams, &g_last_error)) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!camera_of(e)) return ZLY_ERR_INVALID_ARGUMENT;
+    StoreFrames src;
+    if (int rc = src.open(e)) return rc;
+    if (int rc = src.frames(n, surfaces)) return rc;
+    return src.read_by([&](const FrameSource& f, hipStream_t* ran) { return camera_locked(e, n, f, streams, stream, ran); });
+}
+
+int32_t zly_camera_read(zly_engine* e, int32_t stream, void* host_out, size_t cap_bytes)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!host_out) return fail(ZLY_ERR_INVALID_ARGUMENT, "null output");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Camera* cm = camera_of(e);
+    if (!cm) return ZLY_ERR_INVALID_ARGUMENT;
+    if (stream < 0 || stream >= cm->max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    if (cap_bytes < (size_t)cm->lay.sad_off) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_camera_read: the header is " + std::to_string(cm->lay.sad_off) + " bytes");
+    return read_back(e, behind_ring(cm->ring), {{host_out, cm->d_recs + (size_t)stream * (size_t)cm->lay.rec_bytes, std::min(cap_bytes, (size_t)cm->lay.rec_bytes)}});
+}
+
+int32_t zly_camera_reset(zly_engine* e, int32_t stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Camera* cm = camera_of(e);
+    if (!cm) return ZLY_ERR_INVALID_ARGUMENT;
+    if (stream < -1 || stream >= cm->max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "stream " + std::to_string(stream) + " out of range");
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    SharedGate gl;
+    // a ring entry of its own orders the reset among the camera calls: behind the last one, in front of the next
+    int r = 0;
+    HIP_TRY(cm->ring.claim_behind_last(e->stream, &r), ZLY_ERR_INFERENCE);
+    const hipError_t le = launch_camera_reset(cm->d_state, cm->d_recs, stream < 0 ? 0 : stream, stream < 0 ? cm->max_streams : 1, e->stream);
+    HIP_TRY(cm->ring.mark(r, e->stream), ZLY_ERR_INFERENCE);
+    HIP_TRY(le, ZLY_ERR_INFERENCE);
+    return ZLY_OK;
+}
+
+int32_t zly_camera_apply_tracks(zly_engine* e, int32_t n, const int32_t* streams, void* stream)
+{
+    if (!e) return fail(ZLY_ERR_NOT_INITIALIZED, "Engine not running");
+    if (!streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "null streams");
+    std::lock_guard<std::mutex> lk(e->mu);
+    Camera* cm = camera_of(e);
+    if (!cm) return ZLY_ERR_INVALID_ARGUMENT;
+    Track* tk = track_of(e);
+    if (!tk) return ZLY_ERR_INVALID_ARGUMENT;
+    if (n < 1 || n > cm->max_streams) return fail(ZLY_ERR_INVALID_ARGUMENT, "zly_camera_apply_tracks: n must lie in 1.." + std::to_string(cm->max_streams));
+    if (int rc = camera_check_streams(n, streams, cm->max_streams, tk->cfg.max_streams, &g_last_error)) return rc;
+    SharedGate gl;
+    HIP_TRY(hipSetDevice(e->dev), ZLY_ERR_SYSTEM);
+    hipStream_t s = nullptr;
+    if (int rc = call_stream(e, stream, &s)) return rc;
+    // behind the camera calls (the entry) and the tracked calls (the track ring's last mark) enqueued so far, on whichever streams they ran
+    int r = 0, tr = 0;
+    HIP_TRY(cm->ring.claim_behind_last(s, &r), ZLY_ERR_INFERENCE);      // behind the camera calls so far: they share scratch grids, states and records
+    const int rc = [&]() -> int {
+        HIP_TRY(tk->ring.wait_last(s), ZLY_ERR_INFERENCE);
+        memcpy(cm->ring.host<int32_t>(r), streams, sizeof(int32_t) * (size_t)n);
+        HIP_TRY(cm->ring.upload(r, sizeof(int32_t) * (size_t)n, s), ZLY_ERR_INFERENCE);
+        HIP_TRY(launch_camera_apply(cm->ring.dev<int>(r), n, cm->d_state, cm->d_recs, tk->d_state, tk->cfg.max_tracks, s), ZLY_ERR_INFERENCE);
+        // ... and ahead of every later one: an entry of the track ring, not filled, is marked behind the kernel -- the tracking kernels of an engine
+        // with this feature (track_enqueue), the zoom plan and zly_track_read all go behind the ring's last mark
+        HIP_TRY(tk->ring.claim(&tr), ZLY_ERR_INFERENCE);
+        HIP_TRY(tk->ring.mark(tr, s), ZLY_ERR_INFERENCE);
+        return ZLY_OK;
+    }();
+    if (cm->ring.mark(r, s) != hipSuccess && rc == ZLY_OK) return fail(ZLY_ERR_INFERENCE, "hipEventRecord failed behind the camera motion's apply kernel");
+    return rc;
 }
 
 // --- zoom regions (include/zly.h "Zoom regions"; the rules: zoom_rules.h; the plan kernel: kernels_zoom.hip) -----------

@@ -6,7 +6,8 @@
 // synchronises with the entry's event, which by then lies DEPTH calls back and has long completed.  `last` is the entry marked most recently: the work
 // of a ring's calls may run on different streams, and wait_last orders a stream behind the most recent of it.
 //
-//   SlotRing     the discipline alone: events, marks, cursor (the descriptor uploads of set_desc, whose device copy is single; zly_change_reset)
+//   SlotRing     the discipline alone: events, marks, cursor (the descriptor uploads of set_desc, whose device copy is single; zly_change_reset);
+//                claim_behind_last is the claim of calls that are chained among themselves (the change map's, camera motion's)
 //   UploadRing   ... plus the storage: DEPTH pinned host records mirrored by DEPTH device records of the same size
 //
 // Every operation returns the HIP error of the call that failed (hipSuccess otherwise); none is thread-safe: the owner's lock covers them.
@@ -47,6 +48,17 @@ struct SlotRing {
         *r = next;
         next = (next + 1) % DEPTH;
         return used[*r] ? hipEventSynchronize(ev[*r]) : hipSuccess;
+    }
+    // claim for work on s that must also run behind the entry marked most recently (calls that share scratch or state whichever streams they run
+    // on): the entry is synchronised and s made to wait first, and the cursor advances only then -- a call that fails here leaves the ring as it was
+    hipError_t claim_behind_last(hipStream_t s, int* r)
+    {
+        *r = next;
+        if (used[*r])
+            if (const hipError_t e = hipEventSynchronize(ev[*r])) return e;
+        if (const hipError_t e = wait_last(s)) return e;
+        next = (next + 1) % DEPTH;
+        return hipSuccess;
     }
     // entry r's event behind what has been enqueued on s
     hipError_t mark(int r, hipStream_t s)

@@ -397,4 +397,16 @@ hipError_t launch_change_sums(const uint8_t* src, const ChipFrame* frames, int n
 hipError_t launch_change_pick(const ChangeItem* items, int n, const uint32_t* sums, ChangeStream* state, uint32_t* prev, void* recs, const zly_change_config& cfg,
                               const ZoomFrame* zf, FrameDesc* desc, int* tab, zly_zoom_region* plan, int K, hipStream_t s);
 
+// ---- camera motion (kernels_camera.hip; the rule: include/zly.h, "Camera motion"; the records and the arithmetic: camera_device.h) ----
+struct CameraItem;
+struct CameraStream;
+// two launches behind launch_change_sums into `sums`: camera_search_kernel, (2R + 1) x n workgroups, writes the SAD tables of the streams items[i].stream
+// in recs (camera_layout apart) from sums[i] against prev[stream]; camera_pick_kernel, one workgroup per frame, writes the records' headers, the
+// streams' states and their grids
+hipError_t launch_camera(const CameraItem* items, int n, const uint32_t* sums, CameraStream* state, uint32_t* prev, void* recs, const zly_camera_config& cfg, hipStream_t s);
+// camera_apply_kernel, one wavefront per stream of streams[n] (device): step A on tracks[stream]
+hipError_t launch_camera_apply(const int* streams, int n, const CameraStream* state, void* recs, TrackStream* tracks, int max_tracks, hipStream_t s);
+// streams [first, first + count): no grid, no geometry, counter 0, pending shift 0
+hipError_t launch_camera_reset(CameraStream* state, void* recs, int first, int count, hipStream_t s);
+
 }  // namespace zly

@@ -66,6 +66,8 @@ SYMBOLS = [
     "zly_default_chip_config", "zly_chips_enable", "zly_chip_layout", "zly_chips_device_view", "zly_chips_surfaces", "zly_read_chips",
     "zly_default_change_config", "zly_change_enable", "zly_change_layout", "zly_change_device_view", "zly_change_surfaces", "zly_change_read", "zly_change_reset",
     "zly_zoom_use_change",
+    "zly_default_camera_config", "zly_camera_enable", "zly_camera_layout", "zly_camera_device_view", "zly_camera_surfaces", "zly_camera_read", "zly_camera_reset",
+    "zly_camera_apply_tracks",
     "zly_num_classes", "zly_weights_fp8", "zly_num_anchors", "zly_num_ops", "zly_op_info_at", "zly_launch_info_at", "zly_op_kernel_name", "zly_profile_ops", "zly_get_stats",
 ]
 
@@ -91,6 +93,12 @@ CHANGE_FIRST, CHANGE_GLOBAL, CHANGE_MAX_CELLS = 1, 2, 8192
 CHANGE_HDR_DTYPE = np.dtype([("n_cells", "<i4"), ("n_active", "<i4"), ("n_peaks", "<i4"), ("flags", "<u4"), ("gw", "<i4"), ("gh", "<i4"), ("step", "<u4"), ("pad", "<u4")])
 CHANGE_PEAK_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("cx", "<i4"), ("cy", "<i4"), ("activity", "<u4"), ("pad", "<u4")])
 assert CHANGE_HDR_DTYPE.itemsize == 32 and CHANGE_PEAK_DTYPE.itemsize == 32
+# zly_camera_header: the head of a stream's camera motion record (zly_camera_read); the SAD table, u64 [17 * 17], lies behind it
+CAMERA_FIRST, CAMERA_LOST, CAMERA_CLIPPED, CAMERA_MAX_RADIUS, CAMERA_SAD_ROOM = 1, 2, 4, 8, 289
+CAMERA_HDR_DTYPE = np.dtype([("flags", "<u4"), ("step", "<u4"), ("gw", "<i4"), ("gh", "<i4"), ("dx", "<i4"), ("dy", "<i4"), ("fx", "<i4"), ("fy", "<i4"),
+                             ("sx_q4", "<i4"), ("sy_q4", "<i4"), ("n_lost", "<u4"), ("n_applied", "<u4"), ("sad_min", "<u8"), ("sad_zero", "<u8"),
+                             ("pend_x_q4", "<i8"), ("pend_y_q4", "<i8"), ("pad", "<u4", (4,))])
+assert CAMERA_HDR_DTYPE.itemsize == 96
 
 
 class Config(C.Structure):
@@ -161,6 +169,11 @@ class ChangeConfig(C.Structure):
     """zly_change_config"""
     _fields_ = [("cell", C.c_int32), ("threshold_q4", C.c_int32), ("max_active_permille", C.c_int32), ("max_peaks", C.c_int32), ("window_w", C.c_int32),
                 ("window_h", C.c_int32)]
+
+
+class CameraConfig(C.Structure):
+    """zly_camera_config"""
+    _fields_ = [("cell", C.c_int32), ("radius", C.c_int32), ("max_residual_q4", C.c_int32)]
 
 
 class ChipConfig(C.Structure):
@@ -286,6 +299,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zly_change_read.argtypes = [vp, i32, vp, sz]; lib.zly_change_read.restype = i32
     lib.zly_change_reset.argtypes = [vp, i32]; lib.zly_change_reset.restype = i32
     lib.zly_zoom_use_change.argtypes = [vp, i32]; lib.zly_zoom_use_change.restype = i32
+    lib.zly_default_camera_config.argtypes = [C.POINTER(CameraConfig)]; lib.zly_default_camera_config.restype = None
+    lib.zly_camera_enable.argtypes = [vp, C.POINTER(CameraConfig), i32]; lib.zly_camera_enable.restype = i32
+    lib.zly_camera_layout.argtypes = [vp, psz, psz, psz]; lib.zly_camera_layout.restype = i32
+    lib.zly_camera_device_view.argtypes = [vp, i32, vp, sz, pv, pi32, vp]; lib.zly_camera_device_view.restype = i32
+    lib.zly_camera_surfaces.argtypes = [vp, i32, pi32, pi32, vp]; lib.zly_camera_surfaces.restype = i32
+    lib.zly_camera_read.argtypes = [vp, i32, vp, sz]; lib.zly_camera_read.restype = i32
+    lib.zly_camera_reset.argtypes = [vp, i32]; lib.zly_camera_reset.restype = i32
+    lib.zly_camera_apply_tracks.argtypes = [vp, i32, pi32, vp]; lib.zly_camera_apply_tracks.restype = i32
     lib.zly_forward.argtypes = [vp, i32, vp, vp]; lib.zly_forward.restype = i32
     lib.zly_head_tensor.argtypes = [vp, i32, vp]; lib.zly_head_tensor.restype = i32
     lib.zly_postprocess.argtypes = [vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, pi32, pi32]; lib.zly_postprocess.restype = i32
@@ -768,6 +789,53 @@ class Engine:
         """zoom calls fill their fallback regions from the change map"""
         _check(self.lib, self.lib.zly_zoom_use_change(self.h, 1 if on else 0))
 
+    # -- camera motion (include/zly.h "Camera motion") ------------------------------------------------------
+    def camera_enable(self, max_streams: int = 8, cell: Optional[int] = None, radius: Optional[int] = None, max_residual_q4: Optional[int] = None):
+        """once per engine; arguments left out keep zly_default_camera_config's values (cells of 16, a radius of 4 cells, 4 luma levels per pixel)"""
+        c = CameraConfig()
+        self.lib.zly_default_camera_config(C.byref(c))
+        for name, v in (("cell", cell), ("radius", radius), ("max_residual_q4", max_residual_q4)):
+            if v is not None:
+                setattr(c, name, v)
+        _check(self.lib, self.lib.zly_camera_enable(self.h, C.byref(c), max_streams))
+        self.camera_cfg = c
+
+    def camera_layout(self) -> Tuple[int, int, int]:
+        """(bytes of a stream's camera record, offset of the SAD table in it, the table's room in entries)"""
+        o = [C.c_size_t() for _ in range(3)]
+        _check(self.lib, self.lib.zly_camera_layout(self.h, *[C.byref(x) for x in o]))
+        return tuple(int(x.value) for x in o)
+
+    def camera_device_view(self, d_base_ptr: int, buf_bytes: int, views: Sequence[FrameView], streams: Sequence[int], stream: int = 0):
+        """view i of the device buffer is the next frame of streams[i]: its shift against the stream's previous frame; enqueued, not synchronised"""
+        n = len(views)
+        cv = (FrameView * max(n, 1))(*views)
+        cs = (C.c_int32 * max(len(streams), 1))(*streams)
+        _check(self.lib, self.lib.zly_camera_device_view(self.h, n, d_base_ptr or None, buf_bytes, cv, cs, stream or None))
+
+    def camera_surfaces(self, surfaces: Sequence[int], streams: Sequence[int], stream: int = 0):
+        """camera_device_view on resident surfaces, whole"""
+        n = len(surfaces)
+        cf = (C.c_int32 * max(n, 1))(*surfaces)
+        cs = (C.c_int32 * max(len(streams), 1))(*streams)
+        _check(self.lib, self.lib.zly_camera_surfaces(self.h, n, cf, cs, stream or None))
+
+    def camera_read(self, stream: int) -> np.ndarray:
+        """the stream's whole record (synchronises) -> u8 [rec_bytes]; parse_camera_record takes it apart"""
+        raw = np.zeros(self.camera_layout()[0], dtype=np.uint8)
+        _check(self.lib, self.lib.zly_camera_read(self.h, stream, raw.ctypes.data, raw.nbytes))
+        return raw
+
+    def camera_reset(self, stream: int = -1):
+        """the stream (-1: every stream) has no previous grid and no pending shift; enqueued"""
+        _check(self.lib, self.lib.zly_camera_reset(self.h, stream))
+
+    def camera_apply_tracks(self, streams: Sequence[int], stream: int = 0):
+        """moves the live tracks of the named streams by their pending shifts, which become 0; enqueued, not synchronised"""
+        n = len(streams)
+        cs = (C.c_int32 * max(n, 1))(*streams)
+        _check(self.lib, self.lib.zly_camera_apply_tracks(self.h, n, cs, stream or None))
+
     def submit(self, frame: np.ndarray, nbytes: Optional[int] = None, fmt: int = PIX_BGR,
                w: Optional[int] = None, h: Optional[int] = None) -> int:
         """copies the frame into the engine's pinned staging ring (on this thread) and returns a ticket"""
@@ -947,3 +1015,12 @@ def parse_change_record(raw: np.ndarray, max_peaks: int):
     peaks = raw[po:ao].view(CHANGE_PEAK_DTYPE)[:int(hdr["n_peaks"])].copy()
     act = raw[ao:ao + 4 * int(hdr["n_cells"])].view(np.uint32).reshape(int(hdr["gh"]), int(hdr["gw"])).copy()
     return hdr, peaks, act
+
+
+def parse_camera_record(raw: np.ndarray, radius: int):
+    """one stream's camera motion record (u8 [rec_bytes]) -> (header record, SAD table u64 [2R+1][2R+1], rows dy = -R..R, columns dx = -R..R)"""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+    hdr = raw[:CAMERA_HDR_DTYPE.itemsize].view(CAMERA_HDR_DTYPE)[0]
+    side = 2 * radius + 1
+    so = CAMERA_HDR_DTYPE.itemsize
+    return hdr, raw[so:so + 8 * side * side].view(np.uint64).reshape(side, side).copy()
